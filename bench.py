@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """bench.py - PCG iterations/s of the gato hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--no-sweep] [--no-cpu] [--sweep-out FILE]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR]
+                    [--full [--no-sweep] [--no-cpu] [--sweep-out FILE]]
+
+A plain run sets up, runs W untimed steps, times exactly K steps (`ms_per_step` = their wall time / K, `value` over the
+same K steps), writes lambda and dz of the last timed step to DIR/lambda.npy and DIR/dz.npy if --dump-outputs is given
+(the synthetic inputs are seeded: the same arguments give the same inputs), and prints the result line.  Everything else
+runs with --full only: the PCG launch timed on its own (`roofline`, `latency_floor`), the CPU baselines and the sweep of
+the other shapes, precisions and kernels.
 
 A step = one pass of the hot path over one synthetic KKT system already resident in HBM:
 CSR->dense scatter, Schur/preconditioner assembly, PCG with exit_tol = 0 (exactly max_iters = 100
@@ -70,7 +77,8 @@ def dtype_name(dt):
     return "f64" if np.dtype(dt) == np.float64 else "f32"
 
 
-def run_single(name, steps, warmup, torch, pcg_mode=None, pcg_reps=20, max_iters=None, variant=0, min_seconds=0.0, pcg_semi=None):
+def run_single(name, steps, warmup, torch, pcg_mode=None, pcg_reps=20, max_iters=None, variant=0, pcg_semi=None,
+               full=True, dump_dir=None):
     global MAX_ITERS, PCG_VARIANT, PCG_SEMI
     PCG_VARIANT = variant
     PCG_SEMI = pcg_semi
@@ -78,9 +86,25 @@ def run_single(name, steps, warmup, torch, pcg_mode=None, pcg_reps=20, max_iters
     if max_iters is not None:
         MAX_ITERS = max_iters
     try:
-        return _run_single(name, steps, warmup, torch, pcg_mode, pcg_reps, min_seconds)
+        return _run_single(name, steps, warmup, torch, pcg_mode, pcg_reps, full, dump_dir)
     finally:
         MAX_ITERS = saved
+
+
+DUMP_LIMIT = 64 << 20      # bytes of --dump-outputs in all
+
+
+def dump_outputs(out_dir, arrays):
+    """What the timed path returned in its last step -> out_dir/<name>.npy (float32 / float64 as computed).  An array
+    beyond its even share of DUMP_LIMIT is written as a fixed, seeded sample of its entries (same indices every run)."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_LIMIT // len(arrays)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a).ravel()
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def latency_floor(sol, bufs, lam, production_us):
@@ -117,7 +141,9 @@ def latency_floor(sol, bufs, lam, production_us):
     return out
 
 
-def _run_single(name, steps, warmup, torch, pcg_mode=None, pcg_reps=20, min_seconds=0.0):
+def _run_single(name, steps, warmup, torch, pcg_mode=None, pcg_reps=20, full=True, dump_dir=None):
+    """`steps` timed steps after `warmup` untimed ones.  full = False stops after the timed steps (and the dump of their
+    last outputs): no PCG-launch timing, no latency floor, the figures a plain run does not report."""
     from gato_python_amd import synth
     from gato_python_amd.solver import Solver
     S, C, K, dt, _ = WORKLOADS[name]
@@ -139,20 +165,28 @@ def _run_single(name, steps, warmup, torch, pcg_mode=None, pcg_reps=20, min_seco
         step()
     torch.cuda.synchronize()
     sol.check_status()
-    # exactly `steps` steps between synchronisations = one block; blocks are repeated until min_seconds of timed work
-    # have accumulated (the driver's --steps 20 is 5 ms of this workload: too thin a sample for one number)
-    dt_s, blocks = 0.0, 0
-    while True:
-        t0 = time.perf_counter()
-        for _ in range(steps):
-            step()
-        torch.cuda.synchronize()
-        dt_s += time.perf_counter() - t0
-        blocks += 1
-        if dt_s >= min_seconds or blocks >= 1000:
-            break
-    steps_timed = steps * blocks
+    # exactly `steps` timed steps between two synchronisations
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        step()
+    torch.cuda.synchronize()
+    dt_s = time.perf_counter() - t0
     sol.check_status()
+    if dump_dir:
+        dump_outputs(dump_dir, {"lambda": lam.cpu().numpy(), "dz": dz.cpu().numpy()})
+    mode = sol.get_option("last_mode")
+    mode_name = {1: "resident", 2: "streaming"}.get(mode) + {0: "", 1: " (semi)", 2: " (semi, no resident rows)",
+                                                             3: " (LDS-DMA ring)"}[sol.get_option("last_semi")] + \
+        {0: "", 1: " (one workgroup, 2 rows/lane)", 2: " (one workgroup, mixed 2/1 rows per lane)"}[sol.get_option("last_pair")]
+    groups, threads = sol.get_option("last_groups"), sol.get_option("last_threads")
+    res = dict(
+        workload=name, S=S, C=C, K=K, dtype=dtype_name(dt),
+        iters_per_s=MAX_ITERS * steps / dt_s, ms_per_step=1e3 * dt_s / steps, timed_steps=steps,
+        pcg_mode=mode_name, pcg_groups=groups, pcg_threads=threads,
+    )
+    if not full:
+        sol.close()
+        return res, sysm
 
     # dominant kernel: the PCG launch AS IT RUNS IN THE STEP (one-workgroup launches also carry the dz back-substitution
     # in their epilogue), HIP events recorded on its stream right around the launch (gato_pcg_last_ms)
@@ -166,23 +200,15 @@ def _run_single(name, steps, warmup, torch, pcg_mode=None, pcg_reps=20, min_seco
             ms.append(v)
     pcg_ms = float(np.mean(ms))
     bytes_launch = b_iter(S, K, np.dtype(dt).itemsize) * MAX_ITERS
-    mode = sol.get_option("last_mode")
-    mode_name = {1: "resident", 2: "streaming"}.get(mode) + {0: "", 1: " (semi)", 2: " (semi, no resident rows)",
-                                                             3: " (LDS-DMA ring)"}[sol.get_option("last_semi")] + \
-        {0: "", 1: " (one workgroup, 2 rows/lane)", 2: " (one workgroup, mixed 2/1 rows per lane)"}[sol.get_option("last_pair")]
-    groups, threads = sol.get_option("last_groups"), sol.get_option("last_threads")
     floor = None
     # the diagnostic builds (timing-only switches) exist for pcg_resident_kernel and the fp64 mixed-rows kernel (last_pair = 2)
     if mode == 1 and not PCG_VARIANT and sol.get_option("last_pair") in (0, 2) and not sol.get_option("last_semi"):
         floor = latency_floor(sol, bufs, lam, 1e3 * pcg_ms / MAX_ITERS)
     sol.set_option("time_pcg", 0)
-    res = dict(
-        workload=name, S=S, C=C, K=K, dtype=dtype_name(dt),
-        iters_per_s=MAX_ITERS * steps_timed / dt_s, ms_per_step=1e3 * dt_s / steps_timed, timed_steps=steps_timed,
+    res.update(
         latency_floor=floor,
         pcg_launch_ms=pcg_ms, pcg_launch_ms_min=float(np.min(ms)),
         pcg_iters_per_s=MAX_ITERS / (pcg_ms * 1e-3), pcg_us_per_iter=1e3 * pcg_ms / MAX_ITERS,
-        pcg_mode=mode_name, pcg_groups=groups, pcg_threads=threads,
         algorithmic_bytes_per_launch=bytes_launch,
         achieved_gbs=bytes_launch / (pcg_ms * 1e-3) / 1e9,
     )
@@ -417,7 +443,7 @@ def headline(res, name, steps, warmup, traffic, traffic_src, cpu=None, sweep_fil
     out = {
         "metric": "PCG iterations/s", "value": res["iters_per_s"], "unit": "iterations/s",
         "n_gpus": 1, "steps": steps, "warmup": warmup, "ms_per_step": res["ms_per_step"],
-        "timed_steps": res["timed_steps"],      # blocks of exactly `steps` steps, repeated until 1 s of timed work
+        "timed_steps": res["timed_steps"],      # = steps
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": res["dtype"], "data": "synthetic",
         "config": {"workload": name, "baseline_config": cfg, "STATE_SIZE": S, "CONTROL_SIZE": C, "KNOT_POINTS": K,
@@ -425,8 +451,9 @@ def headline(res, name, steps, warmup, traffic, traffic_src, cpu=None, sweep_fil
                    "step": "convert + Schur/stair assembly + PCG(100 iterations) + dz, inputs resident in HBM",
                    "pcg_kernel": res["pcg_mode"], "pcg_workgroups": res["pcg_groups"],
                    "pcg_threads": res["pcg_threads"]},
-        "roofline": roofline_object(res, traffic, traffic_src),
     }
+    if "pcg_launch_ms" in res:                  # --full: the PCG launch was timed on its own
+        out["roofline"] = roofline_object(res, traffic, traffic_src)
     if cpu is not None:
         out["cpu_baseline"] = {k: cpu[k] for k in ("value", "unit", "cores", "kind", "sample") if k in cpu}
         if "tried" in cpu:
@@ -528,11 +555,20 @@ def main():
     ap.add_argument("--no-sweep", action="store_true")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--pcg-mode", type=int, default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="also time the PCG launch on its own (roofline, latency floor), the CPU baselines and the sweep")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write lambda and dz of the last timed step as DIR/<name>.npy")
     ap.add_argument("--sweep-out", default=os.path.join("gpurun_out", "bench_sweep.json"),
                     help="file that receives the sweep entries and the method notes (the last stdout line stays compact)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
-    world = int(os.environ.get("WORLD_SIZE", "1"))
+    world =int(os.environ.get("WORLD_SIZE", "1"))
+    multi = args.gpus > 1 or world > 1 or (args.workload or "").startswith(("sharded", "batched", "replicas"))
+    if multi and args.dump_outputs:
+        raise SystemExit("bench.py: --dump-outputs is implemented for the single-GPU workloads only")
     if args.gpus > 1 and "RANK" not in os.environ:
         # started by hand without the launcher: start the N ranks as a child job (nothing has touched the GPU yet) and
         # pass its exit code on - never a silent one-rank run
@@ -547,7 +583,7 @@ def main():
     if world > 1 and args.gpus != world:
         raise SystemExit(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world}")
     import torch
-    if args.gpus > 1 or world > 1 or (args.workload or "").startswith(("sharded", "batched", "replicas")):
+    if multi:
         from gato_python_amd import dist_bench
         return dist_bench.main(args)
 
@@ -556,17 +592,17 @@ def main():
     torch.cuda.set_device(0)
     name = args.workload or "iiwa_14_7_k50_f64"
     S, C, K, dt, cfg = WORKLOADS[name]
-    res, sysm = run_single(name, args.steps, args.warmup, torch, args.pcg_mode, min_seconds=1.0)
-    traffic, traffic_src = committed_traffic(name, res)
+    res, sysm = run_single(name, args.steps, args.warmup, torch, args.pcg_mode, full=args.full, dump_dir=args.dump_outputs)
+    traffic, traffic_src = committed_traffic(name, res) if args.full else (None, None)
     cpu = None
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         cpu = cpu_baseline(sysm, dt)
         try:
             cpu["secondary"] = scipy_cg_baseline(sysm, dt)
         except Exception as ex:       # noqa: BLE001
             cpu["secondary"] = {"error": f"{type(ex).__name__}: {ex}"[:200]}
     sweep, sweep_err = [], None
-    do_sweep = not args.no_sweep and args.workload is None
+    do_sweep = args.full and not args.no_sweep and args.workload is None
 
     def emit(entry):
         sweep.append(entry)

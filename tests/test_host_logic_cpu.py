@@ -154,6 +154,26 @@ def test_bench_headline_is_compact_strict_json():
         bench.dumps_strict({"x": "y" * 5000}, bench.LINE_LIMIT)
 
 
+def test_bench_plain_line_and_output_dump(tmp_path, monkeypatch):
+    """A plain bench run (no --full) has no PCG-launch timing: its line carries the headline fields and no roofline.
+    --dump-outputs keeps dtype and values, and writes an array beyond its share of the size limit as a fixed sample."""
+    import bench
+    plain = {k: v for k, v in _canned_result().items()
+             if k in ("workload", "S", "C", "K", "dtype", "iters_per_s", "ms_per_step", "timed_steps", "pcg_mode", "pcg_groups", "pcg_threads")}
+    back = json.loads(bench.dumps_strict(bench.headline(plain, "iiwa_14_7_k50_f64", 20, 5, None, None), bench.LINE_LIMIT))
+    assert back["metric"] == "PCG iterations/s" and back["unit"] == "iterations/s" and back["higher_is_better"] is True
+    assert back["dtype"] == "f64" and back["ms_per_step"] == 0.22064 and back["steps"] == 20
+    assert "roofline" not in back and "cpu_baseline" not in back and "sweep" not in back
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 8192)
+    big, small = np.linspace(-1.0, 1.0, 5000), np.arange(7, dtype=np.float32)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"lambda": big, "dz": small})
+    a, b = np.load(tmp_path / "a" / "lambda.npy"), np.load(tmp_path / "b" / "lambda.npy")
+    assert a.dtype == np.float64 and a.nbytes <= 4096 and np.array_equal(a, b) and np.all(np.diff(a) > 0) and np.isin(a, big).all()
+    dz = np.load(tmp_path / "a" / "dz.npy")
+    assert dz.dtype == np.float32 and np.array_equal(dz, small)
+
+
 def test_bench_multi_gpu_line_is_led_by_the_sharded_system():
     """the last line of `bench.py --gpus N` leads with BASELINE configs[3] knot-sharded over the ranks
     ("scaling": "strong", the same system on one GPU beside it as `one_gpu_value` / `sharded_speedup`); the N replicas of the

@@ -7,7 +7,7 @@ set -o pipefail
 TAG=${1:-r01}
 PART=${2:-all}          # all | main (bench passes + issue counters) | cache (per-counter passes of the HBM-bound launches)
 R=$PWD
-ARGS=${BENCH_ARGS:---steps 50 --warmup 5 --no-cpu}
+ARGS=${BENCH_ARGS:---steps 50 --warmup 5 --full --no-cpu}   # --full: the sweep entries give summarize_profile.py the grids
 cd /tmp && export TMPDIR=/tmp
 if [ "$PART" != "cache" ]; then
 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_${TAG}_stats -- python3 $R/bench.py $ARGS > $R/gpurun_out/prof_${TAG}_bench.json 2> $R/gpurun_out/prof_${TAG}_stats.err || exit 1
