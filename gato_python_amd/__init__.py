@@ -2,10 +2,11 @@
 
 Public surface:
   gato_python_amd.linsys_solve(...)      drop-in for gpu_library.linsys_solve (gpu_library.cu:236-239)
+  gato_python_amd.linsys_resolve(...)    the last linsys_solve's system again, for a new g / c (no re-assembly)
   gato_python_amd.Solver                 device-resident stage-level API over include/gato_hip.h
   gato_python_amd.synth                  synthetic OCP inputs (the reference ships pendulum data only)
 """
-from .linsys import (clear_problem_size, last_stats, linsys_solve, set_precision,  # noqa: F401
+from .linsys import (clear_problem_size, last_stats, linsys_resolve, linsys_solve, set_precision,  # noqa: F401
                      set_problem_size)
 
 

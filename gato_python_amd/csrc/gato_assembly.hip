@@ -830,7 +830,8 @@ __global__ __launch_bounds__(WAVE) void dz_kernel(const T *__restrict__ Ginv, co
     constexpr int n = S + C, SS = S * S, CC = C * C, SC = S * C;
     int sysi, kidx;
     xcd_knot_map(sysi, kidx);
-    Ginv += sysi * bs.g; Cd += sysi * bs.c; g += sysi * bs.n; lambda += sysi * bs.sk;
+    const int msys = bs.rhs > 1 ? sysi / bs.rhs : sysi;                 // re-solves: rhs right-hand sides share one system's blocks
+    Ginv += msys * bs.g; Cd += msys * bs.c; g += sysi * bs.n; lambda += sysi * bs.sk;
     dz += sysi * bs.n;
     __shared__ T sQi[SS], sA[SS], sRi[CC > 0 ? CC : 1], sB[SC > 0 ? SC : 1], sl[2 * S], st[S + C], sg[S + C];
     const int lane = threadIdx.x;

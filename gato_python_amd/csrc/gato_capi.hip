@@ -49,6 +49,11 @@ static Ops make_ops(int dtype)
                       hipStream_t st) {
         return launch_compute_dz<T, S, C>(d, (const T *)Gi, (const T *)Cd, (const T *)g, (const T *)lam, (T *)dz, st);
     };
+    o.rhs_gamma = [](const Dims &d, int R, const void *Gi, const void *Cd, const void *Sb, const void *g, const void *c,
+                     void *gam, hipStream_t st) {
+        return launch_rhs_gamma<T, S, C>(d, R, (const T *)Gi, (const T *)Cd, (const T *)Sb, (const T *)g, (const T *)c,
+                                         (T *)gam, st);
+    };
     o.pcg_plan = [](PcgPlan *p) { return pcg_resident_plan<T, S>(p); };
     o.pcg_resident = [](const PcgLaunch &a, hipStream_t st) { return launch_pcg_resident<T, S>(a, st); };   // incl. the DPP-row layout
     o.pcg_dma_max_knots = []() { return pcg_dma_max_knots<T, S>(); };
@@ -165,6 +170,8 @@ struct gato_solver {
         void *lam, *dz;
         double exit_tol;
         int max_iters;
+        int rhs;                      // > 0: it was a re-solve (gato_solve_rhs) of this many right-hand sides per system
+        int *its;                     // its iteration counts [B][rhs]
     } lc;
     // multi-GPU cluster (gato_cluster_*): this rank's mirror, the peers' mirrors as mapped here
     struct {
@@ -189,6 +196,15 @@ struct gato_solver {
     int *dz_flag;                     // device word for the helper blocks of the one-workgroup fp64 launch
     int no_fuse_dz;                   // option
     unsigned long long **cl_tab;      // device copy of cl.peer (the kernel reads the peers' mirror addresses from it)
+    struct {                          // the most recent whole-solve assembly, for gato_solve_rhs
+        int valid;                    // S / Pinv / Ginv hold it (cleared by a stage entry that writes the workspace, a cluster set-up)
+        const void *Cd;               // the C blocks it read: the solver's C_dense, or the caller's d_C_blocks of _blocks
+        int img;                      // the fused launch also wrote the transposed images imgS / imgP
+        unsigned long long gen;       // assemblies so far
+    } as;
+    char *rhs_ws;                     // re-solve work area: gamma [B][rhs_R][S K] (buffer 11) | iters [B][rhs_R]
+    size_t rhs_ws_bytes;
+    int rhs_R;                        // right-hand sides per system it has room for
 };
 
 // ---- co-residency gate (A12: check_sms + cudaLaunchCooperativeKernel in the reference, gato_utils.cuh:829-854,
@@ -454,6 +470,7 @@ extern "C" int gato_solver_destroy(gato_solver *s)
     for (int i = 0; i < 4; ++i)
         if (s->ev_stage[i]) (void)hipEventDestroy(s->ev_stage[i]);
     if (s->arena) (void)hipFree(s->arena);
+    if (s->rhs_ws) (void)hipFree(s->rhs_ws);
     if (s->in_arena) (void)hipFree(s->in_arena);
     for (int i = 0; i < 2; ++i)
         if (s->host_ev[i]) (void)hipEventDestroy(s->host_ev[i]);
@@ -476,6 +493,7 @@ extern "C" void *gato_solver_buffer(gato_solver *s, int which)
         case 8: return s->iters;
         case 9: return (unsigned long long *)s->sw.scalars + 8;   // diagnostic stamps (option stamp_pcg)
         case 10: return s->eta_hist;                              // double[max_iters + 1] (option record_eta)
+        case 11: return s->rhs_ws;                                // gamma of the re-solves [B][rhs_R][S K] (nullptr: none reserved)
         default: return nullptr;
     }
 }
@@ -576,6 +594,8 @@ extern "C" int gato_solver_get_option(gato_solver *s, const char *name, int *val
     else if (!strcmp(name, "cluster_mem_kind")) *value = s->cl.on ? s->cl.mem_kind : -1;
     else if (!strcmp(name, "num_cus")) *value = s->num_cus;
     else if (!strcmp(name, "batch")) *value = s->d.B;
+    else if (!strcmp(name, "rhs_reserved")) *value = s->rhs_R;
+    else if (!strcmp(name, "assembly_valid")) *value = s->as.valid;
     else if (!strcmp(name, "max_semi_knots"))
         *value = s->plan.semi_threads > 0 ? (s->plan.semi_threads / s->d.S + s->plan.semi_rows * s->plan.semi_threads / s->d.S) * (s->num_cus < 256 ? s->num_cus : 256) : 0;
     else if (!strcmp(name, "max_resident_knots")) *value = s->plan.max_knots_per_wg * (s->num_cus < 256 ? s->num_cus : 256);
@@ -584,10 +604,23 @@ extern "C" int gato_solver_get_option(gato_solver *s, const char *name, int *val
 }
 
 // ---- stage-level entry points -------------------------------------------------------------------
+// A stage entry that writes into the solver's own workspace may overwrite the blocks of the latest assembly: the re-solve
+// (gato_solve_rhs) then has nothing it can trust any more.
+static bool owned(const gato_solver *s, const void *p)
+{
+    const char *q = (const char *)p;
+    return q && ((q >= s->arena && q < s->arena + s->arena_bytes) || (s->rhs_ws && q >= s->rhs_ws && q < s->rhs_ws + s->rhs_ws_bytes));
+}
+static void note_stage_outputs(gato_solver *s, const void *a, const void *b, const void *c = nullptr, const void *d = nullptr)
+{
+    if (owned(s, a) || owned(s, b) || owned(s, c) || owned(s, d)) s->as.valid = 0;
+}
+
 extern "C" int gato_convert(gato_solver *s, const int *d_G_row, const int *d_G_col, const void *d_G_val,
                             const int *d_C_row, const int *d_C_col, const void *d_C_val, double rho,
                             void *d_G_dense, void *d_C_dense, void *stream)
 {
+    note_stage_outputs(s, d_G_dense, d_C_dense);
     if (s->d.B > 1 && (s->d.nnzG <= 0 || s->d.nnzC <= 0)) {
         set_error("convert: a batched solver needs the per-system nnz (gato_linsys_device_batched, or options "
                   "batch_nnz_G / batch_nnz_C)");
@@ -601,12 +634,14 @@ extern "C" int gato_form_schur(gato_solver *s, const void *d_G_dense, const void
                                const void *d_c, void *d_S, void *d_Pinv, void *d_gamma, void *d_Ginv_dense,
                                void *stream)
 {
+    note_stage_outputs(s, d_S, d_Pinv, d_gamma, d_Ginv_dense);
     return s->ops->form_schur(s->d, d_G_dense, d_C_dense, d_g, d_c, d_S, d_Pinv, d_gamma, d_Ginv_dense, false,
                               (hipStream_t)stream);
 }
 
 extern "C" int gato_form_ss(gato_solver *s, const void *d_S, void *d_Pinv, void *stream)
 {
+    note_stage_outputs(s, d_Pinv, nullptr);
     return s->ops->form_ss(s->d, d_S, d_Pinv, (hipStream_t)stream);
 }
 
@@ -885,7 +920,7 @@ static bool stream_is_capturing(hipStream_t st)
 }
 
 static int pcg_one(gato_solver *s, const void *d_S, const void *d_Pinv, const void *d_gamma, void *d_lambda,
-                   double exit_tol, int max_iters, int *d_iters, int batch, hipStream_t st)
+                   double exit_tol, int max_iters, int *d_iters, int batch, hipStream_t st, int rhs = 1)
 {
     int groups = 0, threads = 0, kpw = 0;
     int mode = s->pcg_mode;
@@ -920,6 +955,7 @@ static int pcg_one(gato_solver *s, const void *d_S, const void *d_Pinv, const vo
         a.lambda0 = s->true_warm_start ? d_lambda : nullptr;      // in place: every lane reads its lambda0 first
         a.K = s->d.K; a.max_iters = max_iters; a.exit_tol = exit_tol;
         a.batch = batch;
+        a.rhs = rhs;
         a.pair = s->plan_pair;
         // (the single-reduction kernel and the LDS-DMA ring keep the plain launch: option coop_launch serves the resident / semi-resident launches)
         a.coop = s->coop_launch && groups > 1 && batch == 1 && !cg1 && s->plan_semi != 3;
@@ -1101,6 +1137,9 @@ extern "C" int gato_pcg_status(gato_solver *s, int *status)
 // hand-off - its workgroups were not co-resident, e.g. another process held the CUs - the PCG is re-run through the
 // streaming kernels (no inter-workgroup hand-off inside a launch, any residency) and dz is recomputed: a slower
 // correct answer instead of an error.  Synchronises `stream`.  *recovered = 1 when that happened.
+static int pcg_rhs(gato_solver *s, int R, const void *gam, void *lam, double exit_tol, int max_iters, int *its, hipStream_t st);
+static int dz_rhs(gato_solver *s, int R, const void *g, const void *lam, void *dz, hipStream_t st);
+
 extern "C" int gato_solver_recover(gato_solver *s, int *recovered, void *stream)
 {
     if (recovered) *recovered = 0;
@@ -1112,10 +1151,13 @@ extern "C" int gato_solver_recover(gato_solver *s, int *recovered, void *stream)
     const int saved = s->pcg_mode;
     s->d.k_lo = s->d.k_hi = 0;
     s->pcg_mode = GATO_PCG_STREAMING;
-    int rc2 = gato_pcg(s, s->lc.S, s->lc.P, s->lc.gamma, s->lc.lam, s->lc.exit_tol, s->lc.max_iters, s->iters, stream);
+    int rc2 = s->lc.rhs > 0 ? pcg_rhs(s, s->lc.rhs, s->lc.gamma, s->lc.lam, s->lc.exit_tol, s->lc.max_iters, s->lc.its, (hipStream_t)stream)
+                            : gato_pcg(s, s->lc.S, s->lc.P, s->lc.gamma, s->lc.lam, s->lc.exit_tol, s->lc.max_iters, s->iters, stream);
     s->pcg_mode = saved;
     if (rc2) return rc2;
-    if (s->lc.dz && (rc2 = gato_compute_dz(s, s->Ginv, s->lc.Cd, s->lc.g, s->lc.lam, s->lc.dz, stream))) return rc2;
+    if (s->lc.rhs > 0) rc2 = dz_rhs(s, s->lc.rhs, s->lc.g, s->lc.lam, s->lc.dz, (hipStream_t)stream);
+    else if (s->lc.dz) rc2 = gato_compute_dz(s, s->Ginv, s->lc.Cd, s->lc.g, s->lc.lam, s->lc.dz, stream);
+    if (rc2) return rc2;
     GATO_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
     s->last_fallback = 1;
     if (recovered) *recovered = 1;
@@ -1145,6 +1187,8 @@ static int assemble(gato_solver *s, int mode, const int *G_row, const int *G_col
     const bool fused = stair && (s->asm_mode == 2 || (s->asm_mode == 0 && knots <= 2ll * s->num_cus));
     s->last_asm_fused = fused;
     s->img_fresh = 0;
+    s->as.valid = 0;                        // until the whole solve around this assembly has been enqueued
+    s->as.img = 0;
     if (!fused) {
         if (mode == 0) {                 // CSR: the gather launch also inverts Q_k, R_k while they sit in LDS
             if (s->d.B > 1 && (s->d.nnzG <= 0 || s->d.nnzC <= 0)) return gato_convert(s, G_row, G_col, G_val, C_row, C_col, C_val, rho, s->G_dense, s->C_dense, st);
@@ -1174,6 +1218,7 @@ static int assemble(gato_solver *s, int mode, const int *G_row, const int *G_col
     if (s->imgS && !s->no_image && s->d.B == 1) {        // the workgroup-per-knot launch also writes the PCG images
         a.imgS = s->imgS; a.imgP = s->imgP; a.img_ld = s->img_ld;
         s->img_fresh = 1;
+        s->as.img = 1;
     }
     return s->ops->assemble(s->d, a, st);
 }
@@ -1199,6 +1244,7 @@ extern "C" int gato_linsys_device(gato_solver *s, const int *d_G_row, const int 
     if (ts) GATO_HIP_CHECK(hipEventRecord(s->ev_stage[2], (hipStream_t)stream));
     if (!s->dz_fused && (rc = gato_compute_dz(s, s->Ginv, s->C_dense, d_g, lam, dz, stream))) return rc;
     if (ts) GATO_HIP_CHECK(hipEventRecord(s->ev_stage[3], (hipStream_t)stream));
+    s->as = {1, s->C_dense, s->as.img, s->as.gen + 1};
     return GATO_OK;
 }
 
@@ -1222,6 +1268,7 @@ extern "C" int gato_linsys_device_blocks(gato_solver *s, const void *d_G_blocks,
     if (ts) GATO_HIP_CHECK(hipEventRecord(s->ev_stage[2], (hipStream_t)stream));
     if (!s->dz_fused && (rc = gato_compute_dz(s, s->Ginv, d_C_blocks, d_g, lam, dz, stream))) return rc;
     if (ts) GATO_HIP_CHECK(hipEventRecord(s->ev_stage[3], (hipStream_t)stream));
+    s->as = {1, d_C_blocks, s->as.img, s->as.gen + 1};
     return GATO_OK;
 }
 
@@ -1243,6 +1290,142 @@ extern "C" int gato_linsys_device_batched(gato_solver *s, const int *d_G_row, co
     if (rc) return rc;
     if (d_iters && d_iters != s->iters)
         GATO_HIP_CHECK(hipMemcpyAsync(d_iters, s->iters, sizeof(int) * s->d.B, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return GATO_OK;
+}
+
+// ---- re-solve: the latest whole-solve assembly for new right-hand sides ("factor once, solve many") ----------------------
+// Reads Ginv, S (its left blocks are -phi), Pinv, the images and the C blocks of that assembly; writes none of them.
+
+static int *rhs_iters(gato_solver *s)
+{
+    return (int *)(s->rhs_ws + align_up((size_t)s->d.B * s->rhs_R * s->d.sk() * s->esz));
+}
+
+extern "C" int gato_solver_reserve_rhs(gato_solver *s, int R)
+{
+    if (!s) { set_error("solver_reserve_rhs: null solver"); return GATO_EINVAL; }
+    if (R < 1 || (long long)R * s->d.B > 65535) {
+        set_error("solver_reserve_rhs: R = %d must be >= 1 and batch x R <= 65535 (batch %d)", R, s->d.B);
+        return GATO_EINVAL;
+    }
+    if (R <= s->rhs_R) return GATO_OK;
+    const size_t n = (size_t)s->d.B * R;
+    const size_t bytes = align_up(n * s->d.sk() * s->esz) + align_up(sizeof(int) * n);
+    GATO_HIP_CHECK(hipSetDevice(s->device));
+    char *p = nullptr;
+    GATO_HIP_CHECK(hipMalloc((void **)&p, bytes));
+    hipError_t e = hipMemset(p, 0, bytes);
+    if (e == hipSuccess) e = hipDeviceSynchronize();          // re-solves still queued may read the old area
+    if (e != hipSuccess) {
+        (void)hipFree(p);
+        set_error("solver_reserve_rhs: %s", hipGetErrorString(e));
+        return GATO_EHIP;
+    }
+    if (s->rhs_ws) (void)hipFree(s->rhs_ws);
+    if (s->lc.rhs > 0) s->lc.valid = 0;                        // its gamma lived in the old area
+    s->rhs_ws = p; s->rhs_ws_bytes = bytes; s->rhs_R = R;
+    return GATO_OK;
+}
+
+// The PCGs of a re-solve: n = B R right-hand sides, gamma / lambda / iters as [B][R] arrays, the R of system b on its S / Pinv.
+// ONE launch with a workgroup per right-hand side where a system fits one workgroup (planned as a batch of n systems is),
+// otherwise a launch per right-hand side on its system's matrices (as gato_pcg runs a batch system by system).
+static int pcg_rhs(gato_solver *s, int R, const void *gam, void *lam, double exit_tol, int max_iters, int *its, hipStream_t st)
+{
+    const int B = s->d.B, n = B * R;
+    if (n == 1) return pcg_one(s, s->Sbd, s->Pbd, gam, lam, exit_tol, max_iters, its, 1, st);
+    int groups = 0, threads = 0, kpw = 0, rc = GATO_OK;
+    s->d.B = n;
+    const bool one = s->pcg_mode != GATO_PCG_STREAMING && plan_resident(s, &groups, &threads, &kpw) != 0 && groups == 1;
+    if (one) rc = pcg_one(s, s->Sbd, s->Pbd, gam, lam, exit_tol, max_iters, its, n, st, R);
+    s->d.B = B;
+    if (one) return rc;
+    s->fz.dz = nullptr;                      // launch by launch: dz is a launch of its own
+    const size_t e = s->esz, bd = s->d.bd() * e, sk = s->d.sk() * e;
+    for (int b = 0; b < B; ++b)
+        for (int r = 0; r < R; ++r) {
+            const size_t i = (size_t)b * R + r;
+            if ((rc = pcg_one(s, (const char *)s->Sbd + b * bd, (const char *)s->Pbd + b * bd, (const char *)gam + i * sk,
+                              (char *)lam + i * sk, exit_tol, max_iters, its + i, 1, st)))
+                return rc;
+        }
+    return GATO_OK;
+}
+
+// dz of a re-solve: one dz_kernel launch over all B R right-hand sides, R consecutive ones on one system's Ginv / C blocks
+static int dz_rhs(gato_solver *s, int R, const void *g, const void *lam, void *dz, hipStream_t st)
+{
+    Dims d = s->d;
+    d.B = s->d.B * R; d.rhs = R; d.k_lo = d.k_hi = 0;
+    return s->ops->compute_dz(d, s->Ginv, s->as.Cd, g, lam, dz, st);
+}
+
+extern "C" int gato_solve_rhs(gato_solver *s, int R, const void *d_g, const void *d_c, double exit_tol, int max_iters,
+                              void *d_lambda, void *d_dz, int *d_iters, void *stream)
+{
+    if (!s) { set_error("solve_rhs: null solver"); return GATO_EINVAL; }
+    if (s->cl.on) { set_error("solve_rhs: the solver is a cluster rank; a sharded re-solve is not supported"); return GATO_EINVAL; }
+    if (!s->as.valid) {
+        set_error("solve_rhs: no assembly to re-solve: run a whole solve (gato_linsys_device, _blocks, _batched) first; a stage "
+                  "entry that wrote into the solver's workspace or a cluster set-up since then invalidates it");
+        return GATO_EINVAL;
+    }
+    if (R < 1 || (long long)R * s->d.B > 65535) {
+        set_error("solve_rhs: R = %d must be >= 1 and batch x R <= 65535 (batch %d)", R, s->d.B);
+        return GATO_EINVAL;
+    }
+    if (!d_g || !d_c || !d_lambda || !d_dz) { set_error("solve_rhs: d_g, d_c, d_lambda and d_dz are required"); return GATO_EINVAL; }
+    hipStream_t st = (hipStream_t)stream;
+    const bool capturing = stream_is_capturing(st);
+    if (R > s->rhs_R) {
+        if (capturing) {
+            set_error("solve_rhs: R = %d is beyond the %d reserved right-hand sides and the stream is being captured; call "
+                      "gato_solver_reserve_rhs before the capture", R, s->rhs_R);
+            return GATO_EINVAL;
+        }
+        const int rc = gato_solver_reserve_rhs(s, R);
+        if (rc) return rc;
+    }
+    {   // what pcg_one would refuse only after the gamma launch had been enqueued
+        const int B = s->d.B, n = B * R;
+        int g = 0, t = 0, k = 0;
+        s->d.B = n;
+        const bool one = n > 1 && s->pcg_mode != GATO_PCG_STREAMING && plan_resident(s, &g, &t, &k) != 0 && g == 1;
+        s->d.B = B;
+        if (!one && s->pcg_mode != GATO_PCG_STREAMING) {
+            const bool fits = plan_resident(s, &g, &t, &k) != 0;
+            int gc = 0;
+            const bool cg1 = s->pcg_variant == 1 && !s->true_warm_start && plan_cg1(s, &gc, &t, &k) != 0;
+            if (s->pcg_mode == GATO_PCG_RESIDENT && !fits && !cg1) {
+                set_error("solve_rhs: K=%d does not fit the resident kernel on %d CUs", s->d.K, s->num_cus);
+                return GATO_EINVAL;
+            }
+            if (capturing && ((fits && g > 1) || (cg1 && gc > 1))) {
+                set_error("solve_rhs: a persistent launch of %d workgroups cannot be captured into a graph (its hand-off epochs "
+                          "are launch arguments); capture the streaming kernels (option pcg_mode = 2) or a system that fits "
+                          "one workgroup", cg1 && gc > 1 ? gc : g);
+                return GATO_EINVAL;
+            }
+        }
+    }
+    int rc;
+    s->d.k_lo = s->d.k_hi = 0;
+    void *gam = s->rhs_ws;
+    int *its = d_iters ? d_iters : rhs_iters(s);
+    const bool ts = s->time_stages != 0;
+    if (ts) GATO_HIP_CHECK(hipEventRecord(s->ev_stage[0], st));
+    if ((rc = s->ops->rhs_gamma(s->d, R, s->Ginv, s->as.Cd, s->Sbd, d_g, d_c, gam, st))) return rc;
+    if (ts) GATO_HIP_CHECK(hipEventRecord(s->ev_stage[1], st));
+    s->lc = {1, s->Sbd, s->Pbd, gam, s->as.Cd, d_g, d_lambda, d_dz, exit_tol, max_iters, R, its};
+    s->fz = {s->Ginv, s->as.Cd, d_g, d_dz};
+    s->img_fresh = s->as.img;                // the assembly's transposed images still hold S and Pinv
+    rc = pcg_rhs(s, R, gam, d_lambda, exit_tol, max_iters, its, st);
+    s->fz = {nullptr, nullptr, nullptr, nullptr};
+    s->img_fresh = 0;
+    if (rc) return rc;
+    if (ts) GATO_HIP_CHECK(hipEventRecord(s->ev_stage[2], st));
+    if (!s->dz_fused && (rc = dz_rhs(s, R, d_g, d_lambda, d_dz, st))) return rc;
+    if (ts) GATO_HIP_CHECK(hipEventRecord(s->ev_stage[3], st));
     return GATO_OK;
 }
 
@@ -1424,6 +1607,86 @@ extern "C" int gato_linsys_solve_f64(const int *G_row, int len_G_row, const int 
     return linsys_solve_host<double>(GATO_F64, G_row, len_G_row, G_col, G_val, nnz_G, C_row, len_C_row, C_col, C_val,
                                      nnz_C, g, len_g, c, len_c, lambda_in, S, C, K, testiters, exit_tol, max_iters,
                                      warm_start, rho, lambda_out, dz_out, iters_out, ms_out);
+}
+
+// List-level re-solve: the system of the most recent gato_linsys_solve_* (the cached solver) for a new g / c.
+template <typename T>
+static int linsys_resolve_host(int dtype, const T *g, int len_g, const T *c, int len_c, T exit_tol, int max_iters,
+                               T *lambda_out, T *dz_out, int *iters_out)
+{
+    const char *name = dtype == GATO_F32 ? "f32" : "f64";
+    if (!g || !c || !lambda_out || !dz_out) { set_error("linsys_resolve_%s: null argument", name); return GATO_EINVAL; }
+    std::lock_guard<std::mutex> lock(g_cache_mu);
+    gato_solver *s = g_cached_solver;
+    if (!s) {
+        set_error("linsys_resolve_%s: no system to re-solve: call gato_linsys_solve_%s first (none since the library was loaded "
+                  "or since gato_release_cache)", name, name);
+        return GATO_EINVAL;
+    }
+    if (s->dtype != dtype) {
+        set_error("linsys_resolve_%s: the most recent linsys_solve ran in %s", name, s->dtype == GATO_F32 ? "f32" : "f64");
+        return GATO_EINVAL;
+    }
+    const int S = s->d.S, K = s->d.K;
+    const long long N = (long long)s->d.N();
+    if (len_g != N || len_c != S * K) {
+        set_error("linsys_resolve_%s: lengths do not match the last solve (S=%d C=%d K=%d): len(g)=%d (want %lld), len(c)=%d "
+                  "(want %d)", name, S, s->d.C, K, len_g, N, len_c, S * K);
+        return GATO_EINVAL;
+    }
+    if (!s->as.valid) { set_error("linsys_resolve_%s: the last solve did not complete", name); return GATO_EINVAL; }
+    (void)hipSetDevice(s->device);
+    // the staging areas of the solve (its inputs included g and c) are large enough for g | c here
+    const size_t oc = align_up(sizeof(T) * (size_t)N), off = oc + align_up(sizeof(T) * (size_t)S * K);
+    const size_t dz_off = (size_t)((const char *)s->dz - (const char *)s->lambda), out_span = dz_off + sizeof(T) * (size_t)N;
+    if (!s->in_arena || s->in_bytes < off || !s->pin || s->pin_bytes < off + 64 + out_span) {
+        set_error("linsys_resolve_%s: the cached solver has no staging area", name);
+        return GATO_EINVAL;
+    }
+    hipStream_t st = nullptr;
+    hipError_t e;
+    memcpy(s->pin, g, sizeof(T) * (size_t)N);
+    memcpy(s->pin + oc, c, sizeof(T) * (size_t)S * K);
+    char *a = s->in_arena, *pout = s->pin + off;
+    if ((e = hipMemcpyAsync(a, s->pin, off, hipMemcpyHostToDevice, st)) != hipSuccess) {
+        set_error("H2D copy failed: %s", hipGetErrorString(e));
+        return GATO_EHIP;
+    }
+    int rc = gato_solve_rhs(s, 1, a, a + oc, (double)exit_tol, max_iters, s->lambda, s->dz, s->iters, st);
+    if (rc) return rc;
+    if ((e = hipMemcpyAsync(pout + 64, s->lambda, out_span, hipMemcpyDeviceToHost, st)) != hipSuccess ||
+        (e = hipMemcpyAsync(pout, s->iters, sizeof(int), hipMemcpyDeviceToHost, st)) != hipSuccess ||
+        (e = hipStreamSynchronize(st)) != hipSuccess) {
+        set_error("re-solve failed: %s", hipGetErrorString(e));
+        return GATO_EHIP;
+    }
+    int iters = *(const int *)pout;
+    if (iters < 0) {                     // in-band time-out mark of a persistent launch: re-run through the streaming kernels
+        int recovered = 0;
+        if ((rc = gato_solver_recover(s, &recovered, st))) return rc;
+        if ((e = hipMemcpy(pout + 64, s->lambda, out_span, hipMemcpyDeviceToHost)) != hipSuccess ||
+            (e = hipMemcpy(pout, s->iters, sizeof(int), hipMemcpyDeviceToHost)) != hipSuccess) {
+            set_error("D2H copy failed: %s", hipGetErrorString(e));
+            return GATO_EHIP;
+        }
+        iters = *(const int *)pout;
+    }
+    if (iters_out) *iters_out = iters;
+    memcpy(lambda_out, pout + 64, sizeof(T) * (size_t)S * K);
+    memcpy(dz_out, pout + 64 + dz_off, sizeof(T) * (size_t)N);
+    return GATO_OK;
+}
+
+extern "C" int gato_linsys_resolve_f32(const float *g, int len_g, const float *c, int len_c, float exit_tol, int max_iters,
+                                       float *lambda_out, float *dz_out, int *iters_out)
+{
+    return linsys_resolve_host<float>(GATO_F32, g, len_g, c, len_c, exit_tol, max_iters, lambda_out, dz_out, iters_out);
+}
+
+extern "C" int gato_linsys_resolve_f64(const double *g, int len_g, const double *c, int len_c, double exit_tol, int max_iters,
+                                       double *lambda_out, double *dz_out, int *iters_out)
+{
+    return linsys_resolve_host<double>(GATO_F64, g, len_g, c, len_c, exit_tol, max_iters, lambda_out, dz_out, iters_out);
 }
 
 // ---- knot-sharded PCG (multi-GPU) ------------------------------------------------------------------
@@ -1629,6 +1892,7 @@ extern "C" int gato_cluster_create(gato_solver *s, int rank, int nranks, void *i
     GATO_HIP_CHECK(hipSetDevice(s->device));
     gato_cluster_destroy(s);
     memset(&s->cl, 0, sizeof(s->cl));
+    s->as.valid = 0;                  // the cluster entries assemble shards into the same workspace
     s->cl.rank = rank; s->cl.nranks = nranks; s->cl.k0 = k0; s->cl.k1 = k1;
     // two-level area (2 parities), then the flat area: a slot for each of up to 256 workgroups of the whole cluster
     s->cl.flat_off = align_up((size_t)2 * pcg_xslot_granules(s->d.S, (int)s->esz), 16);

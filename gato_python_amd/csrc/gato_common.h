@@ -129,6 +129,7 @@ struct Dims {
     // just the block rows its PCG shard reads (gato_python_amd/dist.py: assemble_shard)
     int k_lo = 0, k_hi = 0;
     int stair_follows = 0;      // internal (whole-solve stage path): the Schur launch need not zero the blocks the stair launch writes
+    int rhs = 0;                // > 1 (gato_solve_rhs): B counts right-hand sides, and rhs consecutive ones share one system's matrices
     __host__ __device__ int lo() const { return k_lo; }
     __host__ __device__ int hi() const { return k_hi > 0 ? k_hi : K; }
     __host__ __device__ int n() const { return S + C; }
@@ -143,10 +144,11 @@ struct BatchStride {
     size_t g, c, bd, sk, n, nnzG, nnzC;     // elements per system: G_dense, C_dense, S/Pinv, gamma/lambda, g/dz, CSR values
     int k_lo, k_hi;                         // knots the launch works on
     int stair_follows;
+    int rhs;                                // > 1: system sysi reads the matrices (G_dense, Ginv, C_dense, S, Pinv) of system sysi / rhs
 };
 inline BatchStride batch_stride(const Dims &d)
 {
-    return BatchStride{d.g_dense(), d.c_dense(), d.bd(), d.sk(), d.N(), (size_t)d.nnzG, (size_t)d.nnzC, d.lo(), d.hi(), 0};
+    return BatchStride{d.g_dense(), d.c_dense(), d.bd(), d.sk(), d.N(), (size_t)d.nnzG, (size_t)d.nnzC, d.lo(), d.hi(), 0, d.rhs};
 }
 
 // ---- persistent (resident) PCG launch description ------------------------------------------
@@ -213,6 +215,8 @@ struct PcgLaunch {
     unsigned long long *stamps;        // optional: diagnostic cycle stamps (16 words), selects the DIAG = 1 build
     int diag;                          // 2: the build with the timing-only switches (ablate) but no stamps
     int coop;                          // multi-workgroup persistent launches through hipLaunchCooperativeKernel (option coop_launch)
+    int rhs;                           // > 1 (batches, gato_solve_rhs): workgroup b reads S / Pinv / dz_Ginv / dz_Cd of system b / rhs
+                                       // and gamma / lambda / dz_g / dz / iters of b; 0 or 1: every workgroup its own system
 };
 
 // Cross-GPU mirror of a cluster launch, per epoch parity (granules): one 128-B line per rank for its total (written by
@@ -292,6 +296,11 @@ int launch_point_jacobi(const Dims &d, const T *Sbd, T *Pbd, hipStream_t st);
 template <typename T, int S, int C>
 int launch_compute_dz(const Dims &d, const T *Ginv, const T *Cd, const T *g, const T *lambda, T *dz,
                       hipStream_t st);
+// gamma = c - C G^-1 g for R new right-hand sides per system from the blocks of the latest assembly (gato_rhs.hip):
+// g [B][R][N], c [B][R][S K] -> gamma [B][R][S K]; Ginv, Cd, Sbd of B systems
+template <typename T, int S, int C>
+int launch_rhs_gamma(const Dims &d, int R, const T *Ginv, const T *Cd, const T *Sbd, const T *g, const T *c, T *gamma,
+                     hipStream_t st);
 template <typename T, int S>
 int pcg_resident_plan(PcgPlan *plan);
 template <typename T, int S>
@@ -367,6 +376,8 @@ struct Ops {
     int (*assemble)(const Dims &, const AsmArgs &, hipStream_t);
     int (*compute_dz)(const Dims &, const void *, const void *, const void *, const void *, void *,
                       hipStream_t);
+    int (*rhs_gamma)(const Dims &, int, const void *, const void *, const void *, const void *, const void *, void *,
+                     hipStream_t);
     int (*pcg_plan)(PcgPlan *);
     int (*pcg_resident)(const PcgLaunch &, hipStream_t);
     int (*pcg_dma_max_knots)();

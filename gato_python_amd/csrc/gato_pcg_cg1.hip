@@ -58,6 +58,7 @@ __global__ __launch_bounds__(MAXT) void pcg_cg1_kernel(PcgLaunch a)
     const int W = batched ? 1 : (X > 0 ? a.groups : (int)gridDim.x);
     if (X > 0 && wg >= W) return;
     const size_t sys = batched ? blockIdx.x : 0;
+    const size_t msys = a.rhs > 1 ? sys / (size_t)a.rhs : sys;      // whose S / Pinv / Ginv / C_dense: rhs consecutive workgroups share one system's
     const int K = a.K;
     const int k_begin = MR ? a.k_begin : 0, k_end = MR ? a.k_end : K;       // this launch's knot range (a rank's shard)
     const int R = MR ? a.nranks : 1;
@@ -74,8 +75,8 @@ __global__ __launch_bounds__(MAXT) void pcg_cg1_kernel(PcgLaunch a)
     const bool loc_left = MR ? wg > 0 : k0 > 0, loc_right = MR ? wg < W - 1 : k1 < K;
     const bool x_left = MR && wg == 0 && k0 > 0, x_right = MR && wg == W - 1 && k1 < K;
 
-    const T *__restrict__ dS = static_cast<const T *>(a.S_bd) + sys * 3 * S * S * K;
-    const T *__restrict__ dP = static_cast<const T *>(a.P_bd) + sys * 3 * S * S * K;
+    const T *__restrict__ dS = static_cast<const T *>(a.S_bd) + msys * 3 * S * S * K;
+    const T *__restrict__ dP = static_cast<const T *>(a.P_bd) + msys * 3 * S * S * K;
     const T *__restrict__ dG = static_cast<const T *>(a.gamma) + sys * S * K;
     T *__restrict__ dL = static_cast<T *>(a.lambda) + sys * S * K;
 

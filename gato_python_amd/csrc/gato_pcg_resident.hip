@@ -189,6 +189,7 @@ __global__ __launch_bounds__(MAXT) void pcg_resident_kernel(PcgLaunch a)
     const int W = (NL > 0 || batched) ? 1 : (X > 0 ? a.groups : (int)gridDim.x);
     if (X > 0 && wg >= W) return;
     const size_t sys = batched ? blockIdx.x : 0;
+    const size_t msys = a.rhs > 1 ? sys / (size_t)a.rhs : sys;      // whose S / Pinv / Ginv / C_dense: rhs consecutive workgroups share one system's
     const int K = a.K;
     // this launch's knot range: the whole system, or this rank's shard of it (MR)
     const int k_begin = MR ? a.k_begin : 0, k_end = MR ? a.k_end : K;
@@ -215,8 +216,8 @@ __global__ __launch_bounds__(MAXT) void pcg_resident_kernel(PcgLaunch a)
     const bool x_right = MR && wg == W - 1 && has_right;
     const bool multi = W > 1 || (MR && R > 1);               // ghost blocks exist and travel through the hand-off
 
-    const T *__restrict__ dS = static_cast<const T *>(a.S_bd) + sys * 3 * S * S * K;
-    const T *__restrict__ dP = static_cast<const T *>(a.P_bd) + sys * 3 * S * S * K;
+    const T *__restrict__ dS = static_cast<const T *>(a.S_bd) + msys * 3 * S * S * K;
+    const T *__restrict__ dP = static_cast<const T *>(a.P_bd) + msys * 3 * S * S * K;
     const T *__restrict__ dG = static_cast<const T *>(a.gamma) + sys * S * K;
     T *__restrict__ dL = static_cast<T *>(a.lambda) + sys * S * K;
 
@@ -1091,8 +1092,8 @@ __global__ __launch_bounds__(MAXT) void pcg_resident_kernel(PcgLaunch a)
         if (a.dz != nullptr && W == 1) {
             const int Cn = a.C, n = S + Cn;
             const size_t gs = (size_t)(S * S + Cn * Cn), cs = (size_t)(S * S + S * Cn), Nn = (size_t)n * K - Cn;
-            const T *__restrict__ Gi = static_cast<const T *>(a.dz_Ginv) + sys * (gs * K - (size_t)Cn * Cn);
-            const T *__restrict__ Cdn = static_cast<const T *>(a.dz_Cd) + sys * (cs * (K - 1));
+            const T *__restrict__ Gi = static_cast<const T *>(a.dz_Ginv) + msys * (gs * K - (size_t)Cn * Cn);
+            const T *__restrict__ Cdn = static_cast<const T *>(a.dz_Cd) + msys * (cs * (K - 1));
             const T *__restrict__ gv = static_cast<const T *>(a.dz_g) + sys * Nn;
             T *__restrict__ dzo = static_cast<T *>(a.dz) + sys * Nn;
             const bool last = k == K - 1;
@@ -1304,12 +1305,13 @@ __global__ __launch_bounds__(MAXT) void pcg_single_f32x2_kernel(PcgLaunch a)
         return;
     }
     const size_t sys = a.batch > 1 ? blockIdx.x : 0;
+    const size_t msys = a.rhs > 1 ? sys / (size_t)a.rhs : sys;      // whose S / Pinv / Ginv / C_dense: rhs consecutive workgroups share one system's
     const int j = tid / H, h = tid - j * H;        // knot, row pair (2h, 2h + 1): adjacent, so every matrix column is ONE 8-byte load
     const bool active = j < K;                     // (pairs (h, h + H) cost two scattered 4-byte loads per column: 10 us per launch)
     const int r0 = 2 * h, r1 = 2 * h + 1;
 
-    const float *__restrict__ dS = static_cast<const float *>(a.S_bd) + sys * 3 * S * S * K;
-    const float *__restrict__ dP = static_cast<const float *>(a.P_bd) + sys * 3 * S * S * K;
+    const float *__restrict__ dS = static_cast<const float *>(a.S_bd) + msys * 3 * S * S * K;
+    const float *__restrict__ dP = static_cast<const float *>(a.P_bd) + msys * 3 * S * S * K;
     const float *__restrict__ dG = static_cast<const float *>(a.gamma) + sys * S * K;
     float *__restrict__ dL = static_cast<float *>(a.lambda) + sys * S * K;
 
@@ -1475,8 +1477,8 @@ __global__ __launch_bounds__(MAXT) void pcg_single_f32x2_kernel(PcgLaunch a)
     if (a.dz != nullptr && !a.dz_helpers) {
         const int Cn = a.C, n = S + Cn, k = j;
         const size_t gs = (size_t)(S * S + Cn * Cn), cs = (size_t)(S * S + S * Cn), Nn = (size_t)n * K - Cn;
-        const float *__restrict__ Gi = static_cast<const float *>(a.dz_Ginv) + sys * (gs * K - (size_t)Cn * Cn);
-        const float *__restrict__ Cdn = static_cast<const float *>(a.dz_Cd) + sys * (cs * (K - 1));
+        const float *__restrict__ Gi = static_cast<const float *>(a.dz_Ginv) + msys * (gs * K - (size_t)Cn * Cn);
+        const float *__restrict__ Cdn = static_cast<const float *>(a.dz_Cd) + msys * (cs * (K - 1));
         const float *__restrict__ gv = static_cast<const float *>(a.dz_g) + sys * Nn;
         float *__restrict__ dzo = static_cast<float *>(a.dz) + sys * Nn;
         const bool last = k == K - 1;
@@ -1664,6 +1666,7 @@ __global__ __launch_bounds__(64 * WT) void pcg_single_f64m_kernel(PcgLaunch a)
         return;
     }
     const size_t sys = a.batch > 1 ? blockIdx.x : 0;
+    const size_t msys = a.rhs > 1 ? sys / (size_t)a.rhs : sys;      // whose S / Pinv / Ginv / C_dense: rhs consecutive workgroups share one system's
     // lane -> row(s): the first K - KD knots (at most K2MAX) in the two-row lanes (rows 2 tid, 2 tid + 1), the last KD knots one
     // per 16-lane row of the other waves.
     int row0, j, r0, tp = tid;                                                      // first row, its knot, its row in the knot; lane slot in ptail
@@ -1682,8 +1685,8 @@ __global__ __launch_bounds__(64 * WT) void pcg_single_f64m_kernel(PcgLaunch a)
     }
     constexpr int abl = ABL;
 
-    const T *__restrict__ dS = static_cast<const T *>(a.S_bd) + sys * 3 * S * S * K;
-    const T *__restrict__ dP = static_cast<const T *>(a.P_bd) + sys * 3 * S * S * K;
+    const T *__restrict__ dS = static_cast<const T *>(a.S_bd) + msys * 3 * S * S * K;
+    const T *__restrict__ dP = static_cast<const T *>(a.P_bd) + msys * 3 * S * S * K;
     const T *__restrict__ dG = static_cast<const T *>(a.gamma) + sys * S * K;
     T *__restrict__ dL = static_cast<T *>(a.lambda) + sys * S * K;
 
@@ -1951,8 +1954,8 @@ __global__ __launch_bounds__(64 * WT) void pcg_single_f64m_kernel(PcgLaunch a)
     if (a.dz != nullptr && !a.dz_helpers) {
         const int Cn = a.C, n = S + Cn, k = j, nrow = two ? 2 : 1;
         const size_t gs = (size_t)(S * S + Cn * Cn), cs = (size_t)(S * S + S * Cn), Nn = (size_t)n * K - Cn;
-        const T *__restrict__ Gi = static_cast<const T *>(a.dz_Ginv) + sys * (gs * K - (size_t)Cn * Cn);
-        const T *__restrict__ Cdn = static_cast<const T *>(a.dz_Cd) + sys * (cs * (K - 1));
+        const T *__restrict__ Gi = static_cast<const T *>(a.dz_Ginv) + msys * (gs * K - (size_t)Cn * Cn);
+        const T *__restrict__ Cdn = static_cast<const T *>(a.dz_Cd) + msys * (cs * (K - 1));
         const T *__restrict__ gv = static_cast<const T *>(a.dz_g) + sys * Nn;
         T *__restrict__ dzo = static_cast<T *>(a.dz) + sys * Nn;
         const bool last = k == K - 1;

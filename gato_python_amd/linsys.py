@@ -122,10 +122,38 @@ def linsys_solve(G_row, G_col, G_val, C_row, C_col, C_val, g_val, c_val, input_l
         raise ValueError(_lib.lib().gato_last_error().decode())
     _lib.check(rc)
     _state["stats"] = dict(iters=iters.value, ms=ms.tolist(), S=S, C=C, K=K, precision=_state["precision"])
+    _state["solved"] = _state["precision"]
     if os.environ.get("GATO_VERBOSE", "1") != "0":
         print("first run PCG terminated in %d iterations, time:  %f" % (iters.value, ms[0]))   # gpu_library.cu:190
         print("avg time: %f" % (float(ms.sum()) / testiters))                                   # gpu_library.cu:198
     if _fs is not None:                 # Python floats widened from float32 like the reference's (gpu_library.cu:221-229)
+        k = "d" if f64 else "f"
+        return _fs.unpack(lam, k), _fs.unpack(dz, k)
+    return lam.astype(np.float64).tolist(), dz.astype(np.float64).tolist()
+
+
+def linsys_resolve(g_val, c_val, exit_tol, max_iters):
+    """Re-solve the system of the most recent linsys_solve (same G and C, kept assembled on the GPU) for a new g and c, in
+    that solve's precision: (lambda list, dz list); last_stats()["iters"] gives the iteration count.  Raises ValueError
+    without such a solve or when the lengths differ from it."""
+    f64 = _state.get("solved", _state["precision"]) == "f64"
+    dt = np.float64 if f64 else np.float32
+    fl = lambda a: (_from_list(a, "d" if f64 else "f", dt) if isinstance(a, (list, tuple))
+                    else np.ascontiguousarray(np.asarray(a, np.float64), dt))
+    g, c = fl(g_val), fl(c_val)
+    st = _state["stats"]
+    n_lam = st["S"] * st["K"] if st else len(c)
+    n_dz = (st["S"] + st["C"]) * st["K"] - st["C"] if st else len(g)
+    lam, dz = np.empty(max(n_lam, 1), dt), np.empty(max(n_dz, 1), dt)
+    iters = ct.c_int(-1)
+    p = lambda a: a.__array_interface__["data"][0]
+    fn = _lib.lib().gato_linsys_resolve_f64 if f64 else _lib.lib().gato_linsys_resolve_f32
+    rc = fn(p(g), len(g), p(c), len(c), float(exit_tol), int(max_iters), p(lam), p(dz), ct.byref(iters))
+    if rc == -1 or rc == -2:
+        raise ValueError(_lib.lib().gato_last_error().decode())
+    _lib.check(rc)
+    _state["stats"] = dict(st, iters=iters.value, ms=[])
+    if _fs is not None:
         k = "d" if f64 else "f"
         return _fs.unpack(lam, k), _fs.unpack(dz, k)
     return lam.astype(np.float64).tolist(), dz.astype(np.float64).tolist()

@@ -141,6 +141,39 @@ class Solver:
             _ptr(g), _ptr(c), float(exit_tol), int(max_iters), float(rho), _ptr(lam), _ptr(dz), _ptr(iters),
             self._stream()))
 
+    # ---- re-solve of the latest assembly for new right-hand sides (gato_solve_rhs) ------------------------------------
+    def reserve_rhs(self, R: int):
+        """Room for up to R right-hand sides per system in the re-solve work area (blocking; only grows)."""
+        _lib.check(_lib.lib().gato_solver_reserve_rhs(self._h, int(R)))
+
+    def solve_rhs(self, g, c, exit_tol, max_iters, lam=None, dz=None, iters=None):
+        """Re-solve the matrices of the most recent linsys / linsys_blocks / linsys_batched call for new right-hand sides:
+        g [B][R][N], c [B][R][S K] (flat device tensors; R = g.numel() / (B N)) -> (lam [B R S K], dz [B R N], iters [B R])."""
+        B, N, sk = self.batch, self.N, self.sizes["sk"]
+        R = g.numel() // (B * N) if g.numel() % (B * N) == 0 else 0
+        if R < 1 or c.numel() != B * R * sk:
+            raise ValueError(f"solve_rhs: g has {g.numel()} entries and c {c.numel()}: want B*R*N and B*R*S*K with B = {B}, "
+                             f"N = {N}, S*K = {sk}, R >= 1")
+        lam = self.new(B * R * sk) if lam is None else lam
+        dz = self.new(B * R * N) if dz is None else dz
+        iters = self.new(B * R, torch.int32) if iters is None else iters
+        if lam.numel() != B * R * sk or dz.numel() != B * R * N or iters.numel() != B * R:
+            raise ValueError("solve_rhs: lam / dz / iters do not hold B*R*S*K / B*R*N / B*R entries")
+        _lib.check(_lib.lib().gato_solve_rhs(self._h, R, _ptr(g), _ptr(c), float(exit_tol), int(max_iters), _ptr(lam),
+                                             _ptr(dz), _ptr(iters), self._stream()))
+        return lam, dz, iters
+
+    def read_rhs_gamma(self, R: int):
+        """Host copy of the re-solve's gamma [B][R][S K] (buffer 11) after a re-solve of R right-hand sides."""
+        n = self.batch * int(R) * self.sizes["sk"]
+        out = np.empty(n, self.np_dtype)
+        torch.cuda.synchronize(self.device)
+        rc = ct.CDLL("libamdhip64.so").hipMemcpy(out.ctypes.data_as(ct.c_void_p), ct.c_void_p(self.buffer_ptr(11)),
+                                                 ct.c_size_t(out.nbytes), 2)
+        if rc != 0:
+            raise RuntimeError(f"hipMemcpy failed: {rc}")
+        return out
+
     def upload_batch(self, systems):
         """list of KKTSystem with identical sparsity -> device tensors in linsys_batched() argument order."""
         s0 = systems[0]

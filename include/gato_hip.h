@@ -79,7 +79,9 @@ int gato_solver_destroy(gato_solver *s);
 /* Workspace device pointers (valid for the solver's lifetime), for stage-level tests:
  * which: 0 G_dense, 1 C_dense, 2 Ginv_dense, 3 S, 4 Pinv, 5 gamma, 6 lambda, 7 dz, 8 iters(int),
  * 10 eta history (double[max_iters+1]: eta = r.Pinv r after the initial step and after every iteration; filled when
- * option record_eta = 1 and max_iters <= 4096 - the reference only prints it under DEBUG_MODE, gato_pcg.cuh:397-400) */
+ * option record_eta = 1 and max_iters <= 4096 - the reference only prints it under DEBUG_MODE, gato_pcg.cuh:397-400),
+ * 11 gamma of the re-solves (gato_solve_rhs: its first B*R*S*K entries are [B][R][S*K] of the latest re-solve of R
+ * right-hand sides; NULL before gato_solver_reserve_rhs or the first re-solve) */
 void *gato_solver_buffer(gato_solver *s, int which);
 /* Options: pcg_mode (GATO_PCG_*), pcg_threads (0 = auto; threads per workgroup of the resident
  * kernel), pcg_groups (0 = auto; workgroups of the resident kernel), true_warm_start (0 = the
@@ -271,6 +273,34 @@ int gato_cluster_destroy(gato_solver *s);
  * gato_cluster_pcg / gato_cluster_linsys refuse a launch that does not fit (GATO_EINVAL). */
 int gato_cluster_launches_left(gato_solver *s, int max_iters, long long *left);
 int gato_cluster_rewind(gato_solver *s);
+
+/* ---- re-solve for new right-hand sides (new; the reference rebuilds the system on every call): the matrices of the most
+ * recent whole solve stay in the workspace - Ginv, S, Pinv, the transposed images - and a re-solve takes R new (g, c) per
+ * system against them: gamma = c - C G^-1 g (one launch), the PCG, dz.  No gather, inversion, Schur, stair or point-Jacobi
+ * kernel runs, and no matrix buffer of the solver is written.
+ * What counts as an assembly: a successful gato_linsys_device / _blocks / _batched (and gato_linsys_solve_* through it).
+ * After _blocks the re-solve reads the caller's d_C_blocks again: keep them unchanged until the next whole solve.
+ * What invalidates it: gato_convert / gato_form_schur / gato_form_ss given any of the solver's own buffers
+ * (gato_solver_buffer) as an output, and gato_cluster_create.  The preconditioner is the one the assembly built. */
+/* Reserve the re-solve work area (gamma, iters) for up to R right-hand sides per system.  Blocking (waits for the device
+ * when it grows); only grows. */
+int gato_solver_reserve_rhs(gato_solver *s, int R);
+/* Re-solve the most recent whole-solve assembly of `s` for R new right-hand sides per system.
+ * Layouts (B = batch): d_g [B][R][N], d_c [B][R][S*K] -> d_lambda [B][R][S*K], d_dz [B][R][N], d_iters [B][R] (NULL: the
+ * work area's).  Option true_warm_start = 1: d_lambda is also the initial guess.  Asynchronous on `stream`, enqueue only;
+ * beyond the reserved R it first grows the work area (blocking) - under stream capture that is refused, as is a persistent
+ * launch of several workgroups (see gato_pcg).  Returns GATO_EINVAL, enqueueing nothing, without a valid assembly, for
+ * R < 1, B*R > 65535 and on a cluster rank.  Options time_stages (ms[0] = gamma, ms[1] = PCG, ms[2] = dz), last_image,
+ * last_dz_fused report the re-solve; gato_solver_recover re-runs its PCGs through the streaming kernels. */
+int gato_solve_rhs(gato_solver *s, int R, const void *d_g, const void *d_c, double exit_tol, int max_iters,
+                   void *d_lambda, void *d_dz, int *d_iters, void *stream);
+/* List-level face: re-solve the system of the most recent gato_linsys_solve_f32 / _f64 (the cached solver, same precision)
+ * for a new g (len N) and c (len S*K); blocking, host pointers.  GATO_EINVAL if there is no such system (none yet, released,
+ * the other precision) or the lengths differ. */
+int gato_linsys_resolve_f32(const float *g, int len_g, const float *c, int len_c, float exit_tol, int max_iters,
+                            float *lambda_out, float *dz_out, int *iters_out);
+int gato_linsys_resolve_f64(const double *g, int len_g, const double *c, int len_c, double exit_tol, int max_iters,
+                            double *lambda_out, double *dz_out, int *iters_out);
 
 /* ---- direct block input (new): the caller already holds the per-knot blocks in the
  * reference's dense layouts - d_G_blocks as G_dense WITHOUT rho, d_C_blocks as C_dense - so the CSR scatter is
