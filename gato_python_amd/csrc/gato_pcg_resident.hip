@@ -917,9 +917,13 @@ __global__ __launch_bounds__(MAXT) void pcg_resident_kernel(PcgLaunch a)
     };
     // ---- optional true warm start (the reference accepts input_lambda but restarts from
     // zero, gato_pcg.cuh:303):  lambda = lambda0,  r = gamma - S lambda0.  The ghost blocks of r then come from the
-    // neighbours through the ordinary hand-off.
+    // neighbours through the ordinary hand-off.  A cluster rank of several reads lambda0 on its OWN rows only (k_begin..k_end-1
+    // of its array: in one process per GPU the other rows of that array are whatever the rank's earlier solves left there):
+    // the ghost blocks of lambda0 cross the ranks in one hand-off of their own before r0 is formed.  That is one epoch more
+    // per warm launch, inside the 2 max_iters + 8 a cluster launch reserves (it uses at most 2 max_iters + 3).
     if (a.lambda0) {
         const T *__restrict__ dL0 = static_cast<const T *>(a.lambda0) + sys * S * K;
+        const bool lam0_xchg = MR && R > 1;
         lam = active ? dL0[(size_t)k * S + r_] : (T)0;
         if (active) xs[0][(j + 1) * SP + r_] = lam;
 #pragma unroll 1
@@ -931,7 +935,21 @@ __global__ __launch_bounds__(MAXT) void pcg_resident_kernel(PcgLaunch a)
                 xs[0][(xk + q / S + 1) * SP + q % S] = l0;
             }
         }
-        if (tid < S) {
+        if (lam0_xchg) {
+            if constexpr (NR) {             // the hand-off publishes from the product array: lambda0's boundary blocks go there
+                __syncthreads();
+                if (tid < S) xst[1][tid] = xst[0][tid];
+                else if (tid < 2 * S) xst[1][(nk - 1) * S + (tid - S)] = xst[0][(nk - 1) * S + (tid - S)];
+            }
+            T dummy;
+            exchange_rt(lam, (T)0, dummy);
+            if constexpr (RG) {
+                if (g_lane) xs[0][gslot] = hv_reg;
+            } else {
+                if (tid < S) xs[0][tid] = gh[0][tid];
+                else if (tid < 2 * S) xs[0][(nk + 1) * SP + (tid - S)] = gh[1][tid - S];
+            }
+        } else if (tid < S) {
             if (has_left) xs[0][tid] = dL0[(size_t)(k0 - 1) * S + tid];
         } else if (tid < 2 * S) {
             if (has_right) xs[0][(nk + 1) * SP + (tid - S)] = dL0[(size_t)(k0 + nk) * S + (tid - S)];

@@ -325,7 +325,9 @@ class ClusterPCG:
         self.rewinds += 1
 
     def pcg(self, Sb, Pb, gamma, exit_tol, max_iters, lam, iters, stream=None):
-        """Enqueue this rank's launch.  lam: full-length S*K buffer, this rank's slice is written."""
+        """Enqueue this rank's launch.  lam: full-length S*K buffer, this rank's slice is written.  With the solver option
+        true_warm_start = 1 lam is also the initial guess, read on this rank's rows k0..k1-1 only (the neighbours' boundary
+        blocks of it cross the ranks inside the launch): the other rows may hold anything."""
         self._renew_epochs_if_used_up(max_iters)
         st = self.sol._stream() if stream is None else ct.c_void_p(stream)
         p = lambda t: ct.c_void_p(t.data_ptr())
@@ -335,7 +337,8 @@ class ClusterPCG:
     def linsys(self, d, exit_tol, max_iters, rho, lam, dz, iters, stream=None):
         """Enqueue this rank's part of a WHOLE solve (gato_cluster_linsys): the stage kernels on the knots its shard reads, its
         persistent launch, dz on its range - one call, nothing on the host or in a collective in between.  d: the device inputs
-        of Solver.upload_system (replicated on every rank); lam / dz: full-length buffers, this rank's rows are written."""
+        of Solver.upload_system (replicated on every rank); lam / dz: full-length buffers, this rank's rows are written.  With
+        true_warm_start = 1 lam is also the initial guess, read on this rank's rows k0..k1-1 only, as in pcg()."""
         self._renew_epochs_if_used_up(max_iters)
         st = self.sol._stream() if stream is None else ct.c_void_p(stream)
         p = lambda t: ct.c_void_p(t.data_ptr())
@@ -557,6 +560,7 @@ def linsys_solve_cluster(sysm, exit_tol, max_iters, dtype=np.float32, device=Non
                      iters=torch.zeros(1, dtype=torch.int32, device=tdev))
 
         def probe(cl):
+            state["lam"].zero_()                 # a warm-started probe (true_warm_start) starts from zero, as a cold one does
             cl.linsys(state["d"], exit_tol, max_iters, sysm.rho, state["lam"], state["dz"], state["iters"])
             return state["iters"]
         try:
@@ -564,6 +568,7 @@ def linsys_solve_cluster(sysm, exit_tol, max_iters, dtype=np.float32, device=Non
         except ClusterUnavailable:
             sol.close()
             raise
+        state["lam"].zero_()                     # the probe's lambda is not the caller's: a fresh state's first solve starts from 0
         state["plan"] = _GatherPlan(sol, nranks, rank, tdev)
     sol, d, cl = state["sol"], state["d"], state["cl"]
     if (sysm.S, sysm.C, sysm.K) != (sol.S, sol.C, sol.K) or np.dtype(dtype) != sol.np_dtype:

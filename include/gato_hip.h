@@ -249,10 +249,13 @@ int gato_shard_pcg_done(gato_solver *s, int *done, void *stream);
  *                         iteration instead of the reference's two reductions (gato_pcg.cuh:353-394); the ranks then also
  *                         read Pinv on the knots k0-1, k1 and gamma on k0-2..k1+1.  On return lambda also holds the right
  *                         neighbour's first block at row k1 (it arrives inside the launch): what dz of knot k1-1 needs
- *                         (gato_schur.cuh:833-838)
+ *                         (gato_schur.cuh:833-838).  Option true_warm_start = 1: lambda0 is read from the rank's OWN rows of
+ *                         d_lambda only (k0..k1-1); the neighbouring ranks' boundary blocks of lambda0 cross inside the launch
+ *                         (one hand-off more), so the other rows may hold anything, NaN included
  *   gato_cluster_linsys   this rank's part of a WHOLE solve (gato_linsys, gpu_library.cu:25-83): stage kernels on the knots
  *                         its shard reads, gato_cluster_pcg, dz on its range - nothing crosses the host or a collective in
- *                         between; inputs replicated, d_lambda / d_dz full-length arrays of which the rank's rows are written */
+ *                         between; inputs replicated, d_lambda / d_dz full-length arrays of which the rank's rows are written;
+ *                         with true_warm_start lambda0 is read from rows k0..k1-1 of d_lambda only, as in gato_cluster_pcg */
 int gato_cluster_knot_range(int K, int rank, int nranks, int *k0, int *k1);
 int gato_cluster_create(gato_solver *s, int rank, int nranks, void *ipc_handle_out);
 void *gato_cluster_local_mirror(gato_solver *s);

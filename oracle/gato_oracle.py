@@ -322,9 +322,10 @@ def compute_dz(Ginv_dense, C_dense, g, lam, S, C, K):
 # L3/L4: whole solve                              (gpu_library.cu:25-83)
 # --------------------------------------------------------------------------------------------
 def linsys_solve(G_row, G_col, G_val, C_row, C_col, C_val, g, c, S, C, K,
-                 exit_tol, max_iters, rho, dtype=np.float32, return_all=False, precon_mode=0):
+                 exit_tol, max_iters, rho, dtype=np.float32, return_all=False, precon_mode=0, lam0=None):
     """precon_mode: 0 = symmetric stair (BLOCK_J_PRECON = SS_PRECON = 1, the reference's setting, gato_defines.h:9-10),
-    1 = block-Jacobi (SS_PRECON = 0: gato_form_ss is not launched, gato_schur.cuh:965-970), 2 = point-Jacobi (both 0)."""
+    1 = block-Jacobi (SS_PRECON = 0: gato_form_ss is not launched, gato_schur.cuh:965-970), 2 = point-Jacobi (both 0).
+    lam0: initial guess of a true warm start (pcg(lam0=...), an extension - D5); dz is computed from the final lambda."""
     dtype = np.dtype(dtype).type
     Gd, Cd = convert(G_row, G_col, G_val, C_row, C_col, C_val, S, C, K, rho, dtype)
     g = np.asarray(g, dtype)
@@ -334,7 +335,7 @@ def linsys_solve(G_row, G_col, G_val, C_row, C_col, C_val, g, c, S, C, K,
         P_bd = form_ss(S_bd, P_bd, S, K)
     elif precon_mode == 2:
         P_bd = point_jacobi(S_bd, S, K)
-    lam, iters, hist = pcg(S_bd, P_bd, gamma, S, K, exit_tol, max_iters, return_history=True)
+    lam, iters, hist = pcg(S_bd, P_bd, gamma, S, K, exit_tol, max_iters, return_history=True, lam0=lam0)
     dz = compute_dz(Ginv, Cd, g, lam, S, C, K)
     if return_all:
         return dict(G_dense=Gd, C_dense=Cd, S=S_bd, Pinv=P_bd, gamma=gamma, Ginv=Ginv,

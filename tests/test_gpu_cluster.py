@@ -27,6 +27,11 @@ def f32_judged(what, gpu, oracle32, truth64):
     check_f32(what, gpu, oracle32, truth64)
 
 
+def rel(a, b):
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    return np.abs(a - b).max() / max(np.abs(b).max(), 1e-300)
+
+
 def converged_f64(Sb, Pb, gam, S, K):
     return co.pcg(Sb.astype(np.float64), Pb.astype(np.float64), gam.astype(np.float64), S, K, 1e-14, 600)[0]
 
@@ -530,3 +535,184 @@ def test_sharded_whole_solve_with_one_knot_per_rank(S, C, R):
             for x in sols:
                 x.check_status()
                 x.close()
+
+
+# ---- true warm start with per-rank buffers (one process per GPU: a rank's lambda array holds its own rows only) -------------
+def _rank_buffers(lam_full, cl, S, dtype):
+    """One full-length buffer per rank: lam_full on the rank's rows k0..k1-1, NaN on every other row."""
+    out = []
+    for c in cl:
+        b = torch.full((lam_full.size,), float("nan"), dtype=dtype, device="cuda")
+        b[c.k0 * S:c.k1 * S] = torch.from_numpy(np.ascontiguousarray(lam_full[c.k0 * S:c.k1 * S])).to("cuda")
+        out.append(b)
+    return out
+
+
+def _gathered(bufs, cl, S):
+    return np.concatenate([bufs[r][c.k0 * S:c.k1 * S].cpu().numpy() for r, c in enumerate(cl)])
+
+
+def _cluster_solvers(S, C, K, R, dt, flat, **opts):
+    from gato_python_amd.dist import ClusterPCG
+    from gato_python_amd.solver import Solver
+    sols = [Solver(S, C, K, dt) for _ in range(R)]
+    for x in sols:
+        x.set_option("cluster_flat", flat)
+        if R > 4:
+            x.set_option("max_workgroups", 256 // R)      # the ranks share ONE GPU here
+        for k, v in opts.items():
+            x.set_option(k, v)
+    cl = [ClusterPCG(x, r, R, inprocess_peers=True) for r, x in enumerate(sols)]
+    ClusterPCG.connect_inprocess(cl)
+    return sols, cl
+
+
+def _close(cl, sols):
+    for c in cl:
+        c.close()
+    for x in sols:
+        x.close()
+
+
+# (K = R in fp64 only: an fp32 system of 3 knots exits right at CG's finite-termination cliff, where one iteration moves the iterate
+#  by 3 % and fp32 iterates of two summation orders differ by 1 %)
+WARM_CASES = [(53, 2, np.float64), (53, 3, np.float32), (53, 8, np.float64), (4096, 2, np.float32), (4096, 3, np.float64),
+              (4096, 8, np.float32), (4096, 8, np.float64), (2, 2, np.float64), (3, 3, np.float64), (8, 8, np.float64)]
+
+
+@pytest.mark.parametrize("K,R,dt", WARM_CASES)
+@pytest.mark.parametrize("flat", [1, 0])
+def test_cluster_warm_start_reads_only_its_own_rows(K, R, dt, flat):
+    """ClusterPCG.pcg with true_warm_start and a buffer per rank that holds lambda0 on the rank's rows and NaN on every other
+    row: lambda0's ghost blocks k0-1 and k1 must come from the neighbouring ranks, not from the rank's own array.  Against
+    oracle.pcg(lam0=...).  K = R: one knot per rank (CG to finite termination on tiny systems: loose bar, as below)."""
+    S, C = 14, 7
+    Sb, Pb, gam = oracle_blocks(S, C, K, dt)
+    f64 = dt == np.float64
+    tol, mi = (1e-9, 150) if f64 else (1e-4, 60)
+    rng = np.random.default_rng(K + R)
+    conv = converged_f64(Sb, Pb, gam, S, K)
+    lam0 = (0.9 * conv + 0.05 * np.abs(conv).max() * rng.standard_normal(S * K)).astype(dt)
+    lam_o, it_o = o.pcg(Sb, Pb, gam, S, K, tol, mi, lam0=lam0)
+    sols, cl = _cluster_solvers(S, C, K, R, dt, flat, true_warm_start=1)
+    dS, dP, dg = sols[0].to_device(Sb), sols[0].to_device(Pb), sols[0].to_device(gam)
+    bufs = _rank_buffers(lam0, cl, S, sols[0].dtype)
+    its = [torch.zeros(1, dtype=torch.int32, device="cuda") for _ in range(R)]
+    streams = lockstep_streams(R)
+    torch.cuda.synchronize()
+    for r in range(R):
+        cl[r].pcg(dS, dP, dg, tol, mi, bufs[r], its[r], stream=streams[r].cuda_stream)
+    torch.cuda.synchronize()
+    for x in sols:
+        x.check_status()
+    got, itg = _gathered(bufs, cl, S), [int(i.cpu()[0]) for i in its]
+    tag = f"cluster warm start 14/7/{K} {R} ranks flat={flat}"
+    assert np.isfinite(got).all(), tag
+    tiny = K == R
+    assert len(set(itg)) == 1 and abs(itg[0] - it_o) <= (0 if f64 and not tiny else 2), (tag, itg, it_o)
+    if tiny and f64:
+        assert rel(got, lam_o) < 1e-5, (tag, rel(got, lam_o))
+    elif f64:
+        assert rel(got, lam_o) < 1e-9, (tag, rel(got, lam_o))
+    else:           # fp32: at the launch's own iteration count, against the fp64 iterate after as many iterations
+        n = itg[0] + 1
+        lam_of = o.pcg(Sb, Pb, gam, S, K, 0.0, n, lam0=lam0)[0]
+        lam_t = o.pcg(Sb.astype(np.float64), Pb.astype(np.float64), gam.astype(np.float64), S, K, 0.0, n,
+                      lam0=lam0.astype(np.float64))[0]
+        f32_judged(f"{tag} after {n} iterations", got, lam_of, lam_t)
+    _close(cl, sols)
+
+
+@pytest.mark.parametrize("K,R,dt,flat", [(53, 2, np.float64, 1), (53, 3, np.float32, 0), (300, 3, np.float64, 0), (4096, 8, np.float64, 1)])
+def test_cluster_warm_start_takes_the_default_recurrence(K, R, dt, flat):
+    """pcg_variant = 1 with true_warm_start: every rank runs the default recurrence (last_variant == 0), with its bits."""
+    S, C = 14, 7
+    Sb, Pb, gam = oracle_blocks(S, C, K, dt)
+    lam0 = (0.5 * converged_f64(Sb, Pb, gam, S, K)).astype(dt)
+    tol, mi = (1e-9, 150) if dt == np.float64 else (1e-4, 60)
+    out = []
+    for variant in (0, 1):
+        sols, cl = _cluster_solvers(S, C, K, R, dt, flat, true_warm_start=1, pcg_variant=variant)
+        dS, dP, dg = sols[0].to_device(Sb), sols[0].to_device(Pb), sols[0].to_device(gam)
+        bufs = _rank_buffers(lam0, cl, S, sols[0].dtype)
+        its = [torch.zeros(1, dtype=torch.int32, device="cuda") for _ in range(R)]
+        streams = lockstep_streams(R)
+        torch.cuda.synchronize()
+        for r in range(R):
+            cl[r].pcg(dS, dP, dg, tol, mi, bufs[r], its[r], stream=streams[r].cuda_stream)
+        torch.cuda.synchronize()
+        for x in sols:
+            x.check_status()
+            assert x.get_option("last_variant") == 0
+        out.append((_gathered(bufs, cl, S), [int(i.cpu()[0]) for i in its]))
+        _close(cl, sols)
+    assert out[0][1] == out[1][1] and np.array_equal(out[0][0], out[1][0])
+    assert np.isfinite(out[0][0]).all()
+
+
+@pytest.mark.parametrize("K,R,dt,flat", [(53, 2, np.float64, 1), (53, 3, np.float32, 0), (53, 8, np.float64, 0),
+                                         (4096, 3, np.float64, 1), (4096, 8, np.float32, 1), (4096, 2, np.float64, 0),
+                                         (3, 3, np.float64, 1)])
+def test_cluster_whole_solve_warm_started_from_its_last_result(K, R, dt, flat):
+    """ClusterPCG.linsys twice with a lambda / dz buffer per rank (NaN to start with): a cold solve, then - option true_warm_start
+    on - a new system of the same pattern, warm-started from each rank's buffer as the first solve left it (rows k0..k1-1 and the
+    ghost row k1, nothing at k0-1).  Against the oracle's warm whole solve from the gathered first lambda."""
+    S, C = 14, 7
+    f64 = dt == np.float64
+    tol, mi = (1e-9, 150) if f64 else (1e-4, 60)
+    s1, s2 = synth.make_system(S, C, K, seed=31), synth.make_system(S, C, K, seed=32)
+    sols, cl = _cluster_solvers(S, C, K, R, dt, flat)
+    N = sols[0].N
+    lams = [torch.full((S * K,), float("nan"), dtype=sols[0].dtype, device="cuda") for _ in range(R)]
+    dzs = [torch.full((N,), float("nan"), dtype=sols[0].dtype, device="cuda") for _ in range(R)]
+    its = [torch.zeros(1, dtype=torch.int32, device="cuda") for _ in range(R)]
+    streams = lockstep_streams(R)
+    n = S + C
+
+    def solve(s):
+        d = sols[0].upload_system(s)
+        torch.cuda.synchronize()
+        for r in range(R):
+            cl[r].linsys(d, tol, mi, s.rho, lams[r], dzs[r], its[r], stream=streams[r].cuda_stream)
+        torch.cuda.synchronize()
+        for x in sols:
+            x.check_status()
+        dz = np.concatenate([dzs[r][c.k0 * n:min(c.k1 * n, N)].cpu().numpy() for r, c in enumerate(cl)])
+        return _gathered(lams, cl, S), dz, [int(i.cpu()[0]) for i in its]
+
+    lam1, _, _ = solve(s1)
+    assert np.isfinite(lam1).all()
+    for x in sols:
+        x.set_option("true_warm_start", 1)
+    lam2, dz2, it2 = solve(s2)
+    tag = f"cluster warm whole solve 14/7/{K} {R} ranks flat={flat}"
+    lam_o, dz_o, it_o = o.linsys_solve(*s2.csr_args(), S, C, K, tol, mi, s2.rho, dtype=dt, lam0=lam1)
+    lam_c, _, it_c = o.linsys_solve(*s2.csr_args(), S, C, K, tol, mi, s2.rho, dtype=dt)
+    assert np.isfinite(lam2).all() and np.isfinite(dz2).all(), tag
+    tiny = K == R
+    assert len(set(it2)) == 1 and abs(it2[0] - it_o) <= (0 if f64 and not tiny else 2), (tag, it2, it_o, it_c)
+    if tiny:
+        assert rel(lam2, lam_o) < 1e-5 and rel(dz2, dz_o) < 1e-4, tag
+    elif f64:
+        assert rel(lam2, lam_o) < 1e-9 and rel(dz2, dz_o) < 1e-9, (tag, rel(lam2, lam_o), rel(dz2, dz_o))
+    else:
+        s64 = s2.astype(np.float32).astype(np.float64)
+        lam_t, dz_t, _ = o.linsys_solve(*s64.csr_args(), S, C, K, 1e-14, 600, float(np.float32(s2.rho)), dtype=np.float64,
+                                        lam0=lam1.astype(np.float64))
+        f32_judged(tag + " lambda", lam2, lam_o, lam_t)
+        f32_judged(tag + " dz", dz2, dz_o, dz_t)
+    _close(cl, sols)
+
+
+def test_cluster_warm_started_solves_one_process_per_rank():
+    """TWO PROCESSES through linsys_solve_cluster(..., solver_options={"true_warm_start": 1}): three solves on one state, a new
+    system each time.  The first equals the cold oracle solve (the connect probe's lambda is not left behind), the next ones the
+    oracle's warm whole solve from the previous gathered lambda (tests/cluster_warm_worker.py)."""
+    env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(free_port()), OMP_NUM_THREADS="4",
+               HSA_ENABLE_IPC_MODE_LEGACY="0")
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
+           "--master-addr", "127.0.0.1", "--master-port", env["MASTER_PORT"],
+           os.path.join(ROOT, "tests", "cluster_warm_worker.py"), "14", "7", "600"]
+    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    assert r.stdout.count(" warm ok") == 2, r.stdout[-2000:]

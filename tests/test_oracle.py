@@ -166,3 +166,69 @@ def test_fp32_point_jacobi_is_order_chaotic_past_ten_iterations():
         assert max(ec, en) < 1e-5 and max(ec, en) / min(ec, en) < 3.0, (n, ec, en)
     ec, en = errs(15)
     assert max(ec, en) > 1e-3 and max(ec, en) / min(ec, en) > 4.0, (ec, en)      # measured: 6.1e-2 (C order) vs 7.7e-3 (numpy order)
+
+
+# ---- true warm start (pcg(lam0=...), linsys_solve(lam0=...)): an extension of the reference (D5), pinned here against direct
+# dense solves so that the GPU suite's warm-start comparisons stand on a checked restatement
+def dense_schur(S_bd, S, K):
+    """The block-tridiagonal S of bd-format blocks as one dense (S K) x (S K) matrix."""
+    L, M, R = o.unpack_bd(S_bd, S, K)
+    D = np.zeros((S * K, S * K), S_bd.dtype)
+    for k in range(K):
+        D[k * S:(k + 1) * S, k * S:(k + 1) * S] = M[k]
+        if k > 0:
+            D[k * S:(k + 1) * S, (k - 1) * S:k * S] = L[k]
+        if k < K - 1:
+            D[k * S:(k + 1) * S, (k + 1) * S:(k + 2) * S] = R[k]
+    return D
+
+
+def _assembled(S, C, K, seed):
+    s = synth.make_system(S, C, K, seed=seed)
+    a = o.linsys_solve(*s.csr_args(), S, C, K, 0.0, 1, s.rho, dtype=np.float64, return_all=True)
+    return s, a
+
+
+@pytest.mark.parametrize("S,C,K", [(14, 7, 12), (2, 1, 5)])
+def test_pcg_warm_start_from_zero_is_the_cold_solve(S, C, K):
+    _, a = _assembled(S, C, K, 4)
+    for tol, mi in ((0.0, 7), (1e-12, 300)):
+        lam_c, it_c, h_c = o.pcg(a["S"], a["Pinv"], a["gamma"], S, K, tol, mi, return_history=True)
+        lam_w, it_w, h_w = o.pcg(a["S"], a["Pinv"], a["gamma"], S, K, tol, mi, return_history=True, lam0=np.zeros(S * K))
+        assert it_w == it_c and h_w == h_c and np.array_equal(lam_w, lam_c)
+
+
+@pytest.mark.parametrize("S,C,K", [(14, 7, 12), (2, 1, 5)])
+def test_pcg_warm_start_converges_to_the_dense_schur_solve(S, C, K):
+    """r0 = gamma - S lambda0: from a random guess, from 0.9 x the solution and from the solution itself fp64 PCG reaches
+    np.linalg.solve(S_dense, gamma); from the solution it exits at once."""
+    _, a = _assembled(S, C, K, 6)
+    lam_d = np.linalg.solve(dense_schur(a["S"], S, K), a["gamma"])
+    rng = np.random.default_rng(S * K)
+    cold = o.pcg(a["S"], a["Pinv"], a["gamma"], S, K, 1e-28, 1000)
+    assert rel(cold[0], lam_d) < 1e-10
+    for lam0 in (rng.standard_normal(S * K) * np.abs(lam_d).max(), 0.9 * lam_d, lam_d):
+        lam, it = o.pcg(a["S"], a["Pinv"], a["gamma"], S, K, 1e-28, 1000, lam0=lam0)
+        assert it < 1000 and rel(lam, lam_d) < 1e-10, (it, rel(lam, lam_d))
+    # exact guess: the initial residual is rounding noise, the exit test fires after the first step (or the next)
+    eta0 = abs(o.pcg(a["S"], a["Pinv"], a["gamma"], S, K, 0.0, 1, return_history=True)[2][0])     # (S is negative definite)
+    lam, it = o.pcg(a["S"], a["Pinv"], a["gamma"], S, K, 1e-20 * eta0, 1000, lam0=lam_d)
+    assert it <= 1 and rel(lam, lam_d) < 1e-12, (it, rel(lam, lam_d))
+    lam, it = o.pcg(a["S"], a["Pinv"], a["gamma"], S, K, 1e-20 * eta0, 1000, lam0=0.9 * lam_d)
+    assert it > 1                                                       # (the bar above is not trivially met)
+
+
+@pytest.mark.parametrize("S,C,K", [(14, 7, 12), (2, 1, 5)])
+def test_warm_whole_solve_equals_the_dense_kkt_solve(S, C, K):
+    """linsys_solve(lam0=...): lambda and dz of a warm-started whole solve (dz from the final lambda) against the dense KKT solve;
+    lam0 = 0 gives the cold solve's bits."""
+    s, a = _assembled(S, C, K, 8)
+    dz_d, lam_d = synth.dense_kkt_solve(s)
+    rng = np.random.default_rng(K)
+    for lam0 in (0.9 * lam_d, rng.standard_normal(S * K)):
+        w = o.linsys_solve(*s.csr_args(), S, C, K, 1e-28, 1000, s.rho, dtype=np.float64, return_all=True, lam0=lam0)
+        assert rel(w["lam"], lam_d) < 1e-8 and np.abs(w["dz"] - dz_d).max() < 1e-7 * max(np.abs(dz_d).max(), 1.0)
+        assert np.array_equal(w["dz"], o.compute_dz(w["Ginv"], w["C_dense"], s.g, w["lam"], S, C, K))
+    cold = o.linsys_solve(*s.csr_args(), S, C, K, 1e-12, 300, s.rho, dtype=np.float64)
+    zero = o.linsys_solve(*s.csr_args(), S, C, K, 1e-12, 300, s.rho, dtype=np.float64, lam0=np.zeros(S * K))
+    assert zero[2] == cold[2] and np.array_equal(zero[0], cold[0]) and np.array_equal(zero[1], cold[1])
