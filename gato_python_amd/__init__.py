@@ -4,6 +4,8 @@ Public surface:
   gato_python_amd.linsys_solve(...)      drop-in for gpu_library.linsys_solve (gpu_library.cu:236-239)
   gato_python_amd.linsys_resolve(...)    the last linsys_solve's system again, for a new g / c (no re-assembly)
   gato_python_amd.Solver                 device-resident stage-level API over include/gato_hip.h
+  gato_python_amd.kkt_solve(...)         differentiable solve from math-shaped blocks (torch autograd, autograd.py)
+  gato_python_amd.kkt_solve_csr(...)     differentiable solve on device CSR input
   gato_python_amd.synth                  synthetic OCP inputs (the reference ships pendulum data only)
 """
 from .linsys import (clear_problem_size, last_stats, linsys_resolve, linsys_solve, set_precision,  # noqa: F401
@@ -14,4 +16,7 @@ def __getattr__(name):
     if name == "Solver":              # torch import deferred: linsys_solve itself needs only ctypes
         from .solver import Solver
         return Solver
+    if name in ("kkt_solve", "kkt_solve_csr"):
+        from . import autograd
+        return getattr(autograd, name)
     raise AttributeError(name)

@@ -32,6 +32,7 @@ SYMBOLS = [
     "gato_cluster_knot_range", "gato_cluster_create", "gato_cluster_local_mirror", "gato_cluster_connect",
     "gato_cluster_pcg", "gato_cluster_linsys", "gato_cluster_destroy", "gato_cluster_launches_left", "gato_cluster_rewind", "gato_cluster_fits", "gato_last_stage_ms", "gato_solver_tune",
     "gato_solver_reserve_rhs", "gato_solve_rhs", "gato_linsys_resolve_f32", "gato_linsys_resolve_f64",
+    "gato_kkt_grad_blocks", "gato_kkt_grad_csr",
 ]
 
 
@@ -104,6 +105,8 @@ def lib() -> ct.CDLL:
         L.gato_solver_tune.argtypes = [vp, vp]
         L.gato_solver_reserve_rhs.argtypes = [vp, i]
         L.gato_solve_rhs.argtypes = [vp, i, vp, vp, d, i, vp, vp, vp, vp]
+        L.gato_kkt_grad_blocks.argtypes = [vp] * 8
+        L.gato_kkt_grad_csr.argtypes = [vp, ip, ip, i, ip, ip, i, vp, vp, vp, vp, vp, vp, vp]
         f = ct.c_float
         L.gato_linsys_solve_f32.argtypes = [ip, i, ip, vp, i, ip, i, ip, vp, i, vp, i, vp, i, vp,
                                             i, i, i, i, f, i, i, f, vp, vp, vp, vp]

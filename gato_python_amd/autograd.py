@@ -1,0 +1,256 @@
+"""torch autograd through the KKT solve.
+
+    kkt_solve(Q, R, A, B, q, r, c, *, rho, exit_tol, max_iters) -> (lam, dz)
+    kkt_solve_csr(G_row, G_col, G_val, C_row, C_col, C_val, g, c, *, rho, exit_tol, max_iters) -> (lam, dz)
+
+The forward is the device solve (Solver.linsys_blocks / linsys / linsys_batched).  The backward is one re-solve of the same
+assembly with the incoming gradients as right-hand side (the KKT matrix is symmetric, so the adjoint system has the forward's
+matrix: Solver.solve_rhs), then one launch that forms the matrix gradients from dz, lambda and the adjoint (gato_grad.hip).
+Only device tensors are taken; there is no CPU fallback.  rho is not differentiated, and double backward is not supported.
+"""
+from __future__ import annotations
+
+import ctypes as ct
+
+import numpy as np
+import torch
+from torch.autograd.function import once_differentiable
+
+from . import _lib
+from .solver import Solver
+
+_NP = {torch.float32: np.float32, torch.float64: np.float64}
+_SOLVERS = {}
+
+
+def _solver(S, C, K, B, dtype, device):
+    """The cached Solver of one (S, C, K, B, dtype, device): every call of one shape shares its workspace."""
+    key = (S, C, K, B, dtype, device)
+    sol = _SOLVERS.get(key)
+    if sol is None:
+        sol = _SOLVERS[key] = Solver(S, C, K, _NP[dtype], device=device, batch=B)
+    return sol
+
+
+def _common(tensors, what):
+    """device index and dtype shared by all value tensors; ValueError before any library call otherwise."""
+    for name, t in tensors.items():
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{what}: {name} must be a torch.Tensor, got {type(t).__name__}")
+        if not t.is_cuda:
+            raise ValueError(f"{what}: {name} is on {t.device}: the solve runs on the GPU only (there is no CPU fallback)")
+    devs = {t.device for t in tensors.values()}
+    if len(devs) != 1:
+        raise ValueError(f"{what}: the tensors are on different devices: {sorted(str(d) for d in devs)}")
+    dts = {t.dtype for t in tensors.values()}
+    if len(dts) != 1 or next(iter(dts)) not in _NP:
+        raise ValueError(f"{what}: the values must share one dtype, float32 or float64; got {sorted(str(d) for d in dts)}")
+    return next(iter(devs)).index, next(iter(dts))
+
+
+def _opts(rho, exit_tol, max_iters):
+    return float(rho), float(exit_tol), int(max_iters)
+
+
+# ---- block form ------------------------------------------------------------------------------------------------------
+class _BlocksSolve(torch.autograd.Function):
+    """(G_blocks [B, G_dense], C_blocks [B, C_dense], g [B, N], c [B, S K]) -> (lam [B, S K], dz [B, N])."""
+
+    @staticmethod
+    def forward(ctx, Gb, Cb, g, c, sol, rho, exit_tol, max_iters):
+        B = sol.batch
+        lam = torch.empty(B, sol.sizes["sk"], dtype=g.dtype, device=g.device)
+        dz = torch.empty(B, sol.N, dtype=g.dtype, device=g.device)
+        sol.linsys_blocks(Gb, Cb, g, c, exit_tol, max_iters, rho, lam, dz)
+        sol.check_status()
+        ctx.sol, ctx.opts, ctx.gen = sol, (rho, exit_tol, max_iters), sol.get_option("assembly_gen")
+        ctx.save_for_backward(Gb, Cb, g, c, lam, dz)      # Cb itself: the re-solve reads the caller's C blocks again
+        ctx.set_materialize_grads(False)
+        return lam, dz
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, lam_bar, dz_bar):
+        Gb, Cb, g, c, lam, dz = ctx.saved_tensors
+        sol = ctx.sol
+        rho, exit_tol, max_iters = ctx.opts
+        if lam_bar is None and dz_bar is None:
+            return (None,) * 8
+        if sol.get_option("assembly_gen") != ctx.gen or sol.get_option("assembly_valid") == 0:
+            sol.linsys_blocks(Gb, Cb, g, c, exit_tol, max_iters, rho)    # another forward replaced the assembly
+            sol.check_status()
+        a, beta = _adjoint(sol, lam, dz, lam_bar, dz_bar, exit_tol, max_iters)
+        need = ctx.needs_input_grad
+        Gbar = torch.empty_like(Gb) if need[0] else None
+        Cbar = torch.empty_like(Cb) if need[1] else None
+        if Gbar is not None or Cbar is not None:
+            sol.kkt_grad_blocks(dz, lam, a, beta, Gbar, Cbar)
+        return (Gbar, Cbar, a if need[2] else None, beta if need[3] else None) + (None,) * 4
+
+
+def _adjoint(sol, lam, dz, lam_bar, dz_bar, exit_tol, max_iters):
+    """[a; beta] = M^-1 [dz_bar; lam_bar]: one re-solve of the current assembly (a missing gradient is zero)."""
+    gin = torch.zeros_like(dz) if dz_bar is None else dz_bar.to(dz.dtype).contiguous()
+    cin = torch.zeros_like(lam) if lam_bar is None else lam_bar.to(lam.dtype).contiguous()
+    sol.reserve_rhs(1)
+    beta, a, _ = sol.solve_rhs(gin, cin, exit_tol, max_iters)
+    sol.check_status()              # a hand-off time-out (iters = -1) raises, as in the forward; running to max_iters does not
+    # a system whose right-hand side is all zero has a zero adjoint; its PCG would divide 0 by 0 (eta / p.Sp) instead
+    zero = ~(gin.ne(0).any(1) | cin.ne(0).any(1))[:, None]
+    return torch.where(zero, 0, a.view_as(dz)), torch.where(zero, 0, beta.view_as(lam))
+
+
+def _pack(Q, R, A, B, q, r, c):
+    """Math-shaped blocks [Bt, ...] -> the solver's G_dense / C_dense / g / c layouts, in torch ops (torch differentiates them)."""
+    Bt, K, S, _ = Q.shape
+    C = R.shape[-1]
+    Qf = Q.transpose(-1, -2).reshape(Bt, K, S * S)                 # column-major per knot
+    Rf = R.transpose(-1, -2).reshape(Bt, K - 1, C * C)
+    Gb = torch.cat([torch.cat([Qf[:, :K - 1], Rf], 2).reshape(Bt, -1), Qf[:, K - 1]], 1)
+    Af = A.transpose(-1, -2).reshape(Bt, K - 1, S * S)
+    Bf = B.transpose(-1, -2).reshape(Bt, K - 1, S * C)
+    Cb = torch.cat([Af, Bf], 2).reshape(Bt, -1)
+    g = torch.cat([torch.cat([q[:, :K - 1], r], 2).reshape(Bt, -1), q[:, K - 1]], 1)
+    return Gb.contiguous(), Cb.contiguous(), g.contiguous(), c.reshape(Bt, -1).contiguous()
+
+
+def kkt_solve(Q, R, A, B, q, r, c, *, rho, exit_tol, max_iters):
+    """Differentiable KKT solve from math-shaped blocks, at most one leading batch dimension:
+    Q [*,K,S,S], R [*,K-1,C,C], A [*,K-1,S,S], B [*,K-1,S,C], q [*,K,S], r [*,K-1,C], c [*,K,S] (A, B as stored in C: the
+    raw values, -A and -B of the dynamics).  Returns flat lam [*, S K] and dz [*, N], as linsys_solve does.
+    Q, R are taken as symmetric: their gradients are those of symmetric perturbations."""
+    args = dict(Q=Q, R=R, A=A, B=B, q=q, r=r, c=c)
+    for name, t in args.items():
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"kkt_solve: {name} must be a torch.Tensor, got {type(t).__name__}")
+    batched = Q.dim() == 4
+    if Q.dim() not in (3, 4) or Q.shape[-1] != Q.shape[-2]:
+        raise ValueError(f"kkt_solve: Q must be [*, K, S, S], got {tuple(Q.shape)}")
+    K, S = Q.shape[-3], Q.shape[-1]
+    if R.dim() < 2:
+        raise ValueError(f"kkt_solve: R must be [*, K-1, C, C], got {tuple(R.shape)}")
+    C = R.shape[-1]
+    lead = (Q.shape[0],) if batched else ()
+    want = dict(Q=(K, S, S), R=(K - 1, C, C), A=(K - 1, S, S), B=(K - 1, S, C), q=(K, S), r=(K - 1, C), c=(K, S))
+    for name, shp in want.items():
+        if tuple(args[name].shape) != lead + shp:
+            raise ValueError(f"kkt_solve: {name} has shape {tuple(args[name].shape)}, want {lead + shp} "
+                             f"(S = {S}, C = {C}, K = {K}{', batch %d' % lead[0] if lead else ''})")
+    if K < 1 or S < 1 or C < 1:
+        raise ValueError(f"kkt_solve: S = {S}, C = {C}, K = {K} must all be >= 1")
+    device, dtype = _common(args, "kkt_solve")
+    if not batched:
+        Q, R, A, B, q, r, c = (t.unsqueeze(0) for t in (Q, R, A, B, q, r, c))
+    Bt = Q.shape[0]
+    rho, exit_tol, max_iters = _opts(rho, exit_tol, max_iters)
+    Gb, Cb, g, cc = _pack(Q, R, A, B, q, r, c)
+    sol = _solver(S, C, K, Bt, dtype, device)
+    lam, dz = _BlocksSolve.apply(Gb, Cb, g, cc, sol, rho, exit_tol, max_iters)
+    return (lam, dz) if batched else (lam[0], dz[0])
+
+
+# ---- CSR form ----------------------------------------------------------------------------------------------------------
+class _CsrSolve(torch.autograd.Function):
+    """(G_val [B, nnz_G], C_val [B, nnz_C], g [B, N], c [B, S K]) on a shared pattern -> (lam [B, S K], dz [B, N])."""
+
+    @staticmethod
+    def forward(ctx, G_val, C_val, g, c, idx, sol, rho, exit_tol, max_iters):
+        B = sol.batch
+        lam = torch.empty(B, sol.sizes["sk"], dtype=g.dtype, device=g.device)
+        dz = torch.empty(B, sol.N, dtype=g.dtype, device=g.device)
+        _csr_forward(sol, idx, G_val, C_val, g, c, exit_tol, max_iters, rho, lam, dz)
+        ctx.sol, ctx.idx, ctx.opts, ctx.gen = sol, idx, (rho, exit_tol, max_iters), sol.get_option("assembly_gen")
+        ctx.save_for_backward(G_val, C_val, g, c, lam, dz)
+        ctx.set_materialize_grads(False)
+        return lam, dz
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, lam_bar, dz_bar):
+        G_val, C_val, g, c, lam, dz = ctx.saved_tensors
+        sol, idx = ctx.sol, ctx.idx
+        rho, exit_tol, max_iters = ctx.opts
+        if lam_bar is None and dz_bar is None:
+            return (None,) * 9
+        if sol.get_option("assembly_gen") != ctx.gen or sol.get_option("assembly_valid") == 0:
+            _csr_forward(sol, idx, G_val, C_val, g, c, exit_tol, max_iters, rho, None, None)
+        a, beta = _adjoint(sol, lam, dz, lam_bar, dz_bar, exit_tol, max_iters)
+        need = ctx.needs_input_grad
+        Gbar = torch.empty_like(G_val) if need[0] else None
+        Cbar = torch.empty_like(C_val) if need[1] else None
+        if Gbar is not None or Cbar is not None:
+            sol.kkt_grad_csr(*idx, dz, lam, a, beta, Gbar, Cbar)
+        return (Gbar, Cbar, a if need[2] else None, beta if need[3] else None) + (None,) * 5
+
+
+def _csr_forward(sol, idx, G_val, C_val, g, c, exit_tol, max_iters, rho, lam, dz):
+    G_row, G_col, C_row, C_col = idx
+    if sol.batch == 1:
+        sol.linsys(G_row, G_col, G_val, C_row, C_col, C_val, g, c, exit_tol, max_iters, rho, lam, dz)
+    else:
+        sol.linsys_batched(G_row, G_col, G_val, C_row, C_col, C_val, g, c, exit_tol, max_iters, rho, lam, dz)
+    sol.check_status()
+
+
+def _index(t, name, what, device):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device.index != device:
+        raise ValueError(f"{what}: {name} must be a CUDA tensor on cuda:{device} (there is no CPU fallback)")
+    if t.dtype not in (torch.int32, torch.int64) or t.dim() != 1:
+        raise ValueError(f"{what}: {name} must be a 1-D int32 / int64 tensor, got {t.dtype} {tuple(t.shape)}")
+    return t.to(torch.int32).contiguous()
+
+
+def _check_pattern(G_row, G_col, C_row, C_col, N):
+    """The scatter kernels trust the indices (as the reference does): refuse, on the host, what would send them out of range."""
+    for name, ptr, col in (("G", G_row, G_col), ("C", C_row, C_col)):
+        p, cidx = ptr.cpu().numpy(), col.cpu().numpy()
+        if p[0] < 0 or p[-1] > cidx.size or np.any(np.diff(p) < 0):
+            raise ValueError(f"kkt_solve_csr: {name}_row must rise from >= 0 to <= len({name}_col) = {cidx.size}")
+        if cidx.size and (cidx.min() < 0 or cidx.max() >= N):
+            raise ValueError(f"kkt_solve_csr: {name}_col holds an index outside [0, {N})")
+    return C_row.cpu().numpy()
+
+
+def _infer_shape(C_row_host, len_g, len_c):
+    h = np.ascontiguousarray(C_row_host, np.int32)
+    S, C, K = ct.c_int(), ct.c_int(), ct.c_int()
+    rc = _lib.lib().gato_infer_shape(h.ctypes.data_as(ct.c_void_p), len(h), len_g, len_c, ct.byref(S), ct.byref(C),
+                                     ct.byref(K))
+    if rc != 0:
+        raise ValueError("kkt_solve_csr: " + _lib.lib().gato_last_error().decode())
+    return S.value, C.value, K.value
+
+
+def kkt_solve_csr(G_row, G_col, G_val, C_row, C_col, C_val, g, c, *, rho, exit_tol, max_iters):
+    """Differentiable KKT solve on CSR input (gpu_library.linsys_solve's arrays, on the device).  Differentiable in G_val,
+    C_val, g and c; the indices are shared by a batch: values [B, nnz] / g [B, N] / c [B, S K], or unbatched [nnz] / [N] /
+    [S K].  The gradient of a value is that of the dense slot the scatter writes it into - 0 where the scatter drops it or a
+    later entry of its row overwrites it.  (S, C, K) come from the lengths and C's leading identity rows."""
+    what = "kkt_solve_csr"
+    vals = dict(G_val=G_val, C_val=C_val, g=g, c=c)
+    for name, t in vals.items():
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{what}: {name} must be a torch.Tensor, got {type(t).__name__}")
+    batched = g.dim() == 2
+    if any(t.dim() != (2 if batched else 1) for t in vals.values()):
+        raise ValueError(f"{what}: G_val, C_val, g, c must all be 1-D or all [B, ...]: "
+                         f"{[tuple(t.shape) for t in vals.values()]}")
+    Bt = g.shape[0] if batched else 1
+    if batched and any(t.shape[0] != Bt for t in vals.values()):
+        raise ValueError(f"{what}: the batch sizes differ: {[tuple(t.shape) for t in vals.values()]}")
+    device, dtype = _common(vals, what)
+    G_row, G_col, C_row, C_col = (_index(t, n, what, device) for t, n in
+                                  ((G_row, "G_row"), (G_col, "G_col"), (C_row, "C_row"), (C_col, "C_col")))
+    if G_val.shape[-1] != G_col.numel() or C_val.shape[-1] != C_col.numel():
+        raise ValueError(f"{what}: G_val / C_val hold {G_val.shape[-1]} / {C_val.shape[-1]} values per system, G_col / C_col "
+                         f"{G_col.numel()} / {C_col.numel()} indices")
+    N, SK = g.shape[-1], c.shape[-1]
+    if G_row.numel() != N + 1 or C_row.numel() != SK + 1:
+        raise ValueError(f"{what}: len(G_row) = {G_row.numel()} and len(C_row) = {C_row.numel()}, want N + 1 = {N + 1} and "
+                         f"S K + 1 = {SK + 1}")
+    S, C, K = _infer_shape(_check_pattern(G_row, G_col, C_row, C_col, N), N, SK)
+    rho, exit_tol, max_iters = _opts(rho, exit_tol, max_iters)
+    G_val2, C_val2, g2, c2 = (t.reshape(Bt, -1).contiguous() for t in (G_val, C_val, g, c))
+    sol = _solver(S, C, K, Bt, dtype, device)
+    lam, dz = _CsrSolve.apply(G_val2, C_val2, g2, c2, (G_row, G_col, C_row, C_col), sol, rho, exit_tol, max_iters)
+    return (lam, dz) if batched else (lam[0], dz[0])

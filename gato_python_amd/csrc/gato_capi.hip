@@ -54,6 +54,15 @@ static Ops make_ops(int dtype)
         return launch_rhs_gamma<T, S, C>(d, R, (const T *)Gi, (const T *)Cd, (const T *)Sb, (const T *)g, (const T *)c,
                                          (T *)gam, st);
     };
+    o.grad_blocks = [](const Dims &d, const void *dz, const void *lam, const void *a, const void *beta, void *Gb, void *Cb,
+                       hipStream_t st) {
+        return launch_grad_blocks<T, S, C>(d, (const T *)dz, (const T *)lam, (const T *)a, (const T *)beta, (T *)Gb, (T *)Cb, st);
+    };
+    o.grad_csr = [](const Dims &d, const int *gr, const int *gc, int nG, const int *cr, const int *cc, int nC, const void *dz,
+                    const void *lam, const void *a, const void *beta, void *Gb, void *Cb, hipStream_t st) {
+        return launch_grad_csr<T, S, C>(d, gr, gc, nG, cr, cc, nC, (const T *)dz, (const T *)lam, (const T *)a,
+                                        (const T *)beta, (T *)Gb, (T *)Cb, st);
+    };
     o.pcg_plan = [](PcgPlan *p) { return pcg_resident_plan<T, S>(p); };
     o.pcg_resident = [](const PcgLaunch &a, hipStream_t st) { return launch_pcg_resident<T, S>(a, st); };   // incl. the DPP-row layout
     o.pcg_dma_max_knots = []() { return pcg_dma_max_knots<T, S>(); };
@@ -596,6 +605,7 @@ extern "C" int gato_solver_get_option(gato_solver *s, const char *name, int *val
     else if (!strcmp(name, "batch")) *value = s->d.B;
     else if (!strcmp(name, "rhs_reserved")) *value = s->rhs_R;
     else if (!strcmp(name, "assembly_valid")) *value = s->as.valid;
+    else if (!strcmp(name, "assembly_gen")) *value = (int)s->as.gen;     // wraps: compare for equality only
     else if (!strcmp(name, "max_semi_knots"))
         *value = s->plan.semi_threads > 0 ? (s->plan.semi_threads / s->d.S + s->plan.semi_rows * s->plan.semi_threads / s->d.S) * (s->num_cus < 256 ? s->num_cus : 256) : 0;
     else if (!strcmp(name, "max_resident_knots")) *value = s->plan.max_knots_per_wg * (s->num_cus < 256 ? s->num_cus : 256);
@@ -1427,6 +1437,37 @@ extern "C" int gato_solve_rhs(gato_solver *s, int R, const void *d_g, const void
     if (!s->dz_fused && (rc = dz_rhs(s, R, d_g, d_lambda, d_dz, st))) return rc;
     if (ts) GATO_HIP_CHECK(hipEventRecord(s->ev_stage[3], st));
     return GATO_OK;
+}
+
+// ---- gradients of a solve (gato_grad.hip): vectors in, no assembly read ------------------------------------------------
+extern "C" int gato_kkt_grad_blocks(gato_solver *s, const void *d_dz, const void *d_lam, const void *d_adz, const void *d_alam,
+                                    void *d_Gbar, void *d_Cbar, void *stream)
+{
+    if (!s) { set_error("kkt_grad_blocks: null solver"); return GATO_EINVAL; }
+    if (s->cl.on || s->cl.local) { set_error("kkt_grad_blocks: the solver is a cluster rank; sharded gradients are not supported"); return GATO_EINVAL; }
+    if (!d_dz || !d_lam || !d_adz || !d_alam) { set_error("kkt_grad_blocks: d_dz, d_lam, d_adz and d_alam are required"); return GATO_EINVAL; }
+    if (!d_Gbar && !d_Cbar) { set_error("kkt_grad_blocks: both outputs are NULL"); return GATO_EINVAL; }
+    Dims d = s->d;
+    d.k_lo = d.k_hi = 0; d.rhs = 0;
+    return s->ops->grad_blocks(d, d_dz, d_lam, d_adz, d_alam, d_Gbar, d_Cbar, (hipStream_t)stream);
+}
+
+extern "C" int gato_kkt_grad_csr(gato_solver *s, const int *d_G_row, const int *d_G_col, int nnz_G, const int *d_C_row,
+                                 const int *d_C_col, int nnz_C, const void *d_dz, const void *d_lam, const void *d_adz,
+                                 const void *d_alam, void *d_Gbar_val, void *d_Cbar_val, void *stream)
+{
+    if (!s) { set_error("kkt_grad_csr: null solver"); return GATO_EINVAL; }
+    if (s->cl.on || s->cl.local) { set_error("kkt_grad_csr: the solver is a cluster rank; sharded gradients are not supported"); return GATO_EINVAL; }
+    if (!d_dz || !d_lam || !d_adz || !d_alam) { set_error("kkt_grad_csr: d_dz, d_lam, d_adz and d_alam are required"); return GATO_EINVAL; }
+    if (!d_Gbar_val && !d_Cbar_val) { set_error("kkt_grad_csr: both outputs are NULL"); return GATO_EINVAL; }
+    if ((d_Gbar_val && (!d_G_row || !d_G_col || nnz_G < 0)) || (d_Cbar_val && (!d_C_row || !d_C_col || nnz_C < 0))) {
+        set_error("kkt_grad_csr: an output needs its row pointers, column indices and nnz >= 0");
+        return GATO_EINVAL;
+    }
+    Dims d = s->d;
+    d.k_lo = d.k_hi = 0; d.rhs = 0;
+    return s->ops->grad_csr(d, d_G_row, d_G_col, nnz_G, d_C_row, d_C_col, nnz_C, d_dz, d_lam, d_adz, d_alam, d_Gbar_val,
+                            d_Cbar_val, (hipStream_t)stream);
 }
 
 static std::mutex g_cache_mu;

@@ -301,6 +301,13 @@ int launch_compute_dz(const Dims &d, const T *Ginv, const T *Cd, const T *g, con
 template <typename T, int S, int C>
 int launch_rhs_gamma(const Dims &d, int R, const T *Ginv, const T *Cd, const T *Sbd, const T *g, const T *c, T *gamma,
                      hipStream_t st);
+// Gradients of a solve from dz, lambda and the adjoint (a, beta) of B systems (gato_grad.hip): G_bar [B][g_dense],
+// C_bar [B][c_dense] (either may be null), or per CSR entry of a pattern the systems share, [B][nnz] (either may be null)
+template <typename T, int S, int C>
+int launch_grad_blocks(const Dims &d, const T *dz, const T *lam, const T *a, const T *beta, T *Gbar, T *Cbar, hipStream_t st);
+template <typename T, int S, int C>
+int launch_grad_csr(const Dims &d, const int *G_row, const int *G_col, int nnzG, const int *C_row, const int *C_col, int nnzC,
+                    const T *dz, const T *lam, const T *a, const T *beta, T *Gbar, T *Cbar, hipStream_t st);
 template <typename T, int S>
 int pcg_resident_plan(PcgPlan *plan);
 template <typename T, int S>
@@ -378,6 +385,9 @@ struct Ops {
                       hipStream_t);
     int (*rhs_gamma)(const Dims &, int, const void *, const void *, const void *, const void *, const void *, void *,
                      hipStream_t);
+    int (*grad_blocks)(const Dims &, const void *, const void *, const void *, const void *, void *, void *, hipStream_t);
+    int (*grad_csr)(const Dims &, const int *, const int *, int, const int *, const int *, int, const void *, const void *,
+                    const void *, const void *, void *, void *, hipStream_t);
     int (*pcg_plan)(PcgPlan *);
     int (*pcg_resident)(const PcgLaunch &, hipStream_t);
     int (*pcg_dma_max_knots)();

@@ -163,6 +163,20 @@ class Solver:
                                              _ptr(dz), _ptr(iters), self._stream()))
         return lam, dz, iters
 
+    # ---- gradients of a solve from dz, lambda and the adjoint (a, beta) (gato_kkt_grad_*) --------------------------------
+    def kkt_grad_blocks(self, dz, lam, adz, alam, Gbar=None, Cbar=None):
+        """G_bar [B][G_dense] and / or C_bar [B][C_dense] (either None: skipped) from dz, adz [B N] and lam, alam [B S K]."""
+        _lib.check(_lib.lib().gato_kkt_grad_blocks(self._h, _ptr(dz), _ptr(lam), _ptr(adz), _ptr(alam), _ptr(Gbar),
+                                                   _ptr(Cbar), self._stream()))
+        return Gbar, Cbar
+
+    def kkt_grad_csr(self, G_row, G_col, C_row, C_col, dz, lam, adz, alam, Gbar_val=None, Cbar_val=None):
+        """The same gradient per CSR value of a pattern the B systems share: Gbar_val [B nnz_G], Cbar_val [B nnz_C]."""
+        _lib.check(_lib.lib().gato_kkt_grad_csr(self._h, _ptr(G_row), _ptr(G_col), G_col.numel(), _ptr(C_row), _ptr(C_col),
+                                                C_col.numel(), _ptr(dz), _ptr(lam), _ptr(adz), _ptr(alam), _ptr(Gbar_val),
+                                                _ptr(Cbar_val), self._stream()))
+        return Gbar_val, Cbar_val
+
     def read_rhs_gamma(self, R: int):
         """Host copy of the re-solve's gamma [B][R][S K] (buffer 11) after a re-solve of R right-hand sides."""
         n = self.batch * int(R) * self.sizes["sk"]

@@ -285,6 +285,8 @@ int gato_cluster_rewind(gato_solver *s);
  * After _blocks the re-solve reads the caller's d_C_blocks again: keep them unchanged until the next whole solve.
  * What invalidates it: gato_convert / gato_form_schur / gato_form_ss given any of the solver's own buffers
  * (gato_solver_buffer) as an output, and gato_cluster_create.  The preconditioner is the one the assembly built. */
+/* Read-only options: assembly_valid (1 while a re-solve has an assembly to read), assembly_gen (whole-solve assemblies so far,
+ * one per successful whole solve, none per re-solve; an int that wraps - compare for equality only). */
 /* Reserve the re-solve work area (gamma, iters) for up to R right-hand sides per system.  Blocking (waits for the device
  * when it grows); only grows. */
 int gato_solver_reserve_rhs(gato_solver *s, int R);
@@ -304,6 +306,26 @@ int gato_linsys_resolve_f32(const float *g, int len_g, const float *c, int len_c
                             float *lambda_out, float *dz_out, int *iters_out);
 int gato_linsys_resolve_f64(const double *g, int len_g, const double *c, int len_c, double exit_tol, int max_iters,
                             double *lambda_out, double *dz_out, int *iters_out);
+
+/* ---- gradients of a solve (new): the backward pass of M [dz; lambda] = [g; c], M = [[G + rho I, C^T],
+ * [C, 0]].  The caller has the forward's dz, lambda and the adjoint [a; beta] = M^-1 [dz_bar; lambda_bar] - a re-solve of the
+ * same assembly (gato_solve_rhs with g = dz_bar, c = lambda_bar: M is symmetric); g_bar = a, c_bar = beta.  These entries form
+ * the matrix gradients from the four vectors alone (no assembly is read, none is needed), asynchronously on `stream`:
+ *   Q_bar_k = -1/2 (a_x,k dz_x,k^T + dz_x,k a_x,k^T), R_bar_k likewise on the u-parts (the gradient for symmetric perturbations
+ *   of Q_k, R_k - the solver treats them as symmetric),  A_bar_k = -(beta_k+1 dz_x,k^T + lambda_k+1 a_x,k^T),
+ *   B_bar_k = -(beta_k+1 dz_u,k^T + lambda_k+1 a_u,k^T)  (A_k, B_k as stored in C_dense: the raw values of C).
+ * Layouts (B = batch): d_dz, d_adz [B][N]; d_lam, d_alam [B][S*K].  GATO_EINVAL for a NULL vector, both outputs NULL, and on a
+ * cluster rank. */
+/* d_Gbar [B][G_dense] and d_Cbar [B][C_dense] in the dense layouts; either may be NULL (skipped). */
+int gato_kkt_grad_blocks(gato_solver *s, const void *d_dz, const void *d_lam, const void *d_adz, const void *d_alam,
+                         void *d_Gbar, void *d_Cbar, void *stream);
+/* The same gradient per value of a CSR pattern the B systems share (as gato_linsys_device_batched takes them): d_Gbar_val
+ * [B][nnz_G], d_Cbar_val [B][nnz_C], either may be NULL.  The exact chain rule through the scatter: an entry gets the block
+ * gradient of the dense slot it is written into - bit for bit what gato_kkt_grad_blocks gives there - and 0 when the scatter
+ * drops it (block row 0 of C, C columns beyond the block row) or a later entry of its row writes the same slot. */
+int gato_kkt_grad_csr(gato_solver *s, const int *d_G_row, const int *d_G_col, int nnz_G, const int *d_C_row, const int *d_C_col,
+                      int nnz_C, const void *d_dz, const void *d_lam, const void *d_adz, const void *d_alam, void *d_Gbar_val,
+                      void *d_Cbar_val, void *stream);
 
 /* ---- direct block input (new): the caller already holds the per-knot blocks in the
  * reference's dense layouts - d_G_blocks as G_dense WITHOUT rho, d_C_blocks as C_dense - so the CSR scatter is
