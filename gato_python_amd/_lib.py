@@ -32,8 +32,18 @@ SYMBOLS = [
     "gato_cluster_knot_range", "gato_cluster_create", "gato_cluster_local_mirror", "gato_cluster_connect",
     "gato_cluster_pcg", "gato_cluster_linsys", "gato_cluster_destroy", "gato_cluster_launches_left", "gato_cluster_rewind", "gato_cluster_fits", "gato_last_stage_ms", "gato_solver_tune",
     "gato_solver_reserve_rhs", "gato_solve_rhs", "gato_linsys_resolve_f32", "gato_linsys_resolve_f64",
-    "gato_kkt_grad_blocks", "gato_kkt_grad_csr",
+    "gato_kkt_grad_blocks", "gato_kkt_grad_csr", "gato_box_qp_default_params", "gato_box_qp_solve",
 ]
+
+
+QP_CONVERGED, QP_MAX_ITERS, QP_NONFINITE, QP_BAD_BOUNDS = 0, 1, 2, 3
+
+
+class BoxQpParams(ct.Structure):
+    """gato_box_qp_params (include/gato_hip.h)."""
+    _fields_ = [("rho", ct.c_double), ("admm_rho", ct.c_double), ("sigma", ct.c_double), ("alpha", ct.c_double),
+                ("eps_abs", ct.c_double), ("eps_rel", ct.c_double), ("exit_tol", ct.c_double), ("max_iters", ct.c_int),
+                ("max_admm_iters", ct.c_int), ("check_every", ct.c_int), ("warm", ct.c_int)]
 
 
 class GatoError(RuntimeError):
@@ -107,6 +117,9 @@ def lib() -> ct.CDLL:
         L.gato_solve_rhs.argtypes = [vp, i, vp, vp, d, i, vp, vp, vp, vp]
         L.gato_kkt_grad_blocks.argtypes = [vp] * 8
         L.gato_kkt_grad_csr.argtypes = [vp, ip, ip, i, ip, ip, i, vp, vp, vp, vp, vp, vp, vp]
+        L.gato_box_qp_default_params.argtypes = [ct.POINTER(BoxQpParams)]
+        L.gato_box_qp_default_params.restype = None
+        L.gato_box_qp_solve.argtypes = [vp] * 7 + [ct.POINTER(BoxQpParams)] + [vp] * 8
         f = ct.c_float
         L.gato_linsys_solve_f32.argtypes = [ip, i, ip, vp, i, ip, i, ip, vp, i, vp, i, vp, i, vp,
                                             i, i, i, i, f, i, i, f, vp, vp, vp, vp]

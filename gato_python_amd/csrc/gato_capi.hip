@@ -1,6 +1,7 @@
 // C ABI of libgato_hip.so (include/gato_hip.h): solver object, stage-level entry points on device
 // pointers, the device-resident whole solve and the host-pointer drop-in for main_call
 // (gpu_library.cu:85-234).
+#include <cmath>
 #include <cstdarg>
 #include <cstdlib>
 #include <mutex>
@@ -62,6 +63,10 @@ static Ops make_ops(int dtype)
                     const void *lam, const void *a, const void *beta, void *Gb, void *Cb, hipStream_t st) {
         return launch_grad_csr<T, S, C>(d, gr, gc, nG, cr, cc, nC, (const T *)dz, (const T *)lam, (const T *)a,
                                         (const T *)beta, (T *)Gb, (T *)Cb, st);
+    };
+    o.qp_prepare = [](const Dims &d, const QpArgs &a, hipStream_t st) { return launch_qp_prepare<T, S, C>(d, a, st); };
+    o.qp_update = [](const Dims &d, const QpArgs &a, int it, int last, hipStream_t st) {
+        return launch_qp_update<T, S, C>(d, a, it, last, st);
     };
     o.pcg_plan = [](PcgPlan *p) { return pcg_resident_plan<T, S>(p); };
     o.pcg_resident = [](const PcgLaunch &a, hipStream_t st) { return launch_pcg_resident<T, S>(a, st); };   // incl. the DPP-row layout
@@ -214,6 +219,9 @@ struct gato_solver {
     char *rhs_ws;                     // re-solve work area: gamma [B][rhs_R][S K] (buffer 11) | iters [B][rhs_R]
     size_t rhs_ws_bytes;
     int rhs_R;                        // right-hand sides per system it has room for
+    char *qp_ws;                      // box-QP work area (gato_box_qp_solve): G' | rho | x ping-pong | g~ | dz | lambda~ | slots | ...
+    size_t qp_ws_bytes;               // only grows
+    int *qp_pcg_total;                // in qp_ws: PCG iterations of every x-step of the latest QP solve, per system [B]
 };
 
 // ---- co-residency gate (A12: check_sms + cudaLaunchCooperativeKernel in the reference, gato_utils.cuh:829-854,
@@ -480,6 +488,7 @@ extern "C" int gato_solver_destroy(gato_solver *s)
         if (s->ev_stage[i]) (void)hipEventDestroy(s->ev_stage[i]);
     if (s->arena) (void)hipFree(s->arena);
     if (s->rhs_ws) (void)hipFree(s->rhs_ws);
+    if (s->qp_ws) (void)hipFree(s->qp_ws);
     if (s->in_arena) (void)hipFree(s->in_arena);
     for (int i = 0; i < 2; ++i)
         if (s->host_ev[i]) (void)hipEventDestroy(s->host_ev[i]);
@@ -503,6 +512,7 @@ extern "C" void *gato_solver_buffer(gato_solver *s, int which)
         case 9: return (unsigned long long *)s->sw.scalars + 8;   // diagnostic stamps (option stamp_pcg)
         case 10: return s->eta_hist;                              // double[max_iters + 1] (option record_eta)
         case 11: return s->rhs_ws;                                // gamma of the re-solves [B][rhs_R][S K] (nullptr: none reserved)
+        case 12: return s->qp_pcg_total;                          // PCG iterations per system of the latest box QP solve [B] (int)
         default: return nullptr;
     }
 }
@@ -606,6 +616,7 @@ extern "C" int gato_solver_get_option(gato_solver *s, const char *name, int *val
     else if (!strcmp(name, "rhs_reserved")) *value = s->rhs_R;
     else if (!strcmp(name, "assembly_valid")) *value = s->as.valid;
     else if (!strcmp(name, "assembly_gen")) *value = (int)s->as.gen;     // wraps: compare for equality only
+    else if (!strcmp(name, "true_warm_start")) *value = s->true_warm_start;
     else if (!strcmp(name, "max_semi_knots"))
         *value = s->plan.semi_threads > 0 ? (s->plan.semi_threads / s->d.S + s->plan.semi_rows * s->plan.semi_threads / s->d.S) * (s->num_cus < 256 ? s->num_cus : 256) : 0;
     else if (!strcmp(name, "max_resident_knots")) *value = s->plan.max_knots_per_wg * (s->num_cus < 256 ? s->num_cus : 256);
@@ -1468,6 +1479,116 @@ extern "C" int gato_kkt_grad_csr(gato_solver *s, const int *d_G_row, const int *
     d.k_lo = d.k_hi = 0; d.rhs = 0;
     return s->ops->grad_csr(d, d_G_row, d_G_col, nnz_G, d_C_row, d_C_col, nnz_C, d_dz, d_lam, d_adz, d_alam, d_Gbar_val,
                             d_Cbar_val, (hipStream_t)stream);
+}
+
+// ---- box-constrained QP by ADMM over the re-solve (gato_qp.hip) ---------------------------------
+extern "C" void gato_box_qp_default_params(gato_box_qp_params *p)
+{
+    if (!p) return;
+    *p = gato_box_qp_params{};
+    p->rho = 0; p->admm_rho = 0.1; p->sigma = 1e-6; p->alpha = 1.6; p->eps_abs = 1e-6; p->eps_rel = 1e-6;
+    p->exit_tol = 1e-6; p->max_iters = 100; p->max_admm_iters = 4000; p->check_every = 25; p->warm = 0;
+}
+
+// One call: prepare, the whole solve on G' (the only assembly), then re-solve + update per iteration and a last launch
+// that only tests.  Frozen systems are never written again, so the outputs do not depend on check_every.
+extern "C" int gato_box_qp_solve(gato_solver *s, const void *d_G_blocks, const void *d_C_blocks, const void *d_g,
+                                 const void *d_c, const void *d_lo, const void *d_hi, const gato_box_qp_params *p, void *d_x,
+                                 void *d_z, void *d_y, void *d_lambda, int *d_iters, int *d_status, double *d_res,
+                                 void *stream)
+{
+    if (!s) { set_error("box_qp_solve: null solver"); return GATO_EINVAL; }
+    if (s->cl.on || s->cl.local) { set_error("box_qp_solve: the solver is a cluster rank; sharded QP solves are not supported"); return GATO_EINVAL; }
+    if (!p || !d_G_blocks || (!d_C_blocks && s->d.K > 1) || !d_g || !d_c || !d_lo || !d_hi || !d_x || !d_z || !d_y ||
+        !d_lambda || !d_iters || !d_status || !d_res) {
+        set_error("box_qp_solve: every pointer is required (d_C_blocks may be NULL only for K = 1)");
+        return GATO_EINVAL;
+    }
+    const bool fin = std::isfinite(p->rho) && std::isfinite(p->admm_rho) && std::isfinite(p->sigma) && std::isfinite(p->alpha) &&
+                     std::isfinite(p->eps_abs) && std::isfinite(p->eps_rel) && std::isfinite(p->exit_tol);
+    if (!fin || p->rho < 0 || !(p->admm_rho > 0) || p->sigma < 0 || !(p->alpha > 0 && p->alpha < 2) || p->eps_abs < 0 ||
+        p->eps_rel < 0 || p->exit_tol < 0 || p->max_iters < 1 || p->max_admm_iters < 1 || p->check_every < 1) {
+        set_error("box_qp_solve: parameters out of range (want finite values, rho >= 0, admm_rho > 0, sigma >= 0, 0 < alpha < 2, "
+                  "eps_abs, eps_rel, exit_tol >= 0, max_iters, max_admm_iters, check_every >= 1)");
+        return GATO_EINVAL;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (stream_is_capturing(st)) {
+        set_error("box_qp_solve: the stream is being captured; the loop reads the live count on the host and cannot be captured");
+        return GATO_EINVAL;
+    }
+    GATO_HIP_CHECK(hipSetDevice(s->device));
+    int rc = gato_solver_reserve_rhs(s, 1);
+    if (rc) return rc;
+    const Dims &d = s->d;
+    const size_t e = s->esz, B = d.B, vN = align_up(B * d.N() * e), vK = align_up(B * d.sk() * e);
+    const size_t o_Gp = 0, o_rho = o_Gp + align_up(B * d.g_dense() * e), o_x0 = o_rho + vN, o_x1 = o_x0 + vN, o_gt = o_x1 + vN;
+    const size_t o_dz = o_gt + vN, o_lt = o_dz + vN, o_sl = o_lt + vK;
+    const size_t o_tot = o_sl + align_up(B * 3 * GATO_QP_NSLOT * 8), o_ctr = o_tot + align_up(B * sizeof(int));
+    const size_t bytes = o_ctr + 256;
+    if (bytes > s->qp_ws_bytes) {
+        char *w = nullptr;
+        GATO_HIP_CHECK(hipStreamSynchronize(st));           // a call still queued on another stream may use the old area
+        GATO_HIP_CHECK(hipDeviceSynchronize());
+        GATO_HIP_CHECK(hipMalloc((void **)&w, bytes));
+        if (s->qp_ws) (void)hipFree(s->qp_ws);
+        s->qp_ws = w; s->qp_ws_bytes = bytes;
+    }
+    char *w = s->qp_ws;
+    int *ctr = (int *)(w + o_ctr);
+    s->qp_pcg_total = (int *)(w + o_tot);
+    GATO_HIP_CHECK(hipMemsetAsync(w + o_sl, 0, o_ctr + 256 - o_sl, st));              // slots, PCG totals, counters
+    GATO_HIP_CHECK(hipMemsetAsync(d_status, 0xff, B * sizeof(int), st));             // -1: running
+    if (p->warm) GATO_HIP_CHECK(hipMemcpyAsync(w + o_lt, d_lambda, B * d.sk() * e, hipMemcpyDeviceToDevice, st));
+    QpArgs a;
+    memset(&a, 0, sizeof(a));
+    a.G = d_G_blocks; a.Cd = d_C_blocks; a.g = d_g; a.c = d_c; a.lo = d_lo; a.hi = d_hi;
+    a.Gp = w + o_Gp; a.rho = w + o_rho; a.x = d_x; a.z = d_z; a.y = d_y; a.lam = d_lambda; a.gt = w + o_gt;
+    a.xt = w + o_dz; a.lt = w + o_lt; a.slots = (unsigned long long *)(w + o_sl);
+    a.status = d_status; a.iters = d_iters; a.ctr = ctr; a.res = d_res; a.pcg_total = (int *)(w + o_tot);
+    a.rho_reg = p->rho; a.admm_rho = p->admm_rho; a.sigma = p->sigma; a.alpha = p->alpha; a.eps_abs = p->eps_abs;
+    a.eps_rel = p->eps_rel; a.warm = p->warm ? 1 : 0;
+    a.xw = w + o_x0;
+    if ((rc = s->ops->qp_prepare(d, a, st))) return rc;
+    int h[2] = {0, 0};
+    GATO_HIP_CHECK(hipMemcpyAsync(h, ctr, sizeof(h), hipMemcpyDeviceToHost, st));
+    GATO_HIP_CHECK(hipStreamSynchronize(st));
+    if (h[1] > 0) {
+        set_error("box_qp_solve: %d bound(s) with lo > hi or NaN; d_status marks the systems (3 = BAD_BOUNDS)", h[1]);
+        return GATO_EINVAL;
+    }
+    const int saved_tws = s->true_warm_start;
+    s->true_warm_start = p->warm ? 1 : 0;              // the first x-step: cold, or from the caller's lambda
+    rc = gato_linsys_device_blocks(s, w + o_Gp, d_C_blocks, w + o_gt, d_c, p->exit_tol, p->max_iters, p->rho, w + o_lt,
+                                   w + o_dz, stream);
+    s->true_warm_start = 1;                            // every later x-step: lambda warm from the previous one
+    int it = 0;
+    for (; rc == GATO_OK; ++it) {
+        a.xr = w + (it % 2 ? o_x1 : o_x0);
+        a.xw = w + (it % 2 ? o_x0 : o_x1);
+        a.pcg_its = it == 0 ? s->iters : rhs_iters(s);
+        if ((rc = s->ops->qp_update(d, a, it, 0, st))) break;
+        if (it + 1 == p->max_admm_iters) {
+            a.xr = a.xw;
+            rc = s->ops->qp_update(d, a, it + 1, 1, st);        // the test of the last iterate only
+            break;
+        }
+        if ((it + 1) % p->check_every == 0) {               // systems still live, after the test of iterate it
+            hipError_t he = hipMemcpyAsync(h, ctr, sizeof(int), hipMemcpyDeviceToHost, st);
+            if (he == hipSuccess) he = hipStreamSynchronize(st);
+            if (he != hipSuccess) {
+                set_error("box_qp_solve: reading the live count failed: %s", hipGetErrorString(he));
+                rc = GATO_EHIP;
+                break;
+            }
+            if (h[0] == 0) break;
+        }
+        rc = gato_solve_rhs(s, 1, w + o_gt, d_c, p->exit_tol, p->max_iters, w + o_lt, w + o_dz, rhs_iters(s), stream);
+    }
+    s->true_warm_start = saved_tws;
+    if (rc) return rc;
+    GATO_HIP_CHECK(hipStreamSynchronize(st));
+    return gato_pcg_status(s, nullptr);
 }
 
 static std::mutex g_cache_mu;

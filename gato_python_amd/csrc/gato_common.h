@@ -308,6 +308,33 @@ int launch_grad_blocks(const Dims &d, const T *dz, const T *lam, const T *a, con
 template <typename T, int S, int C>
 int launch_grad_csr(const Dims &d, const int *G_row, const int *G_col, int nnzG, const int *C_row, const int *C_col, int nnzC,
                     const T *dz, const T *lam, const T *a, const T *beta, T *Gbar, T *Cbar, hipStream_t st);
+// Box-constrained QP by ADMM over the KKT re-solve (gato_qp.hip).  Per-system arrays [B][...]:
+// vectors in the dz layout [B][N] unless noted.  `slots` [B][3][GATO_QP_NSLOT] rotating maxima (bit patterns of
+// non-negative doubles), `status` [B] (-1 while the system runs), `ctr` {live systems, bad bound variables}.
+#define GATO_QP_NSLOT 10
+struct QpArgs {
+    const void *G, *Cd, *g, *c, *lo, *hi;   // the caller's blocks (G without rho, C raw) and vectors; c [B][S K]
+    void *Gp;                               // prepare: G + diag(sigma + rho_i) [B][G_dense]
+    void *rho;                              // penalties rho_i
+    const void *xr;                         // x^k (update: read; neighbours read it too)
+    void *xw;                               // x^k+1 (update) / x^0 (prepare)
+    void *x, *z, *y, *lam;                  // the caller's outputs (z, y, lam also the warm start of prepare); lam [B][S K]
+    void *gt;                               // right-hand side of the next x-step
+    const void *xt;                         // the x-step's solution: dz [B][N] ...
+    void *lt;                               // ... and lambda [B][S K] (written only to zero it after a zero right-hand side)
+    unsigned long long *slots;
+    int *status, *iters, *ctr;
+    double *res;                            // [B][2]
+    const int *pcg_its;                     // update: PCG iterations of the x-step, one per system (nullptr: none)
+    int *pcg_total;                         // [B] PCG iterations of all x-steps of a system so far
+    double rho_reg, admm_rho, sigma, alpha, eps_abs, eps_rel;
+    int warm;
+};
+template <typename T, int S, int C>
+int launch_qp_prepare(const Dims &d, const QpArgs &a, hipStream_t st);
+// iteration `it` of the loop; last = 1: only the convergence test of the iterate the previous launch wrote
+template <typename T, int S, int C>
+int launch_qp_update(const Dims &d, const QpArgs &a, int it, int last, hipStream_t st);
 template <typename T, int S>
 int pcg_resident_plan(PcgPlan *plan);
 template <typename T, int S>
@@ -388,6 +415,8 @@ struct Ops {
     int (*grad_blocks)(const Dims &, const void *, const void *, const void *, const void *, void *, void *, hipStream_t);
     int (*grad_csr)(const Dims &, const int *, const int *, int, const int *, const int *, int, const void *, const void *,
                     const void *, const void *, void *, void *, hipStream_t);
+    int (*qp_prepare)(const Dims &, const QpArgs &, hipStream_t);
+    int (*qp_update)(const Dims &, const QpArgs &, int, int, hipStream_t);
     int (*pcg_plan)(PcgPlan *);
     int (*pcg_resident)(const PcgLaunch &, hipStream_t);
     int (*pcg_dma_max_knots)();

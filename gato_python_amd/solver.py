@@ -17,6 +17,20 @@ from . import _lib
 _TORCH_DT = {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64}
 
 
+class BoxQPResult:
+    """Result of a box-constrained QP solve: x, z, y [.., N], lam [.., S K], iters, status [..] (int32: _lib.QP_*),
+    res_prim, res_dual [..] (float64) - the true QP residuals of the returned iterate."""
+    __slots__ = ("x", "z", "y", "lam", "iters", "status", "res_prim", "res_dual")
+
+    def __init__(self, x, z, y, lam, iters, status, res_prim, res_dual):
+        self.x, self.z, self.y, self.lam = x, z, y, lam
+        self.iters, self.status, self.res_prim, self.res_dual = iters, status, res_prim, res_dual
+
+    def __repr__(self):
+        return (f"BoxQPResult(iters={self.iters.tolist()}, status={self.status.tolist()}, "
+                f"res_prim={self.res_prim.tolist()}, res_dual={self.res_dual.tolist()})")
+
+
 def _ptr(t):
     if t is None:
         return None
@@ -176,6 +190,54 @@ class Solver:
                                                 C_col.numel(), _ptr(dz), _ptr(lam), _ptr(adz), _ptr(alam), _ptr(Gbar_val),
                                                 _ptr(Cbar_val), self._stream()))
         return Gbar_val, Cbar_val
+
+    # ---- box-constrained QP by ADMM over the re-solve (gato_box_qp_solve) ------------------------
+    def box_qp(self, Gb, Cb, g, c, lo, hi, *, rho, exit_tol, max_iters, admm_rho=0.1, sigma=1e-6, alpha=1.6, eps_abs=1e-6,
+               eps_rel=1e-6, max_admm_iters=4000, check_every=25, x=None, z=None, y=None, lam=None, warm=False):
+        """min 1/2 x^T (G + rho I) x - g^T x  s.t.  C x = c,  lo <= x <= hi  for every system of the batch.  Gb [B G_dense]
+        (without rho), Cb [B C_dense], g / lo / hi [B N] (dz layout, +-inf allowed), c [B S K], flat or 2-D device tensors.
+        x, z, y, lam: optional output tensors; warm=True reads z, y and lam (all three required) as the start.  Blocking.
+        Raises ValueError for a NaN bound or lo > hi.  The solver's assembly is the QP's x-step matrix afterwards."""
+        B, N, sk = self.batch, self.N, self.sizes["sk"]
+        if warm and (z is None or y is None or lam is None):
+            raise ValueError("box_qp: warm=True reads z, y and lam: give all three")
+        x = self.new(B * N) if x is None else x
+        z = self.new(B * N) if z is None else z
+        y = self.new(B * N) if y is None else y
+        lam = self.new(B * sk) if lam is None else lam
+        for name, t, n in (("Gb", Gb, B * self.sizes["G_dense"]), ("Cb", Cb, B * self.sizes["C_dense"]), ("g", g, B * N),
+                           ("c", c, B * sk), ("lo", lo, B * N), ("hi", hi, B * N), ("x", x, B * N), ("z", z, B * N),
+                           ("y", y, B * N), ("lam", lam, B * sk)):
+            if t.numel() != n or t.dtype != self.dtype or not t.is_cuda or not t.is_contiguous():
+                raise ValueError(f"box_qp: {name} must be a contiguous {self.dtype} CUDA tensor of {n} entries, got "
+                                 f"{t.dtype} {tuple(t.shape)} on {t.device}")
+        iters = self.new(B, torch.int32)
+        status = self.new(B, torch.int32)
+        res = self.new(2 * B, torch.float64)
+        p = _lib.BoxQpParams()
+        _lib.lib().gato_box_qp_default_params(ct.byref(p))
+        p.rho, p.admm_rho, p.sigma, p.alpha = float(rho), float(admm_rho), float(sigma), float(alpha)
+        p.eps_abs, p.eps_rel, p.exit_tol = float(eps_abs), float(eps_rel), float(exit_tol)
+        p.max_iters, p.max_admm_iters, p.check_every, p.warm = int(max_iters), int(max_admm_iters), int(check_every), int(bool(warm))
+        rc = _lib.lib().gato_box_qp_solve(self._h, _ptr(Gb), _ptr(Cb), _ptr(g), _ptr(c), _ptr(lo), _ptr(hi), ct.byref(p),
+                                          _ptr(x), _ptr(z), _ptr(y), _ptr(lam), _ptr(iters), _ptr(status), _ptr(res),
+                                          self._stream())
+        if rc != 0 and "BAD_BOUNDS" in _lib.lib().gato_last_error().decode():
+            bad = (status.cpu() == _lib.QP_BAD_BOUNDS).nonzero().flatten().tolist()
+            raise ValueError(f"box_qp: systems {bad}: " + _lib.lib().gato_last_error().decode())
+        _lib.check(rc)
+        res = res.view(B, 2)
+        return BoxQPResult(x, z, y, lam, iters, status, res[:, 0], res[:, 1])
+
+    def box_qp_pcg_iters(self):
+        """PCG iterations of all x-steps of the latest box_qp call, per system (host int array)."""
+        out = np.zeros(self.batch, np.int32)
+        torch.cuda.synchronize(self.device)
+        rc = ct.CDLL("libamdhip64.so").hipMemcpy(out.ctypes.data_as(ct.c_void_p), ct.c_void_p(self.buffer_ptr(12)),
+                                                 ct.c_size_t(out.nbytes), 2)
+        if rc != 0:
+            raise RuntimeError(f"hipMemcpy failed: {rc}")
+        return out
 
     def read_rhs_gamma(self, R: int):
         """Host copy of the re-solve's gamma [B][R][S K] (buffer 11) after a re-solve of R right-hand sides."""

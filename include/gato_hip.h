@@ -286,7 +286,8 @@ int gato_cluster_rewind(gato_solver *s);
  * What invalidates it: gato_convert / gato_form_schur / gato_form_ss given any of the solver's own buffers
  * (gato_solver_buffer) as an output, and gato_cluster_create.  The preconditioner is the one the assembly built. */
 /* Read-only options: assembly_valid (1 while a re-solve has an assembly to read), assembly_gen (whole-solve assemblies so far,
- * one per successful whole solve, none per re-solve; an int that wraps - compare for equality only). */
+ * one per successful whole solve, none per re-solve; an int that wraps - compare for equality only).
+ * gato_box_qp_solve assembles its own x-step matrix once per call: a re-solve after it re-solves that matrix. */
 /* Reserve the re-solve work area (gamma, iters) for up to R right-hand sides per system.  Blocking (waits for the device
  * when it grows); only grows. */
 int gato_solver_reserve_rhs(gato_solver *s, int R);
@@ -326,6 +327,46 @@ int gato_kkt_grad_blocks(gato_solver *s, const void *d_dz, const void *d_lam, co
 int gato_kkt_grad_csr(gato_solver *s, const int *d_G_row, const int *d_G_col, int nnz_G, const int *d_C_row, const int *d_C_col,
                       int nnz_C, const void *d_dz, const void *d_lam, const void *d_adz, const void *d_alam, void *d_Gbar_val,
                       void *d_Cbar_val, void *stream);
+
+/* ---- box-constrained QP solves (new): per system b of the batch
+ *     min 1/2 x^T H x - g^T x   s.t.  C x = c,  lo <= x <= hi,      H = G + rho I
+ * by ADMM (the OSQP splitting, the dynamics kept as hard equality constraints) over the re-solve.  The x-step matrix
+ * [[H + sigma I + diag(rho_i), C^T], [C, 0]] is assembled ONCE per call: gato_linsys_device_blocks on G + diag(sigma + rho_i),
+ * with rho_i = 0 on free variables (both bounds infinite), 1e3 admm_rho where lo_i == hi_i, admm_rho otherwise.  Every later
+ * iteration is one gato_solve_rhs with lambda warm from the previous x-step plus one update launch (relaxation alpha,
+ * projection onto the box, dual update, next right-hand side and the true QP residuals).  With all bounds infinite the
+ * solution is the dz / lambda of gato_linsys_device_blocks.
+ * Inputs: d_G_blocks [B][G_dense] WITHOUT rho and d_C_blocks [B][C_dense] (raw values, as _blocks takes them), d_g, d_lo, d_hi
+ * [B][N] (dz layout; +-inf allowed), d_c [B][S*K].  Outputs: d_x, d_z, d_y [B][N], d_lambda [B][S*K], d_iters, d_status [B],
+ * d_res [B][2] = (r_prim, r_dual) of the returned iterate:
+ *     r_prim = max(|x - z|inf, |C x - c|inf),   r_dual = |H x - g + C^T lambda + y|inf
+ * converged when r_prim <= eps_abs + eps_rel max(|x|, |z|, |c|) and r_dual <= eps_abs + eps_rel max(|H x|, |C^T lambda|, |y|, |g|).
+ * y is the multiplier of the box: > 0 at an active upper bound, < 0 at an active lower bound.  iters = the x-steps whose result
+ * is returned.  Status: GATO_QP_CONVERGED, _MAX_ITERS, _NONFINITE (a residual is NaN or inf); there is no infeasibility
+ * detection (an infeasible box ends in MAX_ITERS).  warm = 1: d_z, d_y, d_lambda are also read as the start (z0 = clip(z),
+ * y0 = y with 0 on free variables, lambda seeds the first PCG); warm = 0: z0 = clip(0), y0 = 0, a cold first PCG.
+ * Blocking: the host reads the count of live systems every check_every iterations; a converged system is frozen - never
+ * written again - so the results are bit-identical for every check_every.  The solver's true_warm_start option is set for the
+ * call's own solves and restored.  GATO_EINVAL, nothing enqueued, for a captured stream, a cluster rank, a NULL pointer or a
+ * parameter out of range; GATO_EINVAL after the prepare launch if a bound is NaN or lo > hi (d_status = GATO_QP_BAD_BOUNDS
+ * names those systems; the other outputs are undefined).
+ * Side effect: afterwards the solver's assembly is the QP's x-step matrix - assembly_gen advances by exactly one per call and a
+ * later gato_solve_rhs re-solves that matrix, not the caller's G + rho I.  Buffer 12 (gato_solver_buffer) holds the PCG
+ * iterations of all x-steps of the latest call, per system [B] (int). */
+#define GATO_QP_CONVERGED 0
+#define GATO_QP_MAX_ITERS 1
+#define GATO_QP_NONFINITE 2
+#define GATO_QP_BAD_BOUNDS 3
+typedef struct {
+    double rho, admm_rho, sigma, alpha, eps_abs, eps_rel, exit_tol;
+    int max_iters, max_admm_iters, check_every, warm;
+} gato_box_qp_params;
+/* admm_rho 0.1, sigma 1e-6, alpha 1.6, eps_abs = eps_rel = 1e-6, max_admm_iters 4000, check_every 25, warm 0; rho 0 and
+ * PCG exit_tol 1e-6 / max_iters 100 (set them as for a whole solve) */
+void gato_box_qp_default_params(gato_box_qp_params *p);
+int gato_box_qp_solve(gato_solver *s, const void *d_G_blocks, const void *d_C_blocks, const void *d_g, const void *d_c,
+                      const void *d_lo, const void *d_hi, const gato_box_qp_params *p, void *d_x, void *d_z, void *d_y,
+                      void *d_lambda, int *d_iters, int *d_status, double *d_res /* [B][2] */, void *stream);
 
 /* ---- direct block input (new): the caller already holds the per-knot blocks in the
  * reference's dense layouts - d_G_blocks as G_dense WITHOUT rho, d_C_blocks as C_dense - so the CSR scatter is
