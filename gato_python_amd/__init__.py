@@ -7,6 +7,7 @@ Public surface:
   gato_python_amd.kkt_solve(...)         differentiable solve from math-shaped blocks (torch autograd, autograd.py)
   gato_python_amd.kkt_solve_csr(...)     differentiable solve on device CSR input
   gato_python_amd.box_qp(...)            box-constrained QP (bounds on states and controls) by ADMM over the re-solve
+  gato_python_amd.box_qp_layer(...)      differentiable box-constrained QP: ADMM, then the polish on its active set
   gato_python_amd.synth                  synthetic OCP inputs (the reference ships pendulum data only)
 """
 from .linsys import (clear_problem_size, last_stats, linsys_resolve, linsys_solve, set_precision,  # noqa: F401
@@ -20,7 +21,7 @@ def __getattr__(name):
     if name in ("kkt_solve", "kkt_solve_csr"):
         from . import autograd
         return getattr(autograd, name)
-    if name == "box_qp":
-        from .qp import box_qp
-        return box_qp
+    if name in ("box_qp", "box_qp_layer"):
+        from . import qp
+        return getattr(qp, name)
     raise AttributeError(name)

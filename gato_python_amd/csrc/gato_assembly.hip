@@ -19,6 +19,7 @@
 //    accumulation order.  This is the only place of the hot path where a dense contraction exists.
 // Boundary fixes D1, D2, D4.
 #include "gato_common.h"
+#include "gato_gj.h"
 
 namespace gato {
 namespace {
@@ -71,39 +72,7 @@ __device__ __forceinline__ void mTv(T *out, const T *A, const T *x, int lane)
     }
 }
 
-// ---- register-resident Gauss-Jordan -----------------------------------------------------------------
-__device__ __forceinline__ float readlane_c(float v, int l)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l));
-}
-__device__ __forceinline__ double readlane_c(double v, int l)
-{
-    const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)b, l);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(b >> 32), l);
-    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-}
-
-// lane c < n holds column c of A, lane n + c holds column c of I; on return lane n + c holds column c of A^-1.
-// Same arithmetic as invertMatrix (gato_utils.cuh:468-495): pivot row *= 1/pv, other rows -= col[r]/pv * row.
-template <typename T, int n>
-__device__ __forceinline__ void gj_inverse_reg(T (&col)[n])
-{
-#pragma unroll
-    for (int p = 0; p < n; ++p) {
-        const T pvinv = (T)1 / readlane_c(col[p], p);
-        const T prow = col[p] * pvinv;                       // this lane's element of the scaled pivot row
-#pragma unroll
-        for (int r = 0; r < n; ++r) {
-            if (r != p) {
-                const T f = readlane_c(col[r], p);           // A[r][p], wave-uniform
-                col[r] = gato::fmaT(-f, prow, col[r]);
-            }
-        }
-        col[p] = prow;
-    }
-}
-
+// ---- register-resident Gauss-Jordan: gj_inverse_reg (gato_gj.h) -------------------------------------------------------
 // Inverts the n x n column-major matrix at src (LDS or global) into dst (column-major), one wave, n <= 32.
 template <typename T, int n>
 __device__ __forceinline__ void invert_to(const T *src, T *dst, int lane, T scale)

@@ -68,6 +68,15 @@ static Ops make_ops(int dtype)
     o.qp_update = [](const Dims &d, const QpArgs &a, int it, int last, hipStream_t st) {
         return launch_qp_update<T, S, C>(d, a, it, last, st);
     };
+    o.qp_active = [](const Dims &d, const void *z, const void *y, const void *lo, const void *hi, signed char *act, hipStream_t st) {
+        return launch_qp_active<T, S, C>(d, z, y, lo, hi, act, st);
+    };
+    o.polish_prepare = [](const Dims &d, const PolishArgs &a, hipStream_t st) { return launch_polish_prepare<T, S, C>(d, a, st); };
+    o.polish_finish = [](const Dims &d, const PolishArgs &a, hipStream_t st) { return launch_polish_finish<T, S, C>(d, a, st); };
+    o.qp_bound_grad = [](const Dims &d, const void *G, const void *Cd, const signed char *act, const void *xbar, const void *adz,
+                         const void *beta, void *lo_bar, void *hi_bar, hipStream_t st) {
+        return launch_qp_bound_grad<T, S, C>(d, G, Cd, act, xbar, adz, beta, lo_bar, hi_bar, st);
+    };
     o.pcg_plan = [](PcgPlan *p) { return pcg_resident_plan<T, S>(p); };
     o.pcg_resident = [](const PcgLaunch &a, hipStream_t st) { return launch_pcg_resident<T, S>(a, st); };   // incl. the DPP-row layout
     o.pcg_dma_max_knots = []() { return pcg_dma_max_knots<T, S>(); };
@@ -222,6 +231,8 @@ struct gato_solver {
     char *qp_ws;                      // box-QP work area (gato_box_qp_solve): G' | rho | x ping-pong | g~ | dz | lambda~ | slots | ...
     size_t qp_ws_bytes;               // only grows
     int *qp_pcg_total;                // in qp_ws: PCG iterations of every x-step of the latest QP solve, per system [B]
+    char *pol_ws;                     // polish work area (gato_box_qp_polish): g' | c' | dz' | lambda' | x, z, y polished | slots | count
+    size_t pol_ws_bytes;              // only grows
 };
 
 // ---- co-residency gate (A12: check_sms + cudaLaunchCooperativeKernel in the reference, gato_utils.cuh:829-854,
@@ -489,6 +500,7 @@ extern "C" int gato_solver_destroy(gato_solver *s)
     if (s->arena) (void)hipFree(s->arena);
     if (s->rhs_ws) (void)hipFree(s->rhs_ws);
     if (s->qp_ws) (void)hipFree(s->qp_ws);
+    if (s->pol_ws) (void)hipFree(s->pol_ws);
     if (s->in_arena) (void)hipFree(s->in_arena);
     for (int i = 0; i < 2; ++i)
         if (s->host_ev[i]) (void)hipEventDestroy(s->host_ev[i]);
@@ -1589,6 +1601,123 @@ extern "C" int gato_box_qp_solve(gato_solver *s, const void *d_G_blocks, const v
     if (rc) return rc;
     GATO_HIP_CHECK(hipStreamSynchronize(st));
     return gato_pcg_status(s, nullptr);
+}
+
+// ---- polish of a box QP and its bound gradients (gato_polish.hip) --------------------------------
+extern "C" int gato_box_qp_active_set(gato_solver *s, const void *d_z, const void *d_y, const void *d_lo, const void *d_hi,
+                                      signed char *d_act, void *stream)
+{
+    if (!s) { set_error("box_qp_active_set: null solver"); return GATO_EINVAL; }
+    if (s->cl.on || s->cl.local) { set_error("box_qp_active_set: the solver is a cluster rank; sharded QP solves are not supported"); return GATO_EINVAL; }
+    if (!d_z || !d_y || !d_lo || !d_hi || !d_act) { set_error("box_qp_active_set: every pointer is required"); return GATO_EINVAL; }
+    Dims d = s->d;
+    d.k_lo = d.k_hi = 0; d.rhs = 0;
+    return s->ops->qp_active(d, d_z, d_y, d_lo, d_hi, d_act, (hipStream_t)stream);
+}
+
+// add rho, the masked inversion and shifted right-hand side (polish_prepare), then the stage kernels of the whole solve with
+// the given inverses: Schur, the preconditioner; the PCG and dz follow as in gato_linsys_device_blocks.
+extern "C" int gato_box_qp_polish(gato_solver *s, const void *d_G_blocks, const void *d_C_blocks, const void *d_g, const void *d_c,
+                                  const void *d_lo, const void *d_hi, const signed char *d_act, const gato_box_qp_params *p,
+                                  void *d_x, void *d_z, void *d_y, void *d_lambda, int *d_status, double *d_res, int *d_polish,
+                                  void *stream)
+{
+    if (!s) { set_error("box_qp_polish: null solver"); return GATO_EINVAL; }
+    if (s->cl.on || s->cl.local) { set_error("box_qp_polish: the solver is a cluster rank; sharded QP solves are not supported"); return GATO_EINVAL; }
+    if (!p || !d_G_blocks || (!d_C_blocks && s->d.K > 1) || !d_g || !d_c || !d_lo || !d_hi || !d_act || !d_x || !d_z || !d_y ||
+        !d_lambda || !d_status || !d_res || !d_polish) {
+        set_error("box_qp_polish: every pointer is required (d_C_blocks may be NULL only for K = 1)");
+        return GATO_EINVAL;
+    }
+    const bool fin = std::isfinite(p->rho) && std::isfinite(p->eps_abs) && std::isfinite(p->eps_rel) && std::isfinite(p->exit_tol);
+    if (!fin || p->rho < 0 || p->eps_abs < 0 || p->eps_rel < 0 || p->exit_tol < 0 || p->max_iters < 1) {
+        set_error("box_qp_polish: parameters out of range (want finite values, rho, eps_abs, eps_rel, exit_tol >= 0, max_iters >= 1)");
+        return GATO_EINVAL;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (stream_is_capturing(st)) {
+        set_error("box_qp_polish: the stream is being captured; the polish reads the active-set check on the host and cannot be captured");
+        return GATO_EINVAL;
+    }
+    GATO_HIP_CHECK(hipSetDevice(s->device));
+    const Dims &d = s->d;
+    const size_t e = s->esz, B = d.B, vN = align_up(B * d.N() * e), vK = align_up(B * d.sk() * e);
+    const size_t o_gp = 0, o_cp = o_gp + vN, o_xt = o_cp + vK, o_lt = o_xt + vN, o_xp = o_lt + vK, o_zp = o_xp + vN;
+    const size_t o_yp = o_zp + vN, o_sl = o_yp + vN, o_bad = o_sl + align_up(B * GATO_POLISH_NSLOT * 8);
+    const size_t bytes = o_bad + 256;
+    if (bytes > s->pol_ws_bytes) {
+        char *w = nullptr;
+        GATO_HIP_CHECK(hipStreamSynchronize(st));           // a call still queued on another stream may use the old area
+        GATO_HIP_CHECK(hipDeviceSynchronize());
+        GATO_HIP_CHECK(hipMalloc((void **)&w, bytes));
+        if (s->pol_ws) (void)hipFree(s->pol_ws);
+        s->pol_ws = w; s->pol_ws_bytes = bytes;
+    }
+    char *w = s->pol_ws;
+    int *nbad = (int *)(w + o_bad);
+    GATO_HIP_CHECK(hipMemsetAsync(w + o_sl, 0, bytes - o_sl, st));                   // slots, the BAD_ACTIVE count
+    GATO_HIP_CHECK(hipMemsetAsync(d_polish, 0xff, B * sizeof(int), st));             // -1 until decided
+    PolishArgs a;
+    memset(&a, 0, sizeof(a));
+    a.G = d_G_blocks; a.Cd = d_C_blocks; a.g = d_g; a.c = d_c; a.lo = d_lo; a.hi = d_hi; a.act = d_act;
+    a.Gd = s->G_dense; a.Ginv = s->Ginv; a.gp = w + o_gp; a.cp = w + o_cp; a.xt = w + o_xt; a.lt = w + o_lt;
+    a.xp = w + o_xp; a.zp = w + o_zp; a.yp = w + o_yp; a.slots = (unsigned long long *)(w + o_sl); a.bad = nbad;
+    a.x = d_x; a.z = d_z; a.y = d_y; a.lam = d_lambda; a.status = d_status; a.polish = d_polish; a.res = d_res;
+    a.rho = p->rho; a.eps_abs = p->eps_abs; a.eps_rel = p->eps_rel;
+    // the assembly: the stage path of assemble() with the masked inverses given to the Schur launch
+    int rc;
+    s->d.k_lo = s->d.k_hi = 0;
+    s->last_asm_fused = 0;
+    s->img_fresh = 0;
+    s->as.valid = 0;
+    s->as.img = 0;
+    s->lc.valid = 0;                        // G_dense and Ginv are rewritten: nothing earlier is left to recover
+    if ((rc = s->ops->add_rho(s->d, d_G_blocks, p->rho, s->G_dense, st))) return rc;
+    if ((rc = s->ops->polish_prepare(s->d, a, st))) return rc;
+    int h = 0;
+    GATO_HIP_CHECK(hipMemcpyAsync(&h, nbad, sizeof(int), hipMemcpyDeviceToHost, st));
+    GATO_HIP_CHECK(hipStreamSynchronize(st));
+    if (h > 0) {
+        set_error("box_qp_polish: %d system(s) with an act that is not -1, 0 or 1, names an infinite bound or a state of x_0; "
+                  "d_polish marks them (3 = BAD_ACTIVE)", h);
+        return GATO_EINVAL;
+    }
+    s->d.stair_follows = s->precon_mode == GATO_PRECON_STAIR;
+    rc = s->ops->form_schur(s->d, s->G_dense, d_C_blocks, w + o_gp, w + o_cp, s->Sbd, s->Pbd, s->gamma, s->Ginv, true, st);
+    s->d.stair_follows = 0;
+    if (rc) return rc;
+    if (s->precon_mode == GATO_PRECON_POINT_JACOBI) rc = s->ops->point_jacobi(s->d, s->Sbd, s->Pbd, st);
+    else if (s->precon_mode == GATO_PRECON_STAIR) rc = gato_form_ss(s, s->Sbd, s->Pbd, st);
+    if (rc) return rc;
+    void *lam = w + o_lt, *dz = w + o_xt;
+    const int saved_tws = s->true_warm_start;
+    s->true_warm_start = 0;
+    s->lc = {1, s->Sbd, s->Pbd, s->gamma, d_C_blocks, w + o_gp, lam, dz, p->exit_tol, p->max_iters};
+    s->fz = {s->Ginv, d_C_blocks, w + o_gp, dz};
+    rc = gato_pcg(s, s->Sbd, s->Pbd, s->gamma, lam, p->exit_tol, p->max_iters, s->iters, stream);
+    s->fz = {nullptr, nullptr, nullptr, nullptr};
+    s->true_warm_start = saved_tws;
+    if (rc) return rc;
+    if (!s->dz_fused && (rc = gato_compute_dz(s, s->Ginv, d_C_blocks, w + o_gp, lam, dz, stream))) return rc;
+    s->as = {1, d_C_blocks, 0, s->as.gen + 1};
+    if ((rc = s->ops->polish_finish(s->d, a, st))) return rc;
+    GATO_HIP_CHECK(hipStreamSynchronize(st));
+    return gato_pcg_status(s, nullptr);
+}
+
+extern "C" int gato_box_qp_bound_grad(gato_solver *s, const void *d_G_blocks, const void *d_C_blocks, const signed char *d_act,
+                                      const void *d_xbar, const void *d_a, const void *d_beta, void *d_lo_bar, void *d_hi_bar,
+                                      void *stream)
+{
+    if (!s) { set_error("box_qp_bound_grad: null solver"); return GATO_EINVAL; }
+    if (s->cl.on || s->cl.local) { set_error("box_qp_bound_grad: the solver is a cluster rank; sharded gradients are not supported"); return GATO_EINVAL; }
+    if (!d_G_blocks || (!d_C_blocks && s->d.K > 1) || !d_act || !d_xbar || !d_a || !d_beta || !d_lo_bar || !d_hi_bar) {
+        set_error("box_qp_bound_grad: every pointer is required (d_C_blocks may be NULL only for K = 1)");
+        return GATO_EINVAL;
+    }
+    Dims d = s->d;
+    d.k_lo = d.k_hi = 0; d.rhs = 0;
+    return s->ops->qp_bound_grad(d, d_G_blocks, d_C_blocks, d_act, d_xbar, d_a, d_beta, d_lo_bar, d_hi_bar, (hipStream_t)stream);
 }
 
 static std::mutex g_cache_mu;

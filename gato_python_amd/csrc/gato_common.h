@@ -335,6 +335,34 @@ int launch_qp_prepare(const Dims &d, const QpArgs &a, hipStream_t st);
 // iteration `it` of the loop; last = 1: only the convergence test of the iterate the previous launch wrote
 template <typename T, int S, int C>
 int launch_qp_update(const Dims &d, const QpArgs &a, int it, int last, hipStream_t st);
+// Polish of an ADMM result and the bound gradients of a polished solution (gato_polish.hip).
+// `act` [B][N] int8: +1 at the upper bound, -1 at the lower one, 0 free.  `slots` [B][GATO_POLISH_NSLOT] maxima as in QpArgs.
+#define GATO_POLISH_NSLOT 12
+struct PolishArgs {
+    const void *G, *Cd, *g, *c, *lo, *hi;   // the caller's blocks (G without rho, C raw) and vectors; never written
+    const signed char *act;
+    const void *Gd;                         // prepare: G + rho I (the solver's G_dense)
+    void *Ginv;                             // prepare: the inverses with the active rows and columns zero (the solver's Ginv)
+    void *gp, *cp;                          // prepare: the reduced system's right-hand side g' [B][N], c' [B][S K]
+    const void *xt, *lt;                    // finish: the reduced solve's dz [B][N] and lambda [B][S K]
+    void *xp, *zp, *yp;                     // finish: the polished point [B][N]
+    unsigned long long *slots;              // zeroed before the finish
+    int *bad;                               // prepare: the count of systems with an act that names an infinite bound or x_0
+    void *x, *z, *y, *lam;                  // write-back: the caller's ADMM result, replaced where the polish is accepted
+    int *status, *polish;
+    double *res;                            // [B][2]
+    double rho, eps_abs, eps_rel;
+};
+template <typename T, int S, int C>
+int launch_qp_active(const Dims &d, const void *z, const void *y, const void *lo, const void *hi, signed char *act, hipStream_t st);
+template <typename T, int S, int C>
+int launch_polish_prepare(const Dims &d, const PolishArgs &a, hipStream_t st);
+// the residuals of the polished point, then the acceptance test and the write-back (two launches)
+template <typename T, int S, int C>
+int launch_polish_finish(const Dims &d, const PolishArgs &a, hipStream_t st);
+template <typename T, int S, int C>
+int launch_qp_bound_grad(const Dims &d, const void *G, const void *Cd, const signed char *act, const void *xbar, const void *adz,
+                         const void *beta, void *lo_bar, void *hi_bar, hipStream_t st);
 template <typename T, int S>
 int pcg_resident_plan(PcgPlan *plan);
 template <typename T, int S>
@@ -417,6 +445,11 @@ struct Ops {
                     const void *, const void *, void *, void *, hipStream_t);
     int (*qp_prepare)(const Dims &, const QpArgs &, hipStream_t);
     int (*qp_update)(const Dims &, const QpArgs &, int, int, hipStream_t);
+    int (*qp_active)(const Dims &, const void *, const void *, const void *, const void *, signed char *, hipStream_t);
+    int (*polish_prepare)(const Dims &, const PolishArgs &, hipStream_t);
+    int (*polish_finish)(const Dims &, const PolishArgs &, hipStream_t);
+    int (*qp_bound_grad)(const Dims &, const void *, const void *, const signed char *, const void *, const void *, const void *,
+                         void *, void *, hipStream_t);
     int (*pcg_plan)(PcgPlan *);
     int (*pcg_resident)(const PcgLaunch &, hipStream_t);
     int (*pcg_dma_max_knots)();

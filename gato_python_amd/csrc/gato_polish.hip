@@ -1,0 +1,399 @@
+// Box-QP solution polishing and the bound gradients of a polished solution.
+// From the active set act of an ADMM result the reduced KKT system [[H_FF, C_F^T], [C_F, 0]] (the active variables fixed at
+// their bounds b) is solved exactly on the whole-solve stage path: C's identity blocks are implicit, so an active variable
+// cannot be dropped from C; instead every stage after the inversion reads G only through Ginv, and Ginv' (the inverse of
+// the free sub-blocks, active rows and columns zero) with the shifted right-hand side g' = g - H_:A b_A, c' = c - C_:A b_A
+// gives x'_A = 0 and the reduced solution on F.  Every kernel: one wave per knot, grid.x strides over the knots, grid.y =
+// system, lane i = variable i of the knot.
+#include "gato_common.h"
+#include "gato_gj.h"
+#include "gato_qp_common.h"
+
+namespace gato {
+namespace {
+
+constexpr int WAVE = 64;
+constexpr int NSL = GATO_POLISH_NSLOT;
+// slot fields: the residuals and scales of the ADMM termination test, the largest wrong-sign multiplier, |lambda|
+enum { F_PRIM, F_DUAL, F_X, F_Z, F_C, F_HX, F_CTL, F_Y, F_G, F_SIGN, F_LAM, F_END };
+static_assert(F_END <= NSL, "slot fields");
+
+template <typename T>
+__device__ __forceinline__ T bound_of(signed char act, T lo, T hi) { return act > 0 ? hi : (act < 0 ? lo : (T)0); }
+
+// Row i of knot k of H v and C^T w, the products of qp_update_kernel: (G v)_i + rho v_i and w_k,i (states) + (C_k^T w_k+1)_i.
+// sQ, sR: the knot's G blocks (without rho); sCk: C block k (rows of block row k+1); sV: v of the knot; sLk, sLn: w_k, w_k+1.
+template <typename T, int S, int C>
+__device__ __forceinline__ void row_products(int i, bool next, const T *sQ, const T *sR, const T *sCk, const T *sV, const T *sLk,
+                                             const T *sLn, T rho, T &hx, T &ctl)
+{
+    hx = (T)0;
+    ctl = (T)0;
+    if (i < S) {
+#pragma unroll 4
+        for (int cc = 0; cc < S; ++cc) hx = fmaT(sQ[i + cc * S], sV[cc], hx);
+        ctl = sLk[i];
+    } else {
+#pragma unroll 4
+        for (int cc = 0; cc < C; ++cc) hx = fmaT(sR[(i - S) + cc * C], sV[S + cc], hx);
+    }
+    hx = fmaT(rho, sV[i], hx);
+    if (next) {
+#pragma unroll 4
+        for (int r = 0; r < S; ++r) ctl = fmaT(sCk[r + i * S], sLn[r], ctl);
+    }
+}
+
+// OSQP's rule on (z, y): +1 where hi - z < y, -1 where z - lo < -y, -1 wherever lo == hi, 0 on the states of x_0.
+template <typename T, int S, int C>
+__global__ __launch_bounds__(WAVE) void qp_active_kernel(const T *__restrict__ z, const T *__restrict__ y, const T *__restrict__ lo,
+                                                         const T *__restrict__ hi, signed char *__restrict__ act, int K, BatchStride bs)
+{
+    constexpr int n = S + C;
+    const int lane = threadIdx.x;
+    const size_t o = blockIdx.y * bs.n;
+    for (int k = blockIdx.x; k < K; k += gridDim.x) {
+        if (lane < (k < K - 1 ? n : S)) {
+            const size_t v = o + (size_t)k * n + lane;
+            const T zi = z[v], yi = y[v], l = lo[v], h = hi[v];
+            signed char a = 0;
+            if (h - zi < yi) a = 1;
+            if (zi - l < -yi) a = -1;
+            if (l == h) a = -1;
+            if (k == 0 && lane < S) a = 0;
+            act[v] = a;
+        }
+    }
+}
+
+// Ginv' of the knot (Q_k and R_k with the active rows and columns replaced by the identity, inverted by the assembly's
+// Gauss-Jordan, then the active entries zeroed: with nothing active, the bits of the assembly's own inverse), g' and c'.
+// An act that is not -1 / 0 / 1, names an infinite bound or a state of x_0 counts the system in *bad and sets polish = 3.
+template <typename T, int S, int C>
+__global__ __launch_bounds__(WAVE) void polish_prepare_kernel(PolishArgs a, int K, BatchStride bs)
+{
+    constexpr int n = S + C, SS = S * S, CC = C * C, SN = S * n;
+    __shared__ T sb[2][n];                   // bound values of knots k-1 (0) and k (1), 0 on free variables
+    __shared__ int sa[2][n];                 // active
+    const int lane = threadIdx.x;
+    const size_t sys = blockIdx.y;
+    const T *Gd = (const T *)a.Gd + sys * bs.g, *Cd = (const T *)a.Cd + sys * bs.c;
+    const T *g = (const T *)a.g + sys * bs.n, *c = (const T *)a.c + sys * bs.sk;
+    const T *lo = (const T *)a.lo + sys * bs.n, *hi = (const T *)a.hi + sys * bs.n;
+    const signed char *act = a.act + sys * bs.n;
+    T *Gi = (T *)a.Ginv + sys * bs.g, *gp = (T *)a.gp + sys * bs.n, *cp = (T *)a.cp + sys * bs.sk;
+    int bad = 0;
+    for (int k = blockIdx.x; k < K; k += gridDim.x) {
+        const int nk = k < K - 1 ? n : S;
+        const size_t v0 = (size_t)k * n, gb = (size_t)k * (SS + CC);
+        __syncthreads();                                                     // the previous knot's readers are done
+        if (lane < n) {
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int kk = k - 1 + h;
+                int on = 0;
+                T b = (T)0;
+                if (kk >= 0 && lane < (kk < K - 1 ? n : S)) {
+                    const size_t v = (size_t)kk * n + lane;
+                    const signed char ai = act[v];
+                    on = ai != 0;
+                    b = bound_of(ai, lo[v], hi[v]);
+                    if (h == 1 && (ai < -1 || ai > 1 || (on && !__builtin_isfinite(b)) || (kk == 0 && lane < S && on))) bad = 1;
+                }
+                sa[h][lane] = on;
+                sb[h][lane] = b;
+            }
+        }
+        __syncthreads();
+        {                                                                    // Q_k
+            T col[S];
+#pragma unroll
+            for (int r = 0; r < S; ++r)
+                col[r] = lane < S ? ((sa[1][lane] || sa[1][r]) ? (T)(lane == r) : Gd[gb + lane * S + r]) : (T)(lane - S == r);
+            gj_inverse_reg<T, S>(col);
+            if (lane >= S && lane < 2 * S) {
+                const int cc = lane - S;
+#pragma unroll
+                for (int r = 0; r < S; ++r) Gi[gb + cc * S + r] = (sa[1][cc] || sa[1][r]) ? (T)0 : col[r];
+            }
+        }
+        if (k < K - 1) {                                                     // R_k
+            T col[C];
+#pragma unroll
+            for (int r = 0; r < C; ++r)
+                col[r] = lane < C ? ((sa[1][S + lane] || sa[1][S + r]) ? (T)(lane == r) : Gd[gb + SS + lane * C + r])
+                                  : (T)(lane - C == r);
+            gj_inverse_reg<T, C>(col);
+            if (lane >= C && lane < 2 * C) {
+                const int cc = lane - C;
+#pragma unroll
+                for (int r = 0; r < C; ++r) Gi[gb + SS + cc * C + r] = (sa[1][S + cc] || sa[1][S + r]) ? (T)0 : col[r];
+            }
+        }
+        if (lane < nk) {                                                     // g' = g - H_:A b_A (0 on A: Ginv' ignores it)
+            T t = g[v0 + lane];
+            if (sa[1][lane]) t = (T)0;
+            else if (lane < S) {
+                for (int j = 0; j < S; ++j)
+                    if (sa[1][j]) t = fmaT(-Gd[gb + j * S + lane], sb[1][j], t);
+            } else {
+                for (int j = 0; j < C; ++j)
+                    if (sa[1][S + j]) t = fmaT(-Gd[gb + SS + j * C + (lane - S)], sb[1][S + j], t);
+            }
+            gp[v0 + lane] = t;
+        }
+        if (lane < S) {                                                      // c' = c - C_:A b_A, C's identity included
+            T t = c[(size_t)k * S + lane];
+            if (sa[1][lane]) t -= sb[1][lane];
+            if (k > 0) {
+                const T *Ck = Cd + (size_t)(k - 1) * SN;
+                for (int j = 0; j < n; ++j)
+                    if (sa[0][j]) t = fmaT(-Ck[lane + j * S], sb[0][j], t);
+            }
+            cp[(size_t)k * S + lane] = t;
+        }
+    }
+    if (__any(bad) && lane == 0) {
+        a.polish[sys] = GATO_QP_POLISH_BAD_ACTIVE;
+        atomicAdd(a.bad, 1);
+    }
+}
+
+// The polished point from the reduced solve (x = x' off the active set, the bound on it, z = clip(x), y_A = (g - H x -
+// C^T lambda)_A, y_F = 0, lambda = lambda') and its residuals, folded per system with integer atomicMax on the bit patterns.
+template <typename T, int S, int C>
+__global__ __launch_bounds__(WAVE) void polish_finish_kernel(PolishArgs a, int K, BatchStride bs)
+{
+    constexpr int n = S + C, SS = S * S, CC = C * C, SN = S * n;
+    __shared__ T sQ[SS], sR[CC], sCp[SN], sCk[SN], sXn[n], sXp[n], sLk[S], sLn[S];
+    const int lane = threadIdx.x;
+    const size_t sys = blockIdx.y;
+    const T *G = (const T *)a.G + sys * bs.g, *Cd = (const T *)a.Cd + sys * bs.c;
+    const T *g = (const T *)a.g + sys * bs.n, *c = (const T *)a.c + sys * bs.sk;
+    const T *lo = (const T *)a.lo + sys * bs.n, *hi = (const T *)a.hi + sys * bs.n;
+    const T *xt = (const T *)a.xt + sys * bs.n, *lt = (const T *)a.lt + sys * bs.sk;
+    const signed char *act = a.act + sys * bs.n;
+    T *xp = (T *)a.xp + sys * bs.n, *zp = (T *)a.zp + sys * bs.n, *yp = (T *)a.yp + sys * bs.n;
+    const T rho = (T)a.rho;
+    unsigned long long m[NSL];
+#pragma unroll
+    for (int f = 0; f < NSL; ++f) m[f] = 0;
+    auto fold = [&](int f, T v) { const unsigned long long b = mag_bits(v); m[f] = b > m[f] ? b : m[f]; };
+    for (int k = blockIdx.x; k < K; k += gridDim.x) {
+        const int nk = k < K - 1 ? n : S;
+        const size_t v0 = (size_t)k * n;
+        __syncthreads();
+        const T *Gk = G + (size_t)k * (SS + CC);
+        for (int e = lane; e < SS; e += WAVE) sQ[e] = Gk[e];
+        if (k < K - 1) {
+            for (int e = lane; e < CC; e += WAVE) sR[e] = Gk[SS + e];
+            for (int e = lane; e < SN; e += WAVE) sCk[e] = Cd[(size_t)k * SN + e];
+        }
+        if (k > 0)
+            for (int e = lane; e < SN; e += WAVE) sCp[e] = Cd[(size_t)(k - 1) * SN + e];
+        if (lane < nk) {
+            const size_t v = v0 + lane;
+            const signed char ai = act[v];
+            sXn[lane] = ai != 0 ? bound_of(ai, lo[v], hi[v]) : xt[v];
+        }
+        if (k > 0 && lane < n) {                                            // knot k-1's x (always a full knot)
+            const size_t v = v0 - n + lane;
+            const signed char ai = act[v];
+            sXp[lane] = ai != 0 ? bound_of(ai, lo[v], hi[v]) : xt[v];
+        }
+        if (lane < S) {
+            sLk[lane] = lt[(size_t)k * S + lane];
+            if (k < K - 1) sLn[lane] = lt[(size_t)(k + 1) * S + lane];
+        }
+        __syncthreads();
+        if (lane < nk) {
+            const int i = lane;
+            const size_t v = v0 + i;
+            const signed char ai = act[v];
+            T hx, ctl;
+            row_products<T, S, C>(i, k < K - 1, sQ, sR, sCk, sXn, sLk, sLn, rho, hx, ctl);
+            const T gv = g[v], l = lo[v], h = hi[v], xn = sXn[i];
+            const T zn = clip(xn, l, h);
+            const T yn = ai != 0 ? (gv - hx) - ctl : (T)0;
+            const T rd = (hx - gv) + ctl + yn;
+            xp[v] = xn; zp[v] = zn; yp[v] = yn;
+            fold(F_PRIM, xn - zn);
+            fold(F_DUAL, rd);
+            fold(F_X, xn);
+            fold(F_Z, zn);
+            fold(F_HX, hx);
+            fold(F_CTL, ctl);
+            fold(F_Y, yn);
+            fold(F_G, gv);
+            if (ai != 0 && l != h) {                                        // the multiplier's sign: y >= 0 upper, <= 0 lower
+                const T w = ai > 0 ? -yn : yn;
+                fold(F_SIGN, w > (T)0 ? w : (T)0);
+            }
+            if (i < S) {                                                    // row block k of C x - c
+                const T ci = c[(size_t)k * S + i];
+                T cx = xn;
+                if (k > 0) {
+#pragma unroll 4
+                    for (int j = 0; j < n; ++j) cx = fmaT(sCp[i + j * S], sXp[j], cx);
+                }
+                fold(F_PRIM, cx - ci);
+                fold(F_C, ci);
+                fold(F_LAM, sLk[i]);
+            }
+        }
+    }
+    // the slot only grows: a wave whose maximum it already holds skips the atomic (most waves of a long system: every wave
+    // of it folds into the same eleven words)
+    unsigned long long *sl = a.slots + sys * NSL;
+#pragma unroll
+    for (int f = 0; f < F_END; ++f) {
+        const unsigned long long w = wave_max_bits(m[f]);
+        if (lane == 0 && w != 0 && w > __hip_atomic_load(sl + f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(sl + f, w);
+    }
+}
+
+// The acceptance test of one system (every workgroup of it reads the same complete maxima) and, if it passes, the polished
+// point over the caller's x, z, y, lambda; status CONVERGED and the residuals.  A rejected system is not written.
+template <typename T, int S, int C>
+__global__ __launch_bounds__(WAVE) void polish_writeback_kernel(PolishArgs a, int K, BatchStride bs)
+{
+    constexpr int n = S + C;
+    const int lane = threadIdx.x;
+    const size_t sys = blockIdx.y;
+    const unsigned long long *sl = a.slots + sys * NSL;
+    bool finite = true;
+#pragma unroll
+    for (int f = 0; f < F_END; ++f) finite = finite && __builtin_isfinite(slot_val(sl, f));
+    const double rp = slot_val(sl, F_PRIM), rd = slot_val(sl, F_DUAL);
+    const double sp = fmax(fmax(slot_val(sl, F_X), slot_val(sl, F_Z)), slot_val(sl, F_C));
+    const double sd = fmax(fmax(slot_val(sl, F_HX), slot_val(sl, F_CTL)), fmax(slot_val(sl, F_Y), slot_val(sl, F_G)));
+    const double tol_d = a.eps_abs + a.eps_rel * sd;
+    const bool ok = finite && rp <= a.eps_abs + a.eps_rel * sp && rd <= tol_d && slot_val(sl, F_SIGN) <= tol_d;
+    if (blockIdx.x == 0 && lane == 0) {
+        a.polish[sys] = ok ? GATO_QP_POLISH_ACCEPTED : (finite ? GATO_QP_POLISH_REJECTED : GATO_QP_POLISH_NONFINITE);
+        if (ok) {
+            a.status[sys] = GATO_QP_CONVERGED;
+            a.res[2 * sys] = rp;
+            a.res[2 * sys + 1] = rd;
+        }
+    }
+    if (!ok) return;
+    const T *xp = (const T *)a.xp + sys * bs.n, *zp = (const T *)a.zp + sys * bs.n, *yp = (const T *)a.yp + sys * bs.n;
+    const T *lt = (const T *)a.lt + sys * bs.sk;
+    T *x = (T *)a.x + sys * bs.n, *z = (T *)a.z + sys * bs.n, *y = (T *)a.y + sys * bs.n, *lam = (T *)a.lam + sys * bs.sk;
+    for (int k = blockIdx.x; k < K; k += gridDim.x) {
+        if (lane < (k < K - 1 ? n : S)) {
+            const size_t v = (size_t)k * n + lane;
+            x[v] = xp[v]; z[v] = zp[v]; y[v] = yp[v];
+        }
+        if (lane < S) lam[(size_t)k * S + lane] = lt[(size_t)k * S + lane];
+    }
+}
+
+// b_bar_i = xbar_i - (H a + C^T beta)_i on the active set - the row products of the finish step with rho 0: a_A = 0, so
+// rho a_i vanishes there - to hi_bar where act = +1, to lo_bar where act = -1; 0 in both elsewhere.
+template <typename T, int S, int C>
+__global__ __launch_bounds__(WAVE) void qp_bound_grad_kernel(const T *__restrict__ G, const T *__restrict__ Cd,
+                                                             const signed char *__restrict__ act, const T *__restrict__ xbar,
+                                                             const T *__restrict__ adz, const T *__restrict__ beta,
+                                                             T *__restrict__ lo_bar, T *__restrict__ hi_bar, int K, BatchStride bs)
+{
+    constexpr int n = S + C, SS = S * S, CC = C * C, SN = S * n;
+    __shared__ T sQ[SS], sR[CC], sCk[SN], sV[n], sLk[S], sLn[S];
+    const int lane = threadIdx.x;
+    const size_t sys = blockIdx.y;
+    G += sys * bs.g; Cd += sys * bs.c; act += sys * bs.n; xbar += sys * bs.n; adz += sys * bs.n; beta += sys * bs.sk;
+    lo_bar += sys * bs.n; hi_bar += sys * bs.n;
+    for (int k = blockIdx.x; k < K; k += gridDim.x) {
+        const int nk = k < K - 1 ? n : S;
+        const size_t v0 = (size_t)k * n;
+        __syncthreads();
+        const T *Gk = G + (size_t)k * (SS + CC);
+        for (int e = lane; e < SS; e += WAVE) sQ[e] = Gk[e];
+        if (k < K - 1) {
+            for (int e = lane; e < CC; e += WAVE) sR[e] = Gk[SS + e];
+            for (int e = lane; e < SN; e += WAVE) sCk[e] = Cd[(size_t)k * SN + e];
+        }
+        if (lane < nk) sV[lane] = adz[v0 + lane];
+        if (lane < S) {
+            sLk[lane] = beta[(size_t)k * S + lane];
+            if (k < K - 1) sLn[lane] = beta[(size_t)(k + 1) * S + lane];
+        }
+        __syncthreads();
+        if (lane < nk) {
+            const size_t v = v0 + lane;
+            const signed char ai = act[v];
+            T bb = (T)0;
+            if (ai != 0) {
+                T hx, ctl;
+                row_products<T, S, C>(lane, k < K - 1, sQ, sR, sCk, sV, sLk, sLn, (T)0, hx, ctl);
+                bb = xbar[v] - (hx + ctl);
+            }
+            lo_bar[v] = ai < 0 ? bb : (T)0;
+            hi_bar[v] = ai > 0 ? bb : (T)0;
+        }
+    }
+}
+
+inline int knot_grid(int K) { return K < 8192 ? K : 8192; }
+
+}  // namespace
+
+template <typename T, int S, int C>
+int launch_qp_active(const Dims &d, const void *z, const void *y, const void *lo, const void *hi, signed char *act, hipStream_t st)
+{
+    if (d.B < 1 || d.B > 65535) { set_error("qp_active: B = %d", d.B); return GATO_EINVAL; }
+    hipLaunchKernelGGL((qp_active_kernel<T, S, C>), dim3(knot_grid(d.K), d.B), dim3(WAVE), 0, st, (const T *)z, (const T *)y,
+                       (const T *)lo, (const T *)hi, act, d.K, batch_stride(d));
+    GATO_HIP_CHECK(hipGetLastError());
+    return GATO_OK;
+}
+
+template <typename T, int S, int C>
+int launch_polish_prepare(const Dims &d, const PolishArgs &a, hipStream_t st)
+{
+    if (d.B < 1 || d.B > 65535) { set_error("polish_prepare: B = %d", d.B); return GATO_EINVAL; }
+    hipLaunchKernelGGL((polish_prepare_kernel<T, S, C>), dim3(knot_grid(d.K), d.B), dim3(WAVE), 0, st, a, d.K, batch_stride(d));
+    GATO_HIP_CHECK(hipGetLastError());
+    return GATO_OK;
+}
+
+template <typename T, int S, int C>
+int launch_polish_finish(const Dims &d, const PolishArgs &a, hipStream_t st)
+{
+    if (d.B < 1 || d.B > 65535) { set_error("polish_finish: B = %d", d.B); return GATO_EINVAL; }
+    hipLaunchKernelGGL((polish_finish_kernel<T, S, C>), dim3(knot_grid(d.K), d.B), dim3(WAVE), 0, st, a, d.K, batch_stride(d));
+    GATO_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL((polish_writeback_kernel<T, S, C>), dim3(knot_grid(d.K), d.B), dim3(WAVE), 0, st, a, d.K, batch_stride(d));
+    GATO_HIP_CHECK(hipGetLastError());
+    return GATO_OK;
+}
+
+template <typename T, int S, int C>
+int launch_qp_bound_grad(const Dims &d, const void *G, const void *Cd, const signed char *act, const void *xbar, const void *adz,
+                         const void *beta, void *lo_bar, void *hi_bar, hipStream_t st)
+{
+    if (d.B < 1 || d.B > 65535) { set_error("qp_bound_grad: B = %d", d.B); return GATO_EINVAL; }
+    hipLaunchKernelGGL((qp_bound_grad_kernel<T, S, C>), dim3(knot_grid(d.K), d.B), dim3(WAVE), 0, st, (const T *)G, (const T *)Cd,
+                       act, (const T *)xbar, (const T *)adz, (const T *)beta, (T *)lo_bar, (T *)hi_bar, d.K, batch_stride(d));
+    GATO_HIP_CHECK(hipGetLastError());
+    return GATO_OK;
+}
+
+#define X(S_, C_)                                                                                                            \
+    template int launch_qp_active<float, S_, C_>(const Dims &, const void *, const void *, const void *, const void *,        \
+                                                 signed char *, hipStream_t);                                               \
+    template int launch_qp_active<double, S_, C_>(const Dims &, const void *, const void *, const void *, const void *,       \
+                                                  signed char *, hipStream_t);                                              \
+    template int launch_polish_prepare<float, S_, C_>(const Dims &, const PolishArgs &, hipStream_t);                       \
+    template int launch_polish_prepare<double, S_, C_>(const Dims &, const PolishArgs &, hipStream_t);                      \
+    template int launch_polish_finish<float, S_, C_>(const Dims &, const PolishArgs &, hipStream_t);                        \
+    template int launch_polish_finish<double, S_, C_>(const Dims &, const PolishArgs &, hipStream_t);                       \
+    template int launch_qp_bound_grad<float, S_, C_>(const Dims &, const void *, const void *, const signed char *,          \
+                                                     const void *, const void *, const void *, void *, void *, hipStream_t); \
+    template int launch_qp_bound_grad<double, S_, C_>(const Dims &, const void *, const void *, const signed char *,         \
+                                                      const void *, const void *, const void *, void *, void *, hipStream_t);
+GATO_SHAPES(X)
+#undef X
+
+}  // namespace gato

@@ -4,6 +4,7 @@
 // [[H + sigma I + diag(rho_i), C^T], [C, 0]] is assembled once per QP (the whole solve on G' = G + diag(sigma + rho_i));
 // every iteration after the first is one warm-started re-solve plus one qp_update_kernel launch.
 #include "gato_common.h"
+#include "gato_qp_common.h"
 
 namespace gato {
 namespace {
@@ -12,25 +13,6 @@ constexpr int WAVE = 64;
 constexpr int NSL = GATO_QP_NSLOT;
 // slot fields: the two residuals, then the scales of the tolerance test, then |g~| of the next x-step
 enum { F_PRIM, F_DUAL, F_X, F_Z, F_C, F_HX, F_CTL, F_Y, F_G, F_GT };
-
-template <typename T>
-__device__ __forceinline__ T clip(T v, T lo, T hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// |v| as the bit pattern of a non-negative double: ordered as the values, NaN above +inf, so an integer max is the max
-template <typename T>
-__device__ __forceinline__ unsigned long long mag_bits(T v) { return __builtin_bit_cast(unsigned long long, fabs((double)v)); }
-
-__device__ __forceinline__ unsigned long long wave_max_bits(unsigned long long v)
-{
-#pragma unroll
-    for (int o = WAVE / 2; o > 0; o >>= 1) {
-        const unsigned long long w = __shfl_xor(v, o, WAVE);
-        v = w > v ? w : v;
-    }
-    return v;
-}
-
-__device__ __forceinline__ double slot_val(const unsigned long long *s, int f) { return __builtin_bit_cast(double, s[f]); }
 
 // penalty of one variable: 0 free (both bounds infinite), 1e3 admm_rho for an equality (lo == hi), admm_rho otherwise
 template <typename T>

@@ -3,15 +3,22 @@
     box_qp(Q, R, A, B, q, r, c, x_lo, x_hi, u_lo, u_hi, *, rho, exit_tol, max_iters, ...) -> BoxQPResult
 
 solves  min 1/2 x^T (G + rho I) x - g^T x  s.t.  C x = c,  lo <= x <= hi  - the KKT system of autograd.kkt_solve plus bounds on
-the states and controls - by ADMM over the device re-solve (Solver.box_qp, gato_box_qp_solve).  It is NOT differentiable: the
-inputs are read detached and the outputs carry no grad_fn.  Only device tensors are taken; there is no CPU fallback.
+the states and controls - by ADMM over the device re-solve (Solver.box_qp, gato_box_qp_solve), optionally polished on the ADMM
+result's active set (polish=True).  It is NOT differentiable: the inputs are read detached and the
+outputs carry no grad_fn.
+
+    box_qp_layer(Q, R, A, B, q, r, c, x_lo, x_hi, u_lo, u_hi, *, rho, exit_tol, max_iters, **admm) -> (x, lam, info)
+
+is the differentiable form: ADMM, the active set, the polish; the backward pass is one re-solve of the polish assembly (the
+reduced KKT system) plus the gradient launches.  Only device tensors are taken; there is no CPU fallback.
 """
 from __future__ import annotations
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _lib
-from .autograd import _common, _pack, _solver
+from .autograd import _adjoint, _common, _pack, _solver
 from .solver import BoxQPResult
 
 
@@ -28,13 +35,15 @@ def _bound(v, shape, name, ref):
 
 
 def box_qp(Q, R, A, B, q, r, c, x_lo, x_hi, u_lo, u_hi, *, rho, exit_tol, max_iters, admm_rho=0.1, sigma=1e-6, alpha=1.6,
-           eps_abs=1e-6, eps_rel=1e-6, max_admm_iters=4000, check_every=25, warm=None):
+           eps_abs=1e-6, eps_rel=1e-6, max_admm_iters=4000, check_every=25, warm=None, polish=False):
     """Box-constrained QP from math-shaped blocks, at most one leading batch dimension:
     Q [*,K,S,S], R [*,K-1,C,C], A [*,K-1,S,S], B [*,K-1,S,C], q [*,K,S], r [*,K-1,C], c [*,K,S] as kkt_solve takes them (A, B
     the raw values stored in C: -A and -B of the dynamics), and the bounds x_lo, x_hi [*,K,S], u_lo, u_hi [*,K-1,C] - numbers
     or tensors that broadcast to those shapes, +-inf allowed.  warm: a previous BoxQPResult of the same shape (its z, y and
     lam start the iteration).  Returns a BoxQPResult with flat x, z, y [*, N], lam [*, S K] (dz layout, as kkt_solve returns
-    dz and lam) and iters, status, res_prim, res_dual [*] (scalars unbatched).  Raises ValueError for lo > hi or a NaN bound."""
+    dz and lam) and iters, status, res_prim, res_dual [*] (scalars unbatched).  Raises ValueError for lo > hi or a NaN bound.
+    polish=True: the ADMM result is then polished on its active set (Solver.box_qp_polish): where the polished point passes
+    the termination test it replaces the result (status CONVERGED); result.polished [*] holds the codes (_lib.POLISH_*)."""
     args = dict(Q=Q, R=R, A=A, B=B, q=q, r=r, c=c)
     for name, t in args.items():
         if not isinstance(t, torch.Tensor):
@@ -73,11 +82,139 @@ def box_qp(Q, R, A, B, q, r, c, x_lo, x_hi, u_lo, u_hi, *, rho, exit_tol, max_it
         res = sol.box_qp(Gb, Cb, g, cc, lo, hi, rho=rho, exit_tol=exit_tol, max_iters=max_iters, admm_rho=admm_rho,
                          sigma=sigma, alpha=alpha, eps_abs=eps_abs, eps_rel=eps_rel, max_admm_iters=max_admm_iters,
                          check_every=check_every, warm=warm is not None, **out)
+        if polish:
+            act = sol.box_qp_active_set(res.z, res.y, lo, hi)
+            sol.box_qp_polish(Gb, Cb, g, cc, lo, hi, act, res, rho=rho, exit_tol=exit_tol, max_iters=max_iters,
+                              eps_abs=eps_abs, eps_rel=eps_rel)
+    return _shaped(res, sol, Bt, batched)
+
+
+def _shaped(res, sol, Bt, batched):
     N, sk = sol.N, sol.sizes["sk"]
     shp = lambda t, n: t.view(Bt, n) if batched else t.view(n)
     first = (lambda t: t) if batched else (lambda t: t[0])
     return BoxQPResult(shp(res.x, N), shp(res.z, N), shp(res.y, N), shp(res.lam, sk), first(res.iters), first(res.status),
-                       first(res.res_prim), first(res.res_dual))
+                       first(res.res_prim), first(res.res_dual), None if res.polished is None else first(res.polished))
+
+
+# ---- the differentiable layer -----------------------------------------------------------------------------------------
+class _BoxQPLayer(torch.autograd.Function):
+    """(G_blocks [B, G_dense], C_blocks [B, C_dense], g [B, N], c [B, S K], lo, hi [B, N]) -> (x [B, N], lam [B, S K]) of the
+    polished solution; box[0] receives the BoxQPResult."""
+
+    @staticmethod
+    def forward(ctx, Gb, Cb, g, c, lo, hi, sol, opts, box):
+        res = sol.box_qp(Gb, Cb, g, c, lo, hi, **opts)
+        act = sol.box_qp_active_set(res.z, res.y, lo, hi)
+        pol = dict(rho=opts["rho"], exit_tol=opts["exit_tol"], max_iters=opts["max_iters"], eps_abs=opts["eps_abs"],
+                   eps_rel=opts["eps_rel"])
+        sol.box_qp_polish(Gb, Cb, g, c, lo, hi, act, res, **pol)
+        box.append(res)
+        ctx.sol, ctx.pol, ctx.gen = sol, pol, sol.get_option("assembly_gen")
+        ctx.codes = res.polished.cpu()
+        x, lam = res.x.view(sol.batch, sol.N), res.lam.view(sol.batch, sol.sizes["sk"])
+        ctx.save_for_backward(Gb, Cb, g, c, lo, hi, act, x, lam)
+        ctx.set_materialize_grads(False)
+        return x.clone(), lam.clone()
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, x_bar, lam_bar):
+        Gb, Cb, g, c, lo, hi, act, x, lam = ctx.saved_tensors
+        sol, pol = ctx.sol, ctx.pol
+        none = (None,) * 9
+        if x_bar is None and lam_bar is None:
+            return none
+        xb = torch.zeros_like(x) if x_bar is None else x_bar.to(x.dtype).contiguous()
+        lb = torch.zeros_like(lam) if lam_bar is None else lam_bar.to(lam.dtype).contiguous()
+        live = (xb.ne(0).any(1) | lb.ne(0).any(1)).cpu()
+        unpolished = live & (ctx.codes != _lib.POLISH_ACCEPTED)
+        if unpolished.any():
+            bad = unpolished.nonzero().flatten().tolist()
+            raise RuntimeError(f"box_qp_layer: systems {bad} have a nonzero upstream gradient but their polish was not accepted "
+                               f"(codes {ctx.codes[bad].tolist()}, _lib.POLISH_*): their x and lam are ADMM iterates, which "
+                               "have no gradient here")
+        if not live.any():                   # every system's gradient is exactly zero: no re-solve (its PCG would form 0/0)
+            zero = lambda t, i: torch.zeros_like(t) if ctx.needs_input_grad[i] else None
+            return (zero(Gb, 0), zero(Cb, 1), zero(g, 2), zero(c, 3), zero(lo, 4), zero(hi, 5)) + (None,) * 3
+        if sol.get_option("assembly_gen") != ctx.gen or sol.get_option("assembly_valid") == 0:
+            # another forward replaced the assembly: rebuild the polish assembly from the saved active set (the assembly is a
+            # function of the inputs and act alone; the polished point goes to scratch copies)
+            res2 = torch.empty(sol.batch, 2, dtype=torch.float64, device=x.device)
+            scratch = BoxQPResult(x.clone(), x.clone(), x.clone(), lam.clone(), None,
+                                  torch.empty(sol.batch, dtype=torch.int32, device=x.device), res2[:, 0], res2[:, 1])
+            sol.box_qp_polish(Gb, Cb, g, c, lo, hi, act, scratch, **pol)
+        # the reduced system reads x_bar on the free coordinates only (Ginv' has zero active rows): with those masked, a
+        # system whose upstream gradient lives on its active set alone has a zero right-hand side, and _adjoint's zero
+        # test gives it a = beta = 0 instead of the PCG's 0/0
+        xf = torch.where(act.view_as(xb) != 0, torch.zeros((), dtype=xb.dtype, device=xb.device), xb)
+        a, beta = _adjoint(sol, lam, x, lb, xf, pol["exit_tol"], pol["max_iters"])
+        need = ctx.needs_input_grad
+        Gbar = torch.empty_like(Gb) if need[0] else None
+        Cbar = torch.empty_like(Cb) if need[1] else None
+        if Gbar is not None or Cbar is not None:
+            sol.kkt_grad_blocks(x, lam, a, beta, Gbar, Cbar)
+        lo_bar, hi_bar = (None, None)
+        if need[4] or need[5]:
+            lo_bar, hi_bar = (t.view_as(lo) for t in sol.box_qp_bound_grad(Gb, Cb, act, xb, a, beta))
+        keep = live.to(x.device)[:, None]
+        mask = lambda t: None if t is None else torch.where(keep, t, torch.zeros((), dtype=t.dtype, device=t.device))
+        return (mask(Gbar), mask(Cbar), mask(a) if need[2] else None, mask(beta) if need[3] else None,
+                mask(lo_bar) if need[4] else None, mask(hi_bar) if need[5] else None) + (None,) * 3
+
+
+def _bound_t(v, shape, name, ref):
+    """A bound as a tensor of `shape` that keeps its autograd history (expand sums the gradient of a broadcast bound)."""
+    if not isinstance(v, torch.Tensor):
+        return torch.full(shape, float(v), dtype=ref.dtype, device=ref.device)
+    if v.device != ref.device or v.dtype != ref.dtype:
+        raise ValueError(f"box_qp_layer: {name} must be a {ref.dtype} tensor on {ref.device}, got {v.dtype} on {v.device}")
+    try:
+        return v.expand(shape)
+    except RuntimeError:
+        raise ValueError(f"box_qp_layer: {name} of shape {tuple(v.shape)} does not broadcast to {shape}") from None
+
+
+def box_qp_layer(Q, R, A, B, q, r, c, x_lo, x_hi, u_lo, u_hi, *, rho, exit_tol, max_iters, admm_rho=0.1, sigma=1e-6,
+                 alpha=1.6, eps_abs=1e-6, eps_rel=1e-6, max_admm_iters=4000, check_every=25):
+    """Differentiable box-constrained QP: the inputs of box_qp; returns (x [*, N], lam [*, S K], info) with x and lam those
+    of the polished solution, differentiable with respect to every tensor input (the bounds included; Q and R as symmetric,
+    DESIGN.md section 3.6), and info a detached BoxQPResult (info.polished: the polish codes).  A system whose polish was not
+    accepted returns its ADMM iterate; a backward pass through it with a nonzero upstream gradient raises RuntimeError.
+    rho is not differentiated and double backward is not supported."""
+    args = dict(Q=Q, R=R, A=A, B=B, q=q, r=r, c=c)
+    for name, t in args.items():
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"box_qp_layer: {name} must be a torch.Tensor, got {type(t).__name__}")
+    batched = Q.dim() == 4
+    if Q.dim() not in (3, 4) or Q.shape[-1] != Q.shape[-2] or R.dim() < 2:
+        raise ValueError(f"box_qp_layer: Q must be [*, K, S, S] and R [*, K-1, C, C], got {tuple(Q.shape)} and {tuple(R.shape)}")
+    K, S, C = Q.shape[-3], Q.shape[-1], R.shape[-1]
+    if K < 2:
+        raise ValueError(f"box_qp_layer: K = {K}: at least two knots")
+    lead = (Q.shape[0],) if batched else ()
+    want = dict(Q=(K, S, S), R=(K - 1, C, C), A=(K - 1, S, S), B=(K - 1, S, C), q=(K, S), r=(K - 1, C), c=(K, S))
+    for name, shp in want.items():
+        if tuple(args[name].shape) != lead + shp:
+            raise ValueError(f"box_qp_layer: {name} has shape {tuple(args[name].shape)}, want {lead + shp}")
+    device, dtype = _common(args, "box_qp_layer")
+    xl, xh = (_bound_t(v, lead + (K, S), n, q) for v, n in ((x_lo, "x_lo"), (x_hi, "x_hi")))
+    ul, uh = (_bound_t(v, lead + (K - 1, C), n, q) for v, n in ((u_lo, "u_lo"), (u_hi, "u_hi")))
+    if not batched:
+        Q, R, A, B, q, r, c, xl, xh, ul, uh = (t.unsqueeze(0) for t in (Q, R, A, B, q, r, c, xl, xh, ul, uh))
+    Bt = Q.shape[0]
+    Gb, Cb, g, cc = _pack(Q, R, A, B, q, r, c)
+    lo = torch.cat([torch.cat([xl[:, :K - 1], ul], 2).reshape(Bt, -1), xl[:, K - 1]], 1).contiguous()
+    hi = torch.cat([torch.cat([xh[:, :K - 1], uh], 2).reshape(Bt, -1), xh[:, K - 1]], 1).contiguous()
+    sol = _solver(S, C, K, Bt, dtype, device)
+    opts = dict(rho=float(rho), exit_tol=float(exit_tol), max_iters=int(max_iters), admm_rho=admm_rho, sigma=sigma, alpha=alpha,
+                eps_abs=eps_abs, eps_rel=eps_rel, max_admm_iters=max_admm_iters, check_every=check_every)
+    box = []
+    x, lam = _BoxQPLayer.apply(Gb, Cb, g, cc, lo, hi, sol, opts, box)
+    info = _shaped(box[0], sol, Bt, batched)
+    info = BoxQPResult(*(t.detach().clone() for t in (info.x, info.z, info.y, info.lam, info.iters, info.status, info.res_prim,
+                                                      info.res_dual, info.polished)))
+    return (x, lam, info) if batched else (x[0], lam[0], info)
 
 
 STATUS = {_lib.QP_CONVERGED: "CONVERGED", _lib.QP_MAX_ITERS: "MAX_ITERS", _lib.QP_NONFINITE: "NONFINITE",

@@ -19,16 +19,19 @@ _TORCH_DT = {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.fl
 
 class BoxQPResult:
     """Result of a box-constrained QP solve: x, z, y [.., N], lam [.., S K], iters, status [..] (int32: _lib.QP_*),
-    res_prim, res_dual [..] (float64) - the true QP residuals of the returned iterate."""
-    __slots__ = ("x", "z", "y", "lam", "iters", "status", "res_prim", "res_dual")
+    res_prim, res_dual [..] (float64) - the true QP residuals of the returned iterate - and polished [..] (int32:
+    _lib.POLISH_*; None unless a polish was asked for)."""
+    __slots__ = ("x", "z", "y", "lam", "iters", "status", "res_prim", "res_dual", "polished")
 
-    def __init__(self, x, z, y, lam, iters, status, res_prim, res_dual):
+    def __init__(self, x, z, y, lam, iters, status, res_prim, res_dual, polished=None):
         self.x, self.z, self.y, self.lam = x, z, y, lam
         self.iters, self.status, self.res_prim, self.res_dual = iters, status, res_prim, res_dual
+        self.polished = polished
 
     def __repr__(self):
+        pol = "" if self.polished is None else f", polished={self.polished.tolist()}"
         return (f"BoxQPResult(iters={self.iters.tolist()}, status={self.status.tolist()}, "
-                f"res_prim={self.res_prim.tolist()}, res_dual={self.res_dual.tolist()})")
+                f"res_prim={self.res_prim.tolist()}, res_dual={self.res_dual.tolist()}{pol})")
 
 
 def _ptr(t):
@@ -228,6 +231,68 @@ class Solver:
         _lib.check(rc)
         res = res.view(B, 2)
         return BoxQPResult(x, z, y, lam, iters, status, res[:, 0], res[:, 1])
+
+    # ---- polish of a box QP and its bound gradients (gato_box_qp_polish) --------------------------
+    def _check_vecs(self, what, items):
+        for name, t, n, dt in items:
+            if not isinstance(t, torch.Tensor) or t.numel() != n or t.dtype != dt or not t.is_cuda or not t.is_contiguous():
+                got = f"{t.dtype} {tuple(t.shape)} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
+                raise ValueError(f"{what}: {name} must be a contiguous {dt} CUDA tensor of {n} entries, got {got}")
+
+    def box_qp_active_set(self, z, y, lo, hi, act=None):
+        """The active set of an ADMM result (z, y [B N]) for the box (lo, hi): int8 [B N], +1 upper, -1 lower (and lo ==
+        hi), 0 free and on the states of x_0."""
+        BN = self.batch * self.N
+        act = self.new(BN, torch.int8) if act is None else act
+        self._check_vecs("box_qp_active_set", [(n, t, BN, self.dtype) for n, t in (("z", z), ("y", y), ("lo", lo), ("hi", hi))]
+                         + [("act", act, BN, torch.int8)])
+        _lib.check(_lib.lib().gato_box_qp_active_set(self._h, _ptr(z), _ptr(y), _ptr(lo), _ptr(hi), _ptr(act), self._stream()))
+        return act
+
+    def box_qp_polish(self, Gb, Cb, g, c, lo, hi, act, result, *, rho, exit_tol, max_iters, eps_abs=1e-6, eps_rel=1e-6):
+        """Polish `result` (a BoxQPResult of box_qp on this solver, same inputs) on the active set act [B N] int8: where the
+        polished point passes the test, result's x, z, y, lam, status and residuals are replaced in place; elsewhere not
+        written.  Returns the polish codes int32 [B] (_lib.POLISH_*), also stored as result.polished.  Blocking.  Raises
+        ValueError for an act that names an infinite bound or a state of x_0.  The solver's assembly is the reduced system
+        afterwards (solve_rhs re-solves it)."""
+        B, N, sk = self.batch, self.N, self.sizes["sk"]
+        res = getattr(result.res_prim, "_base", None)        # the [B][2] residual array the two are views of
+        if (res is None or res is not getattr(result.res_dual, "_base", None) or res.numel() != 2 * B
+                or result.res_prim.data_ptr() != res.data_ptr() or res.dtype != torch.float64 or not res.is_contiguous()):
+            raise ValueError("box_qp_polish: result must be the BoxQPResult of Solver.box_qp on this solver")
+        self._check_vecs("box_qp_polish", [
+            ("Gb", Gb, B * self.sizes["G_dense"], self.dtype), ("Cb", Cb, B * self.sizes["C_dense"], self.dtype),
+            ("g", g, B * N, self.dtype), ("c", c, B * sk, self.dtype), ("lo", lo, B * N, self.dtype),
+            ("hi", hi, B * N, self.dtype), ("act", act, B * N, torch.int8), ("x", result.x, B * N, self.dtype),
+            ("z", result.z, B * N, self.dtype), ("y", result.y, B * N, self.dtype), ("lam", result.lam, B * sk, self.dtype),
+            ("status", result.status, B, torch.int32)])
+        p = _lib.BoxQpParams()
+        _lib.lib().gato_box_qp_default_params(ct.byref(p))
+        p.rho, p.eps_abs, p.eps_rel, p.exit_tol, p.max_iters = float(rho), float(eps_abs), float(eps_rel), float(exit_tol), int(max_iters)
+        codes = self.new(B, torch.int32)
+        rc = _lib.lib().gato_box_qp_polish(self._h, _ptr(Gb), _ptr(Cb), _ptr(g), _ptr(c), _ptr(lo), _ptr(hi), _ptr(act), ct.byref(p),
+                                           _ptr(result.x), _ptr(result.z), _ptr(result.y), _ptr(result.lam), _ptr(result.status),
+                                           _ptr(res), _ptr(codes), self._stream())
+        if rc != 0 and "BAD_ACTIVE" in _lib.lib().gato_last_error().decode():
+            bad = (codes.cpu() == _lib.POLISH_BAD_ACTIVE).nonzero().flatten().tolist()
+            raise ValueError(f"box_qp_polish: systems {bad}: " + _lib.lib().gato_last_error().decode())
+        _lib.check(rc)
+        result.polished = codes
+        return codes
+
+    def box_qp_bound_grad(self, Gb, Cb, act, xbar, a, beta, lo_bar=None, hi_bar=None):
+        """(lo_bar, hi_bar) [B N] of a polished solution from its active set, the upstream x_bar and the adjoint (a, beta) of
+        the reduced system (solve_rhs after the polish)."""
+        B, N, sk = self.batch, self.N, self.sizes["sk"]
+        lo_bar = self.new(B * N) if lo_bar is None else lo_bar
+        hi_bar = self.new(B * N) if hi_bar is None else hi_bar
+        self._check_vecs("box_qp_bound_grad", [
+            ("Gb", Gb, B * self.sizes["G_dense"], self.dtype), ("Cb", Cb, B * self.sizes["C_dense"], self.dtype),
+            ("act", act, B * N, torch.int8), ("xbar", xbar, B * N, self.dtype), ("a", a, B * N, self.dtype),
+            ("beta", beta, B * sk, self.dtype), ("lo_bar", lo_bar, B * N, self.dtype), ("hi_bar", hi_bar, B * N, self.dtype)])
+        _lib.check(_lib.lib().gato_box_qp_bound_grad(self._h, _ptr(Gb), _ptr(Cb), _ptr(act), _ptr(xbar), _ptr(a), _ptr(beta),
+                                                     _ptr(lo_bar), _ptr(hi_bar), self._stream()))
+        return lo_bar, hi_bar
 
     def box_qp_pcg_iters(self):
         """PCG iterations of all x-steps of the latest box_qp call, per system (host int array)."""

@@ -368,6 +368,43 @@ int gato_box_qp_solve(gato_solver *s, const void *d_G_blocks, const void *d_C_bl
                       const void *d_lo, const void *d_hi, const gato_box_qp_params *p, void *d_x, void *d_z, void *d_y,
                       void *d_lambda, int *d_iters, int *d_status, double *d_res /* [B][2] */, void *stream);
 
+/* ---- solution polishing of a box QP and gradients through the polished solution (new) ----------
+ * The active set of an ADMM result (OSQP's rule): d_act [B][N] int8, +1 where hi - z < y (upper bound), -1 where
+ * z - lo < -y (lower bound) and wherever lo == hi, 0 otherwise and always on the S states of x_0.  An infinite bound is never
+ * active.  Asynchronous on `stream`.  GATO_EINVAL for a NULL pointer and on a cluster rank. */
+int gato_box_qp_active_set(gato_solver *s, const void *d_z, const void *d_y, const void *d_lo, const void *d_hi, signed char *d_act,
+                           void *stream);
+/* Polish: the exact KKT solution of the QP with the variables of d_act fixed at their bounds (x_A = the bounds bit for bit,
+ * x_F from the reduced system [[H_FF, C_F^T], [C_F, 0]] - one assembly on the stage kernels, one PCG, one dz - and the bound
+ * multipliers y_A = (g - H x - C^T lambda)_A, y_F = 0).  The polished point (x, z = clip(x, lo, hi), y, lambda) is accepted
+ * iff every value is finite, it passes the termination test of gato_box_qp_solve with p's eps_abs and eps_rel, and every
+ * active multiplier has its sign within the dual tolerance (y >= -tol at an upper bound, <= tol at a lower one, any sign
+ * where lo == hi).  An accepted system's d_x, d_z, d_y, d_lambda and d_res are replaced and d_status becomes
+ * GATO_QP_CONVERGED; a rejected one is not written, bit for bit.  d_polish [B] gets the GATO_QP_POLISH_* code per system.
+ * Inputs as gato_box_qp_solve takes them (G without rho); of p only rho, exit_tol, max_iters (the PCG), eps_abs and eps_rel
+ * are read.  The reduced system needs C_F of full row rank (LICQ): a degenerate active set ends in NONFINITE or REJECTED.
+ * Blocking.  GATO_EINVAL, nothing enqueued, for a captured stream, a cluster rank, a NULL pointer or a parameter out of range;
+ * GATO_EINVAL after the prepare launch if an act is not -1, 0 or 1, names an infinite bound or a state of x_0 (d_polish =
+ * GATO_QP_POLISH_BAD_ACTIVE names those systems, -1 the others; no output is written and the solver has no assembly).
+ * Side effect: a whole-solve assembly - assembly_valid = 1, assembly_gen advances by one - of the REDUCED system: a later
+ * gato_solve_rhs re-solves it (its dz is 0 on the active set), which is the adjoint of the backward pass.  The solver's
+ * true_warm_start option is set to 0 for the call's PCG and restored. */
+#define GATO_QP_POLISH_ACCEPTED 0
+#define GATO_QP_POLISH_REJECTED 1
+#define GATO_QP_POLISH_NONFINITE 2
+#define GATO_QP_POLISH_BAD_ACTIVE 3
+int gato_box_qp_polish(gato_solver *s, const void *d_G_blocks, const void *d_C_blocks, const void *d_g, const void *d_c,
+                       const void *d_lo, const void *d_hi, const signed char *d_act, const gato_box_qp_params *p, void *d_x, void *d_z,
+                       void *d_y, void *d_lambda, int *d_status, double *d_res /* [B][2] */, int *d_polish, void *stream);
+/* Bound gradients of a polished solution: with the adjoint [a; beta] of the reduced system (gato_solve_rhs after the polish
+ * with g = x_bar, c = lambda_bar; a is 0 on the active set), b_bar_i = x_bar_i - (H a + C^T beta)_i on the active set goes to
+ * d_hi_bar where act = +1 and to d_lo_bar where act = -1 (lo == hi: to lo; a shift of both bounds together gets b_bar);
+ * 0 in both elsewhere.  g_bar = a, c_bar = beta and the block gradients are gato_kkt_grad_blocks(x, lambda, a, beta).
+ * d_xbar, d_a, d_lo_bar, d_hi_bar [B][N], d_beta [B][S*K].  Asynchronous.  GATO_EINVAL for a NULL pointer (d_C_blocks may be
+ * NULL only for K = 1) and on a cluster rank. */
+int gato_box_qp_bound_grad(gato_solver *s, const void *d_G_blocks, const void *d_C_blocks, const signed char *d_act, const void *d_xbar,
+                           const void *d_a, const void *d_beta, void *d_lo_bar, void *d_hi_bar, void *stream);
+
 /* ---- direct block input (new): the caller already holds the per-knot blocks in the
  * reference's dense layouts - d_G_blocks as G_dense WITHOUT rho, d_C_blocks as C_dense - so the CSR scatter is
  * skipped; rho is added to the diagonals of Q_k, R_k on the way into the solver's workspace.  Otherwise identical
