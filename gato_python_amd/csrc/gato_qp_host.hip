@@ -1,0 +1,206 @@
+// Box-constrained QP (ADMM over the re-solve), its polish and bound gradients: the host side of gato_qp.hip / gato_polish.hip.
+#include <cmath>
+
+#include "gato_solver.h"
+
+// Grow-only work area (qp_ws, pol_ws): waits for everything that may still use the old one before it is replaced.
+static int grow_ws(char **ws, size_t *have, size_t bytes, hipStream_t st)
+{
+    if (bytes <= *have) return GATO_OK;
+    char *w = nullptr;
+    GATO_HIP_CHECK(hipStreamSynchronize(st));           // a call still queued on another stream may use the old area
+    GATO_HIP_CHECK(hipDeviceSynchronize());
+    GATO_HIP_CHECK(hipMalloc((void **)&w, bytes));
+    if (*ws) (void)hipFree(*ws);
+    *ws = w; *have = bytes;
+    return GATO_OK;
+}
+
+// ---- box-constrained QP by ADMM over the re-solve (gato_qp.hip) ---------------------------------
+extern "C" void gato_box_qp_default_params(gato_box_qp_params *p)
+{
+    if (!p) return;
+    *p = gato_box_qp_params{};
+    p->rho = 0; p->admm_rho = 0.1; p->sigma = 1e-6; p->alpha = 1.6; p->eps_abs = 1e-6; p->eps_rel = 1e-6;
+    p->exit_tol = 1e-6; p->max_iters = 100; p->max_admm_iters = 4000; p->check_every = 25; p->warm = 0;
+}
+
+// One call: prepare, the whole solve on G' (the only assembly), then re-solve + update per iteration and a last launch
+// that only tests.  Frozen systems are never written again, so the outputs do not depend on check_every.
+extern "C" int gato_box_qp_solve(gato_solver *s, const void *d_G_blocks, const void *d_C_blocks, const void *d_g,
+                                 const void *d_c, const void *d_lo, const void *d_hi, const gato_box_qp_params *p, void *d_x,
+                                 void *d_z, void *d_y, void *d_lambda, int *d_iters, int *d_status, double *d_res,
+                                 void *stream)
+{
+    if (!solver_usable(s, "box_qp_solve", "QP solves")) return GATO_EINVAL;
+    if (!p || !d_G_blocks || (!d_C_blocks && s->d.K > 1) || !d_g || !d_c || !d_lo || !d_hi || !d_x || !d_z || !d_y ||
+        !d_lambda || !d_iters || !d_status || !d_res) {
+        set_error("box_qp_solve: every pointer is required (d_C_blocks may be NULL only for K = 1)");
+        return GATO_EINVAL;
+    }
+    const bool fin = std::isfinite(p->rho) && std::isfinite(p->admm_rho) && std::isfinite(p->sigma) && std::isfinite(p->alpha) &&
+                     std::isfinite(p->eps_abs) && std::isfinite(p->eps_rel) && std::isfinite(p->exit_tol);
+    if (!fin || p->rho < 0 || !(p->admm_rho > 0) || p->sigma < 0 || !(p->alpha > 0 && p->alpha < 2) || p->eps_abs < 0 ||
+        p->eps_rel < 0 || p->exit_tol < 0 || p->max_iters < 1 || p->max_admm_iters < 1 || p->check_every < 1) {
+        set_error("box_qp_solve: parameters out of range (want finite values, rho >= 0, admm_rho > 0, sigma >= 0, 0 < alpha < 2, "
+                  "eps_abs, eps_rel, exit_tol >= 0, max_iters, max_admm_iters, check_every >= 1)");
+        return GATO_EINVAL;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (stream_is_capturing(st)) {
+        set_error("box_qp_solve: the stream is being captured; the loop reads the live count on the host and cannot be captured");
+        return GATO_EINVAL;
+    }
+    GATO_HIP_CHECK(hipSetDevice(s->device));
+    int rc = gato_solver_reserve_rhs(s, 1);
+    if (rc) return rc;
+    const Dims &d = s->d;
+    const size_t e = s->esz, B = d.B, vN = align_up(B * d.N() * e), vK = align_up(B * d.sk() * e);
+    const size_t o_Gp = 0, o_rho = o_Gp + align_up(B * d.g_dense() * e), o_x0 = o_rho + vN, o_x1 = o_x0 + vN, o_gt = o_x1 + vN;
+    const size_t o_dz = o_gt + vN, o_lt = o_dz + vN, o_sl = o_lt + vK;
+    const size_t o_tot = o_sl + align_up(B * 3 * GATO_QP_NSLOT * 8), o_ctr = o_tot + align_up(B * sizeof(int));
+    const size_t bytes = o_ctr + 256;
+    if ((rc = grow_ws(&s->qp_ws, &s->qp_ws_bytes, bytes, st))) return rc;
+    char *w = s->qp_ws;
+    int *ctr = (int *)(w + o_ctr);
+    s->qp_pcg_total = (int *)(w + o_tot);
+    GATO_HIP_CHECK(hipMemsetAsync(w + o_sl, 0, o_ctr + 256 - o_sl, st));              // slots, PCG totals, counters
+    GATO_HIP_CHECK(hipMemsetAsync(d_status, 0xff, B * sizeof(int), st));             // -1: running
+    if (p->warm) GATO_HIP_CHECK(hipMemcpyAsync(w + o_lt, d_lambda, B * d.sk() * e, hipMemcpyDeviceToDevice, st));
+    QpArgs a;
+    memset(&a, 0, sizeof(a));
+    a.G = d_G_blocks; a.Cd = d_C_blocks; a.g = d_g; a.c = d_c; a.lo = d_lo; a.hi = d_hi;
+    a.Gp = w + o_Gp; a.rho = w + o_rho; a.x = d_x; a.z = d_z; a.y = d_y; a.lam = d_lambda; a.gt = w + o_gt;
+    a.xt = w + o_dz; a.lt = w + o_lt; a.slots = (unsigned long long *)(w + o_sl);
+    a.status = d_status; a.iters = d_iters; a.ctr = ctr; a.res = d_res; a.pcg_total = (int *)(w + o_tot);
+    a.rho_reg = p->rho; a.admm_rho = p->admm_rho; a.sigma = p->sigma; a.alpha = p->alpha; a.eps_abs = p->eps_abs;
+    a.eps_rel = p->eps_rel; a.warm = p->warm ? 1 : 0;
+    a.xw = w + o_x0;
+    if ((rc = s->ops->qp_prepare(d, a, st))) return rc;
+    int h[2] = {0, 0};
+    GATO_HIP_CHECK(hipMemcpyAsync(h, ctr, sizeof(h), hipMemcpyDeviceToHost, st));
+    GATO_HIP_CHECK(hipStreamSynchronize(st));
+    if (h[1] > 0) {
+        set_error("box_qp_solve: %d bound(s) with lo > hi or NaN; d_status marks the systems (3 = BAD_BOUNDS)", h[1]);
+        return GATO_EINVAL;
+    }
+    PcgOpts o = pcg_opts(*s);
+    o.warm = p->warm ? 1 : 0;                          // the first x-step: cold, or from the caller's lambda
+    const AsmInput in{2, nullptr, nullptr, w + o_Gp, nullptr, nullptr, nullptr, d_C_blocks, false};
+    if ((rc = whole_solve(s, o, in, w + o_gt, d_c, p->exit_tol, p->max_iters, p->rho, w + o_lt, w + o_dz, st))) return rc;
+    o.warm = 1;                                        // every later x-step: lambda warm from the previous one
+    for (int it = 0;; ++it) {
+        a.xr = w + (it % 2 ? o_x1 : o_x0);
+        a.xw = w + (it % 2 ? o_x0 : o_x1);
+        a.pcg_its = it == 0 ? s->iters : rhs_iters(s);
+        if ((rc = s->ops->qp_update(d, a, it, 0, st))) return rc;
+        if (it + 1 == p->max_admm_iters) {
+            a.xr = a.xw;
+            if ((rc = s->ops->qp_update(d, a, it + 1, 1, st))) return rc;        // the test of the last iterate only
+            break;
+        }
+        if ((it + 1) % p->check_every == 0) {               // systems still live, after the test of iterate it
+            hipError_t he = hipMemcpyAsync(h, ctr, sizeof(int), hipMemcpyDeviceToHost, st);
+            if (he == hipSuccess) he = hipStreamSynchronize(st);
+            if (he != hipSuccess) {
+                set_error("box_qp_solve: reading the live count failed: %s", hipGetErrorString(he));
+                return GATO_EHIP;
+            }
+            if (h[0] == 0) break;
+        }
+        if ((rc = solve_rhs(s, o, 1, w + o_gt, d_c, p->exit_tol, p->max_iters, w + o_lt, w + o_dz, rhs_iters(s), st))) return rc;
+    }
+    GATO_HIP_CHECK(hipStreamSynchronize(st));
+    return gato_pcg_status(s, nullptr);
+}
+
+// ---- polish of a box QP and its bound gradients (gato_polish.hip) --------------------------------
+extern "C" int gato_box_qp_active_set(gato_solver *s, const void *d_z, const void *d_y, const void *d_lo, const void *d_hi,
+                                      signed char *d_act, void *stream)
+{
+    if (!solver_usable(s, "box_qp_active_set", "QP solves")) return GATO_EINVAL;
+    if (!d_z || !d_y || !d_lo || !d_hi || !d_act) { set_error("box_qp_active_set: every pointer is required"); return GATO_EINVAL; }
+    Dims d = s->d;
+    d.k_lo = d.k_hi = 0; d.rhs = 0;
+    return s->ops->qp_active(d, d_z, d_y, d_lo, d_hi, d_act, (hipStream_t)stream);
+}
+
+// add rho, the masked inversion and shifted right-hand side (polish_prepare), then the stage kernels of the whole solve with
+// the given inverses: Schur, the preconditioner; the PCG and dz follow as in gato_linsys_device_blocks.
+extern "C" int gato_box_qp_polish(gato_solver *s, const void *d_G_blocks, const void *d_C_blocks, const void *d_g, const void *d_c,
+                                  const void *d_lo, const void *d_hi, const signed char *d_act, const gato_box_qp_params *p,
+                                  void *d_x, void *d_z, void *d_y, void *d_lambda, int *d_status, double *d_res, int *d_polish,
+                                  void *stream)
+{
+    if (!solver_usable(s, "box_qp_polish", "QP solves")) return GATO_EINVAL;
+    if (!p || !d_G_blocks || (!d_C_blocks && s->d.K > 1) || !d_g || !d_c || !d_lo || !d_hi || !d_act || !d_x || !d_z || !d_y ||
+        !d_lambda || !d_status || !d_res || !d_polish) {
+        set_error("box_qp_polish: every pointer is required (d_C_blocks may be NULL only for K = 1)");
+        return GATO_EINVAL;
+    }
+    const bool fin = std::isfinite(p->rho) && std::isfinite(p->eps_abs) && std::isfinite(p->eps_rel) && std::isfinite(p->exit_tol);
+    if (!fin || p->rho < 0 || p->eps_abs < 0 || p->eps_rel < 0 || p->exit_tol < 0 || p->max_iters < 1) {
+        set_error("box_qp_polish: parameters out of range (want finite values, rho, eps_abs, eps_rel, exit_tol >= 0, max_iters >= 1)");
+        return GATO_EINVAL;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (stream_is_capturing(st)) {
+        set_error("box_qp_polish: the stream is being captured; the polish reads the active-set check on the host and cannot be captured");
+        return GATO_EINVAL;
+    }
+    GATO_HIP_CHECK(hipSetDevice(s->device));
+    const Dims &d = s->d;
+    const size_t e = s->esz, B = d.B, vN = align_up(B * d.N() * e), vK = align_up(B * d.sk() * e);
+    const size_t o_gp = 0, o_cp = o_gp + vN, o_xt = o_cp + vK, o_lt = o_xt + vN, o_xp = o_lt + vK, o_zp = o_xp + vN;
+    const size_t o_yp = o_zp + vN, o_sl = o_yp + vN, o_bad = o_sl + align_up(B * GATO_POLISH_NSLOT * 8);
+    const size_t bytes = o_bad + 256;
+    int rc;
+    if ((rc = grow_ws(&s->pol_ws, &s->pol_ws_bytes, bytes, st))) return rc;
+    char *w = s->pol_ws;
+    int *nbad = (int *)(w + o_bad);
+    GATO_HIP_CHECK(hipMemsetAsync(w + o_sl, 0, bytes - o_sl, st));                   // slots, the BAD_ACTIVE count
+    GATO_HIP_CHECK(hipMemsetAsync(d_polish, 0xff, B * sizeof(int), st));             // -1 until decided
+    PolishArgs a;
+    memset(&a, 0, sizeof(a));
+    a.G = d_G_blocks; a.Cd = d_C_blocks; a.g = d_g; a.c = d_c; a.lo = d_lo; a.hi = d_hi; a.act = d_act;
+    a.Gd = s->G_dense; a.Ginv = s->Ginv; a.gp = w + o_gp; a.cp = w + o_cp; a.xt = w + o_xt; a.lt = w + o_lt;
+    a.xp = w + o_xp; a.zp = w + o_zp; a.yp = w + o_yp; a.slots = (unsigned long long *)(w + o_sl); a.bad = nbad;
+    a.x = d_x; a.z = d_z; a.y = d_y; a.lam = d_lambda; a.status = d_status; a.polish = d_polish; a.res = d_res;
+    a.rho = p->rho; a.eps_abs = p->eps_abs; a.eps_rel = p->eps_rel;
+    // the assembly: add rho and the masked inversion here, then the stage path of the whole solve with the inverses given
+    s->d.k_lo = s->d.k_hi = 0;
+    s->as.valid = 0;
+    s->lc.valid = 0;                        // G_dense and Ginv are rewritten: nothing earlier is left to recover
+    if ((rc = s->ops->add_rho(s->d, d_G_blocks, p->rho, s->G_dense, st))) return rc;
+    if ((rc = s->ops->polish_prepare(s->d, a, st))) return rc;
+    int h = 0;
+    GATO_HIP_CHECK(hipMemcpyAsync(&h, nbad, sizeof(int), hipMemcpyDeviceToHost, st));
+    GATO_HIP_CHECK(hipStreamSynchronize(st));
+    if (h > 0) {
+        set_error("box_qp_polish: %d system(s) with an act that is not -1, 0 or 1, names an infinite bound or a state of x_0; "
+                  "d_polish marks them (3 = BAD_ACTIVE)", h);
+        return GATO_EINVAL;
+    }
+    PcgOpts o = pcg_opts(*s);
+    o.warm = 0;                             // always a cold start
+    const AsmInput in{2, nullptr, nullptr, d_G_blocks, nullptr, nullptr, nullptr, d_C_blocks, true};
+    if ((rc = whole_solve(s, o, in, w + o_gp, w + o_cp, p->exit_tol, p->max_iters, p->rho, w + o_lt, w + o_xt, st))) return rc;
+    if ((rc = s->ops->polish_finish(s->d, a, st))) return rc;
+    GATO_HIP_CHECK(hipStreamSynchronize(st));
+    return gato_pcg_status(s, nullptr);
+}
+
+extern "C" int gato_box_qp_bound_grad(gato_solver *s, const void *d_G_blocks, const void *d_C_blocks, const signed char *d_act,
+                                      const void *d_xbar, const void *d_a, const void *d_beta, void *d_lo_bar, void *d_hi_bar,
+                                      void *stream)
+{
+    if (!solver_usable(s, "box_qp_bound_grad", "gradients")) return GATO_EINVAL;
+    if (!d_G_blocks || (!d_C_blocks && s->d.K > 1) || !d_act || !d_xbar || !d_a || !d_beta || !d_lo_bar || !d_hi_bar) {
+        set_error("box_qp_bound_grad: every pointer is required (d_C_blocks may be NULL only for K = 1)");
+        return GATO_EINVAL;
+    }
+    Dims d = s->d;
+    d.k_lo = d.k_hi = 0; d.rhs = 0;
+    return s->ops->qp_bound_grad(d, d_G_blocks, d_C_blocks, d_act, d_xbar, d_a, d_beta, d_lo_bar, d_hi_bar, (hipStream_t)stream);
+}
+

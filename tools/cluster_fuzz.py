@@ -2,7 +2,7 @@
 type, workgroup size - every PCG solve against the C oracle (default recurrence) or the numpy restatement of the single-reduction
 recurrence, every whole sharded solve (gato_cluster_linsys) against the oracle's whole solve.  Prints the failing case, if any.
 Solvers and clusters are created and destroyed case after case in one process, so the run also covers what one cluster leaves
-behind for the next (round 5: recycled uncached mirrors, gato_capi.hip mirror_take; FUZZ_ONLY=29,30,31 with seed 1 was the
+behind for the next (round 5: recycled uncached mirrors, gato_cluster.hip mirror_take; FUZZ_ONLY=29,30,31 with seed 1 was the
 shortest sequence that showed it).
       python tools/cluster_fuzz.py [cases] [seed]          FUZZ_ONLY=i,j,...: draw every case, run only these"""
 import os, sys
@@ -72,7 +72,8 @@ def case(rng, i, only=None):
         ok = ok and got_it[0] == it_c and rel(lam.cpu().numpy(), lam_c) < 1e-7 and rel(lam.cpu().numpy(), lam_o) < 1e-5
     else:
         ok = ok and got_it[0] == it_o and rel(lam.cpu().numpy(), lam_o) < 1e-8
-    msg = f"{tag} ran_variant={ran} groups={[x.get_option('last_groups') for x in sols]} iters={got_it} (oracle {it_o}) rel {rel(lam.cpu().numpy(), lam_o):.1e}"
+    geo = " ".join(f"{n}={[x.get_option('last_' + n) for x in sols]}" for n in ("groups", "threads", "semi", "dpp", "cluster_flat"))
+    msg = f"{tag} ran_variant={ran} {geo} iters={got_it} (oracle {it_o}) rel {rel(lam.cpu().numpy(), lam_o):.1e}"
     # whole sharded solve through the one-call entry
     d = sols[0].upload_system(s)
     lams = [torch.full((S * K,), float("nan"), dtype=torch.float64, device="cuda") for _ in range(R)]

@@ -1,5 +1,5 @@
 """where the LDS-DMA ring (pcg_semi = 3) overtakes the semi-resident launch (1) and the launch without
-resident rows (2), per dtype and STATE_SIZE - the numbers behind the auto rule in plan_resident_k (gato_capi.hip).
+resident rows (2), per dtype and STATE_SIZE - the numbers behind the auto rule in plan_resident (gato_plan.hip).
 usage: ring_crossover.py [f64|f32|s32|s32f64]    (us per PCG iteration, 20 iterations, median of 5)"""
 import os, sys
 import numpy as np

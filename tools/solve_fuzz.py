@@ -143,7 +143,8 @@ def run_gpu(s, p, systems):
         torch.cuda.synchronize()
         sol.check_status()
         what = f"mode {sol.get_option('last_mode')} groups {sol.get_option('last_groups')} threads {sol.get_option('last_threads')} " \
-               f"semi {sol.get_option('last_semi')} variant {sol.get_option('last_variant')} fallback {sol.get_option('last_fallback')}"
+               f"semi {sol.get_option('last_semi')} variant {sol.get_option('last_variant')} fallback {sol.get_option('last_fallback')} " \
+               + " ".join(f"{n} {sol.get_option('last_' + n)}" for n in ("pair", "dpp", "dz_fused", "image", "asm_fused"))
         ran_variant = sol.get_option("last_variant")
         return lam.cpu().numpy(), dz.cpu().numpy(), (its.cpu().numpy() if its is not None else None), what, ran_variant
     finally:
