@@ -368,9 +368,9 @@ int pcg_resident_plan(PcgPlan *plan);
 template <typename T, int S>
 int launch_pcg_resident(const PcgLaunch &a, hipStream_t st);
 template <typename T, int S>
-int launch_pcg_resident_dpp(const PcgLaunch &a, hipStream_t st);      // gato_pcg_resident_dpp.hip; called by launch_pcg_resident
+int launch_pcg_resident_dpp(const PcgLaunch &a, hipStream_t st);      // gato_pcg_resident_dpp.hip (DPP-row instantiations); called by launch_pcg_resident
 template <typename T, int S>
-int launch_pcg_single(const PcgLaunch &a, bool mr, hipStream_t st);   // gato_pcg_resident_single.hip; called by launch_pcg_resident
+int launch_pcg_single(const PcgLaunch &a, bool mr, hipStream_t st);   // gato_pcg_resident_single.hip (the one-workgroup kernels); called by launch_pcg_resident
 template <typename T, int S> int pcg_dma_max_knots();          // knots per workgroup of the LDS-DMA variant (0: none for this shape)
 template <typename T, int S>
 int launch_pcg_dma(const PcgLaunch &a, hipStream_t st);

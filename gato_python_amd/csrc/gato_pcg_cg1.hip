@@ -17,6 +17,7 @@
 // takes r two knots deep on each side, which every workgroup advances locally (ghost_s = ghost_w + beta ghost_s,
 // ghost_r -= alpha ghost_s) from the neighbours' first/last TWO blocks of w - the only vector data in the hand-off.
 #include "gato_pcg_device.h"
+#include "gato_pcg_launch.h"
 
 namespace gato {
 namespace {
@@ -496,13 +497,8 @@ int launch_pcg_cg1(const PcgLaunch &a0, hipStream_t st)
     constexpr int MAXT = Cg1Threads<T, S>::v;
     const bool mr = a0.xslots != nullptr;                   // one rank of a cluster launch
     PcgLaunch a = a0;
-    if (!mr) { a.k_begin = 0; a.k_end = a.K; a.rank = 0; a.nranks = 1; }
-    const int Kl = a.k_end - a.k_begin;                     // knots this launch works on
-    if (mr && (a.batch > 1 || a.xcd_pack || a.nranks < 1 || a.nranks > GATO_MAX_RANKS || a.rank < 0 || a.rank >= a.nranks ||
-               a.k_begin < 0 || Kl < 1 || a.k_end > a.K || (a.rank == 0) != (a.k_begin == 0) || (a.rank == a.nranks - 1) != (a.k_end == a.K))) {
-        set_error("pcg_cg1(cluster): bad shard rank=%d/%d knots [%d,%d) of %d", a.rank, a.nranks, a.k_begin, a.k_end, a.K);
-        return GATO_EINVAL;
-    }
+    int Kl;                                                 // knots this launch works on
+    if (pcg_shard(a, mr, a.batch > 1 || a.xcd_pack, "pcg_cg1", &Kl) != GATO_OK) return GATO_EINVAL;
     const int lanes_needed = (a.knots_per_wg + 2) * S;
     // (every workgroup hands its first / last TWO blocks of w to its neighbours: two knots each, whenever the solve has neighbours)
     const bool neighbours = a.groups > 1 || (mr && a.nranks > 1);
@@ -513,7 +509,7 @@ int launch_pcg_cg1(const PcgLaunch &a0, hipStream_t st)
         a.split_extra = Kl - a.groups * (a.knots_per_wg - 1);
     const bool balanced = a.split_extra > 0;
     if (a.threads > MAXT || a.threads % 64 != 0 || a.threads < 4 * S || lanes_needed > a.threads || a.groups < 1 ||
-        a.groups > 256 || (long long)a.groups * a.knots_per_wg < Kl || (long long)(a.groups - 1) * a.knots_per_wg >= Kl ||
+        a.groups > 256 || !pcg_groups_cover(a, Kl) ||
         (balanced && (a.split_extra >= a.groups || a.split_extra * a.knots_per_wg + (a.groups - a.split_extra) * (a.knots_per_wg - 1) != Kl)) ||
         (neighbours && !balanced && (a.knots_per_wg < 2 || Kl - (a.groups - 1) * a.knots_per_wg < 2))) {
         set_error("pcg_cg1: bad launch geometry (K=%d groups=%d knots/wg=%d threads=%d max=%d)", Kl, a.groups,
@@ -521,13 +517,8 @@ int launch_pcg_cg1(const PcgLaunch &a0, hipStream_t st)
         return GATO_EINVAL;
     }
     if (a.batch > 1 && a.groups != 1) { set_error("pcg_cg1: a batch needs one workgroup per system"); return GATO_EINVAL; }
-    if (a.ev_start) GATO_HIP_CHECK(hipEventRecord(a.ev_start, st));
     const int nblocks = a.batch > 1 ? a.batch : (a.xcd_pack > 0 ? 8 * ((a.groups + a.xcd_pack - 1) / a.xcd_pack) : a.groups);
-    if (mr) hipLaunchKernelGGL((pcg_cg1_kernel<T, S, MAXT, true>), dim3(nblocks), dim3(a.threads), 0, st, a);
-    else hipLaunchKernelGGL((pcg_cg1_kernel<T, S, MAXT>), dim3(nblocks), dim3(a.threads), 0, st, a);
-    GATO_HIP_CHECK(hipGetLastError());
-    if (a.ev_stop) GATO_HIP_CHECK(hipEventRecord(a.ev_stop, st));
-    return GATO_OK;
+    return pcg_launch(mr ? pcg_cg1_kernel<T, S, MAXT, true> : pcg_cg1_kernel<T, S, MAXT>, dim3(nblocks), dim3(a.threads), a, st);
 }
 
 #define X(S_, C_)                                                              \

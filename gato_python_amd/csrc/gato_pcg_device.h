@@ -1,4 +1,5 @@
-// Device helpers shared by the resident PCG kernels (gato_pcg_resident.hip, gato_pcg_cg1.hip).
+// Device helpers shared by the persistent PCG kernels (gato_pcg_resident_kernel.h, gato_pcg_resident_single.hip, gato_pcg_cg1.hip,
+// gato_pcg_dma.hip).
 #pragma once
 #include "gato_common.h"
 

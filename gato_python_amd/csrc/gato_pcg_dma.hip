@@ -19,6 +19,7 @@
 //  * wave 0 does not stream: it runs the hand-off (its polling loads must not queue behind a DMA ring).
 // Same iteration, same boundary rules (gato_utils.cuh:157-174) and same exit test (gato_pcg.cuh:404) as everywhere.
 #include "gato_pcg_device.h"
+#include "gato_pcg_launch.h"
 
 namespace gato {
 namespace {
@@ -467,25 +468,15 @@ int launch_pcg_dma(const PcgLaunch &a0, hipStream_t st)
         typedef DmaCfg<T, S> Cfg;
         const bool mr = a0.xslots != nullptr;                   // one rank of a cluster launch
         PcgLaunch a = a0;
-        if (!mr) { a.k_begin = 0; a.k_end = a.K; a.rank = 0; a.nranks = 1; }
-        const int Kl = a.k_end - a.k_begin;
-        if (mr && (a.nranks < 1 || a.nranks > GATO_MAX_RANKS || a.rank < 0 || a.rank >= a.nranks || a.k_begin < 0 || Kl < 1 || a.k_end > a.K ||
-                   (a.rank == 0) != (a.k_begin == 0) || (a.rank == a.nranks - 1) != (a.k_end == a.K) || a.flat)) {
-            set_error("pcg_dma(cluster): bad shard rank=%d/%d knots [%d,%d) of %d", a.rank, a.nranks, a.k_begin, a.k_end, a.K);
-            return GATO_EINVAL;
-        }
+        int Kl;                                                 // knots this launch works on
+        if (pcg_shard(a, mr, a.flat, "pcg_dma", &Kl) != GATO_OK) return GATO_EINVAL;
         if (a.batch > 1 || a.lambda0 || a.groups < (mr ? 1 : 2) || a.groups > 256 || a.threads != 512 || a.knots_per_wg > Cfg::MAXK ||
-            a.knots_per_wg < 1 || (long long)a.groups * a.knots_per_wg < Kl || (long long)(a.groups - 1) * a.knots_per_wg >= Kl ||
+            a.knots_per_wg < 1 || !pcg_groups_cover(a, Kl) ||
             (reinterpret_cast<uintptr_t>(a.S_bd) & 15) || (reinterpret_cast<uintptr_t>(a.P_bd) & 15)) {
             set_error("pcg_dma: bad launch (K=%d groups=%d knots/wg=%d threads=%d)", a.K, a.groups, a.knots_per_wg, a.threads);
             return GATO_EINVAL;
         }
-        if (a.ev_start) GATO_HIP_CHECK(hipEventRecord(a.ev_start, st));
-        if (mr) hipLaunchKernelGGL((pcg_dma_kernel<T, S, true>), dim3(a.groups), dim3(512), 0, st, a);
-        else hipLaunchKernelGGL((pcg_dma_kernel<T, S, false>), dim3(a.groups), dim3(512), 0, st, a);
-        GATO_HIP_CHECK(hipGetLastError());
-        if (a.ev_stop) GATO_HIP_CHECK(hipEventRecord(a.ev_stop, st));
-        return GATO_OK;
+        return pcg_launch(mr ? pcg_dma_kernel<T, S, true> : pcg_dma_kernel<T, S, false>, dim3(a.groups), dim3(512), a, st);
     } else {
         set_error("pcg_dma: STATE_SIZE %d has no DMA variant", S);
         return GATO_EINVAL;
