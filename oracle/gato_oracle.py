@@ -143,7 +143,9 @@ def gauss_jordan_inverse(A):
 # --------------------------------------------------------------------------------------------
 # A2: Schur complement + block-Jacobi main blocks + gamma   (src/gato_schur.cuh:13-460)
 # --------------------------------------------------------------------------------------------
-def form_schur(G_dense, C_dense, g, c, S, C, K):
+def form_schur(G_dense, C_dense, g, c, S, C, K, inverses=None):
+    """inverses: optional (Qi [K,S,S], Ri [K-1,C,C]) used in place of the Gauss-Jordan inverses of Q and R (a caller that
+    inverts modified blocks itself: the reduced system of a box-QP polish)."""
     dtype = G_dense.dtype
     n = S + C
     Q, R = unpack_G(G_dense, S, C, K)
@@ -153,8 +155,11 @@ def form_schur(G_dense, C_dense, g, c, S, C, K):
     q = np.stack([g[k * n: k * n + S] for k in range(K)])
     r = np.stack([g[k * n + S: (k + 1) * n] for k in range(K - 1)]) if K > 1 else np.zeros((0, C), dtype)
 
-    Qi = gauss_jordan_inverse(Q)                       # :86-88, :224-235
-    Ri = gauss_jordan_inverse(R) if K > 1 else R
+    if inverses is None:
+        Qi = gauss_jordan_inverse(Q)                   # :86-88, :224-235
+        Ri = gauss_jordan_inverse(R) if K > 1 else R
+    else:
+        Qi, Ri = (np.asarray(m, dtype) for m in inverses)
 
     Sl = np.zeros((K, S, S), dtype)
     Sm = np.zeros((K, S, S), dtype)

@@ -3,7 +3,10 @@
 The problem is that of box_qp_ref:  min 1/2 x^T H x - g^T x  s.t.  C x = c,  lo <= x <= hi,  H = G + rho I  (dz layout).
 active_set() is OSQP's rule on (z, y) of an ADMM result; reduced_solve() is the exact KKT solution with the active variables
 fixed at their bounds, [[H_FF, C_F^T], [C_F, 0]] [x_F; lam] = [g_F - H_FA b_A; c - C_A b_A]; polish() adds the device's
-acceptance test; grads() is the backward pass of DESIGN.md section 3.6 applied to the reduced system."""
+acceptance test; grads() is the backward pass of DESIGN.md section 3.6 applied to the reduced system.  H and C may be
+scipy.sparse matrices (box_qp_ref.sparse_parts).  constructed_problem() builds QPs with a known active set (active states
+included) at any shape, constructed() walks its seeds by a rule on the reference alone, and reduced_stage_solve() restates
+the device's route to the reduced solution on the oracle's stages in a given dtype."""
 import os
 import sys
 
@@ -38,28 +41,55 @@ def bound_values(act, lo, hi):
     return np.where(act > 0, hi, np.where(act < 0, lo, 0.0))
 
 
-def _reduced_matrix(H, Cm, act):
-    F = act == 0
+def _cols(M, idx):
+    return M[:, idx]
+
+
+def _sub(M, rows, cols):
+    return M[rows][:, cols] if ref.is_sparse(M) else M[np.ix_(rows, cols)]
+
+
+def _reduced_solver(H, Cm, act):
+    """(solve, F) of the reduced matrix [[H_FF, C_F^T], [C_F, 0]]; F the indices of the free variables.  solve(rhs) gives
+    NaN where the matrix is singular (LICQ fails).  Dense: np.linalg.solve; sparse: one splu factorisation."""
+    F = np.flatnonzero(np.asarray(act) == 0)
+    if not ref.is_sparse(H):
+        M = reduced_matrix(H, Cm, act)
+
+        def solve(rhs):
+            try:
+                return np.linalg.solve(M, rhs)
+            except np.linalg.LinAlgError:
+                return np.full(len(rhs), np.nan)
+        return solve, F
+    try:
+        solve = ref.kkt_solver(_sub(H, F, F), _cols(Cm, F))
+    except RuntimeError:                                  # splu: "Factor is exactly singular"
+        solve = lambda rhs: np.full(len(rhs), np.nan)
+    return solve, F
+
+
+def reduced_matrix(H, Cm, act):
+    """The dense reduced matrix [[H_FF, C_F^T], [C_F, 0]] (for its condition number; dense sizes only)."""
+    F = np.flatnonzero(np.asarray(act) == 0)
     m = Cm.shape[0]
-    return np.block([[H[np.ix_(F, F)], Cm[:, F].T], [Cm[:, F], np.zeros((m, m))]]), F
+    dense = lambda M: M.toarray() if ref.is_sparse(M) else M
+    return np.block([[dense(_sub(H, F, F)), dense(_cols(Cm, F)).T], [dense(_cols(Cm, F)), np.zeros((m, m))]])
 
 
 def reduced_solve(H, Cm, g, c, lo, hi, act):
     """(x, y, lam) of the reduced KKT system: x_A = b_A exactly, y_A = (g - H x - C^T lam)_A, y_F = 0.  A singular reduced
-    system (LICQ fails) gives NaN."""
+    system (LICQ fails) gives NaN.  H, Cm dense or scipy.sparse."""
     act = np.asarray(act)
-    A = act != 0
+    A = np.flatnonzero(act != 0)
     b = bound_values(act, lo, hi)
-    M, F = _reduced_matrix(H, Cm, act)
-    rhs = np.concatenate([g[F] - H[np.ix_(F, A)] @ b[A], c - Cm[:, A] @ b[A]])
-    try:
-        sol = np.linalg.solve(M, rhs)
-    except np.linalg.LinAlgError:
-        sol = np.full(M.shape[0], np.nan)
+    solve, F = _reduced_solver(H, Cm, act)
+    rhs = np.concatenate([g[F] - _sub(H, F, A) @ b[A], c - _cols(Cm, A) @ b[A]])
+    sol = solve(rhs)
     x = np.zeros(len(g))
     x[A] = b[A]
-    x[F] = sol[:F.sum()]
-    lam = sol[F.sum():]
+    x[F] = sol[:len(F)]
+    lam = sol[len(F):]
     y = np.zeros(len(g))
     y[A] = (g - H @ x - Cm.T @ lam)[A]
     return x, y, lam
@@ -87,11 +117,11 @@ def polish(H, Cm, g, c, lo, hi, z, y, S, eps_abs=1e-6, eps_rel=1e-6, act=None):
 
 def adjoint(H, Cm, act, xbar, lambar):
     """[a; beta] of the reduced system for upstream gradients (xbar, lambar): a_A = 0."""
-    M, F = _reduced_matrix(H, Cm, np.asarray(act))
-    sol = np.linalg.solve(M, np.concatenate([np.asarray(xbar, np.float64)[F], np.asarray(lambar, np.float64)]))
+    solve, F = _reduced_solver(H, Cm, act)
+    sol = solve(np.concatenate([np.asarray(xbar, np.float64)[F], np.asarray(lambar, np.float64)]))
     a = np.zeros(H.shape[0])
-    a[F] = sol[:F.sum()]
-    return a, sol[F.sum():]
+    a[F] = sol[:len(F)]
+    return a, sol[len(F):]
 
 
 def bound_grads(H, Cm, act, xbar, a, beta):
@@ -143,11 +173,13 @@ def dense_from_blocks(Q, R, A, B, q, r, c, rho):
 
 
 # ---- the problems of DESIGN.md section 3.8 ------------------------------------------------------------------------------
-def boxes(s, seed, eq=True, states=True):
+def boxes(s, seed, eq=True, states=True, dz=None):
     """The box of tests/test_gpu_box_qp.py's boxes(): controls and every other state bounded around half their unconstrained
-    value, x_0 free, one control fixed (lo == hi) when eq.  states=False: the states are all free (a control-only box)."""
+    value, x_0 free, one control fixed (lo == hi) when eq.  states=False: the states are all free (a control-only box).
+    dz: the unconstrained solution, where the dense solve that finds it otherwise is out of reach."""
     rng = np.random.default_rng(seed)
-    dz, _ = synth.dense_kkt_solve(s)
+    if dz is None:
+        dz, _ = synth.dense_kkt_solve(s)
     n, N = s.S + s.C, s.N
     w = 0.5 * np.abs(dz) + 0.05 * rng.uniform(0.5, 1.5, N)
     lo, hi = -w, w.copy()
@@ -178,6 +210,220 @@ def problem(name):
         lo, hi = boxes(s, 3, eq=False, states=False)
         return s, lo, hi, 1.0
     raise KeyError(name)
+
+
+# ---- constructed problems: a known active set with active states, without running ADMM -----------------------------------
+def constructed_system(S, C, K, seed):
+    """synth's seeded system with dense Q_k and R_k (synth.make_blocks(dense_q=True) plus a dense positive semidefinite
+    part on R_k): with diagonal blocks a wrong mask, a transposed index or a missed shift through H_:A would change
+    nothing."""
+    Q, R, A, B, q, r, c = synth.make_blocks(S, C, K, seed, dense_q=True)
+    M = 0.1 * np.random.default_rng([seed, 11]).standard_normal((K - 1, C, C))
+    return synth.blocks_to_csr(Q, R + M @ M.transpose(0, 2, 1), A, B, q, r, c)
+
+
+def constructed_problem(S, C, K, seed, sparse=False, scale=1.0, release=0.0):
+    """A box QP on constructed_system(S, C, K, seed) whose exact solution has a known active set, built backwards:
+      1. the active index set A: per knot k < K-1 about half the controls (at least one where C >= 2; with C = 1 the
+         control, or nothing where a state of the next knot must be active), per knot k >= 1 a random number of states
+         between 0 and min(free controls of knot k-1, S-1) - so that LICQ holds generically - with at least one state of
+         knot 1 and one of the last knot when K >= 3, and never a state of x_0;
+      2. bound values b_A = 0.5 dz_A + 0.05 N(0, 1), dz the unconstrained solution;
+      3. one reduced solve with every active variable an upper bound gives y_A;
+      4. act = sign(y_A) (+1 where y >= 0) and b on that side; every other active variable gets a finite opposite bound
+         at distance 1 + |b|, the rest an infinite one;
+      5. every third free variable gets a loose finite box around x, and one active control lo == hi when K >= 3, C >= 2.
+    Long horizons (thousands of active variables, states that drift over thousands of knots) cannot meet the seed rule
+    as built above - the smallest of 6000 multipliers is below 1e-3 and |x| reaches 1e2 on every seed - so two knobs of
+    the construction, not of the rule, exist for them: scale multiplies g, c and the noise of b (and with them x, y, lam), after
+    step 3 the active variables with |y| < release are set free and the solve repeated until none is left.
+    The reduced point is then the QP's optimum by construction.  Returns a dict: s, H, Cm, g, c (dense, or scipy.sparse
+    with sparse=True), lo, hi, act, x, y, lam, seed."""
+    s = constructed_system(S, C, K, seed)
+    s.g, s.c = s.g * scale, s.c * scale
+    H, Cm, g, c = ref.sparse_parts(s) if sparse else ref.parts(s)
+    rng = np.random.default_rng([seed, S, C, K])
+    n, N = S + C, s.N
+    inf = np.full(N, np.inf)
+    dz, _, _ = reduced_solve(H, Cm, g, c, -inf, inf, np.zeros(N, np.int8))
+    A = np.zeros(N, bool)
+    free_prev = 0
+    for k in range(K):
+        if k >= 1:
+            most = min(free_prev, S - 1)
+            ns = int(rng.integers(0, most + 1))
+            if K >= 3 and k in (1, K - 1):
+                ns = max(ns, 1)
+            A[k * n + rng.permutation(S)[:ns]] = True
+        if k < K - 1:
+            must_leave = K >= 3 and k in (0, K - 2)                 # a state of knot k+1 must be active: keep a control free
+            if C >= 2:
+                nc = int(np.clip(C // 2 + rng.integers(-1, 2), 1, C - 1))
+            else:
+                nc = 0 if must_leave else (1 if K == 2 else int(rng.integers(0, 2)))
+            A[k * n + S + rng.permutation(C)[:nc]] = True
+            free_prev = C - nc
+    b = np.where(A, 0.5 * dz + 0.05 * scale * rng.standard_normal(N), 0.0)
+    _, y0, _ = reduced_solve(H, Cm, g, c, -inf, np.where(A, b, np.inf), A.astype(np.int8))
+    while release > 0 and np.any(np.abs(y0[A]) < release):
+        A &= np.abs(y0) >= release
+        b = np.where(A, b, 0.0)
+        _, y0, _ = reduced_solve(H, Cm, g, c, -inf, np.where(A, b, np.inf), A.astype(np.int8))
+    act = np.where(A, np.where(y0 >= 0, 1, -1), 0).astype(np.int8)
+    lo, hi = -inf, inf.copy()
+    lo[act < 0], hi[act > 0] = b[act < 0], b[act > 0]
+    other = np.zeros(N, bool)
+    other[np.flatnonzero(A)[::2]] = True
+    lo[other & (act > 0)] = (b - (1 + np.abs(b)))[other & (act > 0)]
+    hi[other & (act < 0)] = (b + (1 + np.abs(b)))[other & (act < 0)]
+    if K >= 3 and C >= 2:
+        j = (K // 2) * n + S + np.flatnonzero(A[(K // 2) * n + S: (K // 2 + 1) * n])[0]
+        lo[j] = hi[j] = b[j]
+        act[j] = -1
+    x, y, lam = reduced_solve(H, Cm, g, c, lo, hi, act)
+    loose = np.flatnonzero(~A)[::3]
+    w = (1 + np.abs(x[loose])) * rng.uniform(0.5, 1.5, len(loose))
+    lo[loose], hi[loose] = x[loose] - w, x[loose] + w
+    return dict(s=s, H=H, Cm=Cm, g=g, c=c, lo=lo, hi=hi, act=act, x=x, y=y, lam=lam, seed=seed)
+
+
+COND_CAP = 1e8
+# the cases of tests/test_gpu_qp_kernel_sweep.py (the CPU suite checks that the seed rule finds a seed for each)
+SWEEP_SHAPES = [(2, 1), (4, 2), (6, 3), (12, 6), (14, 7), (32, 16)]
+SWEEP_SHORT_K = (2, 3, 9)
+SWEEP_F32 = [(S, C, 9) for S, C in SWEEP_SHAPES] + [(14, 7, 3), (32, 16, 3)]
+SWEEP_BATCH = (14, 7, 9, 5)                       # S, C, K, systems of the batch test
+SWEEP_LONG = (2, 1, 8197)
+F32_EPS = 1e-4                                    # eps_abs = eps_rel of the fp32 polishes
+
+
+def meets_seed_rule(p, cond=True):
+    """The conditions a constructed problem must meet, from the reference alone: its polish ACCEPTED, cond(M_reduced) <=
+    1e8 (dense sizes), |x| <= 10, every non-equality active multiplier at least 1e-3 from 0 and every bounded free
+    variable at least 1e-3 inside its box.  -> (ok, dict of the measured figures)."""
+    H, Cm, g, c, lo, hi, act, x, y = (p[k] for k in ("H", "Cm", "g", "c", "lo", "hi", "act", "x", "y"))
+    N = len(g)
+    dec = polish(H, Cm, g, c, lo, hi, np.zeros(N), np.zeros(N), p["s"].S, act=act)
+    on, eq = act != 0, lo == hi
+    fig = dict(decision=dec["decision"], res_prim=dec["res_prim"], res_dual=dec["res_dual"])
+    if dec["decision"] != ACCEPTED:
+        return False, fig
+    fig["xmax"] = float(np.abs(x).max())
+    fig["ymin"] = float(np.abs(y[on & ~eq]).min()) if (on & ~eq).any() else np.inf
+    with np.errstate(invalid="ignore"):
+        fig["inside"] = float(np.min(np.minimum(x - lo, hi - x)[~on]))
+    fig["cond"] = float(np.linalg.cond(reduced_matrix(H, Cm, act))) if cond and not ref.is_sparse(H) else None
+    ok = fig["xmax"] <= 10 and fig["ymin"] >= 1e-3 and fig["inside"] >= 1e-3 and (fig["cond"] is None or fig["cond"] <= COND_CAP)
+    return bool(ok), fig
+
+
+def rounded(p):
+    """The constructed problem with every input rounded to fp32 (values held in fp64; rho rounded too) and its fp64 reduced
+    solution: the truth an fp32 polish is judged against."""
+    s = p["s"].astype(np.float32).astype(np.float64)
+    s.rho = float(np.float32(p["s"].rho))
+    f32 = lambda a: np.asarray(a, np.float32).astype(np.float64)
+    H, Cm, g, c = ref.parts(s)
+    lo, hi = f32(p["lo"]), f32(p["hi"])
+    x, y, lam = reduced_solve(H, Cm, g, c, lo, hi, p["act"])
+    return dict(p, s=s, H=H, Cm=Cm, g=g, c=c, lo=lo, hi=hi, x=x, y=y, lam=lam)
+
+
+def restatement_accepted(p, dtype, eps, max_iters=1000):
+    """(accepted, pcg iterations): the acceptance test of polish() on the point reduced_stage_solve gives in `dtype`
+    (residuals evaluated in fp64)."""
+    H, Cm, g, c, lo, hi, act = (p[k] for k in ("H", "Cm", "g", "c", "lo", "hi", "act"))
+    x, lam, iters = reduced_stage_solve(p["s"], lo, hi, act, dtype, max_iters=max_iters)
+    x, lam = np.asarray(x, np.float64), np.asarray(lam, np.float64)
+    if not (np.isfinite(x).all() and np.isfinite(lam).all()):
+        return False, iters
+    on, eq = act != 0, lo == hi
+    y = np.where(on, g - H @ x - Cm.T @ lam, 0.0)
+    rp, rd, sp, sd = ref.residuals(H, Cm, g, c, x, np.clip(x, lo, hi), y, lam)
+    tol_d = eps + eps * sd
+    sign_ok = np.all(y[(act > 0) & ~eq] >= -tol_d) and np.all(y[(act < 0) & ~eq] <= tol_d)
+    return bool(rp <= eps + eps * sp and rd <= tol_d and sign_ok), iters
+
+
+def f32_ok(p):
+    """The further seed condition of the fp32 cases: the fp32 restatement of the rounded problem passes the acceptance
+    test, and passes it with its PCG stopped one iteration sooner too.  In fp32 the PCG of these systems ends within a
+    few iterations of the test's threshold (14/7/3 seed 0: |C x - c| 3.6e-4 one iteration before the exit, 8.4e-5 at it,
+    the bar 2.1e-4), and another summation order leaves the loop an iteration sooner or later: a seed whose decision hangs
+    on that last iteration decides nothing about a kernel."""
+    q = rounded(p)
+    ok, iters = restatement_accepted(q, np.float32, F32_EPS)
+    return ok and iters >= 1 and restatement_accepted(q, np.float32, F32_EPS, max_iters=iters)[0]
+
+
+_CONSTRUCTED = {}
+
+
+LONG_KNOBS = dict(sparse=True, scale=1.0 / 64, release=2e-3)       # constructed_problem's knobs at SWEEP_LONG
+
+
+def constructed(S, C, K, count=1, sparse=False, extra=None, tag=None, limit=20, **knobs):
+    """The first `count` constructed problems of seeds 0, 1, 2, ... < limit that meet the seed rule (and extra(p), a further
+    condition on the reference alone, cached under tag), as a list; fewer than count if the walk runs out."""
+    key = (S, C, K, sparse, tag, tuple(sorted(knobs.items())))
+    got = _CONSTRUCTED.setdefault(key, dict(next=0, found=[]))
+    while len(got["found"]) < count and got["next"] < limit:
+        p = constructed_problem(S, C, K, got["next"], sparse=sparse, **knobs)
+        got["next"] += 1
+        ok, fig = meets_seed_rule(p, cond=not sparse)
+        if ok and (extra is None or extra(p)):
+            p["figures"] = fig
+            got["found"].append(p)
+    return got["found"][:count]
+
+
+def wrong_sign(p):
+    """(act, index) of the constructed problem with the sign of one active non-equality control flipped (the first one whose
+    opposite bound is finite, so that the flipped act names a finite bound)."""
+    S, n = p["s"].S, p["s"].S + p["s"].C
+    act, lo, hi = p["act"], p["lo"], p["hi"]
+    idx = np.arange(len(act))
+    cand = np.flatnonzero((act != 0) & (lo != hi) & (idx % n >= S) & np.isfinite(lo) & np.isfinite(hi))
+    j = int(cand[0])
+    flipped = act.copy()
+    flipped[j] = -act[j]
+    return flipped, j
+
+
+# ---- the reduced stage path restated in a given dtype ----------------------------------------------------------------------
+def reduced_stage_solve(s, lo, hi, act, dtype, exit_tol=1e-8, max_iters=1000):
+    """What the device's polish computes, restated in `dtype` on the oracle's stages: Q_k and R_k (rho added) with the active
+    rows and columns replaced by the identity, the oracle's Gauss-Jordan inverse, the active entries zeroed; g' = g - H_:A
+    b_A (0 on A), c' = c - C_:A b_A (C's identity blocks included); form_schur with those inverses, form_ss, pcg,
+    compute_dz; x = b on A, dz elsewhere.  -> (x, lam, pcg iterations)."""
+    from oracle import gato_oracle as o
+    dt = np.dtype(dtype).type
+    S, C, K, n = s.S, s.C, s.K, s.S + s.C
+    Q, R, A, B, q, r, c = (np.asarray(t, dt) for t in kgr.blocks_of(s))
+    rho = dt(s.rho)
+    Q = Q + rho * np.eye(S, dtype=dt)
+    R = R + rho * np.eye(C, dtype=dt)
+    act = np.asarray(act)
+    on = act != 0
+    b = bound_values(act, np.asarray(lo, dt), np.asarray(hi, dt)).astype(dt)
+    xs, us = (np.arange(K)[:, None] * n + np.arange(S)), (np.arange(K - 1)[:, None] * n + S + np.arange(C))
+    onx, onu, bx, bu = on[xs], on[us], b[xs], b[us]
+    eye = lambda m: np.eye(m, dtype=dt)[None]
+    mx, mu = onx[:, :, None] | onx[:, None, :], onu[:, :, None] | onu[:, None, :]
+    Qi = np.where(mx, dt(0), o.gauss_jordan_inverse(np.where(mx, eye(S), Q)))
+    Ri = np.where(mu, dt(0), o.gauss_jordan_inverse(np.where(mu, eye(C), R)))
+    # g' and c': the kernel's fma chains are sums of a few products; numpy's matrix products in dt stand for them
+    qp = np.where(onx, dt(0), q - np.einsum("kij,kj->ki", Q, bx))
+    rp = np.where(onu, dt(0), r - np.einsum("kij,kj->ki", R, bu))
+    cp = c - bx
+    cp[1:] -= np.einsum("kij,kj->ki", A, bx[:-1]) + np.einsum("kij,kj->ki", B, bu)
+    gp = ref.dz_layout(qp, rp, S, C, K).astype(dt)
+    Gd, Cd = o.pack_G(Q, R), kgr.pack_C(A, B).astype(dt)
+    S_bd, P_bd, gam, Ginv = o.form_schur(Gd, Cd, gp, cp.reshape(-1), S, C, K, inverses=(Qi, Ri))
+    P_bd = o.form_ss(S_bd, P_bd, S, K)
+    lam, iters = o.pcg(S_bd, P_bd, gam, S, K, exit_tol, max_iters)
+    dz = o.compute_dz(Ginv, Cd, gp, lam, S, C, K)
+    return np.where(on, b, dz), lam, iters
 
 
 PROBLEMS = ("pendulum", "double_integrator", "6_3_20", "14_7_50")

@@ -2,7 +2,9 @@
 
 The problem, per system:  min 1/2 x^T H x - g^T x  s.t.  C x = c,  lo <= x <= hi,  H = G + rho I  (the solver's KKT system
 M [dz; lambda] = [g; c] plus a box in the dz layout).  admm() restates the device iteration with dense solves of the x-step
-matrix; qp_kkt_residuals() is an algorithm-free optimality check of a returned point."""
+matrix; qp_kkt_residuals() is an algorithm-free optimality check of a returned point.  H and C may be scipy.sparse matrices
+(sparse_parts): the solves then go through scipy.sparse.linalg.splu, which reaches horizons the dense path cannot hold
+(the KKT matrix of 2/1/8197 would take 13 GB)."""
 import os
 import sys
 
@@ -22,6 +24,37 @@ def parts(s):
     M, rhs = synth.dense_kkt(s)
     N = s.N
     return M[:N, :N].copy(), M[N:, :N].copy(), rhs[:N].copy(), rhs[N:].copy()
+
+
+def sparse_parts(s):
+    """parts(s) as scipy.sparse CSR matrices, straight from the system's CSR arrays: the same entries, bit for bit."""
+    from scipy import sparse
+    N, SK = s.N, s.S * s.K
+    G = sparse.csr_matrix((np.asarray(s.G_val, np.float64), s.G_col, s.G_row), shape=(N, N))
+    Cm = sparse.csr_matrix((np.asarray(s.C_val, np.float64), s.C_col, s.C_row), shape=(SK, N))
+    H = (G + s.rho * sparse.identity(N, format="csr")).tocsr()
+    return H, Cm, np.asarray(s.g, np.float64).copy(), np.asarray(s.c, np.float64).copy()
+
+
+def is_sparse(M):
+    from scipy import sparse
+    return sparse.issparse(M)
+
+
+def kkt_solver(H, Cm, diag=None):
+    """solve(rhs) of [[H + diag(diag), C^T], [C, 0]]: an LU factorisation, dense (scipy.linalg.lu_factor) or sparse (splu)
+    as H is."""
+    N, m = H.shape[0], Cm.shape[0]
+    if is_sparse(H):
+        from scipy import sparse
+        from scipy.sparse.linalg import splu
+        Hd = H if diag is None else H + sparse.diags(np.broadcast_to(diag, (N,)))
+        lu = splu(sparse.bmat([[Hd, Cm.T], [Cm, None]], format="csc"))
+        return lu.solve
+    from scipy.linalg import lu_factor, lu_solve
+    Hd = H if diag is None else H + np.diag(np.broadcast_to(diag, (N,)))
+    lu = lu_factor(np.block([[Hd, Cm.T], [Cm, np.zeros((m, m))]]))
+    return lambda rhs: lu_solve(lu, rhs)
 
 
 def dz_layout(xv, uv, S, C, K):
@@ -47,21 +80,20 @@ def residuals(H, Cm, g, c, x, z, y, lam):
 
 def admm(H, Cm, g, c, lo, hi, *, admm_rho=0.1, sigma=1e-6, alpha=1.6, eps_abs=1e-6, eps_rel=1e-6, max_admm_iters=4000,
          z0=None, y0=None):
-    """The device iteration with dense x-steps.  Returns dict x, z, y, lam, iters, status, res_prim, res_dual - the iterate
+    """The device iteration with exact (LU) x-steps.  Returns dict x, z, y, lam, iters, status, res_prim, res_dual - the iterate
     after `iters` x-steps, where the test first passed (or the last one: MAX_ITERS)."""
     N, m = H.shape[0], Cm.shape[0]
     lo, hi = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
     rho = penalties(lo, hi, admm_rho)
     free = rho == 0
-    from scipy.linalg import lu_factor, lu_solve
-    lu = lu_factor(np.block([[H + np.diag(sigma + rho), Cm.T], [Cm, np.zeros((m, m))]]))
+    solve = kkt_solver(H, Cm, sigma + rho)
     z = np.clip(np.zeros(N) if z0 is None else np.asarray(z0, np.float64), lo, hi)
     x = z.copy()
     y = np.where(free, 0.0, np.zeros(N) if y0 is None else np.asarray(y0, np.float64))
     lam = np.zeros(m)
     for it in range(1, max_admm_iters + 1):
         gt = g + sigma * x + rho * z - y
-        sol = lu_solve(lu, np.concatenate([gt, c]))
+        sol = solve(np.concatenate([gt, c]))
         xt, lam = sol[:N], sol[N:]
         xh = alpha * xt + (1 - alpha) * z
         x = alpha * xt + (1 - alpha) * x

@@ -88,6 +88,41 @@ def test_trivial_qp_and_infeasible_box():
     assert out["status"] == ref.MAX_ITERS and all(np.isfinite(out[k]).all() for k in ("x", "z", "y", "lam"))
 
 
+def _close(a, b, tol=1e-12):
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    return np.abs(a - b).max() <= tol * max(1.0, np.abs(b).max())
+
+
+@pytest.mark.parametrize("shape", [(2, 1, 5), (4, 2, 9), (14, 7, 12)])
+def test_sparse_parts_are_the_dense_parts(shape):
+    s = synth.make_system(*shape, seed=4, dense_q=True)
+    H, Cm, g, c = ref.parts(s)
+    Hs, Cs, gs, cs = ref.sparse_parts(s)
+    assert ref.is_sparse(Hs) and ref.is_sparse(Cs) and not ref.is_sparse(H)
+    assert np.array_equal(Hs.toarray(), H) and np.array_equal(Cs.toarray(), Cm)
+    assert np.array_equal(gs, g) and np.array_equal(cs, c)
+
+
+@pytest.mark.parametrize("shape", [(4, 2, 9), (14, 7, 12)])
+def test_sparse_functions_equal_dense(shape):
+    """residuals, qp_kkt_residuals and admm on scipy.sparse H, C against the dense path: 1e-12 relative to the larger of 1
+    and the vector's infinity norm (two LU factorisations of the same matrix, ten iterations)."""
+    from box_qp_polish_ref import boxes
+    s = synth.make_system(*shape, seed=4, dense_q=True)
+    lo, hi = boxes(s, 5)
+    dense, sparse = ref.parts(s), ref.sparse_parts(s)
+    kw = dict(admm_rho=10.0, eps_abs=0.0, eps_rel=0.0, max_admm_iters=10)
+    a, b = ref.admm(*dense, lo, hi, **kw), ref.admm(*sparse, lo, hi, **kw)
+    assert a["iters"] == b["iters"] == 10 and a["status"] == b["status"] == ref.MAX_ITERS
+    for k in ("x", "z", "y", "lam"):
+        assert _close(b[k], a[k]), (k, np.abs(a[k] - b[k]).max())
+    pt = (a["x"], a["z"], a["y"], a["lam"])
+    assert _close(ref.residuals(*sparse, *pt), ref.residuals(*dense, *pt))
+    kd = ref.qp_kkt_residuals(*dense, lo, hi, a["z"], a["y"], a["lam"])
+    ks = ref.qp_kkt_residuals(*sparse, lo, hi, a["z"], a["y"], a["lam"])
+    assert _close([ks[k] for k in sorted(ks)], [kd[k] for k in sorted(kd)])
+
+
 def test_entry_declared_and_exported():
     hdr = open(os.path.join(ROOT, "include", "gato_hip.h")).read()
     assert re.search(r"int\s+gato_box_qp_solve\s*\(", hdr)

@@ -154,6 +154,134 @@ def test_gradients_match_finite_differences(name):
         assert abs(an - fd) <= tol, (key, an, fd, tol)
 
 
+# ---- sparse references, constructed problems and the reduced stage path (tests/test_gpu_qp_kernel_sweep.py) ---------------
+def _close(a, b, tol):
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    return np.abs(a - b).max() <= tol * max(1.0, np.abs(b).max())
+
+
+@pytest.mark.parametrize("shape", [(4, 2, 9), (14, 7, 12)])
+def test_sparse_functions_equal_dense(shape):
+    """reduced_solve, polish, adjoint and bound_grads on scipy.sparse H, C against the dense path, on a constructed problem
+    (active states included): 1e-12 relative to the larger of 1 and the vector's infinity norm."""
+    p = P.constructed(*shape)[0]
+    dense = (p["H"], p["Cm"], p["g"], p["c"])
+    sparse = ref.sparse_parts(p["s"])
+    lo, hi, act = p["lo"], p["hi"], p["act"]
+    rd, rs = P.reduced_solve(*dense, lo, hi, act), P.reduced_solve(*sparse, lo, hi, act)
+    for a, b in zip(rs, rd):
+        assert _close(a, b, 1e-12)
+    assert np.array_equal(rs[0][act != 0], rd[0][act != 0])
+    zero = np.zeros(len(act))
+    pd, ps = (P.polish(*parts, lo, hi, zero, zero, p["s"].S, act=act) for parts in (dense, sparse))
+    assert pd["decision"] == ps["decision"] == P.ACCEPTED
+    rng = np.random.default_rng(1)
+    xbar, lbar = rng.standard_normal(len(act)), rng.standard_normal(len(p["c"]))
+    ad, as_ = P.adjoint(dense[0], dense[1], act, xbar, lbar), P.adjoint(sparse[0], sparse[1], act, xbar, lbar)
+    for a, b in zip(as_, ad):
+        assert _close(a, b, 1e-12)
+    assert not ad[0][act != 0].any() and not as_[0][act != 0].any()
+    bd, bs = P.bound_grads(dense[0], dense[1], act, xbar, *ad), P.bound_grads(sparse[0], sparse[1], act, xbar, *ad)
+    for a, b in zip(bs, bd):
+        assert _close(a, b, 1e-12)
+
+
+def _sweep_cases():
+    short = [(S, C, K, "f64") for S, C in P.SWEEP_SHAPES for K in P.SWEEP_SHORT_K]
+    return short + [(S, C, K, "f32") for S, C, K in P.SWEEP_F32]
+
+
+def _check_constructed(p):
+    """A constructed problem against its own conditions: the seed rule, the reference's polish, a KKT point of the QP to
+    1e-9, and the shape of its active set."""
+    s, act, lo, hi = p["s"], p["act"], p["lo"], p["hi"]
+    ok, fig = P.meets_seed_rule(p, cond=not ref.is_sparse(p["H"]))
+    assert ok, fig
+    kk = ref.qp_kkt_residuals(p["H"], p["Cm"], p["g"], p["c"], lo, hi, p["x"], p["y"], p["lam"])
+    assert max(kk.values()) <= 1e-9, kk
+    n = s.S + s.C
+    knot, var = np.arange(s.N) // n, np.arange(s.N) % n
+    on = act != 0
+    assert on.any() and not on[:s.S].any()
+    assert np.all(np.isfinite(P.bound_values(act, lo, hi)[on]))
+    assert np.array_equal(act[lo == hi], np.full(int((lo == hi).sum()), -1))
+    if s.K >= 3 and not ref.is_sparse(p["H"]):
+        assert (on & (var < s.S) & (knot == 1)).any() and (on & (var < s.S) & (knot == s.K - 1)).any()
+        assert (lo == hi).sum() == (1 if s.C >= 2 else 0)
+    return fig
+
+
+@pytest.mark.parametrize("S,C,K,kind", _sweep_cases())
+def test_constructed_problem_meets_its_conditions(S, C, K, kind):
+    """The seed rule finds a seed below 20 for every case of the GPU sweep (printed), and the problem of that seed is what
+    it claims to be.  The fp32 cases add the condition that the fp32 restatement of the rounded problem is accepted."""
+    found = P.constructed(S, C, K, extra=P.f32_ok, tag="f32") if kind == "f32" else P.constructed(S, C, K)
+    assert len(found) == 1, "no seed below 20 meets the rule"
+    p = found[0]
+    print("seed", (S, C, K, kind), p["seed"], p["figures"])
+    _check_constructed(p)
+    if kind == "f32":
+        q = P.rounded(p)
+        assert P.f32_ok(p) and P.restatement_accepted(q, np.float32, P.F32_EPS)[0]
+        assert max(ref.qp_kkt_residuals(q["H"], q["Cm"], q["g"], q["c"], q["lo"], q["hi"], q["x"], q["y"], q["lam"]).values()) <= 1e-9
+
+
+def test_constructed_batch_and_long_horizon_seeds():
+    S, C, K, B = P.SWEEP_BATCH
+    found = P.constructed(S, C, K, count=B)
+    assert len(found) == B and len({p["seed"] for p in found}) == B
+    print("batch seeds", [p["seed"] for p in found])
+    for p in found:
+        _check_constructed(p)
+    found = P.constructed(*P.SWEEP_LONG, **P.LONG_KNOBS)
+    assert len(found) == 1
+    p = found[0]
+    print("long-horizon seed", p["seed"], p["figures"], "active", int((p["act"] != 0).sum()))
+    _check_constructed(p)
+    n = P.SWEEP_LONG[0] + P.SWEEP_LONG[1]
+    assert (np.flatnonzero(p["act"]) // n >= 8192).any()
+
+
+@pytest.mark.parametrize("S,C", P.SWEEP_SHAPES)
+def test_wrong_sign_is_rejected_by_the_reference(S, C):
+    p = P.constructed(S, C, 9)[0]
+    flipped, j = P.wrong_sign(p)
+    assert j % (S + C) >= S and p["lo"][j] != p["hi"][j] and flipped[j] == -p["act"][j] != 0
+    zero = np.zeros(len(flipped))
+    dec = P.polish(p["H"], p["Cm"], p["g"], p["c"], p["lo"], p["hi"], zero, zero, S, act=flipped)
+    print((S, C), j, dec["decision"], dec["res_prim"], dec["res_dual"])
+    assert dec["decision"] == P.REJECTED
+
+
+@pytest.mark.parametrize("S,C,K,kind", [c for c in _sweep_cases() if c[3] == "f64"])
+def test_reduced_stage_path_is_the_reduced_solve(S, C, K, kind):
+    """reduced_stage_solve in fp64 - masked Gauss-Jordan inverses, shifted right-hand sides, Schur complement, PCG, dz -
+    against the dense LU of the reduced matrix: two different routes to one point.  Bar: 1e-9 of the larger of 1 and the
+    vector's infinity norm (the multipliers of these problems reach 5e3; the matrices' condition numbers 1e8)."""
+    p = P.constructed(S, C, K)[0]
+    x, lam, iters = P.reduced_stage_solve(p["s"], p["lo"], p["hi"], p["act"], np.float64, exit_tol=1e-30)
+    ex = np.abs(x - p["x"]).max() / max(1.0, np.abs(p["x"]).max())
+    el = np.abs(lam - p["lam"]).max() / max(1.0, np.abs(p["lam"]).max())
+    print((S, C, K), "pcg iterations", iters, "x", ex, "lam", el)
+    assert ex <= 1e-9 and el <= 1e-9
+    on = p["act"] != 0
+    assert np.array_equal(x[on], P.bound_values(p["act"], p["lo"], p["hi"])[on])
+
+
+def test_form_schur_takes_given_inverses():
+    """form_schur(inverses=...) with the Gauss-Jordan inverses it would compute itself returns the bits of the default path."""
+    from gato_python_amd import synth
+    from oracle import gato_oracle as o
+    s = P.constructed_system(6, 3, 5, 1)
+    for dt in (np.float64, np.float32):
+        Gd, Cd = o.convert(s.G_row, s.G_col, s.G_val, s.C_row, s.C_col, s.C_val, 6, 3, 5, s.rho, dt)
+        Q, R = o.unpack_G(Gd, 6, 3, 5)
+        want = o.form_schur(Gd, Cd, s.g.astype(dt), s.c.astype(dt), 6, 3, 5)
+        got = o.form_schur(Gd, Cd, s.g.astype(dt), s.c.astype(dt), 6, 3, 5,
+                           inverses=(o.gauss_jordan_inverse(Q), o.gauss_jordan_inverse(R)))
+        assert all(a.dtype == b.dtype and a.tobytes() == b.tobytes() for a, b in zip(got, want))
+
+
 def test_entries_declared_and_exported():
     hdr = open(os.path.join(ROOT, "include", "gato_hip.h")).read()
     for name in ("gato_box_qp_active_set", "gato_box_qp_polish", "gato_box_qp_bound_grad"):
