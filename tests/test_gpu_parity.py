@@ -40,6 +40,7 @@ def _need_gpu():
 
 
 from f32_parity import check_f32                # noqa: E402  (tests/f32_parity.py: the measured fp32 bar and its log)
+from csr_patterns import shuffle_rows, thin_rows, with_duplicates   # noqa: E402  (the odd CSR patterns of the scatter tests)
 
 
 def make_solver(S, C, K, dt):
@@ -1146,17 +1147,8 @@ def test_csr_with_unsorted_columns_and_explicit_zeros(dt):
     s = synth.make_system(S, C, K, seed=31, dense_q=True)
     rng = np.random.default_rng(5)
 
-    def shuffle(indptr, indices, data):
-        idx, dat, ptr = [], [], [0]
-        for r in range(len(indptr) - 1):
-            cols = list(indices[indptr[r]:indptr[r + 1]]); vals = list(data[indptr[r]:indptr[r + 1]])
-            perm = rng.permutation(len(cols))
-            idx += [cols[i] for i in perm]; dat += [vals[i] for i in perm]
-            ptr.append(len(idx))
-        return np.asarray(ptr, np.int32), np.asarray(idx, np.int32), np.asarray(dat, np.float64)
-
-    G_row, G_col, G_val = shuffle(s.G_row, s.G_col, s.G_val)
-    C_row, C_col, C_val = shuffle(s.C_row, s.C_col, s.C_val)
+    G_row, G_col, G_val = shuffle_rows(rng, s.G_row, s.G_col, s.G_val)
+    C_row, C_col, C_val = shuffle_rows(rng, s.C_row, s.C_col, s.C_val)
     G_val[rng.random(len(G_val)) < 0.1] = 0.0                  # explicit zeros off the diagonal are just values
     s2 = synth.KKTSystem(S, C, K, G_row, G_col, G_val, C_row, C_col, C_val, s.g, s.c, s.rho)
     Gd_o, Cd_o = co.convert(*s2.csr_args()[:6], S, C, K, s2.rho, dt)
@@ -1181,17 +1173,8 @@ def test_csr_with_structurally_empty_rows(dt):
     rng = np.random.default_rng(11)
     n = S + C
 
-    def thin(indptr, indices, data, keep):
-        idx, dat, ptr = [], [], [0]
-        for r in range(len(indptr) - 1):
-            for e in range(indptr[r], indptr[r + 1]):
-                if keep(r, int(indices[e])):
-                    idx.append(indices[e]); dat.append(data[e])
-            ptr.append(len(idx))
-        return np.asarray(ptr, np.int32), np.asarray(idx, np.int32), np.asarray(dat, np.float64)
-
     diag_only = set(int(r) for r in rng.choice(n * K - C, 40, replace=False))
-    G_row, G_col, G_val = thin(s.G_row, s.G_col, s.G_val, lambda r, c: r == c or (r not in diag_only and c not in diag_only))   # (symmetric)
+    G_row, G_col, G_val = thin_rows(s.G_row, s.G_col, s.G_val, lambda r, c: r == c or (r not in diag_only and c not in diag_only))   # (symmetric)
     bare = set(int(r) for r in rng.choice(np.arange(S, S * K), 25, replace=False))        # C rows that keep only their identity entry
     gone = set(int(r) for r in rng.choice(np.arange(S, S * K), 6, replace=False))          # ... and rows with NO entry at all
     noB = {3, 7}                                                                            # knots whose B block is structurally empty
@@ -1206,7 +1189,7 @@ def test_csr_with_structurally_empty_rows(dt):
         if r >= S and br in noB and br * n + S <= c < (br + 1) * n:
             return False
         return True
-    C_row, C_col, C_val = thin(s.C_row, s.C_col, s.C_val, keep_c)
+    C_row, C_col, C_val = thin_rows(s.C_row, s.C_col, s.C_val, keep_c)
     assert np.any(np.diff(C_row) == 0) and np.any(np.diff(C_row) == 1) and len(C_val) < len(s.C_val)
     s2 = synth.KKTSystem(S, C, K, G_row, G_col, G_val, C_row, C_col, C_val, s.g, s.c, s.rho)
     Gd_o, Cd_o = co.convert(*s2.csr_args()[:6], S, C, K, s2.rho, dt)
@@ -1238,21 +1221,8 @@ def test_csr_rows_with_duplicate_columns_keep_the_last_entry(S, C, K, dt):
     s = synth.make_system(S, C, K, seed=41, dense_q=True)
     rng = np.random.default_rng(9)
 
-    def with_duplicates(indptr, indices, data, frac):
-        idx, dat, ptr = [], [], [0]
-        for r in range(len(indptr) - 1):
-            cols = list(indices[indptr[r]:indptr[r + 1]]); vals = list(data[indptr[r]:indptr[r + 1]])
-            if cols and rng.random() < frac:
-                for _ in range(int(rng.integers(1, 4))):           # 1..3 extra entries: copies of columns already in the row ...
-                    j = int(rng.integers(0, len(cols)))
-                    at = int(rng.integers(0, len(cols) + 1))       # ... anywhere in the row: before or after the original, adjacent or not
-                    cols.insert(at, cols[j]); vals.insert(at, float(rng.standard_normal()))
-            idx += cols; dat += vals
-            ptr.append(len(idx))
-        return np.asarray(ptr, np.int32), np.asarray(idx, np.int32), np.asarray(dat, np.float64)
-
-    G_row, G_col, G_val = with_duplicates(s.G_row, s.G_col, s.G_val, 0.3)
-    C_row, C_col, C_val = with_duplicates(s.C_row, s.C_col, s.C_val, 0.3)
+    G_row, G_col, G_val = with_duplicates(rng, s.G_row, s.G_col, s.G_val, 0.3)
+    C_row, C_col, C_val = with_duplicates(rng, s.C_row, s.C_col, s.C_val, 0.3)
     assert len(G_val) > len(s.G_val) and len(C_val) > len(s.C_val)
     s2 = synth.KKTSystem(S, C, K, G_row, G_col, G_val, C_row, C_col, C_val, s.g, s.c, s.rho)
     Gd_o, Cd_o = co.convert(*s2.csr_args()[:6], S, C, K, s2.rho, dt)
