@@ -33,11 +33,11 @@ SYMBOLS = [
     "gato_cluster_pcg", "gato_cluster_linsys", "gato_cluster_destroy", "gato_cluster_launches_left", "gato_cluster_rewind", "gato_cluster_fits", "gato_last_stage_ms", "gato_solver_tune",
     "gato_solver_reserve_rhs", "gato_solve_rhs", "gato_linsys_resolve_f32", "gato_linsys_resolve_f64",
     "gato_kkt_grad_blocks", "gato_kkt_grad_csr", "gato_box_qp_default_params", "gato_box_qp_solve",
-    "gato_box_qp_active_set", "gato_box_qp_polish", "gato_box_qp_bound_grad",
+    "gato_box_qp_active_set", "gato_box_qp_polish", "gato_box_qp_bound_grad", "gato_box_qp_pdas",
 ]
 
 
-QP_CONVERGED, QP_MAX_ITERS, QP_NONFINITE, QP_BAD_BOUNDS = 0, 1, 2, 3
+QP_CONVERGED, QP_MAX_ITERS, QP_NONFINITE, QP_BAD_BOUNDS, QP_BAD_ACTIVE = 0, 1, 2, 3, 4
 POLISH_ACCEPTED, POLISH_REJECTED, POLISH_NONFINITE, POLISH_BAD_ACTIVE = 0, 1, 2, 3
 
 
@@ -125,6 +125,7 @@ def lib() -> ct.CDLL:
         L.gato_box_qp_active_set.argtypes = [vp] * 7
         L.gato_box_qp_polish.argtypes = [vp] * 8 + [ct.POINTER(BoxQpParams)] + [vp] * 8
         L.gato_box_qp_bound_grad.argtypes = [vp] * 10
+        L.gato_box_qp_pdas.argtypes = [vp] * 8 + [ct.POINTER(BoxQpParams), i] + [vp] * 8
         f = ct.c_float
         L.gato_linsys_solve_f32.argtypes = [ip, i, ip, vp, i, ip, i, ip, vp, i, vp, i, vp, i, vp,
                                             i, i, i, i, f, i, i, f, vp, vp, vp, vp]

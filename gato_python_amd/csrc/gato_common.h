@@ -363,6 +363,21 @@ int launch_polish_finish(const Dims &d, const PolishArgs &a, hipStream_t st);
 template <typename T, int S, int C>
 int launch_qp_bound_grad(const Dims &d, const void *G, const void *Cd, const signed char *act, const void *xbar, const void *adz,
                          const void *beta, void *lo_bar, void *hi_bar, hipStream_t st);
+// Primal-dual active-set iteration over the polish path (gato_pdas.hip).
+struct PdasArgs {
+    PolishArgs p;                           // p.act: the current act; p.slots [B][2][GATO_POLISH_NSLOT], set it % 2 of solve it
+    signed char *act;                       // p.act again, written by the decision (the caller's: in the start, out the final act)
+    signed char *act2;                      // act' [B][N]
+    int *round;                             // [B][2][2] per set: {entries where act' differs from act, system frozen before the solve}
+    int *ctr;                               // {live systems, waves that saw a bad bound, waves that saw a bad start act}
+    int *iters;                             // [B] solves until the system froze
+};
+// the checks of the bounds and of the start act (first launch of a call)
+template <typename T, int S, int C>
+int launch_pdas_check(const Dims &d, const PdasArgs &a, hipStream_t st);
+// after reduced solve `it` (1, 2, ...): the point, act' and the maxima, then the decision (two launches); last: no solve follows
+template <typename T, int S, int C>
+int launch_pdas_step(const Dims &d, const PdasArgs &a, int it, int last, hipStream_t st);
 template <typename T, int S>
 int pcg_resident_plan(PcgPlan *plan);
 template <typename T, int S>
@@ -450,6 +465,8 @@ struct Ops {
     int (*polish_finish)(const Dims &, const PolishArgs &, hipStream_t);
     int (*qp_bound_grad)(const Dims &, const void *, const void *, const signed char *, const void *, const void *, const void *,
                          void *, void *, hipStream_t);
+    int (*pdas_check)(const Dims &, const PdasArgs &, hipStream_t);
+    int (*pdas_step)(const Dims &, const PdasArgs &, int, int, hipStream_t);
     int (*pcg_plan)(PcgPlan *);
     int (*pcg_resident)(const PcgLaunch &, hipStream_t);
     int (*pcg_dma_max_knots)();

@@ -61,6 +61,10 @@ static Ops make_ops(int dtype)
                          const void *beta, void *lo_bar, void *hi_bar, hipStream_t st) {
         return launch_qp_bound_grad<T, S, C>(d, G, Cd, act, xbar, adz, beta, lo_bar, hi_bar, st);
     };
+    o.pdas_check = [](const Dims &d, const PdasArgs &a, hipStream_t st) { return launch_pdas_check<T, S, C>(d, a, st); };
+    o.pdas_step = [](const Dims &d, const PdasArgs &a, int it, int last, hipStream_t st) {
+        return launch_pdas_step<T, S, C>(d, a, it, last, st);
+    };
     o.pcg_plan = [](PcgPlan *p) { return pcg_resident_plan<T, S>(p); };
     o.pcg_resident = [](const PcgLaunch &a, hipStream_t st) { return launch_pcg_resident<T, S>(a, st); };   // incl. the DPP-row layout
     o.pcg_dma_max_knots = []() { return pcg_dma_max_knots<T, S>(); };

@@ -1,0 +1,164 @@
+// Primal-dual active-set iteration for box QPs over the polish path (gato_box_qp_pdas).
+// Every iteration is the reduced solve of the polish on the current act (add_rho, polish_prepare_kernel, the whole solve with
+// the given inverses), then pdas_step_kernel - the polished point, its residuals and the next active set act' - and
+// pdas_decide_kernel, which accepts the point, freezes the system or moves act' into act.  The per-system maxima and the count
+// of changed entries live in two sets, set it % 2 for solve it: the decision of solve it clears the set solve it + 1 folds into.
+// Every kernel: one wave per knot, grid.x strides over the knots, grid.y = system, lane i = variable i of the knot.
+#include "gato_common.h"
+#include "gato_qp_common.h"
+
+namespace gato {
+namespace {
+
+constexpr int WAVE = 64;
+constexpr int NSL = GATO_POLISH_NSLOT;
+
+// The first launch of a call: a NaN bound or lo > hi marks the system BAD_BOUNDS, a start act the reduced system cannot take
+// (polish_prepare_kernel's rule) BAD_ACTIVE; ctr = {B live systems, waves that saw a bad bound, waves that saw a bad act}.
+template <typename T, int S, int C>
+__global__ __launch_bounds__(WAVE) void pdas_check_kernel(PdasArgs a, int K, int B, BatchStride bs)
+{
+    constexpr int n = S + C;
+    const int lane = threadIdx.x;
+    const size_t sys = blockIdx.y;
+    const T *lo = (const T *)a.p.lo + sys * bs.n, *hi = (const T *)a.p.hi + sys * bs.n;
+    const signed char *act = a.p.act + sys * bs.n;
+    if (blockIdx.x == 0 && blockIdx.y == 0 && lane == 0) a.ctr[0] = B;
+    int bad_b = 0, bad_a = 0;
+    for (int k = blockIdx.x; k < K; k += gridDim.x) {
+        if (lane < (k < K - 1 ? n : S)) {
+            const size_t v = (size_t)k * n + lane;
+            const T l = lo[v], h = hi[v];
+            const signed char ai = act[v];
+            if (l != l || h != h || l > h) bad_b = 1;
+            else if (bad_active(ai, bound_of(ai, l, h), k == 0 && lane < S)) bad_a = 1;
+        }
+    }
+    const int any_b = __any(bad_b), any_a = __any(bad_a);
+    if (lane == 0) {
+        if (any_b) { atomicMax(a.p.status + sys, GATO_QP_BAD_BOUNDS); atomicAdd(a.ctr + 1, 1); }
+        if (any_a) { atomicMax(a.p.status + sys, GATO_QP_BAD_ACTIVE); atomicAdd(a.ctr + 2, 1); }
+    }
+}
+
+// Solve `it`: the polished point of the reduced solve and its eleven maxima (polished_point_knot, the polish's own pass), and
+// in the same pass act' from the point:
+//   0 on the states of x_0, -1 where lo == hi;  free: +1 where x > hi, -1 where x < lo;  active upper: kept while y > 0;
+//   active lower: kept while y < 0;  0 otherwise
+// - exact comparisons: near-ties are the acceptance test's, which runs first - and the count of entries where act' differs
+// from act (an integer atomicAdd per wave that saw a change).  A system frozen before this solve is only marked.
+template <typename T, int S, int C>
+__global__ __launch_bounds__(WAVE) void pdas_step_kernel(PdasArgs a, int it, int K, BatchStride bs)
+{
+    constexpr int n = S + C;
+    __shared__ PointLds<T, S, C> lds;
+    const int lane = threadIdx.x;
+    const size_t sys = blockIdx.y;
+    const int cur = it & 1;
+    int *rn = a.round + (sys * 2 + cur) * 2;
+    if (a.p.status[sys] >= 0) {
+        if (blockIdx.x == 0 && lane == 0) rn[1] = 1;
+        return;
+    }
+    const PointSys<T> p = point_sys<T>(a.p, sys, bs);
+    signed char *act2 = a.act2 + sys * bs.n;
+    unsigned long long m[NSL];
+#pragma unroll
+    for (int f = 0; f < NSL; ++f) m[f] = 0;
+    int changed = 0;
+    for (int k = blockIdx.x; k < K; k += gridDim.x) {
+        const PointVar<T> v = polished_point_knot<T, S, C>(lds, p, k, K, lane, m);
+        if (v.on) {
+            signed char a2;
+            if (k == 0 && lane < S) a2 = 0;
+            else if (v.lo == v.hi) a2 = -1;
+            else if (v.act == 0) a2 = v.x > v.hi ? 1 : (v.x < v.lo ? -1 : 0);
+            else if (v.act > 0) a2 = v.y > (T)0 ? 1 : 0;
+            else a2 = v.y < (T)0 ? -1 : 0;
+            act2[(size_t)k * n + lane] = a2;
+            changed += a2 != v.act;
+        }
+    }
+    fold_into_slots(m, a.p.slots + (sys * 2 + cur) * NSL, lane);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) changed += __shfl_xor(changed, o, 64);
+    if (lane == 0 && changed > 0) atomicAdd(rn, changed);
+}
+
+// The decision of solve `it` for one system (every workgroup of it reads the same complete maxima and change count):
+//   the acceptance test passes   the point over the caller's x, z, y, lambda; CONVERGED, the residuals
+//   a maximum is not finite      NONFINITE
+//   act' == act, or the last     MAX_ITERS (the next solve would repeat this one)
+// - iters = it and the system is frozen: nothing of it is written again - otherwise act' moves into act and the other set
+// of maxima and counts is cleared for solve it + 1.  The knot-0 workgroup records the decision and keeps the live count.
+template <typename T, int S, int C>
+__global__ __launch_bounds__(WAVE) void pdas_decide_kernel(PdasArgs a, int it, int last, int K, BatchStride bs)
+{
+    constexpr int n = S + C;
+    const int lane = threadIdx.x;
+    const size_t sys = blockIdx.y;
+    const int cur = it & 1;
+    const int *rn = a.round + (sys * 2 + cur) * 2;
+    if (rn[1]) return;                                                      // frozen before this solve
+    const PointTest t = point_test(a.p.slots + (sys * 2 + cur) * NSL, a.p.eps_abs, a.p.eps_rel);
+    const bool stop = t.ok || !t.finite || rn[0] == 0 || last;
+    if (blockIdx.x == 0) {
+        if (stop) {
+            if (lane == 0) {
+                a.p.status[sys] = t.ok ? GATO_QP_CONVERGED : (t.finite ? GATO_QP_MAX_ITERS : GATO_QP_NONFINITE);
+                a.iters[sys] = it;
+                if (t.ok) {
+                    a.p.res[2 * sys] = t.rp;
+                    a.p.res[2 * sys + 1] = t.rd;
+                }
+                atomicSub(a.ctr, 1);
+            }
+        } else {
+            if (lane < NSL) a.p.slots[(sys * 2 + (cur ^ 1)) * NSL + lane] = 0;
+            if (lane < 2) a.round[(sys * 2 + (cur ^ 1)) * 2 + lane] = 0;
+        }
+    }
+    if (t.ok) write_point<T, S, C>(a.p, sys, bs, K, lane);
+    else if (!stop) {
+        signed char *act = a.act + sys * bs.n;
+        const signed char *act2 = a.act2 + sys * bs.n;
+        for (int k = blockIdx.x; k < K; k += gridDim.x) {
+            if (lane < (k < K - 1 ? n : S)) {
+                const size_t v = (size_t)k * n + lane;
+                act[v] = act2[v];
+            }
+        }
+    }
+}
+
+}  // namespace
+
+template <typename T, int S, int C>
+int launch_pdas_check(const Dims &d, const PdasArgs &a, hipStream_t st)
+{
+    if (d.B < 1 || d.B > 65535) { set_error("pdas_check: B = %d", d.B); return GATO_EINVAL; }
+    hipLaunchKernelGGL((pdas_check_kernel<T, S, C>), dim3(knot_grid(d.K), d.B), dim3(WAVE), 0, st, a, d.K, d.B, batch_stride(d));
+    GATO_HIP_CHECK(hipGetLastError());
+    return GATO_OK;
+}
+
+template <typename T, int S, int C>
+int launch_pdas_step(const Dims &d, const PdasArgs &a, int it, int last, hipStream_t st)
+{
+    if (d.B < 1 || d.B > 65535) { set_error("pdas_step: B = %d", d.B); return GATO_EINVAL; }
+    hipLaunchKernelGGL((pdas_step_kernel<T, S, C>), dim3(knot_grid(d.K), d.B), dim3(WAVE), 0, st, a, it, d.K, batch_stride(d));
+    GATO_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL((pdas_decide_kernel<T, S, C>), dim3(knot_grid(d.K), d.B), dim3(WAVE), 0, st, a, it, last, d.K, batch_stride(d));
+    GATO_HIP_CHECK(hipGetLastError());
+    return GATO_OK;
+}
+
+#define X(S_, C_)                                                                                        \
+    template int launch_pdas_check<float, S_, C_>(const Dims &, const PdasArgs &, hipStream_t);         \
+    template int launch_pdas_check<double, S_, C_>(const Dims &, const PdasArgs &, hipStream_t);        \
+    template int launch_pdas_step<float, S_, C_>(const Dims &, const PdasArgs &, int, int, hipStream_t); \
+    template int launch_pdas_step<double, S_, C_>(const Dims &, const PdasArgs &, int, int, hipStream_t);
+GATO_SHAPES(X)
+#undef X
+
+}  // namespace gato

@@ -13,36 +13,7 @@ namespace gato {
 namespace {
 
 constexpr int WAVE = 64;
-constexpr int NSL = GATO_POLISH_NSLOT;
-// slot fields: the residuals and scales of the ADMM termination test, the largest wrong-sign multiplier, |lambda|
-enum { F_PRIM, F_DUAL, F_X, F_Z, F_C, F_HX, F_CTL, F_Y, F_G, F_SIGN, F_LAM, F_END };
-static_assert(F_END <= NSL, "slot fields");
-
-template <typename T>
-__device__ __forceinline__ T bound_of(signed char act, T lo, T hi) { return act > 0 ? hi : (act < 0 ? lo : (T)0); }
-
-// Row i of knot k of H v and C^T w, the products of qp_update_kernel: (G v)_i + rho v_i and w_k,i (states) + (C_k^T w_k+1)_i.
-// sQ, sR: the knot's G blocks (without rho); sCk: C block k (rows of block row k+1); sV: v of the knot; sLk, sLn: w_k, w_k+1.
-template <typename T, int S, int C>
-__device__ __forceinline__ void row_products(int i, bool next, const T *sQ, const T *sR, const T *sCk, const T *sV, const T *sLk,
-                                             const T *sLn, T rho, T &hx, T &ctl)
-{
-    hx = (T)0;
-    ctl = (T)0;
-    if (i < S) {
-#pragma unroll 4
-        for (int cc = 0; cc < S; ++cc) hx = fmaT(sQ[i + cc * S], sV[cc], hx);
-        ctl = sLk[i];
-    } else {
-#pragma unroll 4
-        for (int cc = 0; cc < C; ++cc) hx = fmaT(sR[(i - S) + cc * C], sV[S + cc], hx);
-    }
-    hx = fmaT(rho, sV[i], hx);
-    if (next) {
-#pragma unroll 4
-        for (int r = 0; r < S; ++r) ctl = fmaT(sCk[r + i * S], sLn[r], ctl);
-    }
-}
+constexpr int NSL = GATO_POLISH_NSLOT;        // the slot fields: gato_qp_common.h
 
 // OSQP's rule on (z, y): +1 where hi - z < y, -1 where z - lo < -y, -1 wherever lo == hi, 0 on the states of x_0.
 template <typename T, int S, int C>
@@ -98,7 +69,7 @@ __global__ __launch_bounds__(WAVE) void polish_prepare_kernel(PolishArgs a, int 
                     const signed char ai = act[v];
                     on = ai != 0;
                     b = bound_of(ai, lo[v], hi[v]);
-                    if (h == 1 && (ai < -1 || ai > 1 || (on && !__builtin_isfinite(b)) || (kk == 0 && lane < S && on))) bad = 1;
+                    if (h == 1 && bad_active(ai, b, kk == 0 && lane < S)) bad = 1;
                 }
                 sa[h][lane] = on;
                 sb[h][lane] = b;
@@ -164,92 +135,15 @@ __global__ __launch_bounds__(WAVE) void polish_prepare_kernel(PolishArgs a, int 
 template <typename T, int S, int C>
 __global__ __launch_bounds__(WAVE) void polish_finish_kernel(PolishArgs a, int K, BatchStride bs)
 {
-    constexpr int n = S + C, SS = S * S, CC = C * C, SN = S * n;
-    __shared__ T sQ[SS], sR[CC], sCp[SN], sCk[SN], sXn[n], sXp[n], sLk[S], sLn[S];
+    __shared__ PointLds<T, S, C> lds;
     const int lane = threadIdx.x;
     const size_t sys = blockIdx.y;
-    const T *G = (const T *)a.G + sys * bs.g, *Cd = (const T *)a.Cd + sys * bs.c;
-    const T *g = (const T *)a.g + sys * bs.n, *c = (const T *)a.c + sys * bs.sk;
-    const T *lo = (const T *)a.lo + sys * bs.n, *hi = (const T *)a.hi + sys * bs.n;
-    const T *xt = (const T *)a.xt + sys * bs.n, *lt = (const T *)a.lt + sys * bs.sk;
-    const signed char *act = a.act + sys * bs.n;
-    T *xp = (T *)a.xp + sys * bs.n, *zp = (T *)a.zp + sys * bs.n, *yp = (T *)a.yp + sys * bs.n;
-    const T rho = (T)a.rho;
+    const PointSys<T> p = point_sys<T>(a, sys, bs);
     unsigned long long m[NSL];
 #pragma unroll
     for (int f = 0; f < NSL; ++f) m[f] = 0;
-    auto fold = [&](int f, T v) { const unsigned long long b = mag_bits(v); m[f] = b > m[f] ? b : m[f]; };
-    for (int k = blockIdx.x; k < K; k += gridDim.x) {
-        const int nk = k < K - 1 ? n : S;
-        const size_t v0 = (size_t)k * n;
-        __syncthreads();
-        const T *Gk = G + (size_t)k * (SS + CC);
-        for (int e = lane; e < SS; e += WAVE) sQ[e] = Gk[e];
-        if (k < K - 1) {
-            for (int e = lane; e < CC; e += WAVE) sR[e] = Gk[SS + e];
-            for (int e = lane; e < SN; e += WAVE) sCk[e] = Cd[(size_t)k * SN + e];
-        }
-        if (k > 0)
-            for (int e = lane; e < SN; e += WAVE) sCp[e] = Cd[(size_t)(k - 1) * SN + e];
-        if (lane < nk) {
-            const size_t v = v0 + lane;
-            const signed char ai = act[v];
-            sXn[lane] = ai != 0 ? bound_of(ai, lo[v], hi[v]) : xt[v];
-        }
-        if (k > 0 && lane < n) {                                            // knot k-1's x (always a full knot)
-            const size_t v = v0 - n + lane;
-            const signed char ai = act[v];
-            sXp[lane] = ai != 0 ? bound_of(ai, lo[v], hi[v]) : xt[v];
-        }
-        if (lane < S) {
-            sLk[lane] = lt[(size_t)k * S + lane];
-            if (k < K - 1) sLn[lane] = lt[(size_t)(k + 1) * S + lane];
-        }
-        __syncthreads();
-        if (lane < nk) {
-            const int i = lane;
-            const size_t v = v0 + i;
-            const signed char ai = act[v];
-            T hx, ctl;
-            row_products<T, S, C>(i, k < K - 1, sQ, sR, sCk, sXn, sLk, sLn, rho, hx, ctl);
-            const T gv = g[v], l = lo[v], h = hi[v], xn = sXn[i];
-            const T zn = clip(xn, l, h);
-            const T yn = ai != 0 ? (gv - hx) - ctl : (T)0;
-            const T rd = (hx - gv) + ctl + yn;
-            xp[v] = xn; zp[v] = zn; yp[v] = yn;
-            fold(F_PRIM, xn - zn);
-            fold(F_DUAL, rd);
-            fold(F_X, xn);
-            fold(F_Z, zn);
-            fold(F_HX, hx);
-            fold(F_CTL, ctl);
-            fold(F_Y, yn);
-            fold(F_G, gv);
-            if (ai != 0 && l != h) {                                        // the multiplier's sign: y >= 0 upper, <= 0 lower
-                const T w = ai > 0 ? -yn : yn;
-                fold(F_SIGN, w > (T)0 ? w : (T)0);
-            }
-            if (i < S) {                                                    // row block k of C x - c
-                const T ci = c[(size_t)k * S + i];
-                T cx = xn;
-                if (k > 0) {
-#pragma unroll 4
-                    for (int j = 0; j < n; ++j) cx = fmaT(sCp[i + j * S], sXp[j], cx);
-                }
-                fold(F_PRIM, cx - ci);
-                fold(F_C, ci);
-                fold(F_LAM, sLk[i]);
-            }
-        }
-    }
-    // the slot only grows: a wave whose maximum it already holds skips the atomic (most waves of a long system: every wave
-    // of it folds into the same eleven words)
-    unsigned long long *sl = a.slots + sys * NSL;
-#pragma unroll
-    for (int f = 0; f < F_END; ++f) {
-        const unsigned long long w = wave_max_bits(m[f]);
-        if (lane == 0 && w != 0 && w > __hip_atomic_load(sl + f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(sl + f, w);
-    }
+    for (int k = blockIdx.x; k < K; k += gridDim.x) polished_point_knot<T, S, C>(lds, p, k, K, lane, m);
+    fold_into_slots(m, a.slots + sys * NSL, lane);
 }
 
 // The acceptance test of one system (every workgroup of it reads the same complete maxima) and, if it passes, the polished
@@ -257,37 +151,18 @@ __global__ __launch_bounds__(WAVE) void polish_finish_kernel(PolishArgs a, int K
 template <typename T, int S, int C>
 __global__ __launch_bounds__(WAVE) void polish_writeback_kernel(PolishArgs a, int K, BatchStride bs)
 {
-    constexpr int n = S + C;
     const int lane = threadIdx.x;
     const size_t sys = blockIdx.y;
-    const unsigned long long *sl = a.slots + sys * NSL;
-    bool finite = true;
-#pragma unroll
-    for (int f = 0; f < F_END; ++f) finite = finite && __builtin_isfinite(slot_val(sl, f));
-    const double rp = slot_val(sl, F_PRIM), rd = slot_val(sl, F_DUAL);
-    const double sp = fmax(fmax(slot_val(sl, F_X), slot_val(sl, F_Z)), slot_val(sl, F_C));
-    const double sd = fmax(fmax(slot_val(sl, F_HX), slot_val(sl, F_CTL)), fmax(slot_val(sl, F_Y), slot_val(sl, F_G)));
-    const double tol_d = a.eps_abs + a.eps_rel * sd;
-    const bool ok = finite && rp <= a.eps_abs + a.eps_rel * sp && rd <= tol_d && slot_val(sl, F_SIGN) <= tol_d;
+    const PointTest t = point_test(a.slots + sys * NSL, a.eps_abs, a.eps_rel);
     if (blockIdx.x == 0 && lane == 0) {
-        a.polish[sys] = ok ? GATO_QP_POLISH_ACCEPTED : (finite ? GATO_QP_POLISH_REJECTED : GATO_QP_POLISH_NONFINITE);
-        if (ok) {
+        a.polish[sys] = t.ok ? GATO_QP_POLISH_ACCEPTED : (t.finite ? GATO_QP_POLISH_REJECTED : GATO_QP_POLISH_NONFINITE);
+        if (t.ok) {
             a.status[sys] = GATO_QP_CONVERGED;
-            a.res[2 * sys] = rp;
-            a.res[2 * sys + 1] = rd;
+            a.res[2 * sys] = t.rp;
+            a.res[2 * sys + 1] = t.rd;
         }
     }
-    if (!ok) return;
-    const T *xp = (const T *)a.xp + sys * bs.n, *zp = (const T *)a.zp + sys * bs.n, *yp = (const T *)a.yp + sys * bs.n;
-    const T *lt = (const T *)a.lt + sys * bs.sk;
-    T *x = (T *)a.x + sys * bs.n, *z = (T *)a.z + sys * bs.n, *y = (T *)a.y + sys * bs.n, *lam = (T *)a.lam + sys * bs.sk;
-    for (int k = blockIdx.x; k < K; k += gridDim.x) {
-        if (lane < (k < K - 1 ? n : S)) {
-            const size_t v = (size_t)k * n + lane;
-            x[v] = xp[v]; z[v] = zp[v]; y[v] = yp[v];
-        }
-        if (lane < S) lam[(size_t)k * S + lane] = lt[(size_t)k * S + lane];
-    }
+    if (t.ok) write_point<T, S, C>(a, sys, bs, K, lane);
 }
 
 // b_bar_i = xbar_i - (H a + C^T beta)_i on the active set - the row products of the finish step with rho 0: a_A = 0, so
@@ -334,8 +209,6 @@ __global__ __launch_bounds__(WAVE) void qp_bound_grad_kernel(const T *__restrict
         }
     }
 }
-
-inline int knot_grid(int K) { return K < 8192 ? K : 8192; }
 
 }  // namespace
 

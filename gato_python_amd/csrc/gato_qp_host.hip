@@ -1,4 +1,5 @@
-// Box-constrained QP (ADMM over the re-solve), its polish and bound gradients: the host side of gato_qp.hip / gato_polish.hip.
+// Box-constrained QP (ADMM over the re-solve), its polish, the active-set iteration and bound gradients: the host side of
+// gato_qp.hip / gato_polish.hip / gato_pdas.hip.
 #include <cmath>
 
 #include "gato_solver.h"
@@ -186,6 +187,89 @@ extern "C" int gato_box_qp_polish(gato_solver *s, const void *d_G_blocks, const 
     const AsmInput in{2, nullptr, nullptr, d_G_blocks, nullptr, nullptr, nullptr, d_C_blocks, true};
     if ((rc = whole_solve(s, o, in, w + o_gp, w + o_cp, p->exit_tol, p->max_iters, p->rho, w + o_lt, w + o_xt, st))) return rc;
     if ((rc = s->ops->polish_finish(s->d, a, st))) return rc;
+    GATO_HIP_CHECK(hipStreamSynchronize(st));
+    return gato_pcg_status(s, nullptr);
+}
+
+// ---- primal-dual active-set iteration: the polish iterated (gato_pdas.hip) -----------------------
+// Per solve: add rho, the masked inversion and shifted right-hand side, the stage path of the whole solve (all as in the
+// polish), then the step and the decision and one read of the live count.
+extern "C" int gato_box_qp_pdas(gato_solver *s, const void *d_G_blocks, const void *d_C_blocks, const void *d_g, const void *d_c,
+                                const void *d_lo, const void *d_hi, signed char *d_act, const gato_box_qp_params *p,
+                                int max_pdas_iters, void *d_x, void *d_z, void *d_y, void *d_lambda, int *d_iters, int *d_status,
+                                double *d_res, void *stream)
+{
+    if (!solver_usable(s, "box_qp_pdas", "QP solves")) return GATO_EINVAL;
+    if (!p || !d_G_blocks || (!d_C_blocks && s->d.K > 1) || !d_g || !d_c || !d_lo || !d_hi || !d_act || !d_x || !d_z || !d_y ||
+        !d_lambda || !d_iters || !d_status || !d_res) {
+        set_error("box_qp_pdas: every pointer is required (d_C_blocks may be NULL only for K = 1)");
+        return GATO_EINVAL;
+    }
+    const bool fin = std::isfinite(p->rho) && std::isfinite(p->eps_abs) && std::isfinite(p->eps_rel) && std::isfinite(p->exit_tol);
+    if (!fin || p->rho < 0 || p->eps_abs < 0 || p->eps_rel < 0 || p->exit_tol < 0 || p->max_iters < 1 || max_pdas_iters < 1) {
+        set_error("box_qp_pdas: parameters out of range (want finite values, rho, eps_abs, eps_rel, exit_tol >= 0, max_iters, "
+                  "max_pdas_iters >= 1)");
+        return GATO_EINVAL;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (stream_is_capturing(st)) {
+        set_error("box_qp_pdas: the stream is being captured; the loop reads the live count on the host and cannot be captured");
+        return GATO_EINVAL;
+    }
+    GATO_HIP_CHECK(hipSetDevice(s->device));
+    const Dims &d = s->d;
+    const size_t e = s->esz, B = d.B, vN = align_up(B * d.N() * e), vK = align_up(B * d.sk() * e);
+    const size_t o_gp = 0, o_cp = o_gp + vN, o_xt = o_cp + vK, o_lt = o_xt + vN, o_xp = o_lt + vK, o_zp = o_xp + vN;
+    const size_t o_yp = o_zp + vN, o_a2 = o_yp + vN, o_sl = o_a2 + align_up(B * d.N());
+    const size_t o_rn = o_sl + align_up(B * 2 * GATO_POLISH_NSLOT * 8), o_pol = o_rn + align_up(B * 4 * sizeof(int));
+    const size_t o_ctr = o_pol + align_up(B * sizeof(int)), bytes = o_ctr + 256;
+    int rc;
+    if ((rc = grow_ws(&s->pol_ws, &s->pol_ws_bytes, bytes, st))) return rc;
+    char *w = s->pol_ws;
+    int *ctr = (int *)(w + o_ctr);
+    GATO_HIP_CHECK(hipMemsetAsync(w + o_sl, 0, bytes - o_sl, st));                   // both sets of maxima and counts, the counters
+    GATO_HIP_CHECK(hipMemsetAsync(d_status, 0xff, B * sizeof(int), st));             // -1: running
+    PdasArgs a;
+    memset(&a, 0, sizeof(a));
+    PolishArgs &q = a.p;
+    q.G = d_G_blocks; q.Cd = d_C_blocks; q.g = d_g; q.c = d_c; q.lo = d_lo; q.hi = d_hi; q.act = d_act;
+    q.Gd = s->G_dense; q.Ginv = s->Ginv; q.gp = w + o_gp; q.cp = w + o_cp; q.xt = w + o_xt; q.lt = w + o_lt;
+    q.xp = w + o_xp; q.zp = w + o_zp; q.yp = w + o_yp; q.slots = (unsigned long long *)(w + o_sl); q.bad = ctr + 3;
+    q.x = d_x; q.z = d_z; q.y = d_y; q.lam = d_lambda; q.status = d_status; q.polish = (int *)(w + o_pol); q.res = d_res;
+    q.rho = p->rho; q.eps_abs = p->eps_abs; q.eps_rel = p->eps_rel;
+    a.act = d_act; a.act2 = (signed char *)(w + o_a2); a.round = (int *)(w + o_rn); a.ctr = ctr; a.iters = d_iters;
+    s->d.k_lo = s->d.k_hi = 0;
+    s->as.valid = 0;
+    s->lc.valid = 0;                        // G_dense and Ginv are rewritten: nothing earlier is left to recover
+    if ((rc = s->ops->pdas_check(s->d, a, st))) return rc;
+    PcgOpts o = pcg_opts(*s);
+    o.warm = 0;                             // every reduced solve is a cold start
+    const AsmInput in{2, nullptr, nullptr, d_G_blocks, nullptr, nullptr, nullptr, d_C_blocks, true};
+    for (int it = 1; it <= max_pdas_iters; ++it) {
+        if ((rc = s->ops->add_rho(s->d, d_G_blocks, p->rho, s->G_dense, st))) return rc;
+        if ((rc = s->ops->polish_prepare(s->d, q, st))) return rc;
+        int h[3] = {0, 0, 0};
+        if (it == 1) {                      // the caller's bounds and start act; later acts are the device's own: valid
+            GATO_HIP_CHECK(hipMemcpyAsync(h, ctr, sizeof(h), hipMemcpyDeviceToHost, st));
+            GATO_HIP_CHECK(hipStreamSynchronize(st));
+            if (h[1] > 0 || h[2] > 0) {
+                set_error("box_qp_pdas:%s%s; d_status marks the systems",
+                          h[1] > 0 ? " a bound is NaN or lo > hi (BAD_BOUNDS)" : "",
+                          h[2] > 0 ? " a start act is not -1, 0 or 1, names an infinite bound or a state of x_0 (BAD_ACTIVE)" : "");
+                return GATO_EINVAL;
+            }
+        }
+        if ((rc = whole_solve(s, o, in, w + o_gp, w + o_cp, p->exit_tol, p->max_iters, p->rho, w + o_lt, w + o_xt, st))) return rc;
+        if ((rc = s->ops->pdas_step(s->d, a, it, it == max_pdas_iters, st))) return rc;
+        if (it == max_pdas_iters) break;    // every system still live froze in that decision
+        hipError_t he = hipMemcpyAsync(h, ctr, sizeof(int), hipMemcpyDeviceToHost, st);
+        if (he == hipSuccess) he = hipStreamSynchronize(st);
+        if (he != hipSuccess) {
+            set_error("box_qp_pdas: reading the live count failed: %s", hipGetErrorString(he));
+            return GATO_EHIP;
+        }
+        if (h[0] == 0) break;
+    }
     GATO_HIP_CHECK(hipStreamSynchronize(st));
     return gato_pcg_status(s, nullptr);
 }

@@ -4,13 +4,15 @@
 
 solves  min 1/2 x^T (G + rho I) x - g^T x  s.t.  C x = c,  lo <= x <= hi  - the KKT system of autograd.kkt_solve plus bounds on
 the states and controls - by ADMM over the device re-solve (Solver.box_qp, gato_box_qp_solve), optionally polished on the ADMM
-result's active set (polish=True).  It is NOT differentiable: the inputs are read detached and the
-outputs carry no grad_fn.
+result's active set (polish=True), or by the primal-dual active-set iteration alone (method="pdas",
+Solver.box_qp_pdas).  It is NOT differentiable: the inputs are read detached and the outputs carry no
+grad_fn.
 
     box_qp_layer(Q, R, A, B, q, r, c, x_lo, x_hi, u_lo, u_hi, *, rho, exit_tol, max_iters, **admm) -> (x, lam, info)
 
-is the differentiable form: ADMM, the active set, the polish; the backward pass is one re-solve of the polish assembly (the
-reduced KKT system) plus the gradient launches.  Only device tensors are taken; there is no CPU fallback.
+is the differentiable form: ADMM, the active set, the polish (or method="pdas": the active-set iteration alone); the backward
+pass is one re-solve of the polish assembly (the reduced KKT system) plus the gradient launches.  Only device tensors are
+taken; there is no CPU fallback.
 """
 from __future__ import annotations
 
@@ -35,7 +37,8 @@ def _bound(v, shape, name, ref):
 
 
 def box_qp(Q, R, A, B, q, r, c, x_lo, x_hi, u_lo, u_hi, *, rho, exit_tol, max_iters, admm_rho=0.1, sigma=1e-6, alpha=1.6,
-           eps_abs=1e-6, eps_rel=1e-6, max_admm_iters=4000, check_every=25, warm=None, polish=False):
+           eps_abs=1e-6, eps_rel=1e-6, max_admm_iters=4000, check_every=25, warm=None, polish=False, method="admm",
+           polish_iters=1, max_pdas_iters=30):
     """Box-constrained QP from math-shaped blocks, at most one leading batch dimension:
     Q [*,K,S,S], R [*,K-1,C,C], A [*,K-1,S,S], B [*,K-1,S,C], q [*,K,S], r [*,K-1,C], c [*,K,S] as kkt_solve takes them (A, B
     the raw values stored in C: -A and -B of the dynamics), and the bounds x_lo, x_hi [*,K,S], u_lo, u_hi [*,K-1,C] - numbers
@@ -43,7 +46,16 @@ def box_qp(Q, R, A, B, q, r, c, x_lo, x_hi, u_lo, u_hi, *, rho, exit_tol, max_it
     lam start the iteration).  Returns a BoxQPResult with flat x, z, y [*, N], lam [*, S K] (dz layout, as kkt_solve returns
     dz and lam) and iters, status, res_prim, res_dual [*] (scalars unbatched).  Raises ValueError for lo > hi or a NaN bound.
     polish=True: the ADMM result is then polished on its active set (Solver.box_qp_polish): where the polished point passes
-    the termination test it replaces the result (status CONVERGED); result.polished [*] holds the codes (_lib.POLISH_*)."""
+    the termination test it replaces the result (status CONVERGED); result.polished [*] holds the codes (_lib.POLISH_*).
+    polish_iters > 1 (with polish=True): the polish stage is the active-set iteration (Solver.box_qp_pdas) started from the
+    ADMM result's active set, at most polish_iters reduced solves; result.act [*, N] is its final active set.
+    method="pdas": no ADMM - the active-set iteration from a cold start (nothing active), or from warm.act when warm is a
+    previous result of method="pdas" (an MPC shift), at most max_pdas_iters reduced solves; iters counts them, and a system
+    that does not end CONVERGED returns zeros.  The ADMM parameters and polish are not read."""
+    if method not in ("admm", "pdas"):
+        raise ValueError(f"box_qp: method must be 'admm' or 'pdas', got {method!r}")
+    if int(polish_iters) < 1 or int(max_pdas_iters) < 1:
+        raise ValueError("box_qp: polish_iters and max_pdas_iters must be at least 1")
     args = dict(Q=Q, R=R, A=A, B=B, q=q, r=r, c=c)
     for name, t in args.items():
         if not isinstance(t, torch.Tensor):
@@ -71,6 +83,17 @@ def box_qp(Q, R, A, B, q, r, c, x_lo, x_hi, u_lo, u_hi, *, rho, exit_tol, max_it
         lo = torch.cat([torch.cat([xl[:, :K - 1], ul], 2).reshape(Bt, -1), xl[:, K - 1]], 1).contiguous()
         hi = torch.cat([torch.cat([xh[:, :K - 1], uh], 2).reshape(Bt, -1), xh[:, K - 1]], 1).contiguous()
         sol = _solver(S, C, K, Bt, g.dtype, g.device.index)
+        if method == "pdas":
+            act = None
+            if warm is not None:
+                act = getattr(warm, "act", None)
+                if not isinstance(act, torch.Tensor) or act.numel() != Bt * sol.N or act.dtype != torch.int8 or act.device != g.device:
+                    raise ValueError(f"box_qp: warm.act does not match this problem ({Bt} x {sol.N} int8 on {g.device}); "
+                                     "method='pdas' starts from the act of a previous method='pdas' result")
+                act = act.reshape(-1).contiguous()
+            res = sol.box_qp_pdas(Gb, Cb, g, cc, lo, hi, rho=rho, exit_tol=exit_tol, max_iters=max_iters, eps_abs=eps_abs,
+                                  eps_rel=eps_rel, max_pdas_iters=max_pdas_iters, act=act)
+            return _shaped(res, sol, Bt, batched)
         out = {}
         if warm is not None:
             for name in ("z", "y", "lam"):
@@ -84,9 +107,25 @@ def box_qp(Q, R, A, B, q, r, c, x_lo, x_hi, u_lo, u_hi, *, rho, exit_tol, max_it
                          check_every=check_every, warm=warm is not None, **out)
         if polish:
             act = sol.box_qp_active_set(res.z, res.y, lo, hi)
-            sol.box_qp_polish(Gb, Cb, g, cc, lo, hi, act, res, rho=rho, exit_tol=exit_tol, max_iters=max_iters,
-                              eps_abs=eps_abs, eps_rel=eps_rel)
+            if int(polish_iters) == 1:
+                sol.box_qp_polish(Gb, Cb, g, cc, lo, hi, act, res, rho=rho, exit_tol=exit_tol, max_iters=max_iters,
+                                  eps_abs=eps_abs, eps_rel=eps_rel)
+            else:
+                _polish_iterated(sol, (Gb, Cb, g, cc, lo, hi), act, res, int(polish_iters), rho=rho, exit_tol=exit_tol,
+                                 max_iters=max_iters, eps_abs=eps_abs, eps_rel=eps_rel)
     return _shaped(res, sol, Bt, batched)
+
+
+def _polish_iterated(sol, inp, act, res, polish_iters, **pol):
+    """The polish stage as the active-set iteration from act: where it converges, its point replaces the ADMM result in place
+    (x, z, y, lam are written by the device only there), status becomes CONVERGED and the residuals the point's; elsewhere
+    the ADMM result stays.  iters stays the count of ADMM x-steps."""
+    pd = sol.box_qp_pdas(*inp, act=act, max_pdas_iters=polish_iters, x=res.x, z=res.z, y=res.y, lam=res.lam, **pol)
+    ok = pd.status == _lib.QP_CONVERGED
+    res.status.copy_(torch.where(ok, pd.status, res.status))
+    res.res_prim.copy_(torch.where(ok, pd.res_prim, res.res_prim))
+    res.res_dual.copy_(torch.where(ok, pd.res_dual, res.res_dual))
+    res.polished, res.act = pd.polished, pd.act
 
 
 def _shaped(res, sol, Bt, batched):
@@ -94,7 +133,8 @@ def _shaped(res, sol, Bt, batched):
     shp = lambda t, n: t.view(Bt, n) if batched else t.view(n)
     first = (lambda t: t) if batched else (lambda t: t[0])
     return BoxQPResult(shp(res.x, N), shp(res.z, N), shp(res.y, N), shp(res.lam, sk), first(res.iters), first(res.status),
-                       first(res.res_prim), first(res.res_dual), None if res.polished is None else first(res.polished))
+                       first(res.res_prim), first(res.res_dual), None if res.polished is None else first(res.polished),
+                       None if res.act is None else shp(res.act, N))
 
 
 # ---- the differentiable layer -----------------------------------------------------------------------------------------
@@ -104,11 +144,17 @@ class _BoxQPLayer(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, Gb, Cb, g, c, lo, hi, sol, opts, box):
-        res = sol.box_qp(Gb, Cb, g, c, lo, hi, **opts)
-        act = sol.box_qp_active_set(res.z, res.y, lo, hi)
+        opts = dict(opts)
+        pdas_iters = opts.pop("max_pdas_iters", None)      # set: the active-set iteration alone (method="pdas")
         pol = dict(rho=opts["rho"], exit_tol=opts["exit_tol"], max_iters=opts["max_iters"], eps_abs=opts["eps_abs"],
                    eps_rel=opts["eps_rel"])
-        sol.box_qp_polish(Gb, Cb, g, c, lo, hi, act, res, **pol)
+        if pdas_iters is not None:
+            res = sol.box_qp_pdas(Gb, Cb, g, c, lo, hi, max_pdas_iters=pdas_iters, **pol)
+            act = res.act
+        else:
+            res = sol.box_qp(Gb, Cb, g, c, lo, hi, **opts)
+            act = sol.box_qp_active_set(res.z, res.y, lo, hi)
+            sol.box_qp_polish(Gb, Cb, g, c, lo, hi, act, res, **pol)
         box.append(res)
         ctx.sol, ctx.pol, ctx.gen = sol, pol, sol.get_option("assembly_gen")
         ctx.codes = res.polished.cpu()
@@ -132,8 +178,8 @@ class _BoxQPLayer(torch.autograd.Function):
         if unpolished.any():
             bad = unpolished.nonzero().flatten().tolist()
             raise RuntimeError(f"box_qp_layer: systems {bad} have a nonzero upstream gradient but their polish was not accepted "
-                               f"(codes {ctx.codes[bad].tolist()}, _lib.POLISH_*): their x and lam are ADMM iterates, which "
-                               "have no gradient here")
+                               f"(codes {ctx.codes[bad].tolist()}, _lib.POLISH_*): their x and lam are ADMM iterates (zeros "
+                               "after method='pdas'), which have no gradient here")
         if not live.any():                   # every system's gradient is exactly zero: no re-solve (its PCG would form 0/0)
             zero = lambda t, i: torch.zeros_like(t) if ctx.needs_input_grad[i] else None
             return (zero(Gb, 0), zero(Cb, 1), zero(g, 2), zero(c, 3), zero(lo, 4), zero(hi, 5)) + (None,) * 3
@@ -176,12 +222,16 @@ def _bound_t(v, shape, name, ref):
 
 
 def box_qp_layer(Q, R, A, B, q, r, c, x_lo, x_hi, u_lo, u_hi, *, rho, exit_tol, max_iters, admm_rho=0.1, sigma=1e-6,
-                 alpha=1.6, eps_abs=1e-6, eps_rel=1e-6, max_admm_iters=4000, check_every=25):
+                 alpha=1.6, eps_abs=1e-6, eps_rel=1e-6, max_admm_iters=4000, check_every=25, method="admm", max_pdas_iters=30):
     """Differentiable box-constrained QP: the inputs of box_qp; returns (x [*, N], lam [*, S K], info) with x and lam those
     of the polished solution, differentiable with respect to every tensor input (the bounds included; Q and R as symmetric,
     DESIGN.md section 3.6), and info a detached BoxQPResult (info.polished: the polish codes).  A system whose polish was not
     accepted returns its ADMM iterate; a backward pass through it with a nonzero upstream gradient raises RuntimeError.
-    rho is not differentiated and double backward is not supported."""
+    method="pdas": the forward pass is the active-set iteration alone (Solver.box_qp_pdas, cold start, at most max_pdas_iters
+    reduced solves; the ADMM parameters are not read; a system that does not converge returns zeros); the backward pass is the
+    same.  rho is not differentiated and double backward is not supported."""
+    if method not in ("admm", "pdas"):
+        raise ValueError(f"box_qp_layer: method must be 'admm' or 'pdas', got {method!r}")
     args = dict(Q=Q, R=R, A=A, B=B, q=q, r=r, c=c)
     for name, t in args.items():
         if not isinstance(t, torch.Tensor):
@@ -209,11 +259,14 @@ def box_qp_layer(Q, R, A, B, q, r, c, x_lo, x_hi, u_lo, u_hi, *, rho, exit_tol, 
     sol = _solver(S, C, K, Bt, dtype, device)
     opts = dict(rho=float(rho), exit_tol=float(exit_tol), max_iters=int(max_iters), admm_rho=admm_rho, sigma=sigma, alpha=alpha,
                 eps_abs=eps_abs, eps_rel=eps_rel, max_admm_iters=max_admm_iters, check_every=check_every)
+    if method == "pdas":
+        opts["max_pdas_iters"] = int(max_pdas_iters)
     box = []
     x, lam = _BoxQPLayer.apply(Gb, Cb, g, cc, lo, hi, sol, opts, box)
     info = _shaped(box[0], sol, Bt, batched)
     info = BoxQPResult(*(t.detach().clone() for t in (info.x, info.z, info.y, info.lam, info.iters, info.status, info.res_prim,
-                                                      info.res_dual, info.polished)))
+                                                      info.res_dual, info.polished)),
+                       act=None if info.act is None else info.act.clone())
     return (x, lam, info) if batched else (x[0], lam[0], info)
 
 

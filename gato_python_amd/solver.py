@@ -20,13 +20,14 @@ _TORCH_DT = {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.fl
 class BoxQPResult:
     """Result of a box-constrained QP solve: x, z, y [.., N], lam [.., S K], iters, status [..] (int32: _lib.QP_*),
     res_prim, res_dual [..] (float64) - the true QP residuals of the returned iterate - and polished [..] (int32:
-    _lib.POLISH_*; None unless a polish was asked for)."""
-    __slots__ = ("x", "z", "y", "lam", "iters", "status", "res_prim", "res_dual", "polished")
+    _lib.POLISH_*; None unless a polish was asked for); act [.., N] (int8) the final active set of an active-set solve
+    (box_qp_pdas; None otherwise)."""
+    __slots__ = ("x", "z", "y", "lam", "iters", "status", "res_prim", "res_dual", "polished", "act")
 
-    def __init__(self, x, z, y, lam, iters, status, res_prim, res_dual, polished=None):
+    def __init__(self, x, z, y, lam, iters, status, res_prim, res_dual, polished=None, act=None):
         self.x, self.z, self.y, self.lam = x, z, y, lam
         self.iters, self.status, self.res_prim, self.res_dual = iters, status, res_prim, res_dual
-        self.polished = polished
+        self.polished, self.act = polished, act
 
     def __repr__(self):
         pol = "" if self.polished is None else f", polished={self.polished.tolist()}"
@@ -279,6 +280,51 @@ class Solver:
         _lib.check(rc)
         result.polished = codes
         return codes
+
+    def box_qp_pdas(self, Gb, Cb, g, c, lo, hi, *, rho, exit_tol, max_iters, eps_abs=1e-6, eps_rel=1e-6, max_pdas_iters=30,
+                    act=None, x=None, z=None, y=None, lam=None):
+        """The box QP of box_qp by the primal-dual active-set iteration (gato_box_qp_pdas): the polish
+        iterated from the active set act [B N] int8 (None: nothing active, a cold start; the tensor is not written) until
+        the polished point passes the polish's test.  No penalty parameter and no ADMM.  Returns a BoxQPResult: status
+        CONVERGED (x, z, y, lam, res_* written), MAX_ITERS or NONFINITE (they are not: the optional output tensors x, z, y, lam
+        keep what they held, new ones are zero); iters the reduced solves; polished ACCEPTED where CONVERGED; act the final
+        active set, that of the solver's assembly afterwards (solve_rhs re-solves the reduced system).  Blocking.  Raises
+        ValueError for a NaN bound or lo > hi, and for an act that names an infinite bound or a state of x_0."""
+        B, N, sk = self.batch, self.N, self.sizes["sk"]
+        zeros = lambda n: torch.zeros(n, dtype=self.dtype, device=f"cuda:{self.device}")
+        x = zeros(B * N) if x is None else x
+        z = zeros(B * N) if z is None else z
+        y = zeros(B * N) if y is None else y
+        lam = zeros(B * sk) if lam is None else lam
+        if act is None:
+            act = torch.zeros(B * N, dtype=torch.int8, device=f"cuda:{self.device}")
+        else:
+            self._check_vecs("box_qp_pdas", [("act", act, B * N, torch.int8)])
+            act = act.detach().reshape(-1).clone()
+        self._check_vecs("box_qp_pdas", [
+            ("Gb", Gb, B * self.sizes["G_dense"], self.dtype), ("Cb", Cb, B * self.sizes["C_dense"], self.dtype),
+            ("g", g, B * N, self.dtype), ("c", c, B * sk, self.dtype), ("lo", lo, B * N, self.dtype),
+            ("hi", hi, B * N, self.dtype), ("x", x, B * N, self.dtype), ("z", z, B * N, self.dtype), ("y", y, B * N, self.dtype),
+            ("lam", lam, B * sk, self.dtype)])
+        iters = torch.zeros(B, dtype=torch.int32, device=act.device)
+        status = self.new(B, torch.int32)
+        res = torch.zeros(2 * B, dtype=torch.float64, device=act.device)
+        p = _lib.BoxQpParams()
+        _lib.lib().gato_box_qp_default_params(ct.byref(p))
+        p.rho, p.eps_abs, p.eps_rel, p.exit_tol, p.max_iters = float(rho), float(eps_abs), float(eps_rel), float(exit_tol), int(max_iters)
+        rc = _lib.lib().gato_box_qp_pdas(self._h, _ptr(Gb), _ptr(Cb), _ptr(g), _ptr(c), _ptr(lo), _ptr(hi), _ptr(act), ct.byref(p),
+                                         int(max_pdas_iters), _ptr(x), _ptr(z), _ptr(y), _ptr(lam), _ptr(iters), _ptr(status),
+                                         _ptr(res), self._stream())
+        msg = _lib.lib().gato_last_error().decode() if rc != 0 else ""
+        if "BAD_BOUNDS" in msg or "BAD_ACTIVE" in msg:
+            st = status.cpu()
+            bad = ((st == _lib.QP_BAD_BOUNDS) | (st == _lib.QP_BAD_ACTIVE)).nonzero().flatten().tolist()
+            raise ValueError(f"box_qp_pdas: systems {bad}: " + msg)
+        _lib.check(rc)
+        res = res.view(B, 2)
+        codes = torch.where(status == _lib.QP_CONVERGED, _lib.POLISH_ACCEPTED,
+                            torch.where(status == _lib.QP_NONFINITE, _lib.POLISH_NONFINITE, _lib.POLISH_REJECTED)).to(torch.int32)
+        return BoxQPResult(x, z, y, lam, iters, status, res[:, 0], res[:, 1], codes, act)
 
     def box_qp_bound_grad(self, Gb, Cb, act, xbar, a, beta, lo_bar=None, hi_bar=None):
         """(lo_bar, hi_bar) [B N] of a polished solution from its active set, the upstream x_bar and the adjoint (a, beta) of

@@ -404,6 +404,29 @@ int gato_box_qp_polish(gato_solver *s, const void *d_G_blocks, const void *d_C_b
  * NULL only for K = 1) and on a cluster rank. */
 int gato_box_qp_bound_grad(gato_solver *s, const void *d_G_blocks, const void *d_C_blocks, const signed char *d_act, const void *d_xbar,
                            const void *d_a, const void *d_beta, void *d_lo_bar, void *d_hi_bar, void *stream);
+/* Primal-dual active-set iteration: the polish iterated.  From the start act in d_act, per system: the reduced
+ * solve of gato_box_qp_polish on act; if the polished point passes the polish's acceptance test it is written to d_x, d_z,
+ * d_y, d_lambda, d_res, d_status = GATO_QP_CONVERGED and d_iters = the number of reduced solves; a non-finite maximum ends
+ * the system in GATO_QP_NONFINITE.  Otherwise the next act is 0 on the states of x_0, -1 where lo == hi, for a free variable +1
+ * where x > hi, -1 where x < lo, for an active one kept while its multiplier has the bound's sign (y > 0 upper, y < 0 lower)
+ * and 0 otherwise - exact comparisons.  GATO_QP_MAX_ITERS after max_pdas_iters solves, or at once when the next act equals
+ * the current one (d_iters = the solves done).  A system that does not end CONVERGED has none of d_x, d_z, d_y, d_lambda, d_res
+ * written.  A system that has ended is not written again and no system's result depends on its batch neighbours.  d_act
+ * [B][N] int8: in the start (all 0: a cold start), out the act of every system's last reduced solve.  No penalty parameter:
+ * of p only rho, exit_tol, max_iters (the PCG), eps_abs and eps_rel are read.  Exact and finite for bounds on the controls
+ * alone (the reduced matrix is never singular); with many active state bounds it may cycle or meet a singular reduced
+ * system, which ends in MAX_ITERS or NONFINITE, never in a wrong answer.  Blocking: the live count is read once per solve.
+ * GATO_EINVAL, nothing enqueued, for a captured stream, a cluster rank, a NULL pointer or a parameter out of range;
+ * GATO_EINVAL after the first launches for a NaN bound or lo > hi (d_status = GATO_QP_BAD_BOUNDS) and for a start act that is
+ * not -1, 0 or 1, names an infinite bound or a state of x_0 (d_status = GATO_QP_BAD_ACTIVE); -1 on the other systems, no
+ * output written, the solver has no assembly.  Side effect: one whole-solve assembly per solve (assembly_gen advances by the
+ * number of solves); the last one is the polish assembly of the returned d_act, so gato_solve_rhs is the adjoint of the
+ * backward pass exactly as after gato_box_qp_polish. */
+#define GATO_QP_BAD_ACTIVE 4
+int gato_box_qp_pdas(gato_solver *s, const void *d_G_blocks, const void *d_C_blocks, const void *d_g, const void *d_c,
+                     const void *d_lo, const void *d_hi, signed char *d_act, const gato_box_qp_params *p, int max_pdas_iters,
+                     void *d_x, void *d_z, void *d_y, void *d_lambda, int *d_iters, int *d_status, double *d_res /* [B][2] */,
+                     void *stream);
 
 /* ---- direct block input (new): the caller already holds the per-knot blocks in the
  * reference's dense layouts - d_G_blocks as G_dense WITHOUT rho, d_C_blocks as C_dense - so the CSR scatter is
