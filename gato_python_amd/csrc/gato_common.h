@@ -378,6 +378,30 @@ int launch_pdas_check(const Dims &d, const PdasArgs &a, hipStream_t st);
 // after reduced solve `it` (1, 2, ...): the point, act' and the maxima, then the decision (two launches); last: no solve follows
 template <typename T, int S, int C>
 int launch_pdas_step(const Dims &d, const PdasArgs &a, int it, int last, hipStream_t st);
+// the decision launch of launch_pdas_step alone (pdas_decide_kernel), for an iteration with a step kernel of its own
+template <typename T, int S, int C>
+int launch_pdas_decide(const Dims &d, const PdasArgs &a, int it, int last, hipStream_t st);
+// Soft bounds in the active-set iteration (gato_soft.hip).
+struct SoftArgs {
+    PdasArgs d;
+    const void *w;                          // [B][N] weights, 0 = a hard bound; nullptr = all hard
+};
+struct SoftGradArgs {
+    const void *G, *Cd;                     // the caller's blocks (G without rho, C raw)
+    const signed char *act;
+    const void *w, *lo, *hi, *x;            // w may be nullptr (all hard)
+    const void *xbar, *adz, *beta;          // the upstream gradient and the adjoint [a; beta]
+    void *lo_bar, *hi_bar, *w_bar;          // [B][N]
+};
+template <typename T, int S, int C>
+int launch_soft_check(const Dims &d, const SoftArgs &a, hipStream_t st);
+template <typename T, int S, int C>
+int launch_soft_prepare(const Dims &d, const SoftArgs &a, hipStream_t st);
+// the point, act' and the maxima after reduced solve `it`; launch_pdas_decide follows
+template <typename T, int S, int C>
+int launch_soft_step(const Dims &d, const SoftArgs &a, int it, hipStream_t st);
+template <typename T, int S, int C>
+int launch_soft_grad(const Dims &d, const SoftGradArgs &a, hipStream_t st);
 template <typename T, int S>
 int pcg_resident_plan(PcgPlan *plan);
 template <typename T, int S>
@@ -467,6 +491,11 @@ struct Ops {
                          void *, void *, hipStream_t);
     int (*pdas_check)(const Dims &, const PdasArgs &, hipStream_t);
     int (*pdas_step)(const Dims &, const PdasArgs &, int, int, hipStream_t);
+    int (*pdas_decide)(const Dims &, const PdasArgs &, int, int, hipStream_t);
+    int (*soft_check)(const Dims &, const SoftArgs &, hipStream_t);
+    int (*soft_prepare)(const Dims &, const SoftArgs &, hipStream_t);
+    int (*soft_step)(const Dims &, const SoftArgs &, int, hipStream_t);
+    int (*soft_grad)(const Dims &, const SoftGradArgs &, hipStream_t);
     int (*pcg_plan)(PcgPlan *);
     int (*pcg_resident)(const PcgLaunch &, hipStream_t);
     int (*pcg_dma_max_knots)();

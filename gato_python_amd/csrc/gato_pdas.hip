@@ -153,7 +153,18 @@ int launch_pdas_step(const Dims &d, const PdasArgs &a, int it, int last, hipStre
     return GATO_OK;
 }
 
+template <typename T, int S, int C>
+int launch_pdas_decide(const Dims &d, const PdasArgs &a, int it, int last, hipStream_t st)
+{
+    if (d.B < 1 || d.B > 65535) { set_error("pdas_decide: B = %d", d.B); return GATO_EINVAL; }
+    hipLaunchKernelGGL((pdas_decide_kernel<T, S, C>), dim3(knot_grid(d.K), d.B), dim3(WAVE), 0, st, a, it, last, d.K, batch_stride(d));
+    GATO_HIP_CHECK(hipGetLastError());
+    return GATO_OK;
+}
+
 #define X(S_, C_)                                                                                        \
+    template int launch_pdas_decide<float, S_, C_>(const Dims &, const PdasArgs &, int, int, hipStream_t);  \
+    template int launch_pdas_decide<double, S_, C_>(const Dims &, const PdasArgs &, int, int, hipStream_t); \
     template int launch_pdas_check<float, S_, C_>(const Dims &, const PdasArgs &, hipStream_t);         \
     template int launch_pdas_check<double, S_, C_>(const Dims &, const PdasArgs &, hipStream_t);        \
     template int launch_pdas_step<float, S_, C_>(const Dims &, const PdasArgs &, int, int, hipStream_t); \

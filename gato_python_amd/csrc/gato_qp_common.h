@@ -1,4 +1,4 @@
-// Device helpers of the box-QP kernels (gato_qp.hip, gato_polish.hip, gato_pdas.hip).  Internal header.
+// Device helpers of the box-QP kernels (gato_qp.hip, gato_polish.hip, gato_pdas.hip, gato_soft.hip).  Internal header.
 #pragma once
 #include "gato_common.h"
 
@@ -147,6 +147,92 @@ __device__ __forceinline__ PointVar<T> polished_point_knot(PointLds<T, S, C> &L,
         if (ai != 0 && l != h) {                                        // the multiplier's sign: y >= 0 upper, <= 0 lower
             const T w = ai > 0 ? -yn : yn;
             fold(F_SIGN, w > (T)0 ? w : (T)0);
+        }
+        if (i < S) {                                                    // row block k of C x - c
+            const T ci = p.c[(size_t)k * S + i];
+            T cx = xn;
+            if (k > 0) {
+#pragma unroll 4
+                for (int j = 0; j < n; ++j) cx = fmaT(L.sCp[i + j * S], L.sXp[j], cx);
+            }
+            fold(F_PRIM, cx - ci);
+            fold(F_C, ci);
+            fold(F_LAM, L.sLk[i]);
+        }
+        out = PointVar<T>{true, ai, xn, yn, l, h};
+    }
+    return out;
+}
+
+// ---- soft bounds (gato_soft.hip) ----------------------------------------------------------------------
+// Variable v of a system is soft-active: it is active and its weight is positive (w: the system's weights, nullptr = all hard).
+template <typename T>
+__device__ __forceinline__ bool soft_active(signed char act, const T *w, size_t v) { return act != 0 && w && w[v] > (T)0; }
+
+// polished_point_knot with soft bounds: a soft-active variable keeps the reduced solution x', its multiplier is the penalty force
+// y = w (x - b) and z = x (the violation is allowed); H in the residuals is without W.  Every other variable, and every variable
+// when w is nullptr or 0, is polished_point_knot's, operation for operation.  The whole wave calls it.
+template <typename T, int S, int C>
+__device__ __forceinline__ PointVar<T> soft_point_knot(PointLds<T, S, C> &L, const PointSys<T> &p, const T *w, int k, int K, int lane,
+                                                       unsigned long long (&m)[GATO_POLISH_NSLOT])
+{
+    using namespace polf;
+    constexpr int WAVE = 64, n = S + C, SS = S * S, CC = C * C, SN = S * n;
+    auto fold = [&](int f, T v) { const unsigned long long b = mag_bits(v); m[f] = b > m[f] ? b : m[f]; };
+    const int nk = k < K - 1 ? n : S;
+    const size_t v0 = (size_t)k * n;
+    PointVar<T> out{false, 0, (T)0, (T)0, (T)0, (T)0};
+    __syncthreads();
+    const T *Gk = p.G + (size_t)k * (SS + CC);
+    for (int e = lane; e < SS; e += WAVE) L.sQ[e] = Gk[e];
+    if (k < K - 1) {
+        for (int e = lane; e < CC; e += WAVE) L.sR[e] = Gk[SS + e];
+        for (int e = lane; e < SN; e += WAVE) L.sCk[e] = p.Cd[(size_t)k * SN + e];
+    }
+    if (k > 0)
+        for (int e = lane; e < SN; e += WAVE) L.sCp[e] = p.Cd[(size_t)(k - 1) * SN + e];
+    if (lane < nk) {
+        const size_t v = v0 + lane;
+        const signed char ai = p.act[v];
+        L.sXn[lane] = (ai != 0 && !soft_active(ai, w, v)) ? bound_of(ai, p.lo[v], p.hi[v]) : p.xt[v];
+    }
+    if (k > 0 && lane < n) {                                            // knot k-1's x (always a full knot)
+        const size_t v = v0 - n + lane;
+        const signed char ai = p.act[v];
+        L.sXp[lane] = (ai != 0 && !soft_active(ai, w, v)) ? bound_of(ai, p.lo[v], p.hi[v]) : p.xt[v];
+    }
+    if (lane < S) {
+        L.sLk[lane] = p.lt[(size_t)k * S + lane];
+        if (k < K - 1) L.sLn[lane] = p.lt[(size_t)(k + 1) * S + lane];
+    }
+    __syncthreads();
+    if (lane < nk) {
+        const int i = lane;
+        const size_t v = v0 + i;
+        const signed char ai = p.act[v];
+        const bool soft = soft_active(ai, w, v);
+        T hx, ctl;
+        row_products<T, S, C>(i, k < K - 1, L.sQ, L.sR, L.sCk, L.sXn, L.sLk, L.sLn, p.rho, hx, ctl);
+        const T gv = p.g[v], l = p.lo[v], h = p.hi[v], xn = L.sXn[i];
+        T zn = clip(xn, l, h);
+        T yn = ai != 0 ? (gv - hx) - ctl : (T)0;
+        if (soft) {
+            zn = xn;
+            yn = w[v] * (xn - bound_of(ai, l, h));
+        }
+        const T rd = (hx - gv) + ctl + yn;
+        p.xp[v] = xn; p.zp[v] = zn; p.yp[v] = yn;
+        fold(F_PRIM, xn - zn);
+        fold(F_DUAL, rd);
+        fold(F_X, xn);
+        fold(F_Z, zn);
+        fold(F_HX, hx);
+        fold(F_CTL, ctl);
+        fold(F_Y, yn);
+        fold(F_G, gv);
+        if (ai != 0 && l != h) {                                        // the multiplier's sign: y >= 0 upper, <= 0 lower
+            const T ws = ai > 0 ? -yn : yn;
+            fold(F_SIGN, ws > (T)0 ? ws : (T)0);
         }
         if (i < S) {                                                    // row block k of C x - c
             const T ci = p.c[(size_t)k * S + i];

@@ -1,5 +1,5 @@
 // Box-constrained QP (ADMM over the re-solve), its polish, the active-set iteration and bound gradients: the host side of
-// gato_qp.hip / gato_polish.hip / gato_pdas.hip.
+// gato_qp.hip / gato_polish.hip / gato_pdas.hip / gato_soft.hip.
 #include <cmath>
 
 #include "gato_solver.h"
@@ -194,26 +194,28 @@ extern "C" int gato_box_qp_polish(gato_solver *s, const void *d_G_blocks, const 
 // ---- primal-dual active-set iteration: the polish iterated (gato_pdas.hip) -----------------------
 // Per solve: add rho, the masked inversion and shifted right-hand side, the stage path of the whole solve (all as in the
 // polish), then the step and the decision and one read of the live count.
-extern "C" int gato_box_qp_pdas(gato_solver *s, const void *d_G_blocks, const void *d_C_blocks, const void *d_g, const void *d_c,
-                                const void *d_lo, const void *d_hi, signed char *d_act, const gato_box_qp_params *p,
-                                int max_pdas_iters, void *d_x, void *d_z, void *d_y, void *d_lambda, int *d_iters, int *d_status,
-                                double *d_res, void *stream)
+// soft: the kernels of gato_soft.hip (section 3.10) with the weights d_soft_w (NULL: all hard) in place of the check, the
+// prepare and the step; the decision, the stage path and the host reads are the same.  `who` names the entry in errors.
+static int pdas_loop(gato_solver *s, const char *who, bool soft, const void *d_G_blocks, const void *d_C_blocks, const void *d_g,
+                     const void *d_c, const void *d_lo, const void *d_hi, const void *d_soft_w, signed char *d_act,
+                     const gato_box_qp_params *p, int max_pdas_iters, void *d_x, void *d_z, void *d_y, void *d_lambda, int *d_iters,
+                     int *d_status, double *d_res, void *stream)
 {
-    if (!solver_usable(s, "box_qp_pdas", "QP solves")) return GATO_EINVAL;
+    if (!solver_usable(s, who, "QP solves")) return GATO_EINVAL;
     if (!p || !d_G_blocks || (!d_C_blocks && s->d.K > 1) || !d_g || !d_c || !d_lo || !d_hi || !d_act || !d_x || !d_z || !d_y ||
         !d_lambda || !d_iters || !d_status || !d_res) {
-        set_error("box_qp_pdas: every pointer is required (d_C_blocks may be NULL only for K = 1)");
+        set_error("%s: every pointer is required (d_C_blocks may be NULL only for K = 1%s)", who, soft ? ", d_soft_w for no soft bound" : "");
         return GATO_EINVAL;
     }
     const bool fin = std::isfinite(p->rho) && std::isfinite(p->eps_abs) && std::isfinite(p->eps_rel) && std::isfinite(p->exit_tol);
     if (!fin || p->rho < 0 || p->eps_abs < 0 || p->eps_rel < 0 || p->exit_tol < 0 || p->max_iters < 1 || max_pdas_iters < 1) {
-        set_error("box_qp_pdas: parameters out of range (want finite values, rho, eps_abs, eps_rel, exit_tol >= 0, max_iters, "
-                  "max_pdas_iters >= 1)");
+        set_error("%s: parameters out of range (want finite values, rho, eps_abs, eps_rel, exit_tol >= 0, max_iters, "
+                  "max_pdas_iters >= 1)", who);
         return GATO_EINVAL;
     }
     hipStream_t st = (hipStream_t)stream;
     if (stream_is_capturing(st)) {
-        set_error("box_qp_pdas: the stream is being captured; the loop reads the live count on the host and cannot be captured");
+        set_error("%s: the stream is being captured; the loop reads the live count on the host and cannot be captured", who);
         return GATO_EINVAL;
     }
     GATO_HIP_CHECK(hipSetDevice(s->device));
@@ -238,40 +240,83 @@ extern "C" int gato_box_qp_pdas(gato_solver *s, const void *d_G_blocks, const vo
     q.x = d_x; q.z = d_z; q.y = d_y; q.lam = d_lambda; q.status = d_status; q.polish = (int *)(w + o_pol); q.res = d_res;
     q.rho = p->rho; q.eps_abs = p->eps_abs; q.eps_rel = p->eps_rel;
     a.act = d_act; a.act2 = (signed char *)(w + o_a2); a.round = (int *)(w + o_rn); a.ctr = ctr; a.iters = d_iters;
+    SoftArgs sa;
+    memset(&sa, 0, sizeof(sa));
+    sa.d = a; sa.w = d_soft_w;
     s->d.k_lo = s->d.k_hi = 0;
     s->as.valid = 0;
     s->lc.valid = 0;                        // G_dense and Ginv are rewritten: nothing earlier is left to recover
-    if ((rc = s->ops->pdas_check(s->d, a, st))) return rc;
+    if ((rc = soft ? s->ops->soft_check(s->d, sa, st) : s->ops->pdas_check(s->d, a, st))) return rc;
     PcgOpts o = pcg_opts(*s);
     o.warm = 0;                             // every reduced solve is a cold start
     const AsmInput in{2, nullptr, nullptr, d_G_blocks, nullptr, nullptr, nullptr, d_C_blocks, true};
     for (int it = 1; it <= max_pdas_iters; ++it) {
         if ((rc = s->ops->add_rho(s->d, d_G_blocks, p->rho, s->G_dense, st))) return rc;
-        if ((rc = s->ops->polish_prepare(s->d, q, st))) return rc;
+        if ((rc = soft ? s->ops->soft_prepare(s->d, sa, st) : s->ops->polish_prepare(s->d, q, st))) return rc;
         int h[3] = {0, 0, 0};
         if (it == 1) {                      // the caller's bounds and start act; later acts are the device's own: valid
             GATO_HIP_CHECK(hipMemcpyAsync(h, ctr, sizeof(h), hipMemcpyDeviceToHost, st));
             GATO_HIP_CHECK(hipStreamSynchronize(st));
             if (h[1] > 0 || h[2] > 0) {
-                set_error("box_qp_pdas:%s%s; d_status marks the systems",
-                          h[1] > 0 ? " a bound is NaN or lo > hi (BAD_BOUNDS)" : "",
+                set_error("%s:%s%s; d_status marks the systems", who,
+                          h[1] > 0 ? (soft ? " a bound is NaN, lo > hi or a weight is NaN, negative or infinite (BAD_BOUNDS)"
+                                           : " a bound is NaN or lo > hi (BAD_BOUNDS)") : "",
                           h[2] > 0 ? " a start act is not -1, 0 or 1, names an infinite bound or a state of x_0 (BAD_ACTIVE)" : "");
                 return GATO_EINVAL;
             }
         }
         if ((rc = whole_solve(s, o, in, w + o_gp, w + o_cp, p->exit_tol, p->max_iters, p->rho, w + o_lt, w + o_xt, st))) return rc;
-        if ((rc = s->ops->pdas_step(s->d, a, it, it == max_pdas_iters, st))) return rc;
+        if (soft) {
+            if ((rc = s->ops->soft_step(s->d, sa, it, st))) return rc;
+            if ((rc = s->ops->pdas_decide(s->d, a, it, it == max_pdas_iters, st))) return rc;
+        } else if ((rc = s->ops->pdas_step(s->d, a, it, it == max_pdas_iters, st))) return rc;
         if (it == max_pdas_iters) break;    // every system still live froze in that decision
         hipError_t he = hipMemcpyAsync(h, ctr, sizeof(int), hipMemcpyDeviceToHost, st);
         if (he == hipSuccess) he = hipStreamSynchronize(st);
         if (he != hipSuccess) {
-            set_error("box_qp_pdas: reading the live count failed: %s", hipGetErrorString(he));
+            set_error("%s: reading the live count failed: %s", who, hipGetErrorString(he));
             return GATO_EHIP;
         }
         if (h[0] == 0) break;
     }
     GATO_HIP_CHECK(hipStreamSynchronize(st));
     return gato_pcg_status(s, nullptr);
+}
+
+extern "C" int gato_box_qp_pdas(gato_solver *s, const void *d_G_blocks, const void *d_C_blocks, const void *d_g, const void *d_c,
+                                const void *d_lo, const void *d_hi, signed char *d_act, const gato_box_qp_params *p,
+                                int max_pdas_iters, void *d_x, void *d_z, void *d_y, void *d_lambda, int *d_iters, int *d_status,
+                                double *d_res, void *stream)
+{
+    return pdas_loop(s, "box_qp_pdas", false, d_G_blocks, d_C_blocks, d_g, d_c, d_lo, d_hi, nullptr, d_act, p, max_pdas_iters, d_x,
+                     d_z, d_y, d_lambda, d_iters, d_status, d_res, stream);
+}
+
+// ---- soft bounds in the active-set iteration (gato_soft.hip) -------------------------------------
+extern "C" int gato_box_qp_pdas_soft(gato_solver *s, const void *d_G_blocks, const void *d_C_blocks, const void *d_g,
+                                     const void *d_c, const void *d_lo, const void *d_hi, const void *d_soft_w, signed char *d_act,
+                                     const gato_box_qp_params *p, int max_pdas_iters, void *d_x, void *d_z, void *d_y,
+                                     void *d_lambda, int *d_iters, int *d_status, double *d_res, void *stream)
+{
+    return pdas_loop(s, "box_qp_pdas_soft", true, d_G_blocks, d_C_blocks, d_g, d_c, d_lo, d_hi, d_soft_w, d_act, p, max_pdas_iters,
+                     d_x, d_z, d_y, d_lambda, d_iters, d_status, d_res, stream);
+}
+
+extern "C" int gato_box_qp_soft_grad(gato_solver *s, const void *d_G_blocks, const void *d_C_blocks, const signed char *d_act,
+                                     const void *d_soft_w, const void *d_lo, const void *d_hi, const void *d_x, const void *d_xbar,
+                                     const void *d_a, const void *d_beta, void *d_lo_bar, void *d_hi_bar, void *d_w_bar,
+                                     void *stream)
+{
+    if (!solver_usable(s, "box_qp_soft_grad", "gradients")) return GATO_EINVAL;
+    if (!d_G_blocks || (!d_C_blocks && s->d.K > 1) || !d_act || !d_lo || !d_hi || !d_x || !d_xbar || !d_a || !d_beta || !d_lo_bar ||
+        !d_hi_bar || !d_w_bar) {
+        set_error("box_qp_soft_grad: every pointer is required (d_C_blocks may be NULL only for K = 1, d_soft_w for no soft bound)");
+        return GATO_EINVAL;
+    }
+    Dims d = s->d;
+    d.k_lo = d.k_hi = 0; d.rhs = 0;
+    const SoftGradArgs a{d_G_blocks, d_C_blocks, d_act, d_soft_w, d_lo, d_hi, d_x, d_xbar, d_a, d_beta, d_lo_bar, d_hi_bar, d_w_bar};
+    return s->ops->soft_grad(d, a, (hipStream_t)stream);
 }
 
 extern "C" int gato_box_qp_bound_grad(gato_solver *s, const void *d_G_blocks, const void *d_C_blocks, const signed char *d_act,

@@ -5,7 +5,7 @@
 solves  min 1/2 x^T (G + rho I) x - g^T x  s.t.  C x = c,  lo <= x <= hi  - the KKT system of autograd.kkt_solve plus bounds on
 the states and controls - by ADMM over the device re-solve (Solver.box_qp, gato_box_qp_solve), optionally polished on the ADMM
 result's active set (polish=True), or by the primal-dual active-set iteration alone (method="pdas",
-Solver.box_qp_pdas).  It is NOT differentiable: the inputs are read detached and the outputs carry no
+Solver.box_qp_pdas; x_soft / u_soft turn bounds into quadratic penalties, section 3.10).  It is NOT differentiable: the inputs are read detached and the outputs carry no
 grad_fn.
 
     box_qp_layer(Q, R, A, B, q, r, c, x_lo, x_hi, u_lo, u_hi, *, rho, exit_tol, max_iters, **admm) -> (x, lam, info)
@@ -38,7 +38,7 @@ def _bound(v, shape, name, ref):
 
 def box_qp(Q, R, A, B, q, r, c, x_lo, x_hi, u_lo, u_hi, *, rho, exit_tol, max_iters, admm_rho=0.1, sigma=1e-6, alpha=1.6,
            eps_abs=1e-6, eps_rel=1e-6, max_admm_iters=4000, check_every=25, warm=None, polish=False, method="admm",
-           polish_iters=1, max_pdas_iters=30):
+           polish_iters=1, max_pdas_iters=30, x_soft=None, u_soft=None):
     """Box-constrained QP from math-shaped blocks, at most one leading batch dimension:
     Q [*,K,S,S], R [*,K-1,C,C], A [*,K-1,S,S], B [*,K-1,S,C], q [*,K,S], r [*,K-1,C], c [*,K,S] as kkt_solve takes them (A, B
     the raw values stored in C: -A and -B of the dynamics), and the bounds x_lo, x_hi [*,K,S], u_lo, u_hi [*,K-1,C] - numbers
@@ -51,9 +51,16 @@ def box_qp(Q, R, A, B, q, r, c, x_lo, x_hi, u_lo, u_hi, *, rho, exit_tol, max_it
     ADMM result's active set, at most polish_iters reduced solves; result.act [*, N] is its final active set.
     method="pdas": no ADMM - the active-set iteration from a cold start (nothing active), or from warm.act when warm is a
     previous result of method="pdas" (an MPC shift), at most max_pdas_iters reduced solves; iters counts them, and a system
-    that does not end CONVERGED returns zeros.  The ADMM parameters and polish are not read."""
+    that does not end CONVERGED returns zeros.  The ADMM parameters and polish are not read.
+    x_soft [*,K,S], u_soft [*,K-1,C] (method="pdas" only; numbers or tensors that broadcast like the bounds; None: 0): soft
+    bounds.  A weight w > 0 replaces the bound of its variable by the penalty (w / 2) dist(x, [lo,
+    hi])^2, a weight 0 keeps the hard bound.  For a soft variable outside its bounds result.y is the penalty force w (x - b)
+    and result.z = x.  ValueError for method="admm" or polish=True, and for a NaN, negative or infinite weight."""
     if method not in ("admm", "pdas"):
         raise ValueError(f"box_qp: method must be 'admm' or 'pdas', got {method!r}")
+    soft = x_soft is not None or u_soft is not None
+    if soft and (method != "pdas" or polish):
+        raise ValueError("box_qp: x_soft and u_soft need method='pdas' without polish (ADMM and the polish have no soft bounds)")
     if int(polish_iters) < 1 or int(max_pdas_iters) < 1:
         raise ValueError("box_qp: polish_iters and max_pdas_iters must be at least 1")
     args = dict(Q=Q, R=R, A=A, B=B, q=q, r=r, c=c)
@@ -84,6 +91,13 @@ def box_qp(Q, R, A, B, q, r, c, x_lo, x_hi, u_lo, u_hi, *, rho, exit_tol, max_it
         hi = torch.cat([torch.cat([xh[:, :K - 1], uh], 2).reshape(Bt, -1), xh[:, K - 1]], 1).contiguous()
         sol = _solver(S, C, K, Bt, g.dtype, g.device.index)
         if method == "pdas":
+            wt = None
+            if soft:
+                xw = _bound(0.0 if x_soft is None else x_soft, lead + (K, S), "x_soft", q)
+                uw = _bound(0.0 if u_soft is None else u_soft, lead + (K - 1, C), "u_soft", q)
+                if not batched:
+                    xw, uw = xw.unsqueeze(0), uw.unsqueeze(0)
+                wt = torch.cat([torch.cat([xw[:, :K - 1], uw], 2).reshape(Bt, -1), xw[:, K - 1]], 1).contiguous()
             act = None
             if warm is not None:
                 act = getattr(warm, "act", None)
@@ -92,7 +106,7 @@ def box_qp(Q, R, A, B, q, r, c, x_lo, x_hi, u_lo, u_hi, *, rho, exit_tol, max_it
                                      "method='pdas' starts from the act of a previous method='pdas' result")
                 act = act.reshape(-1).contiguous()
             res = sol.box_qp_pdas(Gb, Cb, g, cc, lo, hi, rho=rho, exit_tol=exit_tol, max_iters=max_iters, eps_abs=eps_abs,
-                                  eps_rel=eps_rel, max_pdas_iters=max_pdas_iters, act=act)
+                                  eps_rel=eps_rel, max_pdas_iters=max_pdas_iters, act=act, soft_weight=wt)
             return _shaped(res, sol, Bt, batched)
         out = {}
         if warm is not None:
@@ -209,6 +223,64 @@ class _BoxQPLayer(torch.autograd.Function):
                 mask(lo_bar) if need[4] else None, mask(hi_bar) if need[5] else None) + (None,) * 3
 
 
+class _BoxQPSoftLayer(torch.autograd.Function):
+    """_BoxQPLayer for the active-set iteration with soft bounds: (G_blocks, C_blocks, g, c, lo, hi, w [B, N]) -> (x, lam);
+    the backward pass is one re-solve of the last assembly (the weights of the soft-active variables on its diagonal) plus the
+    gradient launches (Solver.box_qp_soft_grad for lo, hi and w)."""
+
+    @staticmethod
+    def forward(ctx, Gb, Cb, g, c, lo, hi, w, sol, opts, box):
+        pol = dict(rho=opts["rho"], exit_tol=opts["exit_tol"], max_iters=opts["max_iters"], eps_abs=opts["eps_abs"],
+                   eps_rel=opts["eps_rel"])
+        res = sol.box_qp_pdas(Gb, Cb, g, c, lo, hi, max_pdas_iters=opts["max_pdas_iters"], soft_weight=w, **pol)
+        box.append(res)
+        ctx.sol, ctx.pol, ctx.gen = sol, pol, sol.get_option("assembly_gen")
+        ctx.codes = res.polished.cpu()
+        x, lam = res.x.view(sol.batch, sol.N), res.lam.view(sol.batch, sol.sizes["sk"])
+        ctx.save_for_backward(Gb, Cb, g, c, lo, hi, w, res.act, x, lam)
+        ctx.set_materialize_grads(False)
+        return x.clone(), lam.clone()
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, x_bar, lam_bar):
+        Gb, Cb, g, c, lo, hi, w, act, x, lam = ctx.saved_tensors
+        sol, pol = ctx.sol, ctx.pol
+        if x_bar is None and lam_bar is None:
+            return (None,) * 10
+        xb = torch.zeros_like(x) if x_bar is None else x_bar.to(x.dtype).contiguous()
+        lb = torch.zeros_like(lam) if lam_bar is None else lam_bar.to(lam.dtype).contiguous()
+        live = (xb.ne(0).any(1) | lb.ne(0).any(1)).cpu()
+        unpolished = live & (ctx.codes != _lib.POLISH_ACCEPTED)
+        if unpolished.any():
+            bad = unpolished.nonzero().flatten().tolist()
+            raise RuntimeError(f"box_qp_layer: systems {bad} have a nonzero upstream gradient but did not converge (codes "
+                               f"{ctx.codes[bad].tolist()}, _lib.POLISH_*): their x and lam are zeros, which have no gradient here")
+        need = ctx.needs_input_grad
+        if not live.any():                   # every system's gradient is exactly zero: no re-solve (its PCG would form 0/0)
+            return tuple(torch.zeros_like(t) if need[i] else None for i, t in enumerate((Gb, Cb, g, c, lo, hi, w))) + (None,) * 3
+        if sol.get_option("assembly_gen") != ctx.gen or sol.get_option("assembly_valid") == 0:
+            # another forward replaced the assembly: one solve from the saved act rebuilds it (a function of the inputs, the
+            # weights and act alone); its point goes to tensors of its own
+            sol.box_qp_pdas(Gb, Cb, g, c, lo, hi, max_pdas_iters=1, act=act, soft_weight=w, **pol)
+        # the reduced system reads x_bar off the hard-active set only (_BoxQPLayer.backward); a soft-active variable is in it
+        hard = (act.view_as(xb) != 0) & ~(w.view_as(xb) > 0)
+        xf = torch.where(hard, torch.zeros((), dtype=xb.dtype, device=xb.device), xb)
+        a, beta = _adjoint(sol, lam, x, lb, xf, pol["exit_tol"], pol["max_iters"])
+        Gbar = torch.empty_like(Gb) if need[0] else None
+        Cbar = torch.empty_like(Cb) if need[1] else None
+        if Gbar is not None or Cbar is not None:
+            sol.kkt_grad_blocks(x, lam, a, beta, Gbar, Cbar)
+        lo_bar = hi_bar = w_bar = None
+        if need[4] or need[5] or need[6]:
+            lo_bar, hi_bar, w_bar = (t.view_as(lo) for t in sol.box_qp_soft_grad(Gb, Cb, act, w.contiguous(), lo, hi, x.contiguous(),
+                                                                                 xb, a.contiguous(), beta.contiguous()))
+        keep = live.to(x.device)[:, None]
+        mask = lambda t: None if t is None else torch.where(keep, t, torch.zeros((), dtype=t.dtype, device=t.device))
+        return (mask(Gbar), mask(Cbar), mask(a) if need[2] else None, mask(beta) if need[3] else None,
+                mask(lo_bar) if need[4] else None, mask(hi_bar) if need[5] else None, mask(w_bar) if need[6] else None) + (None,) * 3
+
+
 def _bound_t(v, shape, name, ref):
     """A bound as a tensor of `shape` that keeps its autograd history (expand sums the gradient of a broadcast bound)."""
     if not isinstance(v, torch.Tensor):
@@ -222,16 +294,21 @@ def _bound_t(v, shape, name, ref):
 
 
 def box_qp_layer(Q, R, A, B, q, r, c, x_lo, x_hi, u_lo, u_hi, *, rho, exit_tol, max_iters, admm_rho=0.1, sigma=1e-6,
-                 alpha=1.6, eps_abs=1e-6, eps_rel=1e-6, max_admm_iters=4000, check_every=25, method="admm", max_pdas_iters=30):
+                 alpha=1.6, eps_abs=1e-6, eps_rel=1e-6, max_admm_iters=4000, check_every=25, method="admm", max_pdas_iters=30,
+                 x_soft=None, u_soft=None):
     """Differentiable box-constrained QP: the inputs of box_qp; returns (x [*, N], lam [*, S K], info) with x and lam those
     of the polished solution, differentiable with respect to every tensor input (the bounds included; Q and R as symmetric,
     DESIGN.md section 3.6), and info a detached BoxQPResult (info.polished: the polish codes).  A system whose polish was not
     accepted returns its ADMM iterate; a backward pass through it with a nonzero upstream gradient raises RuntimeError.
     method="pdas": the forward pass is the active-set iteration alone (Solver.box_qp_pdas, cold start, at most max_pdas_iters
     reduced solves; the ADMM parameters are not read; a system that does not converge returns zeros); the backward pass is the
-    same.  rho is not differentiated and double backward is not supported."""
+    same.  x_soft, u_soft (method="pdas" only): the soft-bound weights of box_qp; the layer is
+    differentiable with respect to them too.  rho is not differentiated and double backward is not supported."""
     if method not in ("admm", "pdas"):
         raise ValueError(f"box_qp_layer: method must be 'admm' or 'pdas', got {method!r}")
+    soft = x_soft is not None or u_soft is not None
+    if soft and method != "pdas":
+        raise ValueError("box_qp_layer: x_soft and u_soft need method='pdas' (ADMM and the polish have no soft bounds)")
     args = dict(Q=Q, R=R, A=A, B=B, q=q, r=r, c=c)
     for name, t in args.items():
         if not isinstance(t, torch.Tensor):
@@ -262,7 +339,15 @@ def box_qp_layer(Q, R, A, B, q, r, c, x_lo, x_hi, u_lo, u_hi, *, rho, exit_tol, 
     if method == "pdas":
         opts["max_pdas_iters"] = int(max_pdas_iters)
     box = []
-    x, lam = _BoxQPLayer.apply(Gb, Cb, g, cc, lo, hi, sol, opts, box)
+    if soft:
+        xw = _bound_t(0.0 if x_soft is None else x_soft, lead + (K, S), "x_soft", q)
+        uw = _bound_t(0.0 if u_soft is None else u_soft, lead + (K - 1, C), "u_soft", q)
+        if not batched:
+            xw, uw = xw.unsqueeze(0), uw.unsqueeze(0)
+        wt = torch.cat([torch.cat([xw[:, :K - 1], uw], 2).reshape(Bt, -1), xw[:, K - 1]], 1).contiguous()
+        x, lam = _BoxQPSoftLayer.apply(Gb, Cb, g, cc, lo, hi, wt, sol, opts, box)
+    else:
+        x, lam = _BoxQPLayer.apply(Gb, Cb, g, cc, lo, hi, sol, opts, box)
     info = _shaped(box[0], sol, Bt, batched)
     info = BoxQPResult(*(t.detach().clone() for t in (info.x, info.z, info.y, info.lam, info.iters, info.status, info.res_prim,
                                                       info.res_dual, info.polished)),

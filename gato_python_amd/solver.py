@@ -282,14 +282,18 @@ class Solver:
         return codes
 
     def box_qp_pdas(self, Gb, Cb, g, c, lo, hi, *, rho, exit_tol, max_iters, eps_abs=1e-6, eps_rel=1e-6, max_pdas_iters=30,
-                    act=None, x=None, z=None, y=None, lam=None):
+                    act=None, x=None, z=None, y=None, lam=None, soft_weight=None):
         """The box QP of box_qp by the primal-dual active-set iteration (gato_box_qp_pdas): the polish
         iterated from the active set act [B N] int8 (None: nothing active, a cold start; the tensor is not written) until
         the polished point passes the polish's test.  No penalty parameter and no ADMM.  Returns a BoxQPResult: status
         CONVERGED (x, z, y, lam, res_* written), MAX_ITERS or NONFINITE (they are not: the optional output tensors x, z, y, lam
         keep what they held, new ones are zero); iters the reduced solves; polished ACCEPTED where CONVERGED; act the final
         active set, that of the solver's assembly afterwards (solve_rhs re-solves the reduced system).  Blocking.  Raises
-        ValueError for a NaN bound or lo > hi, and for an act that names an infinite bound or a state of x_0."""
+        ValueError for a NaN bound or lo > hi, and for an act that names an infinite bound or a state of x_0.
+        soft_weight [B N] (gato_box_qp_pdas_soft): a weight w_i >= 0 per variable; w_i > 0 replaces the
+        bound of variable i by the penalty (w_i / 2) dist(x_i, [lo_i, hi_i])^2 - where such a variable violates its bound it is
+        active, x holds the reduced solution, z = x and y = w_i (x_i - b_i) - and w_i = 0 keeps the hard bound.  A weight that
+        is NaN, negative or infinite raises ValueError.  None: gato_box_qp_pdas."""
         B, N, sk = self.batch, self.N, self.sizes["sk"]
         zeros = lambda n: torch.zeros(n, dtype=self.dtype, device=f"cuda:{self.device}")
         x = zeros(B * N) if x is None else x
@@ -306,15 +310,21 @@ class Solver:
             ("g", g, B * N, self.dtype), ("c", c, B * sk, self.dtype), ("lo", lo, B * N, self.dtype),
             ("hi", hi, B * N, self.dtype), ("x", x, B * N, self.dtype), ("z", z, B * N, self.dtype), ("y", y, B * N, self.dtype),
             ("lam", lam, B * sk, self.dtype)])
+        if soft_weight is not None:
+            self._check_vecs("box_qp_pdas", [("soft_weight", soft_weight, B * N, self.dtype)])
         iters = torch.zeros(B, dtype=torch.int32, device=act.device)
         status = self.new(B, torch.int32)
         res = torch.zeros(2 * B, dtype=torch.float64, device=act.device)
         p = _lib.BoxQpParams()
         _lib.lib().gato_box_qp_default_params(ct.byref(p))
         p.rho, p.eps_abs, p.eps_rel, p.exit_tol, p.max_iters = float(rho), float(eps_abs), float(eps_rel), float(exit_tol), int(max_iters)
-        rc = _lib.lib().gato_box_qp_pdas(self._h, _ptr(Gb), _ptr(Cb), _ptr(g), _ptr(c), _ptr(lo), _ptr(hi), _ptr(act), ct.byref(p),
-                                         int(max_pdas_iters), _ptr(x), _ptr(z), _ptr(y), _ptr(lam), _ptr(iters), _ptr(status),
-                                         _ptr(res), self._stream())
+        tail = (ct.byref(p), int(max_pdas_iters), _ptr(x), _ptr(z), _ptr(y), _ptr(lam), _ptr(iters), _ptr(status), _ptr(res),
+                self._stream())
+        if soft_weight is None:
+            rc = _lib.lib().gato_box_qp_pdas(self._h, _ptr(Gb), _ptr(Cb), _ptr(g), _ptr(c), _ptr(lo), _ptr(hi), _ptr(act), *tail)
+        else:
+            rc = _lib.lib().gato_box_qp_pdas_soft(self._h, _ptr(Gb), _ptr(Cb), _ptr(g), _ptr(c), _ptr(lo), _ptr(hi),
+                                                  _ptr(soft_weight), _ptr(act), *tail)
         msg = _lib.lib().gato_last_error().decode() if rc != 0 else ""
         if "BAD_BOUNDS" in msg or "BAD_ACTIVE" in msg:
             st = status.cpu()
@@ -339,6 +349,26 @@ class Solver:
         _lib.check(_lib.lib().gato_box_qp_bound_grad(self._h, _ptr(Gb), _ptr(Cb), _ptr(act), _ptr(xbar), _ptr(a), _ptr(beta),
                                                      _ptr(lo_bar), _ptr(hi_bar), self._stream()))
         return lo_bar, hi_bar
+
+    def box_qp_soft_grad(self, Gb, Cb, act, soft_weight, lo, hi, x, xbar, a, beta, lo_bar=None, hi_bar=None, w_bar=None):
+        """(lo_bar, hi_bar, w_bar) [B N] of a converged box_qp_pdas(soft_weight=) point (gato_box_qp_soft_grad) from its act,
+        the upstream x_bar and the adjoint (a, beta) of its last assembly (solve_rhs after the call): the hard formula of
+        box_qp_bound_grad on the hard-active set, w_i a_i and a_i (b_i - x_i) on the soft-active one, 0 elsewhere.
+        soft_weight None: all hard."""
+        B, N, sk = self.batch, self.N, self.sizes["sk"]
+        lo_bar = self.new(B * N) if lo_bar is None else lo_bar
+        hi_bar = self.new(B * N) if hi_bar is None else hi_bar
+        w_bar = self.new(B * N) if w_bar is None else w_bar
+        vecs = [("lo", lo), ("hi", hi), ("x", x), ("xbar", xbar), ("a", a), ("lo_bar", lo_bar), ("hi_bar", hi_bar), ("w_bar", w_bar)]
+        if soft_weight is not None:
+            vecs.append(("soft_weight", soft_weight))
+        self._check_vecs("box_qp_soft_grad", [
+            ("Gb", Gb, B * self.sizes["G_dense"], self.dtype), ("Cb", Cb, B * self.sizes["C_dense"], self.dtype),
+            ("act", act, B * N, torch.int8), ("beta", beta, B * sk, self.dtype)] + [(n, t, B * N, self.dtype) for n, t in vecs])
+        wp = None if soft_weight is None else _ptr(soft_weight)
+        _lib.check(_lib.lib().gato_box_qp_soft_grad(self._h, _ptr(Gb), _ptr(Cb), _ptr(act), wp, _ptr(lo), _ptr(hi), _ptr(x), _ptr(xbar),
+                                                    _ptr(a), _ptr(beta), _ptr(lo_bar), _ptr(hi_bar), _ptr(w_bar), self._stream()))
+        return lo_bar, hi_bar, w_bar
 
     def box_qp_pcg_iters(self):
         """PCG iterations of all x-steps of the latest box_qp call, per system (host int array)."""

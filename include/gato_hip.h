@@ -427,6 +427,34 @@ int gato_box_qp_pdas(gato_solver *s, const void *d_G_blocks, const void *d_C_blo
                      const void *d_lo, const void *d_hi, signed char *d_act, const gato_box_qp_params *p, int max_pdas_iters,
                      void *d_x, void *d_z, void *d_y, void *d_lambda, int *d_iters, int *d_status, double *d_res /* [B][2] */,
                      void *stream);
+/* gato_box_qp_pdas with soft bounds: d_soft_w [B][N] holds a weight w_i >= 0 per variable (dz layout; NULL: all
+ * 0).  w_i = 0 is the hard bound of gato_box_qp_pdas; w_i > 0 replaces the bound of variable i by the penalty
+ * (w_i / 2) dist(x_i, [lo_i, hi_i])^2.  A soft variable that violates its bound is active (+1 above hi, -1 below lo, -1 where
+ * lo == hi: a tracking term) but stays in the reduced system: the diagonal of Q_k or R_k gains w_i, g gains w_i b_i; d_x holds
+ * the reduced solution there, d_z = d_x and d_y = w_i (x_i - b_i), the penalty force.  The acceptance test is that of
+ * gato_box_qp_polish with the dual residual H x - g + C^T lambda + y (H without the weights); the sign test covers the
+ * soft-active variables too.  The next act of a soft variable is decided from x alone (+1 where x > hi, -1 where x < lo, -1
+ * where lo == hi, else 0), that of a hard one as in gato_box_qp_pdas.  The states of x_0 are never active and a variable with
+ * both bounds infinite never is, whatever their weights.  Soft-active variables cannot make a reduced system singular; the
+ * iteration is undamped, so for large weights (1e4 on the synthetic state boxes) it may cycle and end in MAX_ITERS as the hard
+ * one does.  With d_soft_w NULL or all 0 every output is bit for bit that of gato_box_qp_pdas.  Refusals, blocking behaviour
+ * (one host read per solve) and side effects are those of gato_box_qp_pdas; a weight that is NaN, negative or +inf marks its
+ * system GATO_QP_BAD_BOUNDS and the call returns GATO_EINVAL with no output written.  The last assembly is that of the returned
+ * d_act with the weights of its soft-active variables on the diagonal, so gato_solve_rhs is the adjoint of the backward pass. */
+int gato_box_qp_pdas_soft(gato_solver *s, const void *d_G_blocks, const void *d_C_blocks, const void *d_g, const void *d_c,
+                          const void *d_lo, const void *d_hi, const void *d_soft_w /* [B][N], NULL = all hard */,
+                          signed char *d_act, const gato_box_qp_params *p, int max_pdas_iters, void *d_x, void *d_z, void *d_y,
+                          void *d_lambda, int *d_iters, int *d_status, double *d_res /* [B][2] */, void *stream);
+/* Bound and weight gradients of a converged gato_box_qp_pdas_soft point, one launch: with the adjoint [a; beta] of its last
+ * assembly (gato_solve_rhs with g = x_bar masked to 0 on the hard-active set, c = lambda_bar), a hard-active variable gets
+ * gato_box_qp_bound_grad's b_bar_i = x_bar_i - (H a + C^T beta)_i, a soft-active one b_bar_i = w_i a_i and d_w_bar_i =
+ * a_i (b_i - x_i); b_bar goes to d_hi_bar where act = +1 and to d_lo_bar where act = -1 (lo == hi: to lo); every other entry
+ * of the three outputs is 0.  g_bar = a, c_bar = beta and the block gradients are gato_kkt_grad_blocks(x, lambda, a, beta).
+ * All vectors [B][N] but d_beta [B][S*K]; d_soft_w may be NULL (all hard).  Asynchronous.  GATO_EINVAL for another NULL pointer
+ * (d_C_blocks may be NULL only for K = 1) and on a cluster rank. */
+int gato_box_qp_soft_grad(gato_solver *s, const void *d_G_blocks, const void *d_C_blocks, const signed char *d_act,
+                          const void *d_soft_w, const void *d_lo, const void *d_hi, const void *d_x, const void *d_xbar,
+                          const void *d_a, const void *d_beta, void *d_lo_bar, void *d_hi_bar, void *d_w_bar, void *stream);
 
 /* ---- direct block input (new): the caller already holds the per-knot blocks in the
  * reference's dense layouts - d_G_blocks as G_dense WITHOUT rho, d_C_blocks as C_dense - so the CSR scatter is

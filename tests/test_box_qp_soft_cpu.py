@@ -1,0 +1,302 @@
+"""The numpy reference of soft bounds in the active-set iteration (tests/box_qp_soft_ref.py) on the CPU:
+the rule, zero weights equal to box_qp_pdas_ref, the converged point against SLSQP on the penalised objective, the 1 / w
+approach to the hard solution, the gradients against finite differences, the stage restatement, and that the seed walks find
+a seed for every case of tests/test_gpu_box_qp_soft.py."""
+import os
+import re
+
+import numpy as np
+import pytest
+
+import box_qp_pdas_ref as D
+import box_qp_polish_ref as P
+import box_qp_ref as ref
+import box_qp_soft_ref as R
+import kkt_grad_ref as kgr
+from gato_python_amd import synth
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_the_rule_on_soft_variables():
+    """A soft variable is decided from x alone, whatever its act was; a hard one by box_qp_pdas_ref's rule; x_0 and lo == hi
+    as there.  The margin takes the distance to the bounds for soft variables, |y| for hard-active ones."""
+    S = 1
+    #              x0    soft above  soft inside(was active)  soft below  soft eq  hard active y>0  hard active y<=0  soft free-bounds
+    lo = np.array([-1.0, -1.0,       -1.0,                    -1.0,       0.5,     -1.0,            -1.0,             -np.inf])
+    hi = np.array([1.0,  1.0,        1.0,                     1.0,        0.5,     1.0,             1.0,              np.inf])
+    w = np.array([5.0,   5.0,        5.0,                     5.0,        5.0,     0.0,             0.0,              5.0])
+    act = np.array([0,   0,          1,                       1,          0,       1,               1,                0], np.int8)
+    x = np.array([3.0,   1.25,       0.75,                    -1.5,       0.7,     1.0,             1.0,              9.0])
+    y = np.array([0.0,   0.0,        -1.25,                   -12.5,      0.0,     0.3,             -0.2,             0.0])
+    assert R.next_act(act, x, y, lo, hi, w, S).tolist() == [0, 1, 0, -1, -1, 1, 0, 0]
+    assert R.decision_margin(act, x, y, lo, hi, w, S) == pytest.approx(0.2)      # the hard multiplier -0.2
+    assert R.decision_margin(act, x, np.where(w > 0, y, 1.0), lo, hi, w, S) == pytest.approx(0.25)   # x = 1.25 / 0.75 against hi = 1
+    assert R.soft_set(act, w).tolist() == [False, False, True, True, False, False, False, False]
+
+
+def test_point_of_a_soft_active_variable():
+    """y = w (x - b), z = x on a soft-active variable, and the reduced solve is the minimiser of the penalised objective with
+    the active set held."""
+    s, H, Cm, g, c, lo, hi, w = R.soft_problem(4, 2, 5, 0)
+    run = R.pdas_soft(H, Cm, g, c, lo, hi, w, 4)
+    assert run["status"] == R.CONVERGED
+    sa = R.soft_set(run["act"], w)
+    assert sa.any()
+    b = P.bound_values(run["act"], lo, hi)
+    assert np.array_equal(run["y"][sa], (w * (run["x"] - b))[sa]) and np.array_equal(run["z"][sa], run["x"][sa])
+    assert np.all((run["x"] > hi)[sa & (run["act"] > 0)]) and np.all((run["x"] < lo)[sa & (run["act"] < 0) & (lo != hi)])
+    kk = R.kkt_residuals(H, Cm, g, c, lo, hi, w, run["x"], run["y"], run["lam"])
+    print(kk)
+    assert max(kk.values()) <= 1e-9
+
+
+ZERO = [("control", 6, 3, 9), ("control", 14, 7, 3), ("constructed", 4, 2, 9), ("states", 6, 3, 9), ("states", 2, 1, 20)]
+
+
+@pytest.mark.parametrize("kind,S,C,K", ZERO)
+def test_zero_weights_are_the_hard_reference(kind, S, C, K):
+    """With w = 0 the reference is box_qp_pdas_ref.pdas exactly: status, act sequence, margins and x - on problems that
+    converge and on hard state boxes that do not."""
+    if kind == "control":
+        p = D.control_box(S, C, K)[0]
+    elif kind == "constructed":
+        p = D.constructed_cold(S, C, K)[0]
+    elif (S, C) == (2, 1):
+        s, H, Cm, g, c, lo, hi, _ = R.double_integrator_soft()
+        p = dict(H=H, Cm=Cm, g=g, c=c, lo=lo, hi=hi)
+    else:
+        s, H, Cm, g, c, lo, hi, _ = R.soft_problem(S, C, K, 0)
+        p = dict(H=H, Cm=Cm, g=g, c=c, lo=lo, hi=hi)
+    args = tuple(p[k] for k in ("H", "Cm", "g", "c", "lo", "hi"))
+    a = D.pdas(*args, S)
+    b = R.pdas_soft(*args, np.zeros(len(p["g"])), S)
+    print(kind, a["status"], a["iters"])
+    assert (a["status"], a["iters"]) == (b["status"], b["iters"])
+    assert len(a["trace"]) == len(b["trace"])
+    for ta, tb in zip(a["trace"], b["trace"]):
+        assert np.array_equal(ta["act"], tb["act"]) and ta["changed"] == tb["changed"]
+        assert ta["margin"] == tb["margin"] or (np.isnan(ta["margin"]) and np.isnan(tb["margin"]))
+    assert np.array_equal(a["x"], b["x"], equal_nan=True) and np.array_equal(a["lam"], b["lam"], equal_nan=True)
+    if kind == "states":
+        assert a["status"] != D.CONVERGED
+
+
+@pytest.mark.parametrize("S,C,K", [(2, 1, 5), (4, 2, 3)])
+def test_converged_point_is_the_slsqp_minimum(S, C, K):
+    """scipy's SLSQP on the penalised objective (equalities C x = c, the hard bounds as bounds) from x = 0 reaches the
+    reference's converged point within 1e-6."""
+    from scipy.optimize import minimize
+    p = R.soft_box(S, C, K)[0]
+    H, Cm, g, c, lo, hi, w = (p[k] for k in ("H", "Cm", "g", "c", "lo", "hi", "w"))
+    sv = w > 0
+    inf = np.full(len(g), np.inf)
+    bounds = list(zip(np.where(sv, -inf, lo), np.where(sv, inf, hi)))
+    bounds = [(None if not np.isfinite(l) else l, None if not np.isfinite(h) else h) for l, h in bounds]
+    f = lambda x: R.penalised_objective(H, g, lo, hi, w, x)
+    out = minimize(f, np.zeros(len(g)), jac=True, method="SLSQP", bounds=bounds,
+                   constraints=[dict(type="eq", fun=lambda x: Cm @ x - c, jac=lambda x: Cm)], options=dict(ftol=1e-16, maxiter=2000))
+    err = np.abs(out.x - p["run"]["x"]).max()
+    print(out.message, out.nit, "x err", err, "objective", out.fun, f(p["run"]["x"])[0])
+    assert err <= 1e-6, err
+
+
+def test_solution_approaches_the_hard_one_as_one_over_w():
+    """A constructed problem on which the hard iteration converges, every bound soft with one weight w.  On the active set x(w) -
+    b = y(w) / w and y(w) -> y_hard, so x(w) = x_hard + d / w (1 + O(kappa / w)), where d is the move of the hard solution
+    for bounds shifted by y_hard (the reduced solve is linear in the bounds: d is exact) and kappa the stiffness the active
+    variables see, the largest eigenvalue of the inverse of their block of the unconstrained KKT inverse.  Over w = 1e2, 1e3,
+    1e4: the distance to x_hard shrinks, and w (x(w) - x_hard) is d within 2 kappa / w of |d| (2: the norms differ)."""
+    S, C, K = 6, 3, 9
+    p = D.constructed_cold(S, C, K)[0]
+    H, Cm, g, c, lo, hi, act = (p[k] for k in ("H", "Cm", "g", "c", "lo", "hi", "act"))
+    N, m = len(g), len(c)
+    A = np.flatnonzero(act != 0)
+    Kxx = np.linalg.inv(np.block([[H, Cm.T], [Cm, np.zeros((m, m))]]))[:N, :N]
+    kappa = 1.0 / np.linalg.eigvalsh(Kxx[np.ix_(A, A)]).min()
+    eq = lo == hi
+    shift = np.where(act != 0, p["y"], 0.0)
+    x1, _, _ = P.reduced_solve(H, Cm, g, c, lo + np.where((act < 0) | eq, shift, 0.0), hi + np.where((act > 0) | eq, shift, 0.0), act)
+    d = x1 - p["x"]
+    errs, devs = [], []
+    for wt in (1e2, 1e3, 1e4):
+        run = R.pdas_soft(H, Cm, g, c, lo, hi, np.full(N, wt), S, act0=act)
+        assert run["status"] == R.CONVERGED and np.array_equal(run["act"], act), wt
+        errs.append(np.abs(run["x"] - p["x"]).max())
+        devs.append(np.abs(wt * (run["x"] - p["x"]) - d).max() / np.abs(d).max())
+        print("w", wt, "|x(w) - x_hard|", errs[-1], "deviation from d / w", devs[-1], "bar", 2 * kappa / wt)
+        assert devs[-1] <= 2 * kappa / wt
+    assert errs[0] > errs[1] > errs[2] > 0 and devs[0] > devs[1] > devs[2]
+
+
+# ---- gradients ---------------------------------------------------------------------------------------------------------------
+FD_STEP = 1e-6
+FD_ROUND = 1e-13                                  # test_box_qp_polish_cpu.py: the relative accuracy of these dense solves
+
+
+def _solve(inp, rho, act, S):
+    H, Cm, g, c = P.dense_from_blocks(inp["Q"], inp["R"], inp["A"], inp["B"], inp["q"], inp["r"], inp["c"], rho)
+    C, K = inp["R"].shape[-1], inp["Q"].shape[0]
+    lo = ref.dz_layout(inp["x_lo"], inp["u_lo"], S, C, K)
+    hi = ref.dz_layout(inp["x_hi"], inp["u_hi"], S, C, K)
+    w = ref.dz_layout(inp["x_soft"], inp["u_soft"], S, C, K)
+    run = R.pdas_soft(H, Cm, g, c, lo, hi, w, S, act0=act, eps_abs=1e-9, eps_rel=1e-9)
+    return run, (H, Cm, g, c, lo, hi, w)
+
+
+def _fd_problem(S, C, K):
+    """The first walked-style seed (weights 3 on the states, 0.5 on every other control: soft controls too) whose final
+    point has every margin >= 1e-3 and both a hard-active and a soft-active non-equality variable."""
+    for seed in range(D.WALK_SEEDS):
+        s, H, Cm, g, c, lo, hi, w = R.soft_problem(S, C, K, seed, weight=3.0)
+        n = S + C
+        idx = np.arange(s.N)
+        w[(idx % n >= S) & ((idx // n) % 2 == 1)] = 0.5
+        run = R.pdas_soft(H, Cm, g, c, lo, hi, w, S)
+        sa = R.soft_set(run["act"], w)
+        if (run["status"] == R.CONVERGED and run["trace"][-1]["margin"] >= 1e-3 and (sa & (lo != hi)).any()
+                and ((run["act"] != 0) & ~sa & (lo != hi)).any()):
+            return s, lo, hi, w, run
+    raise AssertionError("no seed")
+
+
+@pytest.mark.parametrize("S,C,K", [(4, 2, 5), (6, 3, 4)])
+def test_gradients_match_finite_differences(S, C, K):
+    """soft_grads for all thirteen inputs of box_qp_layer (Q, R symmetric; the weights included) against central differences
+    of the penalised-QP solution along a random direction per input.  Every perturbed problem is solved by the iteration
+    from the unperturbed act and must converge on it at once - the active set is kept, a condition on the inputs (margins >=
+    1e-3 against steps of 1e-6), asserted.  The bound is test_box_qp_polish_cpu.py's."""
+    s, lo, hi, w, run0 = _fd_problem(S, C, K)
+    Q, Rm, A, B, q, r, c = kgr.blocks_of(s)
+    split = lambda v: P.split_states_controls(v, S, C, K)
+    inp = dict(Q=Q, R=Rm, A=A, B=B, q=q, r=r, c=c)
+    for name, v in (("lo", lo), ("hi", hi), ("soft", w)):
+        inp["x_" + name], inp["u_" + name] = split(v)
+    act = run0["act"]
+    run, (H, Cm, g, cc, lo2, hi2, w2) = _solve(inp, s.rho, act, S)
+    assert run["status"] == R.CONVERGED and run["iters"] == 1 and np.array_equal(lo2, lo) and np.array_equal(w2, w)
+    x, lam = run["x"], run["lam"]
+    rng = np.random.default_rng(7)
+    xbar, lambar = rng.standard_normal(len(x)), rng.standard_normal(len(lam))
+    gr = R.soft_grads(H, Cm, act, w, lo, hi, x, lam, xbar, lambar, S, C, K)
+    sa = R.soft_set(act, w)
+    assert not gr["a"][(act != 0) & ~sa].any() and gr["a"][sa].any()
+    L = lambda rr: float(xbar @ rr["x"] + lambar @ rr["lam"])
+    lmag = float(np.abs(xbar) @ np.abs(x) + np.abs(lambar) @ np.abs(lam))
+    for key in ("Q", "R", "A", "B", "q", "r", "c", "x_lo", "x_hi", "u_lo", "u_hi", "x_soft", "u_soft"):
+        V = rng.standard_normal(inp[key].shape)
+        if key in ("Q", "R"):
+            V = 0.5 * (V + np.swapaxes(V, -1, -2))
+        partner = None
+        if key.endswith(("_lo", "_hi")):
+            V = np.where(np.isfinite(inp[key]), V, 0.0)
+            eq = inp[key[0] + "_lo"] == inp[key[0] + "_hi"]
+            if key.endswith("_hi"):
+                V = np.where(eq, 0.0, V)                 # where lo == hi the gradient goes to lo ...
+            else:
+                partner = (key[0] + "_hi", np.where(eq, V, 0.0))   # ... for a shift of both bounds together
+        if key.endswith("_soft"):
+            V = np.where(inp[key] > 0, V, 0.0)           # a hard bound stays hard
+        vals = []
+        for sgn in (1.0, -1.0):
+            pert = dict(inp)
+            pert[key] = inp[key] + sgn * FD_STEP * V
+            if partner is not None:
+                pert[partner[0]] = inp[partner[0]] + sgn * FD_STEP * partner[1]
+            rp, _ = _solve(pert, s.rho, act, S)
+            assert rp["status"] == R.CONVERGED and rp["iters"] == 1, (key, sgn)
+            vals.append(L(rp))
+        fd = (vals[0] - vals[1]) / (2 * FD_STEP)
+        an = float(np.sum(gr[key] * V))
+        tol = 1e-6 * max(1.0, float(np.sum(np.abs(gr[key] * V)))) + FD_ROUND * lmag / FD_STEP
+        print(key, an, fd, abs(an - fd), tol)
+        assert abs(an - fd) <= tol, (key, an, fd, tol)
+    assert np.abs(gr["x_soft"]).max() > 0 and np.abs(gr["u_soft"]).max() > 0
+
+
+# ---- the stage restatement and sparse form --------------------------------------------------------------------------------
+@pytest.mark.parametrize("S,C,K", [(4, 2, 9), (14, 7, 3)])
+def test_stage_path_is_the_reduced_solve(S, C, K):
+    """stage_solve in fp64 - the soft rule on the masked Gauss-Jordan inverses and right-hand sides, Schur complement, PCG, dz -
+    against the dense solve of the reduced matrix on every act of a walked run.  Bar: test_box_qp_polish_cpu.py's 1e-9."""
+    p = R.soft_box(S, C, K)[0]
+    for t in p["run"]["trace"]:
+        xr, _, lr = R.reduced_solve(p["H"], p["Cm"], p["g"], p["c"], p["lo"], p["hi"], p["w"], t["act"])
+        x, lam, iters = R.stage_solve(p["s"], p["lo"], p["hi"], p["w"], t["act"], np.float64, exit_tol=1e-30)
+        ex = np.abs(x - xr).max() / max(1.0, np.abs(xr).max())
+        el = np.abs(lam - lr).max() / max(1.0, np.abs(lr).max())
+        print("pcg iterations", iters, "x", ex, "lam", el)
+        assert ex <= 1e-9 and el <= 1e-9
+    status, acts = R.soft_stage(p["s"], p["lo"], p["hi"], p["w"], np.float64, 1e-6, exit_tol=1e-30)
+    assert status == R.CONVERGED and len(acts) == p["run"]["iters"]
+
+
+def test_sparse_reference_equals_dense():
+    s, H, Cm, g, c, lo, hi, w = R.soft_problem(4, 2, 9, 1)
+    Hs, Cs, gs, cs = ref.sparse_parts(s)
+    a = R.pdas_soft(H, Cm, g, c, lo, hi, w, 4)
+    b = R.pdas_soft(Hs, Cs, gs, cs, lo, hi, w, 4)
+    assert a["status"] == b["status"] == R.CONVERGED and a["iters"] == b["iters"] and np.array_equal(a["act"], b["act"])
+    assert np.abs(a["x"] - b["x"]).max() <= 1e-9 and np.abs(a["lam"] - b["lam"]).max() <= 1e-9
+    assert all(abs(ta["margin"] - tb["margin"]) <= 1e-9 for ta, tb in zip(a["trace"], b["trace"]))
+
+
+# ---- the cases of tests/test_gpu_box_qp_soft.py have seeds --------------------------------------------------------------------
+COLD = [(S, C, K) for S, C in R.SHAPES for K in R.COLD_K]
+
+
+@pytest.mark.parametrize("S,C,K", COLD, ids=["%d-%d-%d" % c for c in COLD])
+def test_walk_finds_an_fp64_seed(S, C, K):
+    ps = R.soft_box(S, C, K)
+    assert ps and ps[0]["seed"] < D.WALK_SEEDS
+    p = ps[0]
+    run = p["run"]
+    n = S + C
+    idx = np.arange(p["s"].N)
+    assert np.array_equal(p["w"] > 0, idx % n < S)                               # every state soft, every control hard
+    if K >= 3:
+        j = (K - 1) * n
+        assert p["lo"][j] == p["hi"][j] and p["w"][j] > 0 and run["act"][j] == -1
+    print("seed", p["seed"], "solves", run["iters"], "margin", D.min_margin(run), "cond", R.max_cond(run, p["H"], p["Cm"], p["w"]))
+    assert R.walk_ok(run, p["lo"], p["hi"], p["w"], p["H"], p["Cm"])
+
+
+@pytest.mark.parametrize("S,C,K", R.F32_CASES, ids=["%d-%d-%d" % c for c in R.F32_CASES])
+def test_walk_finds_an_fp32_seed(S, C, K):
+    ps = R.soft_box(S, C, K, f32=True)
+    assert ps and ps[0]["seed"] < D.WALK_SEEDS
+    print("seed", ps[0]["seed"], "solves", ps[0]["run"]["iters"])
+    assert R.f32_ok(ps[0])
+
+
+def test_the_other_gpu_cases_exist():
+    """The batch's two soft seeds with different solve counts, a hard state box that does not converge, the double integrator,
+    and the long horizon: CONVERGED, with soft-active and hard-active variables past knot 8192."""
+    S, C, K, B = R.BATCH
+    a, b = R.soft_box(S, C, K, count=2)
+    assert a["run"]["iters"] != b["run"]["iters"]
+    s = synth.make_system(S, C, K, seed=0)
+    H, Cm, g, c = ref.parts(s)
+    lo, hi = P.boxes(s, 1, eq=True, states=True)
+    assert D.pdas(H, Cm, g, c, lo, hi, S)["status"] != D.CONVERGED
+    s, H, Cm, g, c, lo, hi, w = R.double_integrator_soft()
+    assert D.pdas(H, Cm, g, c, lo, hi, 2)["status"] in (D.MAX_ITERS, D.NONFINITE)
+    run = R.pdas_soft(H, Cm, g, c, lo, hi, w, 2)
+    print("double integrator: solves", run["iters"], "margin", D.min_margin(run), "cond", R.max_cond(run, H, Cm, w))
+    assert run["status"] == R.CONVERGED and D.min_margin(run) >= D.MARGIN and R.soft_set(run["act"], w).any()
+    p = R.soft_long()
+    run = p["run"]
+    n = 3
+    sa = R.soft_set(run["act"], p["w"])
+    print("long: solves", run["iters"], "margin", D.min_margin(run), "|x|", np.abs(run["x"]).max())
+    assert run["status"] == R.CONVERGED
+    assert (np.flatnonzero(sa) // n >= 8192).any() and (np.flatnonzero((run["act"] != 0) & ~sa) // n >= 8192).any()
+
+
+def test_entries_declared_and_exported():
+    hdr = open(os.path.join(ROOT, "include", "gato_hip.h")).read()
+    from gato_python_amd import _lib
+    L = _lib.lib()
+    for name in ("gato_box_qp_pdas_soft", "gato_box_qp_soft_grad"):
+        assert re.search(r"int\s+%s\s*\(" % name, hdr), name
+        assert name in _lib.SYMBOLS and hasattr(L, name)
