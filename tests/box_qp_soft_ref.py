@@ -370,6 +370,156 @@ def soft_long():
     return _LONG["p"]
 
 
+# ---- mixed problems: hard and soft bounds side by side, on states and controls, a weight per variable -------------------------
+def mixed_weights(N, seed):
+    """Per variable, independently: soft with probability 1/2 and then w = 10 ** uniform(0, 3), else w = 0 (a hard bound)."""
+    rng = np.random.default_rng([seed, 310])
+    return np.where(rng.random(N) < 0.5, 10.0 ** rng.uniform(0.0, 3.0, N), 0.0)
+
+
+def mixed_problem(S, C, K, seed, sparse=False, hard_states=True):
+    """soft_problem's system, boxes and (K >= 3) lo == hi tracking state with mixed_weights: states and controls both draw, so
+    both may be soft, and the tracking state may be hard.  hard_states=False: a state that drew 0 draws a weight of the same
+    law instead - every state soft, each with its own weight; the controls as before.  -> (s, H, Cm, g, c, lo, hi, w)."""
+    s, H, Cm, g, c, lo, hi, _ = soft_problem(S, C, K, seed, sparse=sparse)
+    w = mixed_weights(s.N, seed)
+    if not hard_states:
+        rng = np.random.default_rng([seed, 311])
+        state = np.arange(s.N) % (S + C) < S
+        w = np.where(state & (w == 0), 10.0 ** rng.uniform(0.0, 3.0, s.N), w)
+    return s, H, Cm, g, c, lo, hi, w
+
+
+def cover(run, w, lo, hi, S, C, K):
+    """What a run's trace exercises of the soft kernels' mixed branches, three booleans over the acts it solved on: (a) a
+    soft-active control with lo != hi; (b) a knot whose states hold a hard-active and a soft-active variable in one act - a
+    masked row next to an augmented diagonal entry in one Q_k; (c) the same among a knot's controls, in one R_k."""
+    n = S + C
+    idx = np.arange(len(w))
+    knot, ctl = idx // n, idx % n >= S
+    a = b = c = False
+    for t in run["trace"]:
+        sa = soft_set(t["act"], w)
+        hard = (t["act"] != 0) & ~sa
+        a |= bool((sa & ctl & (lo != hi)).any())
+        for part in (~ctl, ctl):
+            both = np.intersect1d(knot[sa & part], knot[hard & part]).size > 0
+            if part is ctl:
+                c |= both
+            else:
+                b |= both
+    return a, b, c
+
+
+def cover_need(S, C, K):
+    """The part of cover() a walked mixed problem of the shape must meet: all of it, except that 2/1 has one control and, with
+    boxes() bounding every other state, one bounded state per knot - no block of it can be mixed - and that 4/2/2 has two
+    bounded states (K = 2: a single control knot, x_0 never active), which no seed below WALK_SEEDS mixes."""
+    if S == 2:
+        return True, False, False
+    if (S, K) == (4, 2):
+        return True, False, True
+    return True, True, True
+
+
+def covers(got, need):
+    return all(g or not n for g, n in zip(got, need))
+
+
+_MIXED = {}
+
+
+def mixed_box(S, C, K, f32=False, count=1):
+    """soft_box's seed walk over mixed_problem: the first `count` seeds < WALK_SEEDS whose cold reference run meets walk_ok (f32:
+    with eps = F32_EPS, and f32_ok) and whose trace meets cover_need; each dict also holds its cover() under "cover"."""
+    got = _MIXED.setdefault((S, C, K, f32), dict(next=0, found=[]))
+    eps = P.F32_EPS if f32 else 1e-6
+    need = cover_need(S, C, K)
+    while len(got["found"]) < count and got["next"] < D.WALK_SEEDS:
+        seed = got["next"]
+        got["next"] += 1
+        s, H, Cm, g, c, lo, hi, w = mixed_problem(S, C, K, seed)
+        run = pdas_soft(H, Cm, g, c, lo, hi, w, S, eps_abs=eps, eps_rel=eps, max_pdas_iters=D.WALK_SOLVES)
+        cov = cover(run, w, lo, hi, S, C, K)
+        if not covers(cov, need) or not walk_ok(run, lo, hi, w, H, Cm):
+            continue
+        p = dict(D.as_problem(s, H, Cm, g, c, lo, hi, run, seed), w=w, cover=cov)
+        if f32 and not f32_ok(p):
+            continue
+        got["found"].append(p)
+    return got["found"][:count]
+
+
+def mixed_layer_box(S, C, K):
+    """The first problem of mixed_box(S, C, K) whose final act - the one the layer differentiates through - holds a soft-active
+    control with lo != hi."""
+    n = S + C
+    for count in range(1, D.WALK_SEEDS + 1):
+        ps = mixed_box(S, C, K, count=count)
+        if len(ps) < count:
+            break
+        p = ps[-1]
+        if (soft_set(p["run"]["act"], p["w"]) & (np.arange(len(p["w"])) % n >= S) & (p["lo"] != p["hi"])).any():
+            return p
+    return None
+
+
+def mixed_long():
+    """mixed_problem(hard_states=False) at box_qp_pdas_ref.LONG (2/1/8197), sparse, of the first seed whose cold reference run
+    converges, with that run (as soft_long: only its final act and point are used).  Soft states, each with its own weight,
+    and mixed controls: with hard state bounds drawn over 8197 knots some knot fixes both its state and its control, and the
+    reference meets a singular reduced system on its second solve (seeds 0 .. 19, all NONFINITE)."""
+    if "mixed" not in _LONG:
+        S, C, K = D.LONG
+        for seed in range(D.WALK_SEEDS):
+            s, H, Cm, g, c, lo, hi, w = mixed_problem(S, C, K, seed, sparse=True, hard_states=False)
+            run = pdas_soft(H, Cm, g, c, lo, hi, w, S, max_pdas_iters=D.WALK_SOLVES)
+            if run["status"] == CONVERGED:
+                break
+        _LONG["mixed"] = dict(D.as_problem(s, H, Cm, g, c, lo, hi, run, seed), w=w)
+    return _LONG["mixed"]
+
+
+def weight_batch(seed):
+    """Four weight vectors on one 14/7/9 system and box: mixed_problem(14, 7, 9, seed) with every state but the first of each
+    knot freed (a hard box over half the states never converges at this shape, and one system here is all hard), and as
+    weights its mixed ones, the same pattern times 10, all zero and state_weights; with each one's cold reference run.
+    -> (problem tuple of mixed_problem, [w], [run])."""
+    S, C, K = BATCH[:3]
+    s, H, Cm, g, c, lo, hi, w = mixed_problem(S, C, K, seed)
+    lane = np.arange(s.N) % (S + C)
+    lo[(lane >= 1) & (lane < S)], hi[(lane >= 1) & (lane < S)] = -np.inf, np.inf
+    ws = [w, 10.0 * w, np.zeros(s.N), state_weights(s)]
+    runs = [pdas_soft(H, Cm, g, c, lo, hi, wi, S, max_pdas_iters=D.WALK_SOLVES) for wi in ws]
+    return (s, H, Cm, g, c, lo, hi, w), ws, runs
+
+
+def weight_batch_ok(prob, ws, runs):
+    """The seed rule of weight_batch: every run meets box_qp_pdas_ref.walk_ok's status, solve count and margins, and its worst
+    reduced matrix has cond / margin <= COND_CAP / MARGIN - the rounding a solve leaves in a decision, cond * eps, relative to
+    the decision's margin is what the walks' two caps bound together, and the all-hard run here has cond 4e8 at a margin of
+    9e-4 where the caps pair 1e8 with 1e-5; the mixed and the scaled run end on different points."""
+    s, H, Cm = prob[:3]
+    for wi, r in zip(ws, runs):
+        if not D.walk_ok(r) or max_cond(r, H, Cm, wi) / D.min_margin(r) > P.COND_CAP / D.MARGIN:
+            return False
+    return bool(np.abs(runs[0]["x"] - runs[1]["x"]).max() > 1e-3)
+
+
+_WBATCH = {}
+
+
+def weight_batch_box():
+    """weight_batch of the first seed < WALK_SEEDS that meets weight_batch_ok.  -> (seed, problem tuple, [w], [run])."""
+    if "p" not in _WBATCH:
+        for seed in range(D.WALK_SEEDS):
+            got = weight_batch(seed)
+            if weight_batch_ok(*got):
+                _WBATCH["p"] = (seed,) + got
+                break
+    return _WBATCH.get("p")
+
+
 def double_integrator_soft(weight=WEIGHT):
     """box_qp_ref.double_integrator(K=20, u_max=0.5, v_max=0.57), where the hard iteration meets a singular reduced system on
     its second solve, with the velocity bound soft: (s, H, Cm, g, c, lo, hi, w)."""
@@ -382,4 +532,5 @@ COLD_K = D.COLD_K                                 # K of the cold fp64 cases
 F32_CASES = [(S, C, 9) for S, C in SHAPES] + [(14, 7, 3), (32, 16, 3)]
 GRAD_K = (2, 3)
 LAYER_CASES = [(6, 3, 9), (14, 7, 3)]
+MIXED_F32_K = 3                                   # K of the fp32 cases on mixed problems, one per shape
 BATCH = D.BATCH

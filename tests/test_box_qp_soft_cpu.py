@@ -1,7 +1,8 @@
 """The numpy reference of soft bounds in the active-set iteration (tests/box_qp_soft_ref.py) on the CPU:
 the rule, zero weights equal to box_qp_pdas_ref, the converged point against SLSQP on the penalised objective, the 1 / w
 approach to the hard solution, the gradients against finite differences, the stage restatement, and that the seed walks find
-a seed for every case of tests/test_gpu_box_qp_soft.py."""
+a seed for every case of tests/test_gpu_box_qp_soft.py and - with the mixed blocks cover() demands - for every case of
+tests/test_gpu_box_qp_soft_sweep.py."""
 import os
 import re
 
@@ -160,13 +161,12 @@ def _fd_problem(S, C, K):
     raise AssertionError("no seed")
 
 
-@pytest.mark.parametrize("S,C,K", [(4, 2, 5), (6, 3, 4)])
-def test_gradients_match_finite_differences(S, C, K):
+def _fd_check(s, lo, hi, w, run0):
     """soft_grads for all thirteen inputs of box_qp_layer (Q, R symmetric; the weights included) against central differences
     of the penalised-QP solution along a random direction per input.  Every perturbed problem is solved by the iteration
     from the unperturbed act and must converge on it at once - the active set is kept, a condition on the inputs (margins >=
-    1e-3 against steps of 1e-6), asserted.  The bound is test_box_qp_polish_cpu.py's."""
-    s, lo, hi, w, run0 = _fd_problem(S, C, K)
+    1e-3 against steps of 1e-6), asserted.  The bound is test_box_qp_polish_cpu.py's.  -> the gradients."""
+    S, C, K = s.S, s.C, s.K
     Q, Rm, A, B, q, r, c = kgr.blocks_of(s)
     split = lambda v: P.split_states_controls(v, S, C, K)
     inp = dict(Q=Q, R=Rm, A=A, B=B, q=q, r=r, c=c)
@@ -211,7 +211,42 @@ def test_gradients_match_finite_differences(S, C, K):
         tol = 1e-6 * max(1.0, float(np.sum(np.abs(gr[key] * V)))) + FD_ROUND * lmag / FD_STEP
         print(key, an, fd, abs(an - fd), tol)
         assert abs(an - fd) <= tol, (key, an, fd, tol)
+    return gr
+
+
+@pytest.mark.parametrize("S,C,K", [(4, 2, 5), (6, 3, 4)])
+def test_gradients_match_finite_differences(S, C, K):
+    gr = _fd_check(*_fd_problem(S, C, K))
     assert np.abs(gr["x_soft"]).max() > 0 and np.abs(gr["u_soft"]).max() > 0
+
+
+def _fd_mixed_problem(S, C, K):
+    """The first mixed_problem seed whose final point has every margin >= 1e-3, a soft-active control with lo != hi and a
+    hard-active non-equality variable and a soft-active state, and whose final reduced matrix has cond <= 1e7.  A difference quotient divides the
+    rounding of two dense solves by the step, and FD_ROUND allows them 1e-13: _fd_problem's matrices have cond 6e5 and keep
+    it; 6/3/4 seed 0, next to an active set without LICQ (cond 7e9, |lam| 2e3), is 2e-2 off in R for that reason alone."""
+    n = S + C
+    for seed in range(D.WALK_SEEDS):
+        s, H, Cm, g, c, lo, hi, w = R.mixed_problem(S, C, K, seed)
+        run = R.pdas_soft(H, Cm, g, c, lo, hi, w, S)
+        sa = R.soft_set(run["act"], w)
+        if (run["status"] == R.CONVERGED and run["trace"][-1]["margin"] >= 1e-3
+                and (sa & (lo != hi) & (np.arange(s.N) % n >= S)).any() and ((run["act"] != 0) & ~sa & (lo != hi)).any()
+                and (sa & (np.arange(s.N) % n < S)).any() and np.linalg.cond(R.reduced_matrix(H, Cm, run["act"], w)) <= 1e7):
+            return s, lo, hi, w, run
+    raise AssertionError("no seed")
+
+
+@pytest.mark.parametrize("S,C,K", [(4, 2, 5), (6, 3, 4)])
+def test_gradients_match_finite_differences_mixed(S, C, K):
+    """_fd_check on a mixed problem: the directions of u_soft, u_lo and u_hi reach a soft-active control, whose expected weight
+    and bound gradients are nonzero."""
+    s, lo, hi, w, run = _fd_mixed_problem(S, C, K)
+    gr = _fd_check(s, lo, hi, w, run)
+    sc = P.split_states_controls(R.soft_set(run["act"], w) & (lo != hi), S, C, K)[1] > 0
+    assert sc.any() and np.abs(gr["u_soft"][sc]).max() > 0
+    assert np.abs(gr["u_lo"][sc]).max() + np.abs(gr["u_hi"][sc]).max() > 0
+    assert np.abs(gr["x_soft"]).max() > 0
 
 
 # ---- the stage restatement and sparse form --------------------------------------------------------------------------------
@@ -291,6 +326,186 @@ def test_the_other_gpu_cases_exist():
     print("long: solves", run["iters"], "margin", D.min_margin(run), "|x|", np.abs(run["x"]).max())
     assert run["status"] == R.CONVERGED
     assert (np.flatnonzero(sa) // n >= 8192).any() and (np.flatnonzero((run["act"] != 0) & ~sa) // n >= 8192).any()
+
+
+# ---- mixed problems: the cases of tests/test_gpu_box_qp_soft_sweep.py -----------------------------------------------------------
+def _issue_need(S, C, K):
+    """What the mixed walks must cover at the least, whatever cover_need asks: (a) everywhere, all three for S >= 6 and
+    K >= 3, (b) and (c) at 4/2 for K in (3, 9)."""
+    full = (S >= 6 and K >= 3) or (S == 4 and K in (3, 9))
+    return True, full, full
+
+
+@pytest.mark.parametrize("S,C,K", COLD, ids=["%d-%d-%d" % c for c in COLD])
+def test_mixed_walk_finds_an_fp64_seed(S, C, K):
+    """The walk finds a seed; its weights are drawn per variable, on states and controls alike; the reference run meets the
+    seed rule and cover(), recomputed here, meets cover_need and the least this file demands; the final point satisfies the
+    penalised KKT system."""
+    ps = R.mixed_box(S, C, K)
+    assert ps and ps[0]["seed"] < D.WALK_SEEDS
+    p = ps[0]
+    run, w, lo, hi = p["run"], p["w"], p["lo"], p["hi"]
+    ctl = np.arange(p["s"].N) % (S + C) >= S
+    assert (w > 0).any() and (w == 0).any() and np.all((w == 0) | ((w >= 1.0) & (w <= 1e3)))
+    if S >= 4:                                                                   # 2/1/2 has a single control
+        assert all((w[part] > 0).any() and (w[part] == 0).any() for part in (ctl, ~ctl))
+    assert len(np.unique(w[w > 0])) == (w > 0).sum()
+    assert R.walk_ok(run, lo, hi, w, p["H"], p["Cm"])
+    cov = R.cover(run, w, lo, hi, S, C, K)
+    print("seed", p["seed"], "solves", run["iters"], "margin", D.min_margin(run), "cond", R.max_cond(run, p["H"], p["Cm"], w), "cover", cov)
+    assert cov == p["cover"] and R.covers(cov, R.cover_need(S, C, K)) and R.covers(cov, _issue_need(S, C, K))
+    assert R.covers(R.cover_need(S, C, K), _issue_need(S, C, K))
+    kk = R.kkt_residuals(p["H"], p["Cm"], p["g"], p["c"], lo, hi, w, run["x"], run["y"], run["lam"])
+    print(kk)
+    assert max(kk.values()) <= 1e-9
+
+
+def test_cover_on_a_hand_made_trace():
+    """2/1/3: dz layout x0 x0 u0 | x1 x1 u1 | x2 x2.  (a) needs a soft-active control off lo == hi; (b) a knot's states, (c) a
+    knot's controls hard- and soft-active in ONE act - a single control per knot can never be."""
+    S, C, K = 2, 1, 3
+    lo, hi = -np.ones(8), np.ones(8)
+    w = np.array([0, 0, 5.0, 5.0, 0, 0, 0, 5.0])
+    tr = lambda *acts: dict(trace=[dict(act=np.array(a, np.int8)) for a in acts])
+    assert R.cover(tr([0, 0, 1, 0, 0, 0, 0, 0]), w, lo, hi, S, C, K) == (True, False, False)
+    assert R.cover(tr([0, 0, 0, 1, -1, 0, 0, 0]), w, lo, hi, S, C, K) == (False, True, False)
+    assert R.cover(tr([0, 0, 0, 1, 0, 0, 0, 0], [0, 0, 0, 0, -1, 0, 0, 0]), w, lo, hi, S, C, K) == (False, False, False)   # two acts
+    assert R.cover(tr([0, 0, 0, 1, 0, 0, -1, 0]), w, lo, hi, S, C, K) == (False, False, False)                              # two knots
+    assert R.cover(tr([0, 0, 1, 0, 0, -1, 0, 0]), w, lo, hi, S, C, K) == (True, False, False)                               # two knots
+    eq = np.where(np.arange(8) == 2, 1.0, lo)
+    assert R.cover(tr([0, 0, -1, 0, 0, 0, 0, 0]), w, eq, hi, S, C, K) == (False, False, False)                              # lo == hi
+    w2 = np.array([0, 0, 5.0, 0, 0, 0, 0, 0, 0, 0])                                                                         # 2/2/3
+    assert R.cover(tr([0, 0, 1, -1, 0, 0, 0, 0, 0, 0]), w2, -np.ones(10), np.ones(10), 2, 2, 3) == (True, False, True)
+
+
+def test_mixed_walks_find_their_other_seeds():
+    """4/2/3 has two fp64 seeds with mixed states and mixed controls; every shape has an fp32 seed at K = MIXED_F32_K with a
+    soft-active control, from 6/3 up with all of cover(), 4/2 with mixed controls; a kept run has a soft-active variable on the
+    last knot; the layer cases end on an act with a soft-active control."""
+    two = R.mixed_box(4, 2, 3, count=2)
+    assert len(two) == 2 and all(p["cover"] == (True, True, True) for p in two)
+    last = False
+    for S, C in R.SHAPES:
+        ps = R.mixed_box(S, C, R.MIXED_F32_K, f32=True)
+        assert ps and ps[0]["seed"] < D.WALK_SEEDS
+        p = ps[0]
+        print((S, C), "fp32 seed", p["seed"], "solves", p["run"]["iters"], "cover", p["cover"])
+        assert R.f32_ok(p) and p["cover"] == R.cover(p["run"], p["w"], p["lo"], p["hi"], S, C, R.MIXED_F32_K)
+        assert p["cover"][0] and (S < 4 or p["cover"][2]) and (S < 6 or p["cover"][1])
+        for K in R.COLD_K:
+            q = R.mixed_box(S, C, K)[0]
+            last |= bool(R.soft_set(q["run"]["act"], q["w"])[(K - 1) * (S + C):].any())
+    assert last
+    for S, C, K in R.LAYER_CASES:
+        p = R.mixed_layer_box(S, C, K)
+        assert p is not None
+        sa = R.soft_set(p["run"]["act"], p["w"])
+        assert (sa & (np.arange(len(sa)) % (S + C) >= S) & (p["lo"] != p["hi"])).any()
+        print((S, C, K), "layer seed", p["seed"])
+
+
+@pytest.mark.parametrize("S,C,K", [(4, 2, 3), (6, 3, 9), (14, 7, 3)])
+def test_mixed_point_is_a_minimum_over_feasible_perturbations(S, C, K):
+    """The reference's final point of a mixed problem: penalised_objective's gradient is -(C^T lam + y) there (stationarity),
+    and no step that keeps C x = c and the hard-active variables on their bounds - small enough to keep every hard free
+    variable inside its box - decreases penalised_objective.  Along such a d the first-order term vanishes and f is convex,
+    so f(x + t d) - f(x) >= 0 up to the rounding of evaluating f: 1e-12 of the sum of the magnitudes of its terms."""
+    from scipy.linalg import null_space
+    p = R.mixed_box(S, C, K)[0]
+    H, Cm, g, lo, hi, w, run = (p[k] for k in ("H", "Cm", "g", "lo", "hi", "w", "run"))
+    x = run["x"]
+    f0, grad = R.penalised_objective(H, g, lo, hi, w, x)
+    assert np.abs(grad + Cm.T @ run["lam"] + np.where(w > 0, 0.0, run["y"])).max() <= 1e-9
+    hard = (run["act"] != 0) & ~R.soft_set(run["act"], w)
+    Z = null_space(np.vstack([Cm, np.eye(len(x))[hard]]))
+    assert Z.shape[1] > 0
+    hv = ~(w > 0)
+    room = np.minimum(x - lo, hi - x)[hv & ~hard].min()
+    assert room > 0
+    dist = x - np.clip(x, lo, hi)
+    mag = 0.5 * np.abs(x) @ np.abs(H) @ np.abs(x) + np.abs(g) @ np.abs(x) + 0.5 * (w * dist * dist).sum()
+    rng = np.random.default_rng(3)
+    worst = np.inf
+    for t in (1e-1, 1e-3, 1e-5):
+        for _ in range(20):
+            d = Z @ rng.standard_normal(Z.shape[1])
+            d[hard] = 0.0                                                        # the null space leaves 1e-18 there
+            d *= min(t, 0.5 * room) / np.abs(d).max()
+            xp = x + d
+            assert np.abs(Cm @ d).max() <= 1e-15 and np.all((xp >= lo)[hv & ~hard]) and np.all((xp <= hi)[hv & ~hard])
+            worst = min(worst, R.penalised_objective(H, g, lo, hi, w, xp)[0] - f0)
+    print("smallest f(x + d) - f(x)", worst, "rounding bar", 1e-12 * mag)
+    assert worst >= -1e-12 * mag
+
+
+def test_mixed_converged_point_is_the_slsqp_minimum():
+    """test_converged_point_is_the_slsqp_minimum on a mixed problem: hard and soft bounds on states and controls."""
+    from scipy.optimize import minimize
+    p = R.mixed_box(4, 2, 3)[0]
+    H, Cm, g, c, lo, hi, w = (p[k] for k in ("H", "Cm", "g", "c", "lo", "hi", "w"))
+    sv = w > 0
+    inf = np.full(len(g), np.inf)
+    bounds = [(None if not np.isfinite(l) else l, None if not np.isfinite(h) else h)
+              for l, h in zip(np.where(sv, -inf, lo), np.where(sv, inf, hi))]
+    f = lambda x: R.penalised_objective(H, g, lo, hi, w, x)
+    out = minimize(f, np.zeros(len(g)), jac=True, method="SLSQP", bounds=bounds,
+                   constraints=[dict(type="eq", fun=lambda x: Cm @ x - c, jac=lambda x: Cm)], options=dict(ftol=1e-16, maxiter=2000))
+    err = np.abs(out.x - p["run"]["x"]).max()
+    print(out.message, out.nit, "x err", err)
+    assert err <= 1e-6, err
+
+
+@pytest.mark.parametrize("S,C,K", [(4, 2, 9), (6, 3, 3), (14, 7, 3)])
+def test_zero_weights_on_a_mixed_box_are_the_hard_reference(S, C, K):
+    """On a mixed problem's box with w = 0, over every act its run solved on: reduced_matrix and reduced_solve are
+    box_qp_polish_ref's and next_act is box_qp_pdas_ref's, bit for bit (a hard state box can be singular: NaN equals NaN);
+    and the whole iteration is box_qp_pdas_ref.pdas."""
+    p = R.mixed_box(S, C, K)[0]
+    H, Cm, g, c, lo, hi = (p[k] for k in ("H", "Cm", "g", "c", "lo", "hi"))
+    zero = np.zeros(len(g))
+    for t in p["run"]["trace"]:
+        act = t["act"]
+        assert np.array_equal(R.reduced_matrix(H, Cm, act, zero), P.reduced_matrix(H, Cm, act))
+        with np.errstate(all="ignore"):
+            got, want = R.reduced_solve(H, Cm, g, c, lo, hi, zero, act), P.reduced_solve(H, Cm, g, c, lo, hi, act)
+        assert all(np.array_equal(a, b, equal_nan=True) for a, b in zip(got, want))
+        x, y = np.nan_to_num(want[0]), np.nan_to_num(want[1])
+        assert np.array_equal(R.next_act(act, x, y, lo, hi, zero, S), D.next_act(act, x, y, lo, hi, S))
+    a, b = D.pdas(H, Cm, g, c, lo, hi, S), R.pdas_soft(H, Cm, g, c, lo, hi, zero, S)
+    assert (a["status"], a["iters"]) == (b["status"], b["iters"]) and len(a["trace"]) == len(b["trace"])
+    assert all(np.array_equal(ta["act"], tb["act"]) and ta["changed"] == tb["changed"] for ta, tb in zip(a["trace"], b["trace"]))
+    assert np.array_equal(a["x"], b["x"], equal_nan=True) and np.array_equal(a["lam"], b["lam"], equal_nan=True)
+
+
+def test_the_batch_of_weights_and_the_mixed_long_horizon_exist():
+    """The four weight vectors on one 14/7/9 system: a seed below WALK_SEEDS on which all four reference runs converge under
+    weight_batch_ok, the vectors as named, the mixed and the scaled run on different points.  mixed_long: CONVERGED, with a
+    soft-active control off lo == hi and a hard-active variable among the knots >= 8192."""
+    got = R.weight_batch_box()
+    assert got is not None and got[0] < D.WALK_SEEDS
+    seed, prob, ws, runs = got
+    s, H, Cm, g, c, lo, hi, w = prob
+    print("batch seed", seed, [(r["iters"], D.min_margin(r), R.max_cond(r, H, Cm, wi)) for wi, r in zip(ws, runs)])
+    assert all(r["status"] == R.CONVERGED for r in runs) and R.weight_batch_ok(prob, ws, runs)
+    assert np.array_equal(ws[0], w) and np.array_equal(ws[1], 10.0 * w) and not ws[2].any() and np.array_equal(ws[3], R.state_weights(s))
+    ctl = np.arange(s.N) % (s.S + s.C) >= s.S
+    assert (w[ctl] > 0).any() and (w[~ctl] > 0).any() and (w == 0).any()
+    assert np.abs(runs[0]["x"] - runs[1]["x"]).max() > 1e-3
+    assert any(R.soft_set(t["act"], w)[ctl].any() for t in runs[0]["trace"])
+    for wi, r in zip(ws, runs):
+        kk = R.kkt_residuals(H, Cm, g, c, lo, hi, wi, r["x"], r["y"], r["lam"])
+        assert max(kk.values()) <= 1e-9, kk
+    p = R.mixed_long()
+    run = p["run"]
+    n = 3
+    idx = np.arange(p["s"].N)
+    sa = R.soft_set(run["act"], p["w"])
+    print("long: seed", p["seed"], "solves", run["iters"], "margin", D.min_margin(run), "|x|", np.abs(run["x"]).max())
+    assert run["status"] == R.CONVERGED
+    assert (sa & (idx // n >= 8192) & (idx % n >= 2) & (p["lo"] != p["hi"])).any()
+    assert ((run["act"] != 0) & ~sa & (idx // n >= 8192)).any()
+    ctl = idx % n >= 2
+    assert (p["w"][ctl] > 0).any() and (p["w"][ctl] == 0).any() and np.all(p["w"][~ctl] > 0)
 
 
 def test_entries_declared_and_exported():
