@@ -335,12 +335,13 @@ int launch_qp_prepare(const Dims &d, const QpArgs &a, hipStream_t st);
 // iteration `it` of the loop; last = 1: only the convergence test of the iterate the previous launch wrote
 template <typename T, int S, int C>
 int launch_qp_update(const Dims &d, const QpArgs &a, int it, int last, hipStream_t st);
-// Polish of an ADMM result and the bound gradients of a polished solution (gato_polish.hip).
+// Polish of an ADMM result and the bound gradients of a polished solution (gato_polish.hip, DESIGN.md sections 3.8, 3.10).
 // `act` [B][N] int8: +1 at the upper bound, -1 at the lower one, 0 free.  `slots` [B][GATO_POLISH_NSLOT] maxima as in QpArgs.
 #define GATO_POLISH_NSLOT 12
 struct PolishArgs {
     const void *G, *Cd, *g, *c, *lo, *hi;   // the caller's blocks (G without rho, C raw) and vectors; never written
     const signed char *act;
+    const void *w;                          // [B][N] soft-bound weights, 0 = a hard bound; nullptr = all hard
     const void *Gd;                         // prepare: G + rho I (the solver's G_dense)
     void *Ginv;                             // prepare: the inverses with the active rows and columns zero (the solver's Ginv)
     void *gp, *cp;                          // prepare: the reduced system's right-hand side g' [B][N], c' [B][S K]
@@ -360,10 +361,16 @@ int launch_polish_prepare(const Dims &d, const PolishArgs &a, hipStream_t st);
 // the residuals of the polished point, then the acceptance test and the write-back (two launches)
 template <typename T, int S, int C>
 int launch_polish_finish(const Dims &d, const PolishArgs &a, hipStream_t st);
+struct BoundGradArgs {
+    const void *G, *Cd;                     // the caller's blocks (G without rho, C raw)
+    const signed char *act;
+    const void *w, *lo, *hi, *x;            // w may be nullptr (all hard): then lo, hi and x are not read
+    const void *xbar, *adz, *beta;          // the upstream gradient and the adjoint [a; beta]
+    void *lo_bar, *hi_bar, *w_bar;          // [B][N]; w_bar may be nullptr (not written)
+};
 template <typename T, int S, int C>
-int launch_qp_bound_grad(const Dims &d, const void *G, const void *Cd, const signed char *act, const void *xbar, const void *adz,
-                         const void *beta, void *lo_bar, void *hi_bar, hipStream_t st);
-// Primal-dual active-set iteration over the polish path (gato_pdas.hip).
+int launch_qp_bound_grad(const Dims &d, const BoundGradArgs &a, hipStream_t st);
+// Primal-dual active-set iteration over the polish path (gato_pdas.hip, DESIGN.md sections 3.9, 3.10).
 struct PdasArgs {
     PolishArgs p;                           // p.act: the current act; p.slots [B][2][GATO_POLISH_NSLOT], set it % 2 of solve it
     signed char *act;                       // p.act again, written by the decision (the caller's: in the start, out the final act)
@@ -372,36 +379,15 @@ struct PdasArgs {
     int *ctr;                               // {live systems, waves that saw a bad bound, waves that saw a bad start act}
     int *iters;                             // [B] solves until the system froze
 };
-// the checks of the bounds and of the start act (first launch of a call)
+// the checks of the bounds, the weights and the start act (first launch of a call)
 template <typename T, int S, int C>
 int launch_pdas_check(const Dims &d, const PdasArgs &a, hipStream_t st);
-// after reduced solve `it` (1, 2, ...): the point, act' and the maxima, then the decision (two launches); last: no solve follows
+// after reduced solve `it` (1, 2, ...): the point, act' and the maxima; launch_pdas_decide follows
 template <typename T, int S, int C>
-int launch_pdas_step(const Dims &d, const PdasArgs &a, int it, int last, hipStream_t st);
-// the decision launch of launch_pdas_step alone (pdas_decide_kernel), for an iteration with a step kernel of its own
+int launch_pdas_step(const Dims &d, const PdasArgs &a, int it, hipStream_t st);
+// the decision of solve `it` (pdas_decide_kernel); last: no solve follows
 template <typename T, int S, int C>
 int launch_pdas_decide(const Dims &d, const PdasArgs &a, int it, int last, hipStream_t st);
-// Soft bounds in the active-set iteration (gato_soft.hip).
-struct SoftArgs {
-    PdasArgs d;
-    const void *w;                          // [B][N] weights, 0 = a hard bound; nullptr = all hard
-};
-struct SoftGradArgs {
-    const void *G, *Cd;                     // the caller's blocks (G without rho, C raw)
-    const signed char *act;
-    const void *w, *lo, *hi, *x;            // w may be nullptr (all hard)
-    const void *xbar, *adz, *beta;          // the upstream gradient and the adjoint [a; beta]
-    void *lo_bar, *hi_bar, *w_bar;          // [B][N]
-};
-template <typename T, int S, int C>
-int launch_soft_check(const Dims &d, const SoftArgs &a, hipStream_t st);
-template <typename T, int S, int C>
-int launch_soft_prepare(const Dims &d, const SoftArgs &a, hipStream_t st);
-// the point, act' and the maxima after reduced solve `it`; launch_pdas_decide follows
-template <typename T, int S, int C>
-int launch_soft_step(const Dims &d, const SoftArgs &a, int it, hipStream_t st);
-template <typename T, int S, int C>
-int launch_soft_grad(const Dims &d, const SoftGradArgs &a, hipStream_t st);
 template <typename T, int S>
 int pcg_resident_plan(PcgPlan *plan);
 template <typename T, int S>
@@ -487,15 +473,10 @@ struct Ops {
     int (*qp_active)(const Dims &, const void *, const void *, const void *, const void *, signed char *, hipStream_t);
     int (*polish_prepare)(const Dims &, const PolishArgs &, hipStream_t);
     int (*polish_finish)(const Dims &, const PolishArgs &, hipStream_t);
-    int (*qp_bound_grad)(const Dims &, const void *, const void *, const signed char *, const void *, const void *, const void *,
-                         void *, void *, hipStream_t);
+    int (*qp_bound_grad)(const Dims &, const BoundGradArgs &, hipStream_t);
     int (*pdas_check)(const Dims &, const PdasArgs &, hipStream_t);
-    int (*pdas_step)(const Dims &, const PdasArgs &, int, int, hipStream_t);
+    int (*pdas_step)(const Dims &, const PdasArgs &, int, hipStream_t);
     int (*pdas_decide)(const Dims &, const PdasArgs &, int, int, hipStream_t);
-    int (*soft_check)(const Dims &, const SoftArgs &, hipStream_t);
-    int (*soft_prepare)(const Dims &, const SoftArgs &, hipStream_t);
-    int (*soft_step)(const Dims &, const SoftArgs &, int, hipStream_t);
-    int (*soft_grad)(const Dims &, const SoftGradArgs &, hipStream_t);
     int (*pcg_plan)(PcgPlan *);
     int (*pcg_resident)(const PcgLaunch &, hipStream_t);
     int (*pcg_dma_max_knots)();

@@ -57,21 +57,12 @@ static Ops make_ops(int dtype)
     };
     o.polish_prepare = [](const Dims &d, const PolishArgs &a, hipStream_t st) { return launch_polish_prepare<T, S, C>(d, a, st); };
     o.polish_finish = [](const Dims &d, const PolishArgs &a, hipStream_t st) { return launch_polish_finish<T, S, C>(d, a, st); };
-    o.qp_bound_grad = [](const Dims &d, const void *G, const void *Cd, const signed char *act, const void *xbar, const void *adz,
-                         const void *beta, void *lo_bar, void *hi_bar, hipStream_t st) {
-        return launch_qp_bound_grad<T, S, C>(d, G, Cd, act, xbar, adz, beta, lo_bar, hi_bar, st);
-    };
+    o.qp_bound_grad = [](const Dims &d, const BoundGradArgs &a, hipStream_t st) { return launch_qp_bound_grad<T, S, C>(d, a, st); };
     o.pdas_check = [](const Dims &d, const PdasArgs &a, hipStream_t st) { return launch_pdas_check<T, S, C>(d, a, st); };
-    o.pdas_step = [](const Dims &d, const PdasArgs &a, int it, int last, hipStream_t st) {
-        return launch_pdas_step<T, S, C>(d, a, it, last, st);
-    };
+    o.pdas_step = [](const Dims &d, const PdasArgs &a, int it, hipStream_t st) { return launch_pdas_step<T, S, C>(d, a, it, st); };
     o.pdas_decide = [](const Dims &d, const PdasArgs &a, int it, int last, hipStream_t st) {
         return launch_pdas_decide<T, S, C>(d, a, it, last, st);
     };
-    o.soft_check = [](const Dims &d, const SoftArgs &a, hipStream_t st) { return launch_soft_check<T, S, C>(d, a, st); };
-    o.soft_prepare = [](const Dims &d, const SoftArgs &a, hipStream_t st) { return launch_soft_prepare<T, S, C>(d, a, st); };
-    o.soft_step = [](const Dims &d, const SoftArgs &a, int it, hipStream_t st) { return launch_soft_step<T, S, C>(d, a, it, st); };
-    o.soft_grad = [](const Dims &d, const SoftGradArgs &a, hipStream_t st) { return launch_soft_grad<T, S, C>(d, a, st); };
     o.pcg_plan = [](PcgPlan *p) { return pcg_resident_plan<T, S>(p); };
     o.pcg_resident = [](const PcgLaunch &a, hipStream_t st) { return launch_pcg_resident<T, S>(a, st); };   // incl. the DPP-row layout
     o.pcg_dma_max_knots = []() { return pcg_dma_max_knots<T, S>(); };

@@ -13,24 +13,26 @@ namespace {
 constexpr int WAVE = 64;
 constexpr int NSL = GATO_POLISH_NSLOT;
 
-// The first launch of a call: a NaN bound or lo > hi marks the system BAD_BOUNDS, a start act the reduced system cannot take
-// (polish_prepare_kernel's rule) BAD_ACTIVE; ctr = {B live systems, waves that saw a bad bound, waves that saw a bad act}.
-template <typename T, int S, int C>
+// The first launch of a call: a NaN bound, lo > hi or a weight that is NaN, negative or +inf marks the system BAD_BOUNDS, a start
+// act the reduced system cannot take (polish_prepare_kernel's rule) BAD_ACTIVE; ctr = {B live systems, waves that saw a bad bound
+// or weight, waves that saw a bad act}.
+template <typename T, int S, int C, bool W>
 __global__ __launch_bounds__(WAVE) void pdas_check_kernel(PdasArgs a, int K, int B, BatchStride bs)
 {
     constexpr int n = S + C;
     const int lane = threadIdx.x;
     const size_t sys = blockIdx.y;
     const T *lo = (const T *)a.p.lo + sys * bs.n, *hi = (const T *)a.p.hi + sys * bs.n;
+    const T *w = sys_weights<T, W>(a.p.w, sys, bs);
     const signed char *act = a.p.act + sys * bs.n;
     if (blockIdx.x == 0 && blockIdx.y == 0 && lane == 0) a.ctr[0] = B;
     int bad_b = 0, bad_a = 0;
     for (int k = blockIdx.x; k < K; k += gridDim.x) {
         if (lane < (k < K - 1 ? n : S)) {
             const size_t v = (size_t)k * n + lane;
-            const T l = lo[v], h = hi[v];
+            const T l = lo[v], h = hi[v], wi = w ? w[v] : (T)0;
             const signed char ai = act[v];
-            if (l != l || h != h || l > h) bad_b = 1;
+            if (l != l || h != h || l > h || !(wi >= (T)0) || !__builtin_isfinite(wi)) bad_b = 1;
             else if (bad_active(ai, bound_of(ai, l, h), k == 0 && lane < S)) bad_a = 1;
         }
     }
@@ -46,8 +48,9 @@ __global__ __launch_bounds__(WAVE) void pdas_check_kernel(PdasArgs a, int K, int
 //   0 on the states of x_0, -1 where lo == hi;  free: +1 where x > hi, -1 where x < lo;  active upper: kept while y > 0;
 //   active lower: kept while y < 0;  0 otherwise
 // - exact comparisons: near-ties are the acceptance test's, which runs first - and the count of entries where act' differs
-// from act (an integer atomicAdd per wave that saw a change).  A system frozen before this solve is only marked.
-template <typename T, int S, int C>
+// from act (an integer atomicAdd per wave that saw a change).  A soft variable (weight > 0) takes the rule of a free one, from x
+// alone, whatever its act was.  A system frozen before this solve is only marked.
+template <typename T, int S, int C, bool W>
 __global__ __launch_bounds__(WAVE) void pdas_step_kernel(PdasArgs a, int it, int K, BatchStride bs)
 {
     constexpr int n = S + C;
@@ -60,7 +63,7 @@ __global__ __launch_bounds__(WAVE) void pdas_step_kernel(PdasArgs a, int it, int
         if (blockIdx.x == 0 && lane == 0) rn[1] = 1;
         return;
     }
-    const PointSys<T> p = point_sys<T>(a.p, sys, bs);
+    const PointSys<T> p = point_sys<T, W>(a.p, sys, bs);
     signed char *act2 = a.act2 + sys * bs.n;
     unsigned long long m[NSL];
 #pragma unroll
@@ -69,13 +72,15 @@ __global__ __launch_bounds__(WAVE) void pdas_step_kernel(PdasArgs a, int it, int
     for (int k = blockIdx.x; k < K; k += gridDim.x) {
         const PointVar<T> v = polished_point_knot<T, S, C>(lds, p, k, K, lane, m);
         if (v.on) {
+            const size_t j = (size_t)k * n + lane;
+            const bool soft = p.w && p.w[j] > (T)0;
             signed char a2;
             if (k == 0 && lane < S) a2 = 0;
             else if (v.lo == v.hi) a2 = -1;
-            else if (v.act == 0) a2 = v.x > v.hi ? 1 : (v.x < v.lo ? -1 : 0);
+            else if (v.act == 0 || soft) a2 = v.x > v.hi ? 1 : (v.x < v.lo ? -1 : 0);
             else if (v.act > 0) a2 = v.y > (T)0 ? 1 : 0;
             else a2 = v.y < (T)0 ? -1 : 0;
-            act2[(size_t)k * n + lane] = a2;
+            act2[j] = a2;
             changed += a2 != v.act;
         }
     }
@@ -137,18 +142,18 @@ template <typename T, int S, int C>
 int launch_pdas_check(const Dims &d, const PdasArgs &a, hipStream_t st)
 {
     if (d.B < 1 || d.B > 65535) { set_error("pdas_check: B = %d", d.B); return GATO_EINVAL; }
-    hipLaunchKernelGGL((pdas_check_kernel<T, S, C>), dim3(knot_grid(d.K), d.B), dim3(WAVE), 0, st, a, d.K, d.B, batch_stride(d));
+    const auto kernel = a.p.w ? pdas_check_kernel<T, S, C, true> : pdas_check_kernel<T, S, C, false>;
+    hipLaunchKernelGGL(kernel, dim3(knot_grid(d.K), d.B), dim3(WAVE), 0, st, a, d.K, d.B, batch_stride(d));
     GATO_HIP_CHECK(hipGetLastError());
     return GATO_OK;
 }
 
 template <typename T, int S, int C>
-int launch_pdas_step(const Dims &d, const PdasArgs &a, int it, int last, hipStream_t st)
+int launch_pdas_step(const Dims &d, const PdasArgs &a, int it, hipStream_t st)
 {
     if (d.B < 1 || d.B > 65535) { set_error("pdas_step: B = %d", d.B); return GATO_EINVAL; }
-    hipLaunchKernelGGL((pdas_step_kernel<T, S, C>), dim3(knot_grid(d.K), d.B), dim3(WAVE), 0, st, a, it, d.K, batch_stride(d));
-    GATO_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL((pdas_decide_kernel<T, S, C>), dim3(knot_grid(d.K), d.B), dim3(WAVE), 0, st, a, it, last, d.K, batch_stride(d));
+    const auto kernel = a.p.w ? pdas_step_kernel<T, S, C, true> : pdas_step_kernel<T, S, C, false>;
+    hipLaunchKernelGGL(kernel, dim3(knot_grid(d.K), d.B), dim3(WAVE), 0, st, a, it, d.K, batch_stride(d));
     GATO_HIP_CHECK(hipGetLastError());
     return GATO_OK;
 }
@@ -167,8 +172,8 @@ int launch_pdas_decide(const Dims &d, const PdasArgs &a, int it, int last, hipSt
     template int launch_pdas_decide<double, S_, C_>(const Dims &, const PdasArgs &, int, int, hipStream_t); \
     template int launch_pdas_check<float, S_, C_>(const Dims &, const PdasArgs &, hipStream_t);         \
     template int launch_pdas_check<double, S_, C_>(const Dims &, const PdasArgs &, hipStream_t);        \
-    template int launch_pdas_step<float, S_, C_>(const Dims &, const PdasArgs &, int, int, hipStream_t); \
-    template int launch_pdas_step<double, S_, C_>(const Dims &, const PdasArgs &, int, int, hipStream_t);
+    template int launch_pdas_step<float, S_, C_>(const Dims &, const PdasArgs &, int, hipStream_t);     \
+    template int launch_pdas_step<double, S_, C_>(const Dims &, const PdasArgs &, int, hipStream_t);
 GATO_SHAPES(X)
 #undef X
 

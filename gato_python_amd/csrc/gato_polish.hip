@@ -3,8 +3,12 @@
 // their bounds b) is solved exactly on the whole-solve stage path: C's identity blocks are implicit, so an active variable
 // cannot be dropped from C; instead every stage after the inversion reads G only through Ginv, and Ginv' (the inverse of
 // the free sub-blocks, active rows and columns zero) with the shifted right-hand side g' = g - H_:A b_A, c' = c - C_:A b_A
-// gives x'_A = 0 and the reduced solution on F.  Every kernel: one wave per knot, grid.x strides over the knots, grid.y =
-// system, lane i = variable i of the knot.
+// gives x'_A = 0 and the reduced solution on F.
+// Soft bounds (PolishArgs::w): a variable with a weight w_i > 0 is penalised by (w_i / 2) dist(x_i,
+// [lo_i, hi_i])^2 instead of bounded: where it is active it stays in the reduced system - the diagonal entry of Q_k or R_k the
+// inversion sees gains w_i, g' gains w_i b_i - and its multiplier is the penalty force y_i = w_i (x_i - b_i).  A variable with
+// w_i = 0 is a hard bound; with no weights (w = nullptr) no kernel reads one and every variable is hard.
+// Every kernel: one wave per knot, grid.x strides over the knots, grid.y = system, lane i = variable i of the knot.
 #include "gato_common.h"
 #include "gato_gj.h"
 #include "gato_qp_common.h"
@@ -37,20 +41,24 @@ __global__ __launch_bounds__(WAVE) void qp_active_kernel(const T *__restrict__ z
     }
 }
 
-// Ginv' of the knot (Q_k and R_k with the active rows and columns replaced by the identity, inverted by the assembly's
-// Gauss-Jordan, then the active entries zeroed: with nothing active, the bits of the assembly's own inverse), g' and c'.
+// Ginv' of the knot (Q_k and R_k with the hard-active rows and columns replaced by the identity, inverted by the assembly's
+// Gauss-Jordan, then the hard-active entries zeroed: with nothing active, the bits of the assembly's own inverse), g' and c'.
+// A soft-active variable keeps its row and column: the diagonal entry the Gauss-Jordan sees gains w_i, g'_i gains w_i b_i
+// (before the hard shift of its row), and c' does not see it.
 // An act that is not -1 / 0 / 1, names an infinite bound or a state of x_0 counts the system in *bad and sets polish = 3.
-template <typename T, int S, int C>
+template <typename T, int S, int C, bool W>
 __global__ __launch_bounds__(WAVE) void polish_prepare_kernel(PolishArgs a, int K, BatchStride bs)
 {
     constexpr int n = S + C, SS = S * S, CC = C * C, SN = S * n;
-    __shared__ T sb[2][n];                   // bound values of knots k-1 (0) and k (1), 0 on free variables
-    __shared__ int sa[2][n];                 // active
+    __shared__ T sb[2][n];                   // bound values of knots k-1 (0) and k (1), 0 off the hard-active set
+    __shared__ int sa[2][n];                 // hard-active
+    __shared__ T sw[n], ss[n];               // W only: knot k's w_i on the soft-active set (0 elsewhere) and the bound there
     const int lane = threadIdx.x;
     const size_t sys = blockIdx.y;
     const T *Gd = (const T *)a.Gd + sys * bs.g, *Cd = (const T *)a.Cd + sys * bs.c;
     const T *g = (const T *)a.g + sys * bs.n, *c = (const T *)a.c + sys * bs.sk;
     const T *lo = (const T *)a.lo + sys * bs.n, *hi = (const T *)a.hi + sys * bs.n;
+    const T *w = sys_weights<T, W>(a.w, sys, bs);
     const signed char *act = a.act + sys * bs.n;
     T *Gi = (T *)a.Ginv + sys * bs.g, *gp = (T *)a.gp + sys * bs.n, *cp = (T *)a.cp + sys * bs.sk;
     int bad = 0;
@@ -63,24 +71,38 @@ __global__ __launch_bounds__(WAVE) void polish_prepare_kernel(PolishArgs a, int 
             for (int h = 0; h < 2; ++h) {
                 const int kk = k - 1 + h;
                 int on = 0;
-                T b = (T)0;
+                T b = (T)0, wi = (T)0, bsoft = (T)0;
                 if (kk >= 0 && lane < (kk < K - 1 ? n : S)) {
                     const size_t v = (size_t)kk * n + lane;
                     const signed char ai = act[v];
-                    on = ai != 0;
                     b = bound_of(ai, lo[v], hi[v]);
                     if (h == 1 && bad_active(ai, b, kk == 0 && lane < S)) bad = 1;
+                    if (soft_active(ai, w, v)) {
+                        wi = w[v];
+                        bsoft = b;
+                        b = (T)0;
+                    } else on = ai != 0;
                 }
                 sa[h][lane] = on;
                 sb[h][lane] = b;
+                if (W && h == 1) { sw[lane] = wi; ss[lane] = bsoft; }
             }
         }
         __syncthreads();
         {                                                                    // Q_k
             T col[S];
 #pragma unroll
-            for (int r = 0; r < S; ++r)
-                col[r] = lane < S ? ((sa[1][lane] || sa[1][r]) ? (T)(lane == r) : Gd[gb + lane * S + r]) : (T)(lane - S == r);
+            for (int r = 0; r < S; ++r) {
+                T e = (T)(lane - S == r);
+                if (lane < S) {
+                    if (sa[1][lane] || sa[1][r]) e = (T)(lane == r);
+                    else {
+                        e = Gd[gb + lane * S + r];
+                        if (W && lane == r && sw[lane] > (T)0) e += sw[lane];
+                    }
+                }
+                col[r] = e;
+            }
             gj_inverse_reg<T, S>(col);
             if (lane >= S && lane < 2 * S) {
                 const int cc = lane - S;
@@ -91,9 +113,17 @@ __global__ __launch_bounds__(WAVE) void polish_prepare_kernel(PolishArgs a, int 
         if (k < K - 1) {                                                     // R_k
             T col[C];
 #pragma unroll
-            for (int r = 0; r < C; ++r)
-                col[r] = lane < C ? ((sa[1][S + lane] || sa[1][S + r]) ? (T)(lane == r) : Gd[gb + SS + lane * C + r])
-                                  : (T)(lane - C == r);
+            for (int r = 0; r < C; ++r) {
+                T e = (T)(lane - C == r);
+                if (lane < C) {
+                    if (sa[1][S + lane] || sa[1][S + r]) e = (T)(lane == r);
+                    else {
+                        e = Gd[gb + SS + lane * C + r];
+                        if (W && lane == r && sw[S + lane] > (T)0) e += sw[S + lane];
+                    }
+                }
+                col[r] = e;
+            }
             gj_inverse_reg<T, C>(col);
             if (lane >= C && lane < 2 * C) {
                 const int cc = lane - C;
@@ -101,15 +131,18 @@ __global__ __launch_bounds__(WAVE) void polish_prepare_kernel(PolishArgs a, int 
                 for (int r = 0; r < C; ++r) Gi[gb + SS + cc * C + r] = (sa[1][S + cc] || sa[1][S + r]) ? (T)0 : col[r];
             }
         }
-        if (lane < nk) {                                                     // g' = g - H_:A b_A (0 on A: Ginv' ignores it)
+        if (lane < nk) {                                                     // g' = g + W b - H_:A b_A (0 on A: Ginv' ignores it)
             T t = g[v0 + lane];
             if (sa[1][lane]) t = (T)0;
-            else if (lane < S) {
-                for (int j = 0; j < S; ++j)
-                    if (sa[1][j]) t = fmaT(-Gd[gb + j * S + lane], sb[1][j], t);
-            } else {
-                for (int j = 0; j < C; ++j)
-                    if (sa[1][S + j]) t = fmaT(-Gd[gb + SS + j * C + (lane - S)], sb[1][S + j], t);
+            else {
+                if (W && sw[lane] > (T)0) t = fmaT(sw[lane], ss[lane], t);
+                if (lane < S) {
+                    for (int j = 0; j < S; ++j)
+                        if (sa[1][j]) t = fmaT(-Gd[gb + j * S + lane], sb[1][j], t);
+                } else {
+                    for (int j = 0; j < C; ++j)
+                        if (sa[1][S + j]) t = fmaT(-Gd[gb + SS + j * C + (lane - S)], sb[1][S + j], t);
+                }
             }
             gp[v0 + lane] = t;
         }
@@ -138,7 +171,7 @@ __global__ __launch_bounds__(WAVE) void polish_finish_kernel(PolishArgs a, int K
     __shared__ PointLds<T, S, C> lds;
     const int lane = threadIdx.x;
     const size_t sys = blockIdx.y;
-    const PointSys<T> p = point_sys<T>(a, sys, bs);
+    const PointSys<T> p = point_sys<T, false>(a, sys, bs);                   // the polish has no weights
     unsigned long long m[NSL];
 #pragma unroll
     for (int f = 0; f < NSL; ++f) m[f] = 0;
@@ -165,20 +198,23 @@ __global__ __launch_bounds__(WAVE) void polish_writeback_kernel(PolishArgs a, in
     if (t.ok) write_point<T, S, C>(a, sys, bs, K, lane);
 }
 
-// b_bar_i = xbar_i - (H a + C^T beta)_i on the active set - the row products of the finish step with rho 0: a_A = 0, so
-// rho a_i vanishes there - to hi_bar where act = +1, to lo_bar where act = -1; 0 in both elsewhere.
-template <typename T, int S, int C>
-__global__ __launch_bounds__(WAVE) void qp_bound_grad_kernel(const T *__restrict__ G, const T *__restrict__ Cd,
-                                                             const signed char *__restrict__ act, const T *__restrict__ xbar,
-                                                             const T *__restrict__ adz, const T *__restrict__ beta,
-                                                             T *__restrict__ lo_bar, T *__restrict__ hi_bar, int K, BatchStride bs)
+// lo_bar, hi_bar and w_bar of a converged point from the adjoint [a; beta] of its last assembly.  Hard-active i: b_bar_i = xbar_i -
+// (H a + C^T beta)_i - the row products of the finish step with rho 0: a_A = 0, so rho a_i vanishes there; soft-active i:
+// b_bar_i = w_i a_i and w_bar_i = a_i (b_i - x_i); b_bar goes to hi_bar where act = +1 and to lo_bar where act = -1; every other
+// entry of the three is 0.  Without weights lo, hi and x are not read; without w_bar it is not written.
+template <typename T, int S, int C, bool W>
+__global__ __launch_bounds__(WAVE) void qp_bound_grad_kernel(BoundGradArgs q, int K, BatchStride bs)
 {
     constexpr int n = S + C, SS = S * S, CC = C * C, SN = S * n;
     __shared__ T sQ[SS], sR[CC], sCk[SN], sV[n], sLk[S], sLn[S];
     const int lane = threadIdx.x;
     const size_t sys = blockIdx.y;
-    G += sys * bs.g; Cd += sys * bs.c; act += sys * bs.n; xbar += sys * bs.n; adz += sys * bs.n; beta += sys * bs.sk;
-    lo_bar += sys * bs.n; hi_bar += sys * bs.n;
+    const T *G = (const T *)q.G + sys * bs.g, *Cd = (const T *)q.Cd + sys * bs.c;
+    const signed char *act = q.act + sys * bs.n;
+    const T *w = sys_weights<T, W>(q.w, sys, bs);
+    const T *xbar = (const T *)q.xbar + sys * bs.n, *adz = (const T *)q.adz + sys * bs.n, *beta = (const T *)q.beta + sys * bs.sk;
+    T *lo_bar = (T *)q.lo_bar + sys * bs.n, *hi_bar = (T *)q.hi_bar + sys * bs.n;
+    T *w_bar = W && q.w_bar ? (T *)q.w_bar + sys * bs.n : nullptr;
     for (int k = blockIdx.x; k < K; k += gridDim.x) {
         const int nk = k < K - 1 ? n : S;
         const size_t v0 = (size_t)k * n;
@@ -198,14 +234,20 @@ __global__ __launch_bounds__(WAVE) void qp_bound_grad_kernel(const T *__restrict
         if (lane < nk) {
             const size_t v = v0 + lane;
             const signed char ai = act[v];
-            T bb = (T)0;
-            if (ai != 0) {
+            T bb = (T)0, wb = (T)0;
+            if (soft_active(ai, w, v)) {
+                const size_t o = sys * bs.n + v;                             // lo, hi and x: given with the weights only
+                const T ad = sV[lane];
+                bb = w[v] * ad;
+                wb = ad * (bound_of(ai, ((const T *)q.lo)[o], ((const T *)q.hi)[o]) - ((const T *)q.x)[o]);
+            } else if (ai != 0) {
                 T hx, ctl;
                 row_products<T, S, C>(lane, k < K - 1, sQ, sR, sCk, sV, sLk, sLn, (T)0, hx, ctl);
                 bb = xbar[v] - (hx + ctl);
             }
             lo_bar[v] = ai < 0 ? bb : (T)0;
             hi_bar[v] = ai > 0 ? bb : (T)0;
+            if (w_bar) w_bar[v] = wb;
         }
     }
 }
@@ -226,7 +268,8 @@ template <typename T, int S, int C>
 int launch_polish_prepare(const Dims &d, const PolishArgs &a, hipStream_t st)
 {
     if (d.B < 1 || d.B > 65535) { set_error("polish_prepare: B = %d", d.B); return GATO_EINVAL; }
-    hipLaunchKernelGGL((polish_prepare_kernel<T, S, C>), dim3(knot_grid(d.K), d.B), dim3(WAVE), 0, st, a, d.K, batch_stride(d));
+    const auto kernel = a.w ? polish_prepare_kernel<T, S, C, true> : polish_prepare_kernel<T, S, C, false>;
+    hipLaunchKernelGGL(kernel, dim3(knot_grid(d.K), d.B), dim3(WAVE), 0, st, a, d.K, batch_stride(d));
     GATO_HIP_CHECK(hipGetLastError());
     return GATO_OK;
 }
@@ -243,12 +286,12 @@ int launch_polish_finish(const Dims &d, const PolishArgs &a, hipStream_t st)
 }
 
 template <typename T, int S, int C>
-int launch_qp_bound_grad(const Dims &d, const void *G, const void *Cd, const signed char *act, const void *xbar, const void *adz,
-                         const void *beta, void *lo_bar, void *hi_bar, hipStream_t st)
+int launch_qp_bound_grad(const Dims &d, const BoundGradArgs &a, hipStream_t st)
 {
     if (d.B < 1 || d.B > 65535) { set_error("qp_bound_grad: B = %d", d.B); return GATO_EINVAL; }
-    hipLaunchKernelGGL((qp_bound_grad_kernel<T, S, C>), dim3(knot_grid(d.K), d.B), dim3(WAVE), 0, st, (const T *)G, (const T *)Cd,
-                       act, (const T *)xbar, (const T *)adz, (const T *)beta, (T *)lo_bar, (T *)hi_bar, d.K, batch_stride(d));
+    // with w_bar alone (the soft entry without weights) the W kernel finds no weight at run time and writes w_bar = 0
+    const auto kernel = a.w || a.w_bar ? qp_bound_grad_kernel<T, S, C, true> : qp_bound_grad_kernel<T, S, C, false>;
+    hipLaunchKernelGGL(kernel, dim3(knot_grid(d.K), d.B), dim3(WAVE), 0, st, a, d.K, batch_stride(d));
     GATO_HIP_CHECK(hipGetLastError());
     return GATO_OK;
 }
@@ -262,10 +305,8 @@ int launch_qp_bound_grad(const Dims &d, const void *G, const void *Cd, const sig
     template int launch_polish_prepare<double, S_, C_>(const Dims &, const PolishArgs &, hipStream_t);                      \
     template int launch_polish_finish<float, S_, C_>(const Dims &, const PolishArgs &, hipStream_t);                        \
     template int launch_polish_finish<double, S_, C_>(const Dims &, const PolishArgs &, hipStream_t);                       \
-    template int launch_qp_bound_grad<float, S_, C_>(const Dims &, const void *, const void *, const signed char *,          \
-                                                     const void *, const void *, const void *, void *, void *, hipStream_t); \
-    template int launch_qp_bound_grad<double, S_, C_>(const Dims &, const void *, const void *, const signed char *,         \
-                                                      const void *, const void *, const void *, void *, void *, hipStream_t);
+    template int launch_qp_bound_grad<float, S_, C_>(const Dims &, const BoundGradArgs &, hipStream_t);                     \
+    template int launch_qp_bound_grad<double, S_, C_>(const Dims &, const BoundGradArgs &, hipStream_t);
 GATO_SHAPES(X)
 #undef X
 

@@ -1,4 +1,4 @@
-// Device helpers of the box-QP kernels (gato_qp.hip, gato_polish.hip, gato_pdas.hip, gato_soft.hip).  Internal header.
+// Device helpers of the box-QP kernels (gato_qp.hip, gato_polish.hip, gato_pdas.hip).  Internal header.
 #pragma once
 #include "gato_common.h"
 
@@ -67,21 +67,32 @@ __device__ __forceinline__ void row_products(int i, bool next, const T *sQ, cons
     }
 }
 
+// The soft weights of system sys (w: [B][N]) in a kernel instantiated with weights (W); nullptr = all hard in one without: every
+// test of it is then decided at compile time and the hard code is what it was before there were weights.
+template <typename T, bool W>
+__device__ __forceinline__ const T *sys_weights(const void *w, size_t sys, const BatchStride &bs)
+{
+    return W && w ? (const T *)w + sys * bs.n : nullptr;
+}
+
 // One system's arrays of PolishArgs, and the LDS one wave stages a knot in.
 template <typename T>
 struct PointSys {
     const T *G, *Cd, *g, *c, *lo, *hi, *xt, *lt;
+    const T *w;                              // the system's soft weights, nullptr = all hard
     const signed char *act;
     T *xp, *zp, *yp;
     T rho;
 };
-template <typename T>
+// W: the kernel is the instantiation with weights; without, w is a compile-time nullptr and no soft branch is compiled
+template <typename T, bool W>
 __device__ __forceinline__ PointSys<T> point_sys(const PolishArgs &a, size_t sys, const BatchStride &bs)
 {
-    return PointSys<T>{(const T *)a.G + sys * bs.g,  (const T *)a.Cd + sys * bs.c, (const T *)a.g + sys * bs.n,
-                       (const T *)a.c + sys * bs.sk, (const T *)a.lo + sys * bs.n, (const T *)a.hi + sys * bs.n,
-                       (const T *)a.xt + sys * bs.n, (const T *)a.lt + sys * bs.sk, a.act + sys * bs.n,
-                       (T *)a.xp + sys * bs.n,       (T *)a.zp + sys * bs.n,       (T *)a.yp + sys * bs.n, (T)a.rho};
+    return PointSys<T>{(const T *)a.G + sys * bs.g,  (const T *)a.Cd + sys * bs.c,  (const T *)a.g + sys * bs.n,
+                       (const T *)a.c + sys * bs.sk, (const T *)a.lo + sys * bs.n,  (const T *)a.hi + sys * bs.n,
+                       (const T *)a.xt + sys * bs.n, (const T *)a.lt + sys * bs.sk, sys_weights<T, W>(a.w, sys, bs),
+                       a.act + sys * bs.n,           (T *)a.xp + sys * bs.n,        (T *)a.zp + sys * bs.n,
+                       (T *)a.yp + sys * bs.n,       (T)a.rho};
 }
 template <typename T, int S, int C>
 struct PointLds { T sQ[S * S], sR[C * C], sCp[S * (S + C)], sCk[S * (S + C)], sXn[S + C], sXp[S + C], sLk[S], sLn[S]; };
@@ -89,8 +100,15 @@ struct PointLds { T sQ[S * S], sR[C * C], sCp[S * (S + C)], sCk[S * (S + C)], sX
 template <typename T>
 struct PointVar { bool on; signed char act; T x, y, lo, hi; };
 
+// Variable v of a system is soft-active: it is active and its weight is positive (w: the system's
+// weights, nullptr = all hard).
+template <typename T>
+__device__ __forceinline__ bool soft_active(signed char act, const T *w, size_t v) { return act != 0 && w && w[v] > (T)0; }
+
 // Knot k of the polished point from the reduced solve (x = x' off the active set, the bound on it, z = clip(x), y_A = (g - H x -
-// C^T lambda)_A, y_F = 0) to xp, zp, yp, and its residuals folded into the lane's maxima m.  The whole wave calls it.
+// C^T lambda)_A, y_F = 0) to xp, zp, yp, and its residuals folded into the lane's maxima m.  A soft-active variable keeps the
+// reduced solution x', its multiplier is the penalty force y = w (x - b) and z = x (the violation is allowed); H in the residuals
+// is without W.  With p.w nullptr or 0 no variable is soft-active.  The whole wave calls it.
 template <typename T, int S, int C>
 __device__ __forceinline__ PointVar<T> polished_point_knot(PointLds<T, S, C> &L, const PointSys<T> &p, int k, int K, int lane,
                                                            unsigned long long (&m)[GATO_POLISH_NSLOT])
@@ -113,12 +131,12 @@ __device__ __forceinline__ PointVar<T> polished_point_knot(PointLds<T, S, C> &L,
     if (lane < nk) {
         const size_t v = v0 + lane;
         const signed char ai = p.act[v];
-        L.sXn[lane] = ai != 0 ? bound_of(ai, p.lo[v], p.hi[v]) : p.xt[v];
+        L.sXn[lane] = (ai != 0 && !soft_active(ai, p.w, v)) ? bound_of(ai, p.lo[v], p.hi[v]) : p.xt[v];
     }
     if (k > 0 && lane < n) {                                            // knot k-1's x (always a full knot)
         const size_t v = v0 - n + lane;
         const signed char ai = p.act[v];
-        L.sXp[lane] = ai != 0 ? bound_of(ai, p.lo[v], p.hi[v]) : p.xt[v];
+        L.sXp[lane] = (ai != 0 && !soft_active(ai, p.w, v)) ? bound_of(ai, p.lo[v], p.hi[v]) : p.xt[v];
     }
     if (lane < S) {
         L.sLk[lane] = p.lt[(size_t)k * S + lane];
@@ -129,88 +147,7 @@ __device__ __forceinline__ PointVar<T> polished_point_knot(PointLds<T, S, C> &L,
         const int i = lane;
         const size_t v = v0 + i;
         const signed char ai = p.act[v];
-        T hx, ctl;
-        row_products<T, S, C>(i, k < K - 1, L.sQ, L.sR, L.sCk, L.sXn, L.sLk, L.sLn, p.rho, hx, ctl);
-        const T gv = p.g[v], l = p.lo[v], h = p.hi[v], xn = L.sXn[i];
-        const T zn = clip(xn, l, h);
-        const T yn = ai != 0 ? (gv - hx) - ctl : (T)0;
-        const T rd = (hx - gv) + ctl + yn;
-        p.xp[v] = xn; p.zp[v] = zn; p.yp[v] = yn;
-        fold(F_PRIM, xn - zn);
-        fold(F_DUAL, rd);
-        fold(F_X, xn);
-        fold(F_Z, zn);
-        fold(F_HX, hx);
-        fold(F_CTL, ctl);
-        fold(F_Y, yn);
-        fold(F_G, gv);
-        if (ai != 0 && l != h) {                                        // the multiplier's sign: y >= 0 upper, <= 0 lower
-            const T w = ai > 0 ? -yn : yn;
-            fold(F_SIGN, w > (T)0 ? w : (T)0);
-        }
-        if (i < S) {                                                    // row block k of C x - c
-            const T ci = p.c[(size_t)k * S + i];
-            T cx = xn;
-            if (k > 0) {
-#pragma unroll 4
-                for (int j = 0; j < n; ++j) cx = fmaT(L.sCp[i + j * S], L.sXp[j], cx);
-            }
-            fold(F_PRIM, cx - ci);
-            fold(F_C, ci);
-            fold(F_LAM, L.sLk[i]);
-        }
-        out = PointVar<T>{true, ai, xn, yn, l, h};
-    }
-    return out;
-}
-
-// ---- soft bounds (gato_soft.hip) ----------------------------------------------------------------------
-// Variable v of a system is soft-active: it is active and its weight is positive (w: the system's weights, nullptr = all hard).
-template <typename T>
-__device__ __forceinline__ bool soft_active(signed char act, const T *w, size_t v) { return act != 0 && w && w[v] > (T)0; }
-
-// polished_point_knot with soft bounds: a soft-active variable keeps the reduced solution x', its multiplier is the penalty force
-// y = w (x - b) and z = x (the violation is allowed); H in the residuals is without W.  Every other variable, and every variable
-// when w is nullptr or 0, is polished_point_knot's, operation for operation.  The whole wave calls it.
-template <typename T, int S, int C>
-__device__ __forceinline__ PointVar<T> soft_point_knot(PointLds<T, S, C> &L, const PointSys<T> &p, const T *w, int k, int K, int lane,
-                                                       unsigned long long (&m)[GATO_POLISH_NSLOT])
-{
-    using namespace polf;
-    constexpr int WAVE = 64, n = S + C, SS = S * S, CC = C * C, SN = S * n;
-    auto fold = [&](int f, T v) { const unsigned long long b = mag_bits(v); m[f] = b > m[f] ? b : m[f]; };
-    const int nk = k < K - 1 ? n : S;
-    const size_t v0 = (size_t)k * n;
-    PointVar<T> out{false, 0, (T)0, (T)0, (T)0, (T)0};
-    __syncthreads();
-    const T *Gk = p.G + (size_t)k * (SS + CC);
-    for (int e = lane; e < SS; e += WAVE) L.sQ[e] = Gk[e];
-    if (k < K - 1) {
-        for (int e = lane; e < CC; e += WAVE) L.sR[e] = Gk[SS + e];
-        for (int e = lane; e < SN; e += WAVE) L.sCk[e] = p.Cd[(size_t)k * SN + e];
-    }
-    if (k > 0)
-        for (int e = lane; e < SN; e += WAVE) L.sCp[e] = p.Cd[(size_t)(k - 1) * SN + e];
-    if (lane < nk) {
-        const size_t v = v0 + lane;
-        const signed char ai = p.act[v];
-        L.sXn[lane] = (ai != 0 && !soft_active(ai, w, v)) ? bound_of(ai, p.lo[v], p.hi[v]) : p.xt[v];
-    }
-    if (k > 0 && lane < n) {                                            // knot k-1's x (always a full knot)
-        const size_t v = v0 - n + lane;
-        const signed char ai = p.act[v];
-        L.sXp[lane] = (ai != 0 && !soft_active(ai, w, v)) ? bound_of(ai, p.lo[v], p.hi[v]) : p.xt[v];
-    }
-    if (lane < S) {
-        L.sLk[lane] = p.lt[(size_t)k * S + lane];
-        if (k < K - 1) L.sLn[lane] = p.lt[(size_t)(k + 1) * S + lane];
-    }
-    __syncthreads();
-    if (lane < nk) {
-        const int i = lane;
-        const size_t v = v0 + i;
-        const signed char ai = p.act[v];
-        const bool soft = soft_active(ai, w, v);
+        const bool soft = soft_active(ai, p.w, v);
         T hx, ctl;
         row_products<T, S, C>(i, k < K - 1, L.sQ, L.sR, L.sCk, L.sXn, L.sLk, L.sLn, p.rho, hx, ctl);
         const T gv = p.g[v], l = p.lo[v], h = p.hi[v], xn = L.sXn[i];
@@ -218,7 +155,7 @@ __device__ __forceinline__ PointVar<T> soft_point_knot(PointLds<T, S, C> &L, con
         T yn = ai != 0 ? (gv - hx) - ctl : (T)0;
         if (soft) {
             zn = xn;
-            yn = w[v] * (xn - bound_of(ai, l, h));
+            yn = p.w[v] * (xn - bound_of(ai, l, h));
         }
         const T rd = (hx - gv) + ctl + yn;
         p.xp[v] = xn; p.zp[v] = zn; p.yp[v] = yn;

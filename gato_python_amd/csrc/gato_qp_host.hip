@@ -1,6 +1,7 @@
 // Box-constrained QP (ADMM over the re-solve), its polish, the active-set iteration and bound gradients: the host side of
-// gato_qp.hip / gato_polish.hip / gato_pdas.hip / gato_soft.hip.
+// gato_qp.hip / gato_polish.hip / gato_pdas.hip.
 #include <cmath>
+#include <initializer_list>
 
 #include "gato_solver.h"
 
@@ -15,6 +16,33 @@ static int grow_ws(char **ws, size_t *have, size_t bytes, hipStream_t st)
     if (*ws) (void)hipFree(*ws);
     *ws = w; *have = bytes;
     return GATO_OK;
+}
+
+// The first check of the solve, polish and active-set entries: a usable solver, then p and every pointer of `required`
+// (d_C_blocks only for K > 1).  ptr_note ends the entry's message inside its parentheses.
+static int check_pointers(gato_solver *s, const char *who, const gato_box_qp_params *p, const void *d_C_blocks,
+                          std::initializer_list<const void *> required, const char *ptr_note = "")
+{
+    if (!solver_usable(s, who, "QP solves")) return GATO_EINVAL;
+    bool ok = p && (d_C_blocks || s->d.K <= 1);
+    for (const void *q : required) ok = ok && q;
+    if (!ok) set_error("%s: every pointer is required (d_C_blocks may be NULL only for K = 1%s)", who, ptr_note);
+    return ok ? GATO_OK : GATO_EINVAL;
+}
+
+// Their last check: these entries read a count on the host (`reads` says which) and cannot run on a stream being captured.
+static int check_not_capturing(const char *who, const char *reads, hipStream_t st)
+{
+    if (!stream_is_capturing(st)) return GATO_OK;
+    set_error("%s: the stream is being captured; %s on the host and cannot be captured", who, reads);
+    return GATO_EINVAL;
+}
+
+// The parameters a reduced solve reads (polish, active-set iteration): finite and in range.
+static bool reduced_params_ok(const gato_box_qp_params &p)
+{
+    const bool fin = std::isfinite(p.rho) && std::isfinite(p.eps_abs) && std::isfinite(p.eps_rel) && std::isfinite(p.exit_tol);
+    return fin && p.rho >= 0 && p.eps_abs >= 0 && p.eps_rel >= 0 && p.exit_tol >= 0 && p.max_iters >= 1;
 }
 
 // ---- box-constrained QP by ADMM over the re-solve (gato_qp.hip) ---------------------------------
@@ -33,12 +61,9 @@ extern "C" int gato_box_qp_solve(gato_solver *s, const void *d_G_blocks, const v
                                  void *d_z, void *d_y, void *d_lambda, int *d_iters, int *d_status, double *d_res,
                                  void *stream)
 {
-    if (!solver_usable(s, "box_qp_solve", "QP solves")) return GATO_EINVAL;
-    if (!p || !d_G_blocks || (!d_C_blocks && s->d.K > 1) || !d_g || !d_c || !d_lo || !d_hi || !d_x || !d_z || !d_y ||
-        !d_lambda || !d_iters || !d_status || !d_res) {
-        set_error("box_qp_solve: every pointer is required (d_C_blocks may be NULL only for K = 1)");
+    if (check_pointers(s, "box_qp_solve", p, d_C_blocks,
+                       {d_G_blocks, d_g, d_c, d_lo, d_hi, d_x, d_z, d_y, d_lambda, d_iters, d_status, d_res}))
         return GATO_EINVAL;
-    }
     const bool fin = std::isfinite(p->rho) && std::isfinite(p->admm_rho) && std::isfinite(p->sigma) && std::isfinite(p->alpha) &&
                      std::isfinite(p->eps_abs) && std::isfinite(p->eps_rel) && std::isfinite(p->exit_tol);
     if (!fin || p->rho < 0 || !(p->admm_rho > 0) || p->sigma < 0 || !(p->alpha > 0 && p->alpha < 2) || p->eps_abs < 0 ||
@@ -48,10 +73,7 @@ extern "C" int gato_box_qp_solve(gato_solver *s, const void *d_G_blocks, const v
         return GATO_EINVAL;
     }
     hipStream_t st = (hipStream_t)stream;
-    if (stream_is_capturing(st)) {
-        set_error("box_qp_solve: the stream is being captured; the loop reads the live count on the host and cannot be captured");
-        return GATO_EINVAL;
-    }
+    if (check_not_capturing("box_qp_solve", "the loop reads the live count", st)) return GATO_EINVAL;
     GATO_HIP_CHECK(hipSetDevice(s->device));
     int rc = gato_solver_reserve_rhs(s, 1);
     if (rc) return rc;
@@ -126,6 +148,42 @@ extern "C" int gato_box_qp_active_set(gato_solver *s, const void *d_z, const voi
     return s->ops->qp_active(d, d_z, d_y, d_lo, d_hi, d_act, (hipStream_t)stream);
 }
 
+// The work area of the polish and of the active-set iteration (pol_ws), as offsets: the reduced system's right-hand side, the
+// reduced solve and the polished point, then what only the iteration has (act', a second set of maxima, the round counts, polish
+// flags of its own) around the maxima and the counters.  Everything from sl on is zeroed at the start of a call.
+struct PolishWs {
+    size_t gp, cp, xt, lt, xp, zp, yp;      // [B][N] each, cp and lt [B][S K]
+    size_t a2;                              // iteration: act' [B][N] int8
+    size_t sl;                              // the maxima, [B][GATO_POLISH_NSLOT]; iteration: [B][2][GATO_POLISH_NSLOT]
+    size_t rn, pol;                         // iteration: PdasArgs::round [B][2][2], PolishArgs::polish [B]
+    size_t ctr;                             // polish: the BAD_ACTIVE count; iteration: PdasArgs::ctr and the count after it
+    size_t bytes;
+};
+static PolishWs polish_ws(const Dims &d, size_t e, bool pdas)
+{
+    const size_t B = d.B, vN = align_up(B * d.N() * e), vK = align_up(B * d.sk() * e);
+    PolishWs o;
+    o.gp = 0; o.cp = o.gp + vN; o.xt = o.cp + vK; o.lt = o.xt + vN; o.xp = o.lt + vK; o.zp = o.xp + vN; o.yp = o.zp + vN;
+    o.a2 = o.yp + vN;
+    o.sl = o.a2 + (pdas ? align_up(B * d.N()) : 0);
+    o.rn = o.sl + align_up(B * (pdas ? 2 : 1) * GATO_POLISH_NSLOT * 8);
+    o.pol = o.rn + (pdas ? align_up(B * 4 * sizeof(int)) : 0);
+    o.ctr = o.pol + (pdas ? align_up(B * sizeof(int)) : 0);
+    o.bytes = o.ctr + 256;
+    return o;
+}
+
+// The part of PolishArgs both entries fill alike: the solver's buffers, the work area at w and the parameters.
+static PolishArgs polish_args(const gato_solver *s, char *w, const PolishWs &o, const gato_box_qp_params *p)
+{
+    PolishArgs a;
+    memset(&a, 0, sizeof(a));
+    a.Gd = s->G_dense; a.Ginv = s->Ginv; a.gp = w + o.gp; a.cp = w + o.cp; a.xt = w + o.xt; a.lt = w + o.lt;
+    a.xp = w + o.xp; a.zp = w + o.zp; a.yp = w + o.yp; a.slots = (unsigned long long *)(w + o.sl);
+    a.rho = p->rho; a.eps_abs = p->eps_abs; a.eps_rel = p->eps_rel;
+    return a;
+}
+
 // add rho, the masked inversion and shifted right-hand side (polish_prepare), then the stage kernels of the whole solve with
 // the given inverses: Schur, the preconditioner; the PCG and dz follow as in gato_linsys_device_blocks.
 extern "C" int gato_box_qp_polish(gato_solver *s, const void *d_G_blocks, const void *d_C_blocks, const void *d_g, const void *d_c,
@@ -133,41 +191,27 @@ extern "C" int gato_box_qp_polish(gato_solver *s, const void *d_G_blocks, const 
                                   void *d_x, void *d_z, void *d_y, void *d_lambda, int *d_status, double *d_res, int *d_polish,
                                   void *stream)
 {
-    if (!solver_usable(s, "box_qp_polish", "QP solves")) return GATO_EINVAL;
-    if (!p || !d_G_blocks || (!d_C_blocks && s->d.K > 1) || !d_g || !d_c || !d_lo || !d_hi || !d_act || !d_x || !d_z || !d_y ||
-        !d_lambda || !d_status || !d_res || !d_polish) {
-        set_error("box_qp_polish: every pointer is required (d_C_blocks may be NULL only for K = 1)");
+    if (check_pointers(s, "box_qp_polish", p, d_C_blocks,
+                       {d_G_blocks, d_g, d_c, d_lo, d_hi, d_act, d_x, d_z, d_y, d_lambda, d_status, d_res, d_polish}))
         return GATO_EINVAL;
-    }
-    const bool fin = std::isfinite(p->rho) && std::isfinite(p->eps_abs) && std::isfinite(p->eps_rel) && std::isfinite(p->exit_tol);
-    if (!fin || p->rho < 0 || p->eps_abs < 0 || p->eps_rel < 0 || p->exit_tol < 0 || p->max_iters < 1) {
+    if (!reduced_params_ok(*p)) {
         set_error("box_qp_polish: parameters out of range (want finite values, rho, eps_abs, eps_rel, exit_tol >= 0, max_iters >= 1)");
         return GATO_EINVAL;
     }
     hipStream_t st = (hipStream_t)stream;
-    if (stream_is_capturing(st)) {
-        set_error("box_qp_polish: the stream is being captured; the polish reads the active-set check on the host and cannot be captured");
-        return GATO_EINVAL;
-    }
+    if (check_not_capturing("box_qp_polish", "the polish reads the active-set check", st)) return GATO_EINVAL;
     GATO_HIP_CHECK(hipSetDevice(s->device));
-    const Dims &d = s->d;
-    const size_t e = s->esz, B = d.B, vN = align_up(B * d.N() * e), vK = align_up(B * d.sk() * e);
-    const size_t o_gp = 0, o_cp = o_gp + vN, o_xt = o_cp + vK, o_lt = o_xt + vN, o_xp = o_lt + vK, o_zp = o_xp + vN;
-    const size_t o_yp = o_zp + vN, o_sl = o_yp + vN, o_bad = o_sl + align_up(B * GATO_POLISH_NSLOT * 8);
-    const size_t bytes = o_bad + 256;
+    const size_t B = s->d.B;
+    const PolishWs o = polish_ws(s->d, s->esz, false);
     int rc;
-    if ((rc = grow_ws(&s->pol_ws, &s->pol_ws_bytes, bytes, st))) return rc;
+    if ((rc = grow_ws(&s->pol_ws, &s->pol_ws_bytes, o.bytes, st))) return rc;
     char *w = s->pol_ws;
-    int *nbad = (int *)(w + o_bad);
-    GATO_HIP_CHECK(hipMemsetAsync(w + o_sl, 0, bytes - o_sl, st));                   // slots, the BAD_ACTIVE count
+    int *nbad = (int *)(w + o.ctr);
+    GATO_HIP_CHECK(hipMemsetAsync(w + o.sl, 0, o.bytes - o.sl, st));                 // slots, the BAD_ACTIVE count
     GATO_HIP_CHECK(hipMemsetAsync(d_polish, 0xff, B * sizeof(int), st));             // -1 until decided
-    PolishArgs a;
-    memset(&a, 0, sizeof(a));
-    a.G = d_G_blocks; a.Cd = d_C_blocks; a.g = d_g; a.c = d_c; a.lo = d_lo; a.hi = d_hi; a.act = d_act;
-    a.Gd = s->G_dense; a.Ginv = s->Ginv; a.gp = w + o_gp; a.cp = w + o_cp; a.xt = w + o_xt; a.lt = w + o_lt;
-    a.xp = w + o_xp; a.zp = w + o_zp; a.yp = w + o_yp; a.slots = (unsigned long long *)(w + o_sl); a.bad = nbad;
+    PolishArgs a = polish_args(s, w, o, p);
+    a.G = d_G_blocks; a.Cd = d_C_blocks; a.g = d_g; a.c = d_c; a.lo = d_lo; a.hi = d_hi; a.act = d_act; a.bad = nbad;
     a.x = d_x; a.z = d_z; a.y = d_y; a.lam = d_lambda; a.status = d_status; a.polish = d_polish; a.res = d_res;
-    a.rho = p->rho; a.eps_abs = p->eps_abs; a.eps_rel = p->eps_rel;
     // the assembly: add rho and the masked inversion here, then the stage path of the whole solve with the inverses given
     s->d.k_lo = s->d.k_hi = 0;
     s->as.valid = 0;
@@ -182,77 +226,61 @@ extern "C" int gato_box_qp_polish(gato_solver *s, const void *d_G_blocks, const 
                   "d_polish marks them (3 = BAD_ACTIVE)", h);
         return GATO_EINVAL;
     }
-    PcgOpts o = pcg_opts(*s);
-    o.warm = 0;                             // always a cold start
+    PcgOpts po = pcg_opts(*s);
+    po.warm = 0;                            // always a cold start
     const AsmInput in{2, nullptr, nullptr, d_G_blocks, nullptr, nullptr, nullptr, d_C_blocks, true};
-    if ((rc = whole_solve(s, o, in, w + o_gp, w + o_cp, p->exit_tol, p->max_iters, p->rho, w + o_lt, w + o_xt, st))) return rc;
+    if ((rc = whole_solve(s, po, in, w + o.gp, w + o.cp, p->exit_tol, p->max_iters, p->rho, w + o.lt, w + o.xt, st))) return rc;
     if ((rc = s->ops->polish_finish(s->d, a, st))) return rc;
     GATO_HIP_CHECK(hipStreamSynchronize(st));
     return gato_pcg_status(s, nullptr);
 }
 
-// ---- primal-dual active-set iteration: the polish iterated (gato_pdas.hip) -----------------------
+// ---- primal-dual active-set iteration: the polish iterated (gato_pdas.hip, DESIGN.md sections 3.9, 3.10) ----------------
 // Per solve: add rho, the masked inversion and shifted right-hand side, the stage path of the whole solve (all as in the
-// polish), then the step and the decision and one read of the live count.
-// soft: the kernels of gato_soft.hip (section 3.10) with the weights d_soft_w (NULL: all hard) in place of the check, the
-// prepare and the step; the decision, the stage path and the host reads are the same.  `who` names the entry in errors.
+// polish), then the step and the decision and one read of the live count.  d_soft_w: the weights of soft bounds (NULL: all
+// hard), read by the check, the prepare and the step.  `who` names the entry in errors; soft: its texts speak of the weights.
 static int pdas_loop(gato_solver *s, const char *who, bool soft, const void *d_G_blocks, const void *d_C_blocks, const void *d_g,
                      const void *d_c, const void *d_lo, const void *d_hi, const void *d_soft_w, signed char *d_act,
                      const gato_box_qp_params *p, int max_pdas_iters, void *d_x, void *d_z, void *d_y, void *d_lambda, int *d_iters,
                      int *d_status, double *d_res, void *stream)
 {
-    if (!solver_usable(s, who, "QP solves")) return GATO_EINVAL;
-    if (!p || !d_G_blocks || (!d_C_blocks && s->d.K > 1) || !d_g || !d_c || !d_lo || !d_hi || !d_act || !d_x || !d_z || !d_y ||
-        !d_lambda || !d_iters || !d_status || !d_res) {
-        set_error("%s: every pointer is required (d_C_blocks may be NULL only for K = 1%s)", who, soft ? ", d_soft_w for no soft bound" : "");
+    if (check_pointers(s, who, p, d_C_blocks, {d_G_blocks, d_g, d_c, d_lo, d_hi, d_act, d_x, d_z, d_y, d_lambda, d_iters, d_status, d_res},
+                       soft ? ", d_soft_w for no soft bound" : ""))
         return GATO_EINVAL;
-    }
-    const bool fin = std::isfinite(p->rho) && std::isfinite(p->eps_abs) && std::isfinite(p->eps_rel) && std::isfinite(p->exit_tol);
-    if (!fin || p->rho < 0 || p->eps_abs < 0 || p->eps_rel < 0 || p->exit_tol < 0 || p->max_iters < 1 || max_pdas_iters < 1) {
+    if (!reduced_params_ok(*p) || max_pdas_iters < 1) {
         set_error("%s: parameters out of range (want finite values, rho, eps_abs, eps_rel, exit_tol >= 0, max_iters, "
                   "max_pdas_iters >= 1)", who);
         return GATO_EINVAL;
     }
     hipStream_t st = (hipStream_t)stream;
-    if (stream_is_capturing(st)) {
-        set_error("%s: the stream is being captured; the loop reads the live count on the host and cannot be captured", who);
-        return GATO_EINVAL;
-    }
+    if (check_not_capturing(who, "the loop reads the live count", st)) return GATO_EINVAL;
     GATO_HIP_CHECK(hipSetDevice(s->device));
-    const Dims &d = s->d;
-    const size_t e = s->esz, B = d.B, vN = align_up(B * d.N() * e), vK = align_up(B * d.sk() * e);
-    const size_t o_gp = 0, o_cp = o_gp + vN, o_xt = o_cp + vK, o_lt = o_xt + vN, o_xp = o_lt + vK, o_zp = o_xp + vN;
-    const size_t o_yp = o_zp + vN, o_a2 = o_yp + vN, o_sl = o_a2 + align_up(B * d.N());
-    const size_t o_rn = o_sl + align_up(B * 2 * GATO_POLISH_NSLOT * 8), o_pol = o_rn + align_up(B * 4 * sizeof(int));
-    const size_t o_ctr = o_pol + align_up(B * sizeof(int)), bytes = o_ctr + 256;
+    const size_t B = s->d.B;
+    const PolishWs o = polish_ws(s->d, s->esz, true);
     int rc;
-    if ((rc = grow_ws(&s->pol_ws, &s->pol_ws_bytes, bytes, st))) return rc;
+    if ((rc = grow_ws(&s->pol_ws, &s->pol_ws_bytes, o.bytes, st))) return rc;
     char *w = s->pol_ws;
-    int *ctr = (int *)(w + o_ctr);
-    GATO_HIP_CHECK(hipMemsetAsync(w + o_sl, 0, bytes - o_sl, st));                   // both sets of maxima and counts, the counters
+    int *ctr = (int *)(w + o.ctr);
+    GATO_HIP_CHECK(hipMemsetAsync(w + o.sl, 0, o.bytes - o.sl, st));                 // both sets of maxima and counts, the counters
     GATO_HIP_CHECK(hipMemsetAsync(d_status, 0xff, B * sizeof(int), st));             // -1: running
     PdasArgs a;
     memset(&a, 0, sizeof(a));
     PolishArgs &q = a.p;
-    q.G = d_G_blocks; q.Cd = d_C_blocks; q.g = d_g; q.c = d_c; q.lo = d_lo; q.hi = d_hi; q.act = d_act;
-    q.Gd = s->G_dense; q.Ginv = s->Ginv; q.gp = w + o_gp; q.cp = w + o_cp; q.xt = w + o_xt; q.lt = w + o_lt;
-    q.xp = w + o_xp; q.zp = w + o_zp; q.yp = w + o_yp; q.slots = (unsigned long long *)(w + o_sl); q.bad = ctr + 3;
-    q.x = d_x; q.z = d_z; q.y = d_y; q.lam = d_lambda; q.status = d_status; q.polish = (int *)(w + o_pol); q.res = d_res;
-    q.rho = p->rho; q.eps_abs = p->eps_abs; q.eps_rel = p->eps_rel;
-    a.act = d_act; a.act2 = (signed char *)(w + o_a2); a.round = (int *)(w + o_rn); a.ctr = ctr; a.iters = d_iters;
-    SoftArgs sa;
-    memset(&sa, 0, sizeof(sa));
-    sa.d = a; sa.w = d_soft_w;
+    q = polish_args(s, w, o, p);
+    q.G = d_G_blocks; q.Cd = d_C_blocks; q.g = d_g; q.c = d_c; q.lo = d_lo; q.hi = d_hi; q.act = d_act; q.w = d_soft_w;
+    q.x = d_x; q.z = d_z; q.y = d_y; q.lam = d_lambda; q.status = d_status; q.polish = (int *)(w + o.pol); q.res = d_res;
+    q.bad = ctr + 3;
+    a.act = d_act; a.act2 = (signed char *)(w + o.a2); a.round = (int *)(w + o.rn); a.ctr = ctr; a.iters = d_iters;
     s->d.k_lo = s->d.k_hi = 0;
     s->as.valid = 0;
     s->lc.valid = 0;                        // G_dense and Ginv are rewritten: nothing earlier is left to recover
-    if ((rc = soft ? s->ops->soft_check(s->d, sa, st) : s->ops->pdas_check(s->d, a, st))) return rc;
-    PcgOpts o = pcg_opts(*s);
-    o.warm = 0;                             // every reduced solve is a cold start
+    if ((rc = s->ops->pdas_check(s->d, a, st))) return rc;
+    PcgOpts po = pcg_opts(*s);
+    po.warm = 0;                            // every reduced solve is a cold start
     const AsmInput in{2, nullptr, nullptr, d_G_blocks, nullptr, nullptr, nullptr, d_C_blocks, true};
     for (int it = 1; it <= max_pdas_iters; ++it) {
         if ((rc = s->ops->add_rho(s->d, d_G_blocks, p->rho, s->G_dense, st))) return rc;
-        if ((rc = soft ? s->ops->soft_prepare(s->d, sa, st) : s->ops->polish_prepare(s->d, q, st))) return rc;
+        if ((rc = s->ops->polish_prepare(s->d, q, st))) return rc;
         int h[3] = {0, 0, 0};
         if (it == 1) {                      // the caller's bounds and start act; later acts are the device's own: valid
             GATO_HIP_CHECK(hipMemcpyAsync(h, ctr, sizeof(h), hipMemcpyDeviceToHost, st));
@@ -265,11 +293,9 @@ static int pdas_loop(gato_solver *s, const char *who, bool soft, const void *d_G
                 return GATO_EINVAL;
             }
         }
-        if ((rc = whole_solve(s, o, in, w + o_gp, w + o_cp, p->exit_tol, p->max_iters, p->rho, w + o_lt, w + o_xt, st))) return rc;
-        if (soft) {
-            if ((rc = s->ops->soft_step(s->d, sa, it, st))) return rc;
-            if ((rc = s->ops->pdas_decide(s->d, a, it, it == max_pdas_iters, st))) return rc;
-        } else if ((rc = s->ops->pdas_step(s->d, a, it, it == max_pdas_iters, st))) return rc;
+        if ((rc = whole_solve(s, po, in, w + o.gp, w + o.cp, p->exit_tol, p->max_iters, p->rho, w + o.lt, w + o.xt, st))) return rc;
+        if ((rc = s->ops->pdas_step(s->d, a, it, st))) return rc;
+        if ((rc = s->ops->pdas_decide(s->d, a, it, it == max_pdas_iters, st))) return rc;
         if (it == max_pdas_iters) break;    // every system still live froze in that decision
         hipError_t he = hipMemcpyAsync(h, ctr, sizeof(int), hipMemcpyDeviceToHost, st);
         if (he == hipSuccess) he = hipStreamSynchronize(st);
@@ -292,7 +318,7 @@ extern "C" int gato_box_qp_pdas(gato_solver *s, const void *d_G_blocks, const vo
                      d_z, d_y, d_lambda, d_iters, d_status, d_res, stream);
 }
 
-// ---- soft bounds in the active-set iteration (gato_soft.hip) -------------------------------------
+// ---- soft bounds in the active-set iteration ------------------------------------------------------
 extern "C" int gato_box_qp_pdas_soft(gato_solver *s, const void *d_G_blocks, const void *d_C_blocks, const void *d_g,
                                      const void *d_c, const void *d_lo, const void *d_hi, const void *d_soft_w, signed char *d_act,
                                      const gato_box_qp_params *p, int max_pdas_iters, void *d_x, void *d_z, void *d_y,
@@ -315,8 +341,8 @@ extern "C" int gato_box_qp_soft_grad(gato_solver *s, const void *d_G_blocks, con
     }
     Dims d = s->d;
     d.k_lo = d.k_hi = 0; d.rhs = 0;
-    const SoftGradArgs a{d_G_blocks, d_C_blocks, d_act, d_soft_w, d_lo, d_hi, d_x, d_xbar, d_a, d_beta, d_lo_bar, d_hi_bar, d_w_bar};
-    return s->ops->soft_grad(d, a, (hipStream_t)stream);
+    const BoundGradArgs a{d_G_blocks, d_C_blocks, d_act, d_soft_w, d_lo, d_hi, d_x, d_xbar, d_a, d_beta, d_lo_bar, d_hi_bar, d_w_bar};
+    return s->ops->qp_bound_grad(d, a, (hipStream_t)stream);
 }
 
 extern "C" int gato_box_qp_bound_grad(gato_solver *s, const void *d_G_blocks, const void *d_C_blocks, const signed char *d_act,
@@ -330,6 +356,8 @@ extern "C" int gato_box_qp_bound_grad(gato_solver *s, const void *d_G_blocks, co
     }
     Dims d = s->d;
     d.k_lo = d.k_hi = 0; d.rhs = 0;
-    return s->ops->qp_bound_grad(d, d_G_blocks, d_C_blocks, d_act, d_xbar, d_a, d_beta, d_lo_bar, d_hi_bar, (hipStream_t)stream);
+    const BoundGradArgs a{d_G_blocks, d_C_blocks, d_act, nullptr, nullptr, nullptr, nullptr,      // no weights: no lo, hi, x
+                          d_xbar, d_a, d_beta, d_lo_bar, d_hi_bar, nullptr};
+    return s->ops->qp_bound_grad(d, a, (hipStream_t)stream);
 }
 

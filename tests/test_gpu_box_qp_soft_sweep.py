@@ -1,7 +1,8 @@
-"""The soft-bound kernels (gato_soft.hip, soft_point_knot) and the x_soft / u_soft surface of qp.py on mixed problems: hard and
-soft bounds side by side in one Q_k or R_k, soft controls, a weight per variable (box_qp_soft_ref.mixed_problem; what its walks
-must find - cover() - is asserted on the CPU by tests/test_box_qp_soft_cpu.py), batches of different weights on one system,
-and soft_grad_kernel as a function of its arrays at every shape, both precisions, two systems and past the grid cap.
+"""The soft-bound branches of the active-set kernels (gato_polish.hip, gato_pdas.hip, polished_point_knot) and the x_soft /
+u_soft surface of qp.py on mixed problems: hard and soft bounds side by side in one Q_k or R_k, soft controls, a weight per
+variable (box_qp_soft_ref.mixed_problem; what its walks must find - cover() - is asserted on the CPU by
+tests/test_box_qp_soft_cpu.py), batches of different weights on one system, and qp_bound_grad_kernel with weights as a function
+of its arrays at every shape, both precisions, two systems and past the grid cap.
 Bars: those of tests/test_gpu_box_qp_soft.py - the reference's solves and final act, x and lambda within 1e-6, penalised KKT
 residuals <= 1e-7, hard-active x the bounds bit for bit; the gradient kernel 1e-12 * scale * (2 S + C) in fp64 and
 tests/f32_parity.py's rule in fp32."""
@@ -215,7 +216,7 @@ def test_batch_of_weight_vectors_on_one_system():
     assert np.abs(got[2][0]).max() > 0 and np.abs(got[2][1]).max() > 0 and not got[2][2].any()
 
 
-# ---- 4. soft_grad_kernel, every shape, two systems, both precisions ---------------------------------------------------------
+# ---- 4. qp_bound_grad_kernel with weights, every shape, two systems, both precisions --------------------------------------------
 @pytest.mark.parametrize("dt", [np.float64, np.float32], ids=["float64", "float32"])
 @pytest.mark.parametrize("K", [2, 9])
 @pytest.mark.parametrize("shape", SHAPES, ids=lambda sh: "%d-%d" % sh)
@@ -249,7 +250,7 @@ def test_soft_grad_direct(shape, K, dt):
                 check_f32("soft grad %s %d/%d/%d system %d" % (name, S, C, K, b), t[b], o32, wt)
 
 
-# ---- 5. soft_grad_kernel past the grid cap ----------------------------------------------------------------------------------
+# ---- 5. qp_bound_grad_kernel with weights past the grid cap ---------------------------------------------------------------------
 def test_soft_grad_long_horizon():
     S, C, K = D.LONG
     n = S + C
