@@ -17,6 +17,7 @@ if HERE not in sys.path:
 
 import box_qp_polish_ref as P                     # noqa: E402
 import box_qp_ref as ref                          # noqa: E402
+import kkt_grad_ref as kgr                        # noqa: E402
 from gato_python_amd import synth                 # noqa: E402
 
 CONVERGED, MAX_ITERS, NONFINITE = ref.CONVERGED, ref.MAX_ITERS, ref.NONFINITE
@@ -213,3 +214,54 @@ def named(name):
     """(s, H, C, g, c, lo, hi) of pendulum_box(0.2) ("pendulum") or box_qp_polish_ref.problem(name)."""
     s, lo, hi, _ = P.problem(name)
     return (s,) + tuple(ref.parts(s)) + (lo, hi)
+
+
+# ---- the inputs of box_qp_layer as numpy arrays (tests/test_gpu_box_qp_layer_sweep.py) ---------------------------------------
+KEYS = ("Q", "R", "A", "B", "q", "r", "c", "x_lo", "x_hi", "u_lo", "u_hi")
+
+
+def math_arrays(s, lo, hi):
+    """[Q, R, A, B, q, r, c, x_lo, x_hi, u_lo, u_hi] of a system and its box (dz layout) as box_qp takes them, in KEYS' order."""
+    xl, ul = P.split_states_controls(lo, s.S, s.C, s.K)
+    xh, uh = P.split_states_controls(hi, s.S, s.C, s.K)
+    return [np.ascontiguousarray(t, np.float64) for t in (*kgr.blocks_of(s), xl, xh, ul, uh)]
+
+
+def batched(arrays):
+    """The per-system lists of math_arrays (or box_qp_soft_ref.soft_math_arrays) stacked along a leading batch dimension."""
+    return [np.stack(ts) for ts in zip(*arrays)]
+
+
+def sum_to(full, shape):
+    """The gradient of an argument of `shape` that broadcasts to full's shape: full summed over the leading dimensions the
+    argument lacks and over those where it has size 1."""
+    full, shape = np.asarray(full, np.float64), tuple(shape)
+    out = full.sum(axis=tuple(range(full.ndim - len(shape))))
+    axes = tuple(i for i, n in enumerate(shape) if n == 1 and out.shape[i] != 1)
+    return (out.sum(axis=axes, keepdims=True) if axes else out).reshape(shape)
+
+
+def di_problem(**kw):
+    """box_qp_ref.double_integrator(**kw) as a problem dict with its cold reference run (30 solves at most, the layer's default)."""
+    s, lo, hi, _ = ref.double_integrator(**kw)
+    H, Cm, g, c = ref.parts(s)
+    return as_problem(s, H, Cm, g, c, lo, hi, pdas(H, Cm, g, c, lo, hi, s.S), None)
+
+
+DI_TRIO = (dict(K=20, u_max=0.5, v_max=None), dict(K=20, u_max=0.5, v_max=0.57), dict(K=20, u_max=0.5, v_max=None, x0=(0.8, 0.3)))
+_DI = {}
+
+
+def di_trio():
+    """Three 2/1/20 double integrators: bounded controls alone, the velocity-bounded one whose second reduced system is
+    singular, bounded controls alone from another start."""
+    if "hard" not in _DI:
+        _DI["hard"] = [di_problem(**kw) for kw in DI_TRIO]
+    return _DI["hard"]
+
+
+def di_broadcast():
+    """double_integrator(K=8, u_max=0.5, v_max=None): every bound one number (the 0-d bounds of the layer's broadcast test)."""
+    if "k8" not in _DI:
+        _DI["k8"] = di_problem(K=8, u_max=0.5, v_max=None)
+    return _DI["k8"]

@@ -534,3 +534,69 @@ GRAD_K = (2, 3)
 LAYER_CASES = [(6, 3, 9), (14, 7, 3)]
 MIXED_F32_K = 3                                   # K of the fp32 cases on mixed problems, one per shape
 BATCH = D.BATCH
+
+
+# ---- the cases of tests/test_gpu_box_qp_layer_sweep.py -----------------------------------------------------------------------------
+SOFT_KEYS = D.KEYS + ("x_soft", "u_soft")
+LAYER_BATCHES = ("control", "constructed", "soft", "mixed")      # the batches whose systems freeze at different solves
+LAYER_SHAPE = (6, 3, 9)
+
+
+def soft_math_arrays(p):
+    """box_qp_pdas_ref.math_arrays of the problem plus x_soft [K, S] and u_soft [K-1, C] (zeros without "w"), in SOFT_KEYS' order."""
+    s = p["s"]
+    w = p["w"] if "w" in p else np.zeros(s.N)
+    return D.math_arrays(s, p["lo"], p["hi"]) + [np.ascontiguousarray(t) for t in P.split_states_controls(w, s.S, s.C, s.K)]
+
+
+def layer_batch(kind, count=5):
+    """(problems, soft): the first `count` problems of one of LAYER_BATCHES; soft: they carry weights."""
+    S, C, K = LAYER_SHAPE
+    if kind == "control":
+        return D.control_box(*D.BATCH[:3], count=count), False
+    if kind == "constructed":
+        return D.constructed_cold(S, C, K, count=count), False
+    if kind == "soft":
+        return soft_box(S, C, K, count=count), True
+    if kind == "mixed":
+        return mixed_box(S, C, K, count=count), True
+    raise KeyError(kind)
+
+
+def reference_grads(p, x, lam, xbar, lambar):
+    """The gradients through problem p's reference act at the point (x, lam): soft_grads with p["w"], box_qp_polish_ref.grads
+    without."""
+    s = p["s"]
+    if "w" in p:
+        return soft_grads(p["H"], p["Cm"], p["run"]["act"], p["w"], p["lo"], p["hi"], x, lam, xbar, lambar, s.S, s.C, s.K)
+    return P.grads(p["H"], p["Cm"], p["run"]["act"], x, lam, xbar, lambar, s.S, s.C, s.K)
+
+
+def di_soft_problem(w, **kw):
+    """box_qp_ref.double_integrator(**kw) with the weights w as a problem dict with its cold reference run."""
+    s, lo, hi, _ = ref.double_integrator(**kw)
+    H, Cm, g, c = ref.parts(s)
+    w = np.broadcast_to(np.asarray(w, np.float64), (s.N,)).copy()
+    return dict(D.as_problem(s, H, Cm, g, c, lo, hi, pdas_soft(H, Cm, g, c, lo, hi, w, s.S), None), w=w)
+
+
+_DI = {}
+
+
+def di_soft_trio():
+    """box_qp_pdas_ref.di_trio with per-system weights: the velocity-bounded problem with WEIGHT on its states, the same with
+    all weights 0 (it fails as the hard one does), the control-only one from the other start with weights 0."""
+    if "trio" not in _DI:
+        bad, other = D.DI_TRIO[1], D.DI_TRIO[2]
+        s = ref.double_integrator(**bad)[0]
+        _DI["trio"] = [di_soft_problem(state_weights(s), **bad), di_soft_problem(0.0, **bad), di_soft_problem(0.0, **other)]
+    return _DI["trio"]
+
+
+def di_soft_pair():
+    """Two velocity-bounded 2/1/20 double integrators with WEIGHT on their states, from two starts: one box for both (the
+    shared [K, S] bound of the layer's broadcast test)."""
+    if "pair" not in _DI:
+        s = ref.double_integrator(**D.DI_TRIO[1])[0]
+        _DI["pair"] = [di_soft_problem(state_weights(s), **D.DI_TRIO[1]), di_soft_problem(state_weights(s), **dict(D.DI_TRIO[1], x0=(0.8, 0.3)))]
+    return _DI["pair"]
