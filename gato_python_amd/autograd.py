@@ -48,6 +48,35 @@ def _common(tensors, what):
     return next(iter(devs)).index, next(iter(dts))
 
 
+def _check_blocks(args, what, qp=False):
+    """The seven math-shaped blocks of `what` (a dict by name): all tensors, Q [*, K, S, S] with at most one leading batch
+    dimension, R at least 2-D, every block of the shape that (K, S, C) and the batch set.  -> (batched, lead, K, S, C);
+    ValueError before any library call otherwise.  qp: the entry is a box QP (K >= 2, and its messages name Q and R together
+    and do not repeat the sizes; kkt_solve takes K = 1 and checks the sizes itself)."""
+    for name, t in args.items():
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{what}: {name} must be a torch.Tensor, got {type(t).__name__}")
+    Q, R = args["Q"], args["R"]
+    batched = Q.dim() == 4
+    bad_Q = Q.dim() not in (3, 4) or Q.shape[-1] != Q.shape[-2]
+    if qp and (bad_Q or R.dim() < 2):
+        raise ValueError(f"{what}: Q must be [*, K, S, S] and R [*, K-1, C, C], got {tuple(Q.shape)} and {tuple(R.shape)}")
+    if bad_Q:
+        raise ValueError(f"{what}: Q must be [*, K, S, S], got {tuple(Q.shape)}")
+    if R.dim() < 2:
+        raise ValueError(f"{what}: R must be [*, K-1, C, C], got {tuple(R.shape)}")
+    K, S, C = Q.shape[-3], Q.shape[-1], R.shape[-1]
+    if qp and K < 2:
+        raise ValueError(f"{what}: K = {K}: at least two knots")
+    lead = (Q.shape[0],) if batched else ()
+    sizes = "" if qp else f" (S = {S}, C = {C}, K = {K}{', batch %d' % lead[0] if lead else ''})"
+    want = dict(Q=(K, S, S), R=(K - 1, C, C), A=(K - 1, S, S), B=(K - 1, S, C), q=(K, S), r=(K - 1, C), c=(K, S))
+    for name, shp in want.items():
+        if tuple(args[name].shape) != lead + shp:
+            raise ValueError(f"{what}: {name} has shape {tuple(args[name].shape)}, want {lead + shp}{sizes}")
+    return batched, lead, K, S, C
+
+
 def _opts(rho, exit_tol, max_iters):
     return float(rho), float(exit_tol), int(max_iters)
 
@@ -110,8 +139,13 @@ def _pack(Q, R, A, B, q, r, c):
     Af = A.transpose(-1, -2).reshape(Bt, K - 1, S * S)
     Bf = B.transpose(-1, -2).reshape(Bt, K - 1, S * C)
     Cb = torch.cat([Af, Bf], 2).reshape(Bt, -1)
-    g = torch.cat([torch.cat([q[:, :K - 1], r], 2).reshape(Bt, -1), q[:, K - 1]], 1)
-    return Gb.contiguous(), Cb.contiguous(), g.contiguous(), c.reshape(Bt, -1).contiguous()
+    return Gb.contiguous(), Cb.contiguous(), _dz_layout(q, r), c.reshape(Bt, -1).contiguous()
+
+
+def _dz_layout(xv, uv):
+    """Per-knot values xv [Bt, K, S] and uv [Bt, K-1, C] -> the dz layout [Bt, N]: (x_k, u_k) per knot, then x_{K-1}."""
+    Bt, K = xv.shape[:2]
+    return torch.cat([torch.cat([xv[:, :K - 1], uv], 2).reshape(Bt, -1), xv[:, K - 1]], 1).contiguous()
 
 
 def kkt_solve(Q, R, A, B, q, r, c, *, rho, exit_tol, max_iters):
@@ -120,22 +154,7 @@ def kkt_solve(Q, R, A, B, q, r, c, *, rho, exit_tol, max_iters):
     raw values, -A and -B of the dynamics).  Returns flat lam [*, S K] and dz [*, N], as linsys_solve does.
     Q, R are taken as symmetric: their gradients are those of symmetric perturbations."""
     args = dict(Q=Q, R=R, A=A, B=B, q=q, r=r, c=c)
-    for name, t in args.items():
-        if not isinstance(t, torch.Tensor):
-            raise ValueError(f"kkt_solve: {name} must be a torch.Tensor, got {type(t).__name__}")
-    batched = Q.dim() == 4
-    if Q.dim() not in (3, 4) or Q.shape[-1] != Q.shape[-2]:
-        raise ValueError(f"kkt_solve: Q must be [*, K, S, S], got {tuple(Q.shape)}")
-    K, S = Q.shape[-3], Q.shape[-1]
-    if R.dim() < 2:
-        raise ValueError(f"kkt_solve: R must be [*, K-1, C, C], got {tuple(R.shape)}")
-    C = R.shape[-1]
-    lead = (Q.shape[0],) if batched else ()
-    want = dict(Q=(K, S, S), R=(K - 1, C, C), A=(K - 1, S, S), B=(K - 1, S, C), q=(K, S), r=(K - 1, C), c=(K, S))
-    for name, shp in want.items():
-        if tuple(args[name].shape) != lead + shp:
-            raise ValueError(f"kkt_solve: {name} has shape {tuple(args[name].shape)}, want {lead + shp} "
-                             f"(S = {S}, C = {C}, K = {K}{', batch %d' % lead[0] if lead else ''})")
+    batched, _, K, S, C = _check_blocks(args, "kkt_solve")
     if K < 1 or S < 1 or C < 1:
         raise ValueError(f"kkt_solve: S = {S}, C = {C}, K = {K} must all be >= 1")
     device, dtype = _common(args, "kkt_solve")

@@ -20,20 +20,45 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from .autograd import _adjoint, _common, _pack, _solver
+from .autograd import _adjoint, _check_blocks, _common, _dz_layout, _pack, _solver
 from .solver import BoxQPResult
 
 
-def _bound(v, shape, name, ref):
-    """A bound as a tensor of `shape` (a Python number or a tensor that broadcasts to it), in ref's dtype and device."""
+def _bound(v, shape, name, ref, what):
+    """A bound of the entry `what` as a tensor of `shape` (a Python number or a tensor that broadcasts to it), in ref's dtype
+    and device.  A tensor keeps its autograd history (expand sums the gradient of a broadcast bound); box_qp calls this under
+    torch.no_grad()."""
     if not isinstance(v, torch.Tensor):
         return torch.full(shape, float(v), dtype=ref.dtype, device=ref.device)
     if v.device != ref.device or v.dtype != ref.dtype:
-        raise ValueError(f"box_qp: {name} must be a {ref.dtype} tensor on {ref.device}, got {v.dtype} on {v.device}")
+        raise ValueError(f"{what}: {name} must be a {ref.dtype} tensor on {ref.device}, got {v.dtype} on {v.device}")
     try:
-        return v.detach().expand(shape)
+        return v.expand(shape)
     except RuntimeError:
-        raise ValueError(f"box_qp: {name} of shape {tuple(v.shape)} does not broadcast to {shape}") from None
+        raise ValueError(f"{what}: {name} of shape {tuple(v.shape)} does not broadcast to {shape}") from None
+
+
+def _prepare(what, blocks, x_lo, x_hi, u_lo, u_hi, x_soft, u_soft):
+    """Everything of box_qp and box_qp_layer (`what`) up to the solver call: the checks of the blocks (Q, R, A, B, q, r, c) and
+    the bounds, then (Gb, Cb, g, c) packed, lo, hi and the soft weights w (None unless x_soft or u_soft is given) in the dz
+    layout [Bt, N], and Bt, batched and the cached solver.  In torch ops, which torch differentiates."""
+    args = dict(zip("Q R A B q r c".split(), blocks))
+    batched, lead, K, S, C = _check_blocks(args, what, qp=True)
+    device, dtype = _common(args, what)
+    q, xs, us = args["q"], lead + (K, S), lead + (K - 1, C)
+    lift = (lambda t: t) if batched else (lambda t: t.unsqueeze(0))
+    xl, xh = (lift(_bound(v, xs, n, q, what)) for v, n in ((x_lo, "x_lo"), (x_hi, "x_hi")))
+    ul, uh = (lift(_bound(v, us, n, q, what)) for v, n in ((u_lo, "u_lo"), (u_hi, "u_hi")))
+    Gb, Cb, g, cc = _pack(*(lift(t) for t in blocks))
+    lo, hi = _dz_layout(xl, ul), _dz_layout(xh, uh)
+    Bt = g.shape[0]
+    sol = _solver(S, C, K, Bt, dtype, device)
+    w = None
+    if x_soft is not None or u_soft is not None:
+        xw = lift(_bound(0.0 if x_soft is None else x_soft, xs, "x_soft", q, what))
+        uw = lift(_bound(0.0 if u_soft is None else u_soft, us, "u_soft", q, what))
+        w = _dz_layout(xw, uw)
+    return Gb, Cb, g, cc, lo, hi, w, Bt, batched, sol
 
 
 def box_qp(Q, R, A, B, q, r, c, x_lo, x_hi, u_lo, u_hi, *, rho, exit_tol, max_iters, admm_rho=0.1, sigma=1e-6, alpha=1.6,
@@ -63,41 +88,10 @@ def box_qp(Q, R, A, B, q, r, c, x_lo, x_hi, u_lo, u_hi, *, rho, exit_tol, max_it
         raise ValueError("box_qp: x_soft and u_soft need method='pdas' without polish (ADMM and the polish have no soft bounds)")
     if int(polish_iters) < 1 or int(max_pdas_iters) < 1:
         raise ValueError("box_qp: polish_iters and max_pdas_iters must be at least 1")
-    args = dict(Q=Q, R=R, A=A, B=B, q=q, r=r, c=c)
-    for name, t in args.items():
-        if not isinstance(t, torch.Tensor):
-            raise ValueError(f"box_qp: {name} must be a torch.Tensor, got {type(t).__name__}")
-    batched = Q.dim() == 4
-    if Q.dim() not in (3, 4) or Q.shape[-1] != Q.shape[-2] or R.dim() < 2:
-        raise ValueError(f"box_qp: Q must be [*, K, S, S] and R [*, K-1, C, C], got {tuple(Q.shape)} and {tuple(R.shape)}")
-    K, S, C = Q.shape[-3], Q.shape[-1], R.shape[-1]
-    if K < 2:
-        raise ValueError(f"box_qp: K = {K}: at least two knots")
-    lead = (Q.shape[0],) if batched else ()
-    want = dict(Q=(K, S, S), R=(K - 1, C, C), A=(K - 1, S, S), B=(K - 1, S, C), q=(K, S), r=(K - 1, C), c=(K, S))
-    for name, shp in want.items():
-        if tuple(args[name].shape) != lead + shp:
-            raise ValueError(f"box_qp: {name} has shape {tuple(args[name].shape)}, want {lead + shp}")
-    _common(args, "box_qp")
     with torch.no_grad():
-        xl, xh = (_bound(v, lead + (K, S), n, q) for v, n in ((x_lo, "x_lo"), (x_hi, "x_hi")))
-        ul, uh = (_bound(v, lead + (K - 1, C), n, q) for v, n in ((u_lo, "u_lo"), (u_hi, "u_hi")))
-        if not batched:
-            Q, R, A, B, q, r, c, xl, xh, ul, uh = (t.unsqueeze(0) for t in (Q, R, A, B, q, r, c, xl, xh, ul, uh))
-        Bt = Q.shape[0]
-        Gb, Cb, g, cc = _pack(*(t.detach() for t in (Q, R, A, B, q, r, c)))
-        # the bounds in the dz layout: the same packing as q / r into g
-        lo = torch.cat([torch.cat([xl[:, :K - 1], ul], 2).reshape(Bt, -1), xl[:, K - 1]], 1).contiguous()
-        hi = torch.cat([torch.cat([xh[:, :K - 1], uh], 2).reshape(Bt, -1), xh[:, K - 1]], 1).contiguous()
-        sol = _solver(S, C, K, Bt, g.dtype, g.device.index)
+        Gb, Cb, g, cc, lo, hi, wt, Bt, batched, sol = _prepare("box_qp", (Q, R, A, B, q, r, c), x_lo, x_hi, u_lo, u_hi,
+                                                               x_soft, u_soft)
         if method == "pdas":
-            wt = None
-            if soft:
-                xw = _bound(0.0 if x_soft is None else x_soft, lead + (K, S), "x_soft", q)
-                uw = _bound(0.0 if u_soft is None else u_soft, lead + (K - 1, C), "u_soft", q)
-                if not batched:
-                    xw, uw = xw.unsqueeze(0), uw.unsqueeze(0)
-                wt = torch.cat([torch.cat([xw[:, :K - 1], uw], 2).reshape(Bt, -1), xw[:, K - 1]], 1).contiguous()
             act = None
             if warm is not None:
                 act = getattr(warm, "act", None)
@@ -153,17 +147,19 @@ def _shaped(res, sol, Bt, batched):
 
 # ---- the differentiable layer -----------------------------------------------------------------------------------------
 class _BoxQPLayer(torch.autograd.Function):
-    """(G_blocks [B, G_dense], C_blocks [B, C_dense], g [B, N], c [B, S K], lo, hi [B, N]) -> (x [B, N], lam [B, S K]) of the
-    polished solution; box[0] receives the BoxQPResult."""
+    """(G_blocks [B, G_dense], C_blocks [B, C_dense], g [B, N], c [B, S K], lo, hi [B, N], w [B, N] or None) -> (x [B, N],
+    lam [B, S K]) of the polished solution; box[0] receives the BoxQPResult.  w: the soft-bound weights, which make the
+    forward pass the active-set iteration; None: hard bounds, by ADMM and the polish or (opts has max_pdas_iters) by the
+    active-set iteration.  The backward pass is one re-solve of the last assembly (the reduced system; with w, the weights of
+    the soft-active variables on its diagonal) plus the gradient launches."""
 
     @staticmethod
-    def forward(ctx, Gb, Cb, g, c, lo, hi, sol, opts, box):
+    def forward(ctx, Gb, Cb, g, c, lo, hi, w, sol, opts, box):
         opts = dict(opts)
         pdas_iters = opts.pop("max_pdas_iters", None)      # set: the active-set iteration alone (method="pdas")
-        pol = dict(rho=opts["rho"], exit_tol=opts["exit_tol"], max_iters=opts["max_iters"], eps_abs=opts["eps_abs"],
-                   eps_rel=opts["eps_rel"])
-        if pdas_iters is not None:
-            res = sol.box_qp_pdas(Gb, Cb, g, c, lo, hi, max_pdas_iters=pdas_iters, **pol)
+        pol = {k: opts[k] for k in ("rho", "exit_tol", "max_iters", "eps_abs", "eps_rel")}
+        if w is not None or pdas_iters is not None:
+            res = sol.box_qp_pdas(Gb, Cb, g, c, lo, hi, max_pdas_iters=pdas_iters, soft_weight=w, **pol)
             act = res.act
         else:
             res = sol.box_qp(Gb, Cb, g, c, lo, hi, **opts)
@@ -173,18 +169,17 @@ class _BoxQPLayer(torch.autograd.Function):
         ctx.sol, ctx.pol, ctx.gen = sol, pol, sol.get_option("assembly_gen")
         ctx.codes = res.polished.cpu()
         x, lam = res.x.view(sol.batch, sol.N), res.lam.view(sol.batch, sol.sizes["sk"])
-        ctx.save_for_backward(Gb, Cb, g, c, lo, hi, act, x, lam)
+        ctx.save_for_backward(Gb, Cb, g, c, lo, hi, w, act, x, lam)
         ctx.set_materialize_grads(False)
         return x.clone(), lam.clone()
 
     @staticmethod
     @once_differentiable
     def backward(ctx, x_bar, lam_bar):
-        Gb, Cb, g, c, lo, hi, act, x, lam = ctx.saved_tensors
-        sol, pol = ctx.sol, ctx.pol
-        none = (None,) * 9
+        Gb, Cb, g, c, lo, hi, w, act, x, lam = ctx.saved_tensors
+        sol, pol, need = ctx.sol, ctx.pol, ctx.needs_input_grad
         if x_bar is None and lam_bar is None:
-            return none
+            return (None,) * 10
         xb = torch.zeros_like(x) if x_bar is None else x_bar.to(x.dtype).contiguous()
         lb = torch.zeros_like(lam) if lam_bar is None else lam_bar.to(lam.dtype).contiguous()
         live = (xb.ne(0).any(1) | lb.ne(0).any(1)).cpu()
@@ -195,76 +190,15 @@ class _BoxQPLayer(torch.autograd.Function):
                                f"(codes {ctx.codes[bad].tolist()}, _lib.POLISH_*): their x and lam are ADMM iterates (zeros "
                                "after method='pdas'), which have no gradient here")
         if not live.any():                   # every system's gradient is exactly zero: no re-solve (its PCG would form 0/0)
-            zero = lambda t, i: torch.zeros_like(t) if ctx.needs_input_grad[i] else None
-            return (zero(Gb, 0), zero(Cb, 1), zero(g, 2), zero(c, 3), zero(lo, 4), zero(hi, 5)) + (None,) * 3
-        if sol.get_option("assembly_gen") != ctx.gen or sol.get_option("assembly_valid") == 0:
-            # another forward replaced the assembly: rebuild the polish assembly from the saved active set (the assembly is a
-            # function of the inputs and act alone; the polished point goes to scratch copies)
-            res2 = torch.empty(sol.batch, 2, dtype=torch.float64, device=x.device)
-            scratch = BoxQPResult(x.clone(), x.clone(), x.clone(), lam.clone(), None,
-                                  torch.empty(sol.batch, dtype=torch.int32, device=x.device), res2[:, 0], res2[:, 1])
-            sol.box_qp_polish(Gb, Cb, g, c, lo, hi, act, scratch, **pol)
-        # the reduced system reads x_bar on the free coordinates only (Ginv' has zero active rows): with those masked, a
-        # system whose upstream gradient lives on its active set alone has a zero right-hand side, and _adjoint's zero
-        # test gives it a = beta = 0 instead of the PCG's 0/0
-        xf = torch.where(act.view_as(xb) != 0, torch.zeros((), dtype=xb.dtype, device=xb.device), xb)
-        a, beta = _adjoint(sol, lam, x, lb, xf, pol["exit_tol"], pol["max_iters"])
-        need = ctx.needs_input_grad
-        Gbar = torch.empty_like(Gb) if need[0] else None
-        Cbar = torch.empty_like(Cb) if need[1] else None
-        if Gbar is not None or Cbar is not None:
-            sol.kkt_grad_blocks(x, lam, a, beta, Gbar, Cbar)
-        lo_bar, hi_bar = (None, None)
-        if need[4] or need[5]:
-            lo_bar, hi_bar = (t.view_as(lo) for t in sol.box_qp_bound_grad(Gb, Cb, act, xb, a, beta))
-        keep = live.to(x.device)[:, None]
-        mask = lambda t: None if t is None else torch.where(keep, t, torch.zeros((), dtype=t.dtype, device=t.device))
-        return (mask(Gbar), mask(Cbar), mask(a) if need[2] else None, mask(beta) if need[3] else None,
-                mask(lo_bar) if need[4] else None, mask(hi_bar) if need[5] else None) + (None,) * 3
-
-
-class _BoxQPSoftLayer(torch.autograd.Function):
-    """_BoxQPLayer for the active-set iteration with soft bounds: (G_blocks, C_blocks, g, c, lo, hi, w [B, N]) -> (x, lam);
-    the backward pass is one re-solve of the last assembly (the weights of the soft-active variables on its diagonal) plus the
-    gradient launches (Solver.box_qp_soft_grad for lo, hi and w)."""
-
-    @staticmethod
-    def forward(ctx, Gb, Cb, g, c, lo, hi, w, sol, opts, box):
-        pol = dict(rho=opts["rho"], exit_tol=opts["exit_tol"], max_iters=opts["max_iters"], eps_abs=opts["eps_abs"],
-                   eps_rel=opts["eps_rel"])
-        res = sol.box_qp_pdas(Gb, Cb, g, c, lo, hi, max_pdas_iters=opts["max_pdas_iters"], soft_weight=w, **pol)
-        box.append(res)
-        ctx.sol, ctx.pol, ctx.gen = sol, pol, sol.get_option("assembly_gen")
-        ctx.codes = res.polished.cpu()
-        x, lam = res.x.view(sol.batch, sol.N), res.lam.view(sol.batch, sol.sizes["sk"])
-        ctx.save_for_backward(Gb, Cb, g, c, lo, hi, w, res.act, x, lam)
-        ctx.set_materialize_grads(False)
-        return x.clone(), lam.clone()
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, x_bar, lam_bar):
-        Gb, Cb, g, c, lo, hi, w, act, x, lam = ctx.saved_tensors
-        sol, pol = ctx.sol, ctx.pol
-        if x_bar is None and lam_bar is None:
-            return (None,) * 10
-        xb = torch.zeros_like(x) if x_bar is None else x_bar.to(x.dtype).contiguous()
-        lb = torch.zeros_like(lam) if lam_bar is None else lam_bar.to(lam.dtype).contiguous()
-        live = (xb.ne(0).any(1) | lb.ne(0).any(1)).cpu()
-        unpolished = live & (ctx.codes != _lib.POLISH_ACCEPTED)
-        if unpolished.any():
-            bad = unpolished.nonzero().flatten().tolist()
-            raise RuntimeError(f"box_qp_layer: systems {bad} have a nonzero upstream gradient but did not converge (codes "
-                               f"{ctx.codes[bad].tolist()}, _lib.POLISH_*): their x and lam are zeros, which have no gradient here")
-        need = ctx.needs_input_grad
-        if not live.any():                   # every system's gradient is exactly zero: no re-solve (its PCG would form 0/0)
             return tuple(torch.zeros_like(t) if need[i] else None for i, t in enumerate((Gb, Cb, g, c, lo, hi, w))) + (None,) * 3
         if sol.get_option("assembly_gen") != ctx.gen or sol.get_option("assembly_valid") == 0:
-            # another forward replaced the assembly: one solve from the saved act rebuilds it (a function of the inputs, the
-            # weights and act alone); its point goes to tensors of its own
-            sol.box_qp_pdas(Gb, Cb, g, c, lo, hi, max_pdas_iters=1, act=act, soft_weight=w, **pol)
-        # the reduced system reads x_bar off the hard-active set only (_BoxQPLayer.backward); a soft-active variable is in it
-        hard = (act.view_as(xb) != 0) & ~(w.view_as(xb) > 0)
+            _rebuild_assembly(sol, Gb, Cb, g, c, lo, hi, w, act, x, lam, pol)      # another forward replaced the assembly
+        # the reduced system reads x_bar off the hard-active set only (Ginv' has zero rows there; a soft-active variable is in
+        # the system): with those masked, a system whose upstream gradient lives on its hard-active set alone has a zero
+        # right-hand side, and _adjoint's zero test gives it a = beta = 0 instead of the PCG's 0/0
+        hard = act.view_as(xb) != 0
+        if w is not None:
+            hard = hard & ~(w.view_as(xb) > 0)
         xf = torch.where(hard, torch.zeros((), dtype=xb.dtype, device=xb.device), xb)
         a, beta = _adjoint(sol, lam, x, lb, xf, pol["exit_tol"], pol["max_iters"])
         Gbar = torch.empty_like(Gb) if need[0] else None
@@ -273,24 +207,28 @@ class _BoxQPSoftLayer(torch.autograd.Function):
             sol.kkt_grad_blocks(x, lam, a, beta, Gbar, Cbar)
         lo_bar = hi_bar = w_bar = None
         if need[4] or need[5] or need[6]:
-            lo_bar, hi_bar, w_bar = (t.view_as(lo) for t in sol.box_qp_soft_grad(Gb, Cb, act, w.contiguous(), lo, hi, x.contiguous(),
-                                                                                 xb, a.contiguous(), beta.contiguous()))
+            if w is None:
+                lo_bar, hi_bar = sol.box_qp_bound_grad(Gb, Cb, act, xb, a, beta)
+            else:
+                lo_bar, hi_bar, w_bar = sol.box_qp_soft_grad(Gb, Cb, act, w.contiguous(), lo, hi, x.contiguous(), xb,
+                                                             a.contiguous(), beta.contiguous())
         keep = live.to(x.device)[:, None]
-        mask = lambda t: None if t is None else torch.where(keep, t, torch.zeros((), dtype=t.dtype, device=t.device))
-        return (mask(Gbar), mask(Cbar), mask(a) if need[2] else None, mask(beta) if need[3] else None,
-                mask(lo_bar) if need[4] else None, mask(hi_bar) if need[5] else None, mask(w_bar) if need[6] else None) + (None,) * 3
+        mask = lambda i, t: None if t is None or not need[i] else torch.where(keep, t.view(sol.batch, -1),
+                                                                              torch.zeros((), dtype=t.dtype, device=t.device))
+        return tuple(mask(i, t) for i, t in enumerate((Gbar, Cbar, a, beta, lo_bar, hi_bar, w_bar))) + (None,) * 3
 
 
-def _bound_t(v, shape, name, ref):
-    """A bound as a tensor of `shape` that keeps its autograd history (expand sums the gradient of a broadcast bound)."""
-    if not isinstance(v, torch.Tensor):
-        return torch.full(shape, float(v), dtype=ref.dtype, device=ref.device)
-    if v.device != ref.device or v.dtype != ref.dtype:
-        raise ValueError(f"box_qp_layer: {name} must be a {ref.dtype} tensor on {ref.device}, got {v.dtype} on {v.device}")
-    try:
-        return v.expand(shape)
-    except RuntimeError:
-        raise ValueError(f"box_qp_layer: {name} of shape {tuple(v.shape)} does not broadcast to {shape}") from None
+def _rebuild_assembly(sol, Gb, Cb, g, c, lo, hi, w, act, x, lam, pol):
+    """The assembly a backward pass re-solves, from the saved active set (it is a function of the inputs, the weights and act
+    alone).  Hard bounds: the polish on act, its point into scratch copies; with weights w: one solve of the active-set
+    iteration from act, its point into tensors of its own."""
+    if w is not None:
+        sol.box_qp_pdas(Gb, Cb, g, c, lo, hi, max_pdas_iters=1, act=act, soft_weight=w, **pol)
+        return
+    res2 = torch.empty(sol.batch, 2, dtype=torch.float64, device=x.device)
+    scratch = BoxQPResult(x.clone(), x.clone(), x.clone(), lam.clone(), None,
+                          torch.empty(sol.batch, dtype=torch.int32, device=x.device), res2[:, 0], res2[:, 1])
+    sol.box_qp_polish(Gb, Cb, g, c, lo, hi, act, scratch, **pol)
 
 
 def box_qp_layer(Q, R, A, B, q, r, c, x_lo, x_hi, u_lo, u_hi, *, rho, exit_tol, max_iters, admm_rho=0.1, sigma=1e-6,
@@ -309,45 +247,14 @@ def box_qp_layer(Q, R, A, B, q, r, c, x_lo, x_hi, u_lo, u_hi, *, rho, exit_tol, 
     soft = x_soft is not None or u_soft is not None
     if soft and method != "pdas":
         raise ValueError("box_qp_layer: x_soft and u_soft need method='pdas' (ADMM and the polish have no soft bounds)")
-    args = dict(Q=Q, R=R, A=A, B=B, q=q, r=r, c=c)
-    for name, t in args.items():
-        if not isinstance(t, torch.Tensor):
-            raise ValueError(f"box_qp_layer: {name} must be a torch.Tensor, got {type(t).__name__}")
-    batched = Q.dim() == 4
-    if Q.dim() not in (3, 4) or Q.shape[-1] != Q.shape[-2] or R.dim() < 2:
-        raise ValueError(f"box_qp_layer: Q must be [*, K, S, S] and R [*, K-1, C, C], got {tuple(Q.shape)} and {tuple(R.shape)}")
-    K, S, C = Q.shape[-3], Q.shape[-1], R.shape[-1]
-    if K < 2:
-        raise ValueError(f"box_qp_layer: K = {K}: at least two knots")
-    lead = (Q.shape[0],) if batched else ()
-    want = dict(Q=(K, S, S), R=(K - 1, C, C), A=(K - 1, S, S), B=(K - 1, S, C), q=(K, S), r=(K - 1, C), c=(K, S))
-    for name, shp in want.items():
-        if tuple(args[name].shape) != lead + shp:
-            raise ValueError(f"box_qp_layer: {name} has shape {tuple(args[name].shape)}, want {lead + shp}")
-    device, dtype = _common(args, "box_qp_layer")
-    xl, xh = (_bound_t(v, lead + (K, S), n, q) for v, n in ((x_lo, "x_lo"), (x_hi, "x_hi")))
-    ul, uh = (_bound_t(v, lead + (K - 1, C), n, q) for v, n in ((u_lo, "u_lo"), (u_hi, "u_hi")))
-    if not batched:
-        Q, R, A, B, q, r, c, xl, xh, ul, uh = (t.unsqueeze(0) for t in (Q, R, A, B, q, r, c, xl, xh, ul, uh))
-    Bt = Q.shape[0]
-    Gb, Cb, g, cc = _pack(Q, R, A, B, q, r, c)
-    lo = torch.cat([torch.cat([xl[:, :K - 1], ul], 2).reshape(Bt, -1), xl[:, K - 1]], 1).contiguous()
-    hi = torch.cat([torch.cat([xh[:, :K - 1], uh], 2).reshape(Bt, -1), xh[:, K - 1]], 1).contiguous()
-    sol = _solver(S, C, K, Bt, dtype, device)
+    Gb, Cb, g, cc, lo, hi, wt, Bt, batched, sol = _prepare("box_qp_layer", (Q, R, A, B, q, r, c), x_lo, x_hi, u_lo, u_hi,
+                                                           x_soft, u_soft)
     opts = dict(rho=float(rho), exit_tol=float(exit_tol), max_iters=int(max_iters), admm_rho=admm_rho, sigma=sigma, alpha=alpha,
                 eps_abs=eps_abs, eps_rel=eps_rel, max_admm_iters=max_admm_iters, check_every=check_every)
     if method == "pdas":
         opts["max_pdas_iters"] = int(max_pdas_iters)
     box = []
-    if soft:
-        xw = _bound_t(0.0 if x_soft is None else x_soft, lead + (K, S), "x_soft", q)
-        uw = _bound_t(0.0 if u_soft is None else u_soft, lead + (K - 1, C), "u_soft", q)
-        if not batched:
-            xw, uw = xw.unsqueeze(0), uw.unsqueeze(0)
-        wt = torch.cat([torch.cat([xw[:, :K - 1], uw], 2).reshape(Bt, -1), xw[:, K - 1]], 1).contiguous()
-        x, lam = _BoxQPSoftLayer.apply(Gb, Cb, g, cc, lo, hi, wt, sol, opts, box)
-    else:
-        x, lam = _BoxQPLayer.apply(Gb, Cb, g, cc, lo, hi, sol, opts, box)
+    x, lam = _BoxQPLayer.apply(Gb, Cb, g, cc, lo, hi, wt, sol, opts, box)
     info = _shaped(box[0], sol, Bt, batched)
     info = BoxQPResult(*(t.detach().clone() for t in (info.x, info.z, info.y, info.lam, info.iters, info.status, info.res_prim,
                                                       info.res_dual, info.polished)),

@@ -209,20 +209,12 @@ class Solver:
         z = self.new(B * N) if z is None else z
         y = self.new(B * N) if y is None else y
         lam = self.new(B * sk) if lam is None else lam
-        for name, t, n in (("Gb", Gb, B * self.sizes["G_dense"]), ("Cb", Cb, B * self.sizes["C_dense"]), ("g", g, B * N),
-                           ("c", c, B * sk), ("lo", lo, B * N), ("hi", hi, B * N), ("x", x, B * N), ("z", z, B * N),
-                           ("y", y, B * N), ("lam", lam, B * sk)):
-            if t.numel() != n or t.dtype != self.dtype or not t.is_cuda or not t.is_contiguous():
-                raise ValueError(f"box_qp: {name} must be a contiguous {self.dtype} CUDA tensor of {n} entries, got "
-                                 f"{t.dtype} {tuple(t.shape)} on {t.device}")
+        self._check_vecs("box_qp", Gb=Gb, Cb=Cb, g=g, c=c, lo=lo, hi=hi, x=x, z=z, y=y, lam=lam)
         iters = self.new(B, torch.int32)
         status = self.new(B, torch.int32)
         res = self.new(2 * B, torch.float64)
-        p = _lib.BoxQpParams()
-        _lib.lib().gato_box_qp_default_params(ct.byref(p))
-        p.rho, p.admm_rho, p.sigma, p.alpha = float(rho), float(admm_rho), float(sigma), float(alpha)
-        p.eps_abs, p.eps_rel, p.exit_tol = float(eps_abs), float(eps_rel), float(exit_tol)
-        p.max_iters, p.max_admm_iters, p.check_every, p.warm = int(max_iters), int(max_admm_iters), int(check_every), int(bool(warm))
+        p = self._qp_params(rho, exit_tol, max_iters, eps_abs, eps_rel, admm_rho=admm_rho, sigma=sigma, alpha=alpha,
+                            max_admm_iters=max_admm_iters, check_every=check_every, warm=bool(warm))
         rc = _lib.lib().gato_box_qp_solve(self._h, _ptr(Gb), _ptr(Cb), _ptr(g), _ptr(c), _ptr(lo), _ptr(hi), ct.byref(p),
                                           _ptr(x), _ptr(z), _ptr(y), _ptr(lam), _ptr(iters), _ptr(status), _ptr(res),
                                           self._stream())
@@ -234,19 +226,33 @@ class Solver:
         return BoxQPResult(x, z, y, lam, iters, status, res[:, 0], res[:, 1])
 
     # ---- polish of a box QP and its bound gradients (gato_box_qp_polish) --------------------------
-    def _check_vecs(self, what, items):
-        for name, t, n, dt in items:
+    def _check_vecs(self, what, **tensors):
+        """ValueError unless every box-QP operand, given by its name, is a contiguous CUDA tensor of its size and dtype: Gb
+        [B G_dense], Cb [B C_dense], c / lam / beta [B S K], act [B N] int8, status [B] int32, every other one [B N]."""
+        per = dict(Gb=self.sizes["G_dense"], Cb=self.sizes["C_dense"], c=self.sizes["sk"], lam=self.sizes["sk"],
+                   beta=self.sizes["sk"], status=1)
+        ints = dict(act=torch.int8, status=torch.int32)
+        for name, t in tensors.items():
+            n, dt = self.batch * per.get(name, self.N), ints.get(name, self.dtype)
             if not isinstance(t, torch.Tensor) or t.numel() != n or t.dtype != dt or not t.is_cuda or not t.is_contiguous():
                 got = f"{t.dtype} {tuple(t.shape)} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
                 raise ValueError(f"{what}: {name} must be a contiguous {dt} CUDA tensor of {n} entries, got {got}")
 
+    @staticmethod
+    def _qp_params(rho, exit_tol, max_iters, eps_abs, eps_rel, **admm):
+        """A gato_box_qp_params: the library's defaults, the five values every box-QP entry reads, and the ADMM fields given."""
+        p = _lib.BoxQpParams()
+        _lib.lib().gato_box_qp_default_params(ct.byref(p))
+        p.rho, p.exit_tol, p.max_iters, p.eps_abs, p.eps_rel = float(rho), float(exit_tol), int(max_iters), float(eps_abs), float(eps_rel)
+        for name, v in admm.items():
+            setattr(p, name, type(getattr(p, name))(v))       # float or int, as the field is
+        return p
+
     def box_qp_active_set(self, z, y, lo, hi, act=None):
         """The active set of an ADMM result (z, y [B N]) for the box (lo, hi): int8 [B N], +1 upper, -1 lower (and lo ==
         hi), 0 free and on the states of x_0."""
-        BN = self.batch * self.N
-        act = self.new(BN, torch.int8) if act is None else act
-        self._check_vecs("box_qp_active_set", [(n, t, BN, self.dtype) for n, t in (("z", z), ("y", y), ("lo", lo), ("hi", hi))]
-                         + [("act", act, BN, torch.int8)])
+        act = self.new(self.batch * self.N, torch.int8) if act is None else act
+        self._check_vecs("box_qp_active_set", z=z, y=y, lo=lo, hi=hi, act=act)
         _lib.check(_lib.lib().gato_box_qp_active_set(self._h, _ptr(z), _ptr(y), _ptr(lo), _ptr(hi), _ptr(act), self._stream()))
         return act
 
@@ -256,20 +262,14 @@ class Solver:
         written.  Returns the polish codes int32 [B] (_lib.POLISH_*), also stored as result.polished.  Blocking.  Raises
         ValueError for an act that names an infinite bound or a state of x_0.  The solver's assembly is the reduced system
         afterwards (solve_rhs re-solves it)."""
-        B, N, sk = self.batch, self.N, self.sizes["sk"]
+        B = self.batch
         res = getattr(result.res_prim, "_base", None)        # the [B][2] residual array the two are views of
         if (res is None or res is not getattr(result.res_dual, "_base", None) or res.numel() != 2 * B
                 or result.res_prim.data_ptr() != res.data_ptr() or res.dtype != torch.float64 or not res.is_contiguous()):
             raise ValueError("box_qp_polish: result must be the BoxQPResult of Solver.box_qp on this solver")
-        self._check_vecs("box_qp_polish", [
-            ("Gb", Gb, B * self.sizes["G_dense"], self.dtype), ("Cb", Cb, B * self.sizes["C_dense"], self.dtype),
-            ("g", g, B * N, self.dtype), ("c", c, B * sk, self.dtype), ("lo", lo, B * N, self.dtype),
-            ("hi", hi, B * N, self.dtype), ("act", act, B * N, torch.int8), ("x", result.x, B * N, self.dtype),
-            ("z", result.z, B * N, self.dtype), ("y", result.y, B * N, self.dtype), ("lam", result.lam, B * sk, self.dtype),
-            ("status", result.status, B, torch.int32)])
-        p = _lib.BoxQpParams()
-        _lib.lib().gato_box_qp_default_params(ct.byref(p))
-        p.rho, p.eps_abs, p.eps_rel, p.exit_tol, p.max_iters = float(rho), float(eps_abs), float(eps_rel), float(exit_tol), int(max_iters)
+        self._check_vecs("box_qp_polish", Gb=Gb, Cb=Cb, g=g, c=c, lo=lo, hi=hi, act=act, x=result.x, z=result.z, y=result.y,
+                         lam=result.lam, status=result.status)
+        p = self._qp_params(rho, exit_tol, max_iters, eps_abs, eps_rel)
         codes = self.new(B, torch.int32)
         rc = _lib.lib().gato_box_qp_polish(self._h, _ptr(Gb), _ptr(Cb), _ptr(g), _ptr(c), _ptr(lo), _ptr(hi), _ptr(act), ct.byref(p),
                                            _ptr(result.x), _ptr(result.z), _ptr(result.y), _ptr(result.lam), _ptr(result.status),
@@ -303,21 +303,15 @@ class Solver:
         if act is None:
             act = torch.zeros(B * N, dtype=torch.int8, device=f"cuda:{self.device}")
         else:
-            self._check_vecs("box_qp_pdas", [("act", act, B * N, torch.int8)])
+            self._check_vecs("box_qp_pdas", act=act)
             act = act.detach().reshape(-1).clone()
-        self._check_vecs("box_qp_pdas", [
-            ("Gb", Gb, B * self.sizes["G_dense"], self.dtype), ("Cb", Cb, B * self.sizes["C_dense"], self.dtype),
-            ("g", g, B * N, self.dtype), ("c", c, B * sk, self.dtype), ("lo", lo, B * N, self.dtype),
-            ("hi", hi, B * N, self.dtype), ("x", x, B * N, self.dtype), ("z", z, B * N, self.dtype), ("y", y, B * N, self.dtype),
-            ("lam", lam, B * sk, self.dtype)])
+        self._check_vecs("box_qp_pdas", Gb=Gb, Cb=Cb, g=g, c=c, lo=lo, hi=hi, x=x, z=z, y=y, lam=lam)
         if soft_weight is not None:
-            self._check_vecs("box_qp_pdas", [("soft_weight", soft_weight, B * N, self.dtype)])
+            self._check_vecs("box_qp_pdas", soft_weight=soft_weight)
         iters = torch.zeros(B, dtype=torch.int32, device=act.device)
         status = self.new(B, torch.int32)
         res = torch.zeros(2 * B, dtype=torch.float64, device=act.device)
-        p = _lib.BoxQpParams()
-        _lib.lib().gato_box_qp_default_params(ct.byref(p))
-        p.rho, p.eps_abs, p.eps_rel, p.exit_tol, p.max_iters = float(rho), float(eps_abs), float(eps_rel), float(exit_tol), int(max_iters)
+        p = self._qp_params(rho, exit_tol, max_iters, eps_abs, eps_rel)
         tail = (ct.byref(p), int(max_pdas_iters), _ptr(x), _ptr(z), _ptr(y), _ptr(lam), _ptr(iters), _ptr(status), _ptr(res),
                 self._stream())
         if soft_weight is None:
@@ -336,46 +330,39 @@ class Solver:
                             torch.where(status == _lib.QP_NONFINITE, _lib.POLISH_NONFINITE, _lib.POLISH_REJECTED)).to(torch.int32)
         return BoxQPResult(x, z, y, lam, iters, status, res[:, 0], res[:, 1], codes, act)
 
+    def _bound_grads(self, entry, what, Gb, Cb, act, soft, xbar, a, beta, **bars):
+        """The body of the two bound-gradient methods: allocates the outputs bars (by name) that are None, checks every
+        operand as `what`, calls the C entry and returns the outputs.  soft: the operands only the soft entry takes, in its
+        order (soft_weight, lo, hi, x; a soft_weight of None goes as a null pointer), or () for the entry without weights."""
+        bars = {name: self.new(self.batch * self.N) if t is None else t for name, t in bars.items()}
+        own = {name: t for name, t in zip(("soft_weight", "lo", "hi", "x"), soft) if name != "soft_weight" or t is not None}
+        self._check_vecs(what, Gb=Gb, Cb=Cb, act=act, **own, xbar=xbar, a=a, beta=beta, **bars)
+        _lib.check(entry(self._h, _ptr(Gb), _ptr(Cb), _ptr(act), *map(_ptr, soft), _ptr(xbar), _ptr(a), _ptr(beta),
+                         *map(_ptr, bars.values()), self._stream()))
+        return tuple(bars.values())
+
     def box_qp_bound_grad(self, Gb, Cb, act, xbar, a, beta, lo_bar=None, hi_bar=None):
         """(lo_bar, hi_bar) [B N] of a polished solution from its active set, the upstream x_bar and the adjoint (a, beta) of
         the reduced system (solve_rhs after the polish)."""
-        B, N, sk = self.batch, self.N, self.sizes["sk"]
-        lo_bar = self.new(B * N) if lo_bar is None else lo_bar
-        hi_bar = self.new(B * N) if hi_bar is None else hi_bar
-        self._check_vecs("box_qp_bound_grad", [
-            ("Gb", Gb, B * self.sizes["G_dense"], self.dtype), ("Cb", Cb, B * self.sizes["C_dense"], self.dtype),
-            ("act", act, B * N, torch.int8), ("xbar", xbar, B * N, self.dtype), ("a", a, B * N, self.dtype),
-            ("beta", beta, B * sk, self.dtype), ("lo_bar", lo_bar, B * N, self.dtype), ("hi_bar", hi_bar, B * N, self.dtype)])
-        _lib.check(_lib.lib().gato_box_qp_bound_grad(self._h, _ptr(Gb), _ptr(Cb), _ptr(act), _ptr(xbar), _ptr(a), _ptr(beta),
-                                                     _ptr(lo_bar), _ptr(hi_bar), self._stream()))
-        return lo_bar, hi_bar
+        return self._bound_grads(_lib.lib().gato_box_qp_bound_grad, "box_qp_bound_grad", Gb, Cb, act, (), xbar, a, beta,
+                                 lo_bar=lo_bar, hi_bar=hi_bar)
 
     def box_qp_soft_grad(self, Gb, Cb, act, soft_weight, lo, hi, x, xbar, a, beta, lo_bar=None, hi_bar=None, w_bar=None):
         """(lo_bar, hi_bar, w_bar) [B N] of a converged box_qp_pdas(soft_weight=) point (gato_box_qp_soft_grad) from its act,
         the upstream x_bar and the adjoint (a, beta) of its last assembly (solve_rhs after the call): the hard formula of
         box_qp_bound_grad on the hard-active set, w_i a_i and a_i (b_i - x_i) on the soft-active one, 0 elsewhere.
         soft_weight None: all hard."""
-        B, N, sk = self.batch, self.N, self.sizes["sk"]
-        lo_bar = self.new(B * N) if lo_bar is None else lo_bar
-        hi_bar = self.new(B * N) if hi_bar is None else hi_bar
-        w_bar = self.new(B * N) if w_bar is None else w_bar
-        vecs = [("lo", lo), ("hi", hi), ("x", x), ("xbar", xbar), ("a", a), ("lo_bar", lo_bar), ("hi_bar", hi_bar), ("w_bar", w_bar)]
-        if soft_weight is not None:
-            vecs.append(("soft_weight", soft_weight))
-        self._check_vecs("box_qp_soft_grad", [
-            ("Gb", Gb, B * self.sizes["G_dense"], self.dtype), ("Cb", Cb, B * self.sizes["C_dense"], self.dtype),
-            ("act", act, B * N, torch.int8), ("beta", beta, B * sk, self.dtype)] + [(n, t, B * N, self.dtype) for n, t in vecs])
-        wp = None if soft_weight is None else _ptr(soft_weight)
-        _lib.check(_lib.lib().gato_box_qp_soft_grad(self._h, _ptr(Gb), _ptr(Cb), _ptr(act), wp, _ptr(lo), _ptr(hi), _ptr(x), _ptr(xbar),
-                                                    _ptr(a), _ptr(beta), _ptr(lo_bar), _ptr(hi_bar), _ptr(w_bar), self._stream()))
-        return lo_bar, hi_bar, w_bar
+        return self._bound_grads(_lib.lib().gato_box_qp_soft_grad, "box_qp_soft_grad", Gb, Cb, act, (soft_weight, lo, hi, x),
+                                 xbar, a, beta, lo_bar=lo_bar, hi_bar=hi_bar, w_bar=w_bar)
 
     def box_qp_pcg_iters(self):
         """PCG iterations of all x-steps of the latest box_qp call, per system (host int array)."""
-        out = np.zeros(self.batch, np.int32)
+        return self._read_device(self.buffer_ptr(12), np.zeros(self.batch, np.int32))
+
+    def _read_device(self, ptr, out):
+        """Fill the host array out from device memory at ptr, after everything queued on the device has finished."""
         torch.cuda.synchronize(self.device)
-        rc = ct.CDLL("libamdhip64.so").hipMemcpy(out.ctypes.data_as(ct.c_void_p), ct.c_void_p(self.buffer_ptr(12)),
-                                                 ct.c_size_t(out.nbytes), 2)
+        rc = ct.CDLL("libamdhip64.so").hipMemcpy(out.ctypes.data_as(ct.c_void_p), ct.c_void_p(ptr), ct.c_size_t(out.nbytes), 2)
         if rc != 0:
             raise RuntimeError(f"hipMemcpy failed: {rc}")
         return out
@@ -383,13 +370,7 @@ class Solver:
     def read_rhs_gamma(self, R: int):
         """Host copy of the re-solve's gamma [B][R][S K] (buffer 11) after a re-solve of R right-hand sides."""
         n = self.batch * int(R) * self.sizes["sk"]
-        out = np.empty(n, self.np_dtype)
-        torch.cuda.synchronize(self.device)
-        rc = ct.CDLL("libamdhip64.so").hipMemcpy(out.ctypes.data_as(ct.c_void_p), ct.c_void_p(self.buffer_ptr(11)),
-                                                 ct.c_size_t(out.nbytes), 2)
-        if rc != 0:
-            raise RuntimeError(f"hipMemcpy failed: {rc}")
-        return out
+        return self._read_device(self.buffer_ptr(11), np.empty(n, self.np_dtype))
 
     def upload_batch(self, systems):
         """list of KKTSystem with identical sparsity -> device tensors in linsys_batched() argument order."""
@@ -415,14 +396,7 @@ class Solver:
         n = {0: self.sizes["G_dense"], 1: self.sizes["C_dense"], 2: self.sizes["G_dense"], 3: self.sizes["bd"],
              4: self.sizes["bd"], 5: self.sizes["sk"], 6: self.sizes["sk"], 7: self.N}[which] * self.batch
         out = np.empty(n, self.np_dtype)
-        if n == 0:
-            return out
-        torch.cuda.synchronize(self.device)
-        rc = ct.CDLL("libamdhip64.so").hipMemcpy(out.ctypes.data_as(ct.c_void_p), ct.c_void_p(self.buffer_ptr(which)),
-                                                 ct.c_size_t(out.nbytes), 2)
-        if rc != 0:
-            raise RuntimeError(f"hipMemcpy failed: {rc}")
-        return out
+        return out if n == 0 else self._read_device(self.buffer_ptr(which), out)
 
     def pcg_last_ms(self) -> float:
         """Device time of the last PCG launch (needs set_option("time_pcg", 1))."""
@@ -438,14 +412,7 @@ class Solver:
 
     def eta_history(self, n: int):
         """eta = r . Pinv r after the initial step and after each of the first n iterations (needs record_eta=1)."""
-        ptr = int(_lib.lib().gato_solver_buffer(self._h, 10))
-        buf = (ct.c_double * (n + 1))()
-        hip = ct.CDLL("libamdhip64.so")
-        torch.cuda.synchronize(self.device)
-        rc = hip.hipMemcpy(buf, ct.c_void_p(ptr), 8 * (n + 1), 2)
-        if rc != 0:
-            raise RuntimeError(f"hipMemcpy failed: {rc}")
-        return np.frombuffer(buf, dtype=np.float64).copy()
+        return self._read_device(self.buffer_ptr(10), np.empty(n + 1, np.float64))
 
     def check_status(self):
         """Raises GatoError(ETIMEOUT) if a hand-off of any PCG launch since the last check timed out."""

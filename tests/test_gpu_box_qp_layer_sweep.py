@@ -1,5 +1,5 @@
 """box_qp_layer(method="pdas"), with and without soft bounds, where its backward pass branches (gato_python_amd/qp.py,
-_BoxQPLayer and _BoxQPSoftLayer; DESIGN.md sections 3.8 - 3.10): batches whose systems freeze at different solves, assemblies
+_BoxQPLayer without and with weights; DESIGN.md sections 3.8 - 3.10): batches whose systems freeze at different solves, assemblies
 another call replaced before the backward pass, one system of a batch that does not converge, subsets of the inputs and of the
 outputs, and bounds and weights that broadcast.  Every gradient is compared with the numpy references - box_qp_polish_ref.grads
 for hard bounds, box_qp_soft_ref.soft_grads for soft ones - on the reference run's final act and the device's x and lam; the bar
