@@ -34,7 +34,7 @@ SYMBOLS = [
     "gato_solver_reserve_rhs", "gato_solve_rhs", "gato_linsys_resolve_f32", "gato_linsys_resolve_f64",
     "gato_kkt_grad_blocks", "gato_kkt_grad_csr", "gato_box_qp_default_params", "gato_box_qp_solve",
     "gato_box_qp_active_set", "gato_box_qp_polish", "gato_box_qp_bound_grad", "gato_box_qp_pdas",
-    "gato_box_qp_pdas_soft", "gato_box_qp_soft_grad",
+    "gato_box_qp_pdas_soft", "gato_box_qp_soft_grad", "gato_box_qp_pdas_huber", "gato_box_qp_huber_grad",
 ]
 
 
@@ -129,6 +129,8 @@ def lib() -> ct.CDLL:
         L.gato_box_qp_pdas.argtypes = [vp] * 8 + [ct.POINTER(BoxQpParams), i] + [vp] * 8
         L.gato_box_qp_pdas_soft.argtypes = [vp] * 9 + [ct.POINTER(BoxQpParams), i] + [vp] * 8
         L.gato_box_qp_soft_grad.argtypes = [vp] * 15
+        L.gato_box_qp_pdas_huber.argtypes = [vp] * 10 + [ct.POINTER(BoxQpParams), i] + [vp] * 8
+        L.gato_box_qp_huber_grad.argtypes = [vp] * 17
         f = ct.c_float
         L.gato_linsys_solve_f32.argtypes = [ip, i, ip, vp, i, ip, i, ip, vp, i, vp, i, vp, i, vp,
                                             i, i, i, i, f, i, i, f, vp, vp, vp, vp]

@@ -342,6 +342,7 @@ struct PolishArgs {
     const void *G, *Cd, *g, *c, *lo, *hi;   // the caller's blocks (G without rho, C raw) and vectors; never written
     const signed char *act;
     const void *w;                          // [B][N] soft-bound weights, 0 = a hard bound; nullptr = all hard
+    const void *cap;                        // [B][N] caps of the penalty force, read where w > 0 (+inf: none); nullptr = no caps
     const void *Gd;                         // prepare: G + rho I (the solver's G_dense)
     void *Ginv;                             // prepare: the inverses with the active rows and columns zero (the solver's Ginv)
     void *gp, *cp;                          // prepare: the reduced system's right-hand side g' [B][N], c' [B][S K]
@@ -367,6 +368,8 @@ struct BoundGradArgs {
     const void *w, *lo, *hi, *x;            // w may be nullptr (all hard): then lo, hi and x are not read
     const void *xbar, *adz, *beta;          // the upstream gradient and the adjoint [a; beta]
     void *lo_bar, *hi_bar, *w_bar;          // [B][N]; w_bar may be nullptr (not written)
+    const void *cap;                        // the capped entry only: [B][N] caps; nullptr = none (no variable is saturated)
+    void *cap_bar;                          // [B][N], the capped entry only; nullptr: not written
 };
 template <typename T, int S, int C>
 int launch_qp_bound_grad(const Dims &d, const BoundGradArgs &a, hipStream_t st);

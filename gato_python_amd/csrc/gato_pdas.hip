@@ -15,8 +15,9 @@ constexpr int NSL = GATO_POLISH_NSLOT;
 
 // The first launch of a call: a NaN bound, lo > hi or a weight that is NaN, negative or +inf marks the system BAD_BOUNDS, a start
 // act the reduced system cannot take (polish_prepare_kernel's rule) BAD_ACTIVE; ctr = {B live systems, waves that saw a bad bound
-// or weight, waves that saw a bad act}.
-template <typename T, int S, int C, bool W>
+// or weight, waves that saw a bad act}.  With caps (W = BOUNDS_CAPPED): a cap that is NaN or negative, read only where the weight
+// is positive, is BAD_BOUNDS too, and a start act of +-2 is taken where bad_active_capped allows it.
+template <typename T, int S, int C, int W>
 __global__ __launch_bounds__(WAVE) void pdas_check_kernel(PdasArgs a, int K, int B, BatchStride bs)
 {
     constexpr int n = S + C;
@@ -24,6 +25,7 @@ __global__ __launch_bounds__(WAVE) void pdas_check_kernel(PdasArgs a, int K, int
     const size_t sys = blockIdx.y;
     const T *lo = (const T *)a.p.lo + sys * bs.n, *hi = (const T *)a.p.hi + sys * bs.n;
     const T *w = sys_weights<T, W>(a.p.w, sys, bs);
+    const T *cap = sys_caps<T, W>(a.p.cap, sys, bs);
     const signed char *act = a.p.act + sys * bs.n;
     if (blockIdx.x == 0 && blockIdx.y == 0 && lane == 0) a.ctr[0] = B;
     int bad_b = 0, bad_a = 0;
@@ -33,6 +35,11 @@ __global__ __launch_bounds__(WAVE) void pdas_check_kernel(PdasArgs a, int K, int
             const T l = lo[v], h = hi[v], wi = w ? w[v] : (T)0;
             const signed char ai = act[v];
             if (l != l || h != h || l > h || !(wi >= (T)0) || !__builtin_isfinite(wi)) bad_b = 1;
+            else if constexpr (W == BOUNDS_CAPPED) {
+                const T mi = cap && wi > (T)0 ? cap[v] : (T)INFINITY;
+                if (!(mi >= (T)0)) bad_b = 1;
+                else if (bad_active_capped(ai, bound_of(ai, l, h), k == 0 && lane < S, wi, mi)) bad_a = 1;
+            }
             else if (bad_active(ai, bound_of(ai, l, h), k == 0 && lane < S)) bad_a = 1;
         }
     }
@@ -49,8 +56,10 @@ __global__ __launch_bounds__(WAVE) void pdas_check_kernel(PdasArgs a, int K, int
 //   active lower: kept while y < 0;  0 otherwise
 // - exact comparisons: near-ties are the acceptance test's, which runs first - and the count of entries where act' differs
 // from act (an integer atomicAdd per wave that saw a change).  A soft variable (weight > 0) takes the rule of a free one, from x
-// alone, whatever its act was.  A system frozen before this solve is only marked.
-template <typename T, int S, int C, bool W>
+// alone, whatever its act was.  A soft variable with a finite cap m (W = BOUNDS_CAPPED) is saturated, +-2,
+// where the product w (x - b) passes the cap: +2 where w (x - hi) > m, else +1 where x > hi; -2 where -(w (x - lo)) > m, else -1 where
+// x < lo; lo == hi: +2, -2 by the same products, else -1.  A system frozen before this solve is only marked.
+template <typename T, int S, int C, int W>
 __global__ __launch_bounds__(WAVE) void pdas_step_kernel(PdasArgs a, int it, int K, BatchStride bs)
 {
     constexpr int n = S + C;
@@ -75,7 +84,23 @@ __global__ __launch_bounds__(WAVE) void pdas_step_kernel(PdasArgs a, int it, int
             const size_t j = (size_t)k * n + lane;
             const bool soft = p.w && p.w[j] > (T)0;
             signed char a2;
+            bool capped = false;
+            T mi = (T)0;
+            if constexpr (W == BOUNDS_CAPPED) {
+                if (soft && p.cap) {
+                    mi = p.cap[j];
+                    capped = __builtin_isfinite(mi);
+                }
+            }
             if (k == 0 && lane < S) a2 = 0;
+            else if (capped) {
+                const T fh = p.w[j] * (v.x - v.hi), fl = p.w[j] * (v.x - v.lo);
+                if (v.lo == v.hi) a2 = fh > mi ? 2 : (-fh > mi ? -2 : -1);
+                else if (fh > mi) a2 = 2;
+                else if (v.x > v.hi) a2 = 1;
+                else if (-fl > mi) a2 = -2;
+                else a2 = v.x < v.lo ? -1 : 0;
+            }
             else if (v.lo == v.hi) a2 = -1;
             else if (v.act == 0 || soft) a2 = v.x > v.hi ? 1 : (v.x < v.lo ? -1 : 0);
             else if (v.act > 0) a2 = v.y > (T)0 ? 1 : 0;
@@ -142,7 +167,9 @@ template <typename T, int S, int C>
 int launch_pdas_check(const Dims &d, const PdasArgs &a, hipStream_t st)
 {
     if (d.B < 1 || d.B > 65535) { set_error("pdas_check: B = %d", d.B); return GATO_EINVAL; }
-    const auto kernel = a.p.w ? pdas_check_kernel<T, S, C, true> : pdas_check_kernel<T, S, C, false>;
+    const int form = bounds_form(a.p.w, a.p.cap);
+    const auto kernel = form == BOUNDS_CAPPED ? pdas_check_kernel<T, S, C, BOUNDS_CAPPED>
+                        : form == BOUNDS_SOFT ? pdas_check_kernel<T, S, C, BOUNDS_SOFT> : pdas_check_kernel<T, S, C, BOUNDS_HARD>;
     hipLaunchKernelGGL(kernel, dim3(knot_grid(d.K), d.B), dim3(WAVE), 0, st, a, d.K, d.B, batch_stride(d));
     GATO_HIP_CHECK(hipGetLastError());
     return GATO_OK;
@@ -152,7 +179,9 @@ template <typename T, int S, int C>
 int launch_pdas_step(const Dims &d, const PdasArgs &a, int it, hipStream_t st)
 {
     if (d.B < 1 || d.B > 65535) { set_error("pdas_step: B = %d", d.B); return GATO_EINVAL; }
-    const auto kernel = a.p.w ? pdas_step_kernel<T, S, C, true> : pdas_step_kernel<T, S, C, false>;
+    const int form = bounds_form(a.p.w, a.p.cap);
+    const auto kernel = form == BOUNDS_CAPPED ? pdas_step_kernel<T, S, C, BOUNDS_CAPPED>
+                        : form == BOUNDS_SOFT ? pdas_step_kernel<T, S, C, BOUNDS_SOFT> : pdas_step_kernel<T, S, C, BOUNDS_HARD>;
     hipLaunchKernelGGL(kernel, dim3(knot_grid(d.K), d.B), dim3(WAVE), 0, st, a, it, d.K, batch_stride(d));
     GATO_HIP_CHECK(hipGetLastError());
     return GATO_OK;

@@ -46,19 +46,23 @@ __global__ __launch_bounds__(WAVE) void qp_active_kernel(const T *__restrict__ z
 // A soft-active variable keeps its row and column: the diagonal entry the Gauss-Jordan sees gains w_i, g'_i gains w_i b_i
 // (before the hard shift of its row), and c' does not see it.
 // An act that is not -1 / 0 / 1, names an infinite bound or a state of x_0 counts the system in *bad and sets polish = 3.
-template <typename T, int S, int C, bool W>
+// With caps (W = BOUNDS_CAPPED) a saturated variable (act = +-2, s its sign) is free: no diagonal term, no
+// shift, g'_i = g_i - s m_i; +-2 is a bad act only where bad_active_capped says so.
+template <typename T, int S, int C, int W>
 __global__ __launch_bounds__(WAVE) void polish_prepare_kernel(PolishArgs a, int K, BatchStride bs)
 {
     constexpr int n = S + C, SS = S * S, CC = C * C, SN = S * n;
     __shared__ T sb[2][n];                   // bound values of knots k-1 (0) and k (1), 0 off the hard-active set
     __shared__ int sa[2][n];                 // hard-active
     __shared__ T sw[n], ss[n];               // W only: knot k's w_i on the soft-active set (0 elsewhere) and the bound there
+    __shared__ T sm[W == BOUNDS_CAPPED ? n : 1];     // caps only: knot k's -s m_i on the saturated set (0 elsewhere)
     const int lane = threadIdx.x;
     const size_t sys = blockIdx.y;
     const T *Gd = (const T *)a.Gd + sys * bs.g, *Cd = (const T *)a.Cd + sys * bs.c;
     const T *g = (const T *)a.g + sys * bs.n, *c = (const T *)a.c + sys * bs.sk;
     const T *lo = (const T *)a.lo + sys * bs.n, *hi = (const T *)a.hi + sys * bs.n;
     const T *w = sys_weights<T, W>(a.w, sys, bs);
+    const T *cap = sys_caps<T, W>(a.cap, sys, bs);
     const signed char *act = a.act + sys * bs.n;
     T *Gi = (T *)a.Ginv + sys * bs.g, *gp = (T *)a.gp + sys * bs.n, *cp = (T *)a.cp + sys * bs.sk;
     int bad = 0;
@@ -71,21 +75,29 @@ __global__ __launch_bounds__(WAVE) void polish_prepare_kernel(PolishArgs a, int 
             for (int h = 0; h < 2; ++h) {
                 const int kk = k - 1 + h;
                 int on = 0;
-                T b = (T)0, wi = (T)0, bsoft = (T)0;
+                T b = (T)0, wi = (T)0, bsoft = (T)0, push = (T)0;
                 if (kk >= 0 && lane < (kk < K - 1 ? n : S)) {
                     const size_t v = (size_t)kk * n + lane;
                     const signed char ai = act[v];
                     b = bound_of(ai, lo[v], hi[v]);
-                    if (h == 1 && bad_active(ai, b, kk == 0 && lane < S)) bad = 1;
+                    if constexpr (W == BOUNDS_CAPPED) {
+                        if (h == 1 && bad_active_capped(ai, b, kk == 0 && lane < S, w ? w[v] : (T)0, cap ? cap[v] : (T)INFINITY)) bad = 1;
+                    } else {
+                        if (h == 1 && bad_active(ai, b, kk == 0 && lane < S)) bad = 1;
+                    }
                     if (soft_active(ai, w, v)) {
-                        wi = w[v];
-                        bsoft = b;
+                        if (W == BOUNDS_CAPPED && cap && saturated(ai)) push = ai > 0 ? -cap[v] : cap[v];
+                        else {
+                            wi = w[v];
+                            bsoft = b;
+                        }
                         b = (T)0;
                     } else on = ai != 0;
                 }
                 sa[h][lane] = on;
                 sb[h][lane] = b;
                 if (W && h == 1) { sw[lane] = wi; ss[lane] = bsoft; }
+                if (W == BOUNDS_CAPPED && h == 1) sm[lane] = push;
             }
         }
         __syncthreads();
@@ -136,6 +148,7 @@ __global__ __launch_bounds__(WAVE) void polish_prepare_kernel(PolishArgs a, int 
             if (sa[1][lane]) t = (T)0;
             else {
                 if (W && sw[lane] > (T)0) t = fmaT(sw[lane], ss[lane], t);
+                if (W == BOUNDS_CAPPED) t += sm[lane];
                 if (lane < S) {
                     for (int j = 0; j < S; ++j)
                         if (sa[1][j]) t = fmaT(-Gd[gb + j * S + lane], sb[1][j], t);
@@ -171,7 +184,7 @@ __global__ __launch_bounds__(WAVE) void polish_finish_kernel(PolishArgs a, int K
     __shared__ PointLds<T, S, C> lds;
     const int lane = threadIdx.x;
     const size_t sys = blockIdx.y;
-    const PointSys<T> p = point_sys<T, false>(a, sys, bs);                   // the polish has no weights
+    const PointSys<T> p = point_sys<T, BOUNDS_HARD>(a, sys, bs);             // the polish has no weights
     unsigned long long m[NSL];
 #pragma unroll
     for (int f = 0; f < NSL; ++f) m[f] = 0;
@@ -201,8 +214,9 @@ __global__ __launch_bounds__(WAVE) void polish_writeback_kernel(PolishArgs a, in
 // lo_bar, hi_bar and w_bar of a converged point from the adjoint [a; beta] of its last assembly.  Hard-active i: b_bar_i = xbar_i -
 // (H a + C^T beta)_i - the row products of the finish step with rho 0: a_A = 0, so rho a_i vanishes there; soft-active i:
 // b_bar_i = w_i a_i and w_bar_i = a_i (b_i - x_i); b_bar goes to hi_bar where act = +1 and to lo_bar where act = -1; every other
-// entry of the three is 0.  Without weights lo, hi and x are not read; without w_bar it is not written.
-template <typename T, int S, int C, bool W>
+// entry of the three is 0.  Without weights lo, hi and x are not read; without w_bar it is not written.  With caps (W = BOUNDS_CAPPED,
+// DESIGN.md section 3.11) a saturated i (act = +-2, s its sign) has cap_bar_i = -s a_i and 0 in the other three; cap_bar is 0 elsewhere.
+template <typename T, int S, int C, int W>
 __global__ __launch_bounds__(WAVE) void qp_bound_grad_kernel(BoundGradArgs q, int K, BatchStride bs)
 {
     constexpr int n = S + C, SS = S * S, CC = C * C, SN = S * n;
@@ -215,6 +229,8 @@ __global__ __launch_bounds__(WAVE) void qp_bound_grad_kernel(BoundGradArgs q, in
     const T *xbar = (const T *)q.xbar + sys * bs.n, *adz = (const T *)q.adz + sys * bs.n, *beta = (const T *)q.beta + sys * bs.sk;
     T *lo_bar = (T *)q.lo_bar + sys * bs.n, *hi_bar = (T *)q.hi_bar + sys * bs.n;
     T *w_bar = W && q.w_bar ? (T *)q.w_bar + sys * bs.n : nullptr;
+    const T *cap = sys_caps<T, W>(q.cap, sys, bs);
+    T *cap_bar = W == BOUNDS_CAPPED && q.cap_bar ? (T *)q.cap_bar + sys * bs.n : nullptr;
     for (int k = blockIdx.x; k < K; k += gridDim.x) {
         const int nk = k < K - 1 ? n : S;
         const size_t v0 = (size_t)k * n;
@@ -234,8 +250,10 @@ __global__ __launch_bounds__(WAVE) void qp_bound_grad_kernel(BoundGradArgs q, in
         if (lane < nk) {
             const size_t v = v0 + lane;
             const signed char ai = act[v];
-            T bb = (T)0, wb = (T)0;
-            if (soft_active(ai, w, v)) {
+            T bb = (T)0, wb = (T)0, cb = (T)0;
+            if (W == BOUNDS_CAPPED && cap && saturated(ai) && soft_active(ai, w, v) && __builtin_isfinite(cap[v])) {
+                cb = ai > 0 ? -sV[lane] : sV[lane];
+            } else if (soft_active(ai, w, v)) {
                 const size_t o = sys * bs.n + v;                             // lo, hi and x: given with the weights only
                 const T ad = sV[lane];
                 bb = w[v] * ad;
@@ -248,6 +266,7 @@ __global__ __launch_bounds__(WAVE) void qp_bound_grad_kernel(BoundGradArgs q, in
             lo_bar[v] = ai < 0 ? bb : (T)0;
             hi_bar[v] = ai > 0 ? bb : (T)0;
             if (w_bar) w_bar[v] = wb;
+            if (cap_bar) cap_bar[v] = cb;
         }
     }
 }
@@ -268,7 +287,9 @@ template <typename T, int S, int C>
 int launch_polish_prepare(const Dims &d, const PolishArgs &a, hipStream_t st)
 {
     if (d.B < 1 || d.B > 65535) { set_error("polish_prepare: B = %d", d.B); return GATO_EINVAL; }
-    const auto kernel = a.w ? polish_prepare_kernel<T, S, C, true> : polish_prepare_kernel<T, S, C, false>;
+    const int form = bounds_form(a.w, a.cap);
+    const auto kernel = form == BOUNDS_CAPPED ? polish_prepare_kernel<T, S, C, BOUNDS_CAPPED>
+                        : form == BOUNDS_SOFT ? polish_prepare_kernel<T, S, C, BOUNDS_SOFT> : polish_prepare_kernel<T, S, C, BOUNDS_HARD>;
     hipLaunchKernelGGL(kernel, dim3(knot_grid(d.K), d.B), dim3(WAVE), 0, st, a, d.K, batch_stride(d));
     GATO_HIP_CHECK(hipGetLastError());
     return GATO_OK;
@@ -290,7 +311,9 @@ int launch_qp_bound_grad(const Dims &d, const BoundGradArgs &a, hipStream_t st)
 {
     if (d.B < 1 || d.B > 65535) { set_error("qp_bound_grad: B = %d", d.B); return GATO_EINVAL; }
     // with w_bar alone (the soft entry without weights) the W kernel finds no weight at run time and writes w_bar = 0
-    const auto kernel = a.w || a.w_bar ? qp_bound_grad_kernel<T, S, C, true> : qp_bound_grad_kernel<T, S, C, false>;
+    // with cap_bar alone (the capped entry without caps) the capped kernel finds no cap at run time and writes cap_bar = 0
+    const auto kernel = a.cap || a.cap_bar ? qp_bound_grad_kernel<T, S, C, BOUNDS_CAPPED>
+                        : a.w || a.w_bar ? qp_bound_grad_kernel<T, S, C, BOUNDS_SOFT> : qp_bound_grad_kernel<T, S, C, BOUNDS_HARD>;
     hipLaunchKernelGGL(kernel, dim3(knot_grid(d.K), d.B), dim3(WAVE), 0, st, a, d.K, batch_stride(d));
     GATO_HIP_CHECK(hipGetLastError());
     return GATO_OK;

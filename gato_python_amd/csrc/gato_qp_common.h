@@ -44,6 +44,19 @@ __device__ __forceinline__ bool bad_active(signed char act, T b, bool x0)
     return act < -1 || act > 1 || (act != 0 && (!__builtin_isfinite(b) || x0));
 }
 
+// Capped soft bounds: act = +-2 names a saturated variable - its penalty force is held at the cap.
+__device__ __forceinline__ bool saturated(signed char act) { return act == 2 || act == -2; }
+
+// bad_active where caps are given: +-2 is an act too, but only on a variable with a weight w > 0 and a finite cap m (the bound
+// finite and off x_0, as for every active variable).
+template <typename T>
+__device__ __forceinline__ bool bad_active_capped(signed char act, T b, bool x0, T w, T m)
+{
+    if (act < -2 || act > 2) return true;
+    if (saturated(act) && !(w > (T)0 && __builtin_isfinite(m))) return true;
+    return act != 0 && (!__builtin_isfinite(b) || x0);
+}
+
 // Row i of knot k of H v and C^T w, the products of qp_update_kernel: (G v)_i + rho v_i and w_k,i (states) + (C_k^T w_k+1)_i.
 // sQ, sR: the knot's G blocks (without rho); sCk: C block k (rows of block row k+1); sV: v of the knot; sLk, sLn: w_k, w_k+1.
 template <typename T, int S, int C>
@@ -67,12 +80,22 @@ __device__ __forceinline__ void row_products(int i, bool next, const T *sQ, cons
     }
 }
 
+// The form of the bounds a kernel is instantiated for (its template parameter W): all hard, soft weights, weights and caps.
+enum { BOUNDS_HARD = 0, BOUNDS_SOFT = 1, BOUNDS_CAPPED = 2 };
+inline int bounds_form(const void *w, const void *cap) { return w ? (cap ? BOUNDS_CAPPED : BOUNDS_SOFT) : BOUNDS_HARD; }
+
 // The soft weights of system sys (w: [B][N]) in a kernel instantiated with weights (W); nullptr = all hard in one without: every
 // test of it is then decided at compile time and the hard code is what it was before there were weights.
-template <typename T, bool W>
+template <typename T, int W>
 __device__ __forceinline__ const T *sys_weights(const void *w, size_t sys, const BatchStride &bs)
 {
     return W && w ? (const T *)w + sys * bs.n : nullptr;
+}
+// The caps of system sys in a kernel instantiated with caps, nullptr in every other: no capped branch is compiled there.
+template <typename T, int W>
+__device__ __forceinline__ const T *sys_caps(const void *cap, size_t sys, const BatchStride &bs)
+{
+    return W == BOUNDS_CAPPED && cap ? (const T *)cap + sys * bs.n : nullptr;
 }
 
 // One system's arrays of PolishArgs, and the LDS one wave stages a knot in.
@@ -80,17 +103,19 @@ template <typename T>
 struct PointSys {
     const T *G, *Cd, *g, *c, *lo, *hi, *xt, *lt;
     const T *w;                              // the system's soft weights, nullptr = all hard
+    const T *cap;                            // the caps of the penalty force, nullptr = none
     const signed char *act;
     T *xp, *zp, *yp;
     T rho;
 };
 // W: the kernel is the instantiation with weights; without, w is a compile-time nullptr and no soft branch is compiled
-template <typename T, bool W>
+template <typename T, int W>
 __device__ __forceinline__ PointSys<T> point_sys(const PolishArgs &a, size_t sys, const BatchStride &bs)
 {
     return PointSys<T>{(const T *)a.G + sys * bs.g,  (const T *)a.Cd + sys * bs.c,  (const T *)a.g + sys * bs.n,
                        (const T *)a.c + sys * bs.sk, (const T *)a.lo + sys * bs.n,  (const T *)a.hi + sys * bs.n,
                        (const T *)a.xt + sys * bs.n, (const T *)a.lt + sys * bs.sk, sys_weights<T, W>(a.w, sys, bs),
+                       sys_caps<T, W>(a.cap, sys, bs),
                        a.act + sys * bs.n,           (T *)a.xp + sys * bs.n,        (T *)a.zp + sys * bs.n,
                        (T *)a.yp + sys * bs.n,       (T)a.rho};
 }
@@ -108,7 +133,9 @@ __device__ __forceinline__ bool soft_active(signed char act, const T *w, size_t 
 // Knot k of the polished point from the reduced solve (x = x' off the active set, the bound on it, z = clip(x), y_A = (g - H x -
 // C^T lambda)_A, y_F = 0) to xp, zp, yp, and its residuals folded into the lane's maxima m.  A soft-active variable keeps the
 // reduced solution x', its multiplier is the penalty force y = w (x - b) and z = x (the violation is allowed); H in the residuals
-// is without W.  With p.w nullptr or 0 no variable is soft-active.  The whole wave calls it.
+// is without W.  With p.w nullptr or 0 no variable is soft-active.  With caps (p.cap) a saturated
+// variable (act = +-2, s its sign) has y = s m bit for bit, and the sign slot also takes what keeps an act to its point: max(|y|
+// - m, 0) of a soft quadratic-active variable, max(m - s w (x - b), 0) of a saturated one.  The whole wave calls it.
 template <typename T, int S, int C>
 __device__ __forceinline__ PointVar<T> polished_point_knot(PointLds<T, S, C> &L, const PointSys<T> &p, int k, int K, int lane,
                                                            unsigned long long (&m)[GATO_POLISH_NSLOT])
@@ -153,9 +180,18 @@ __device__ __forceinline__ PointVar<T> polished_point_knot(PointLds<T, S, C> &L,
         const T gv = p.g[v], l = p.lo[v], h = p.hi[v], xn = L.sXn[i];
         T zn = clip(xn, l, h);
         T yn = ai != 0 ? (gv - hx) - ctl : (T)0;
+        T over = (T)0;                                                  // capped: how far the force is on the wrong side of its cap
         if (soft) {
             zn = xn;
             yn = p.w[v] * (xn - bound_of(ai, l, h));
+            if (p.cap) {
+                const T mi = p.cap[v];
+                if (saturated(ai)) {
+                    const T sf = ai > 0 ? yn : -yn;
+                    over = mi - sf;
+                    yn = ai > 0 ? mi : -mi;
+                } else over = fabs(yn) - mi;
+            }
         }
         const T rd = (hx - gv) + ctl + yn;
         p.xp[v] = xn; p.zp[v] = zn; p.yp[v] = yn;
@@ -171,6 +207,7 @@ __device__ __forceinline__ PointVar<T> polished_point_knot(PointLds<T, S, C> &L,
             const T ws = ai > 0 ? -yn : yn;
             fold(F_SIGN, ws > (T)0 ? ws : (T)0);
         }
+        if (p.cap && soft) fold(F_SIGN, over > (T)0 ? over : (T)0);
         if (i < S) {                                                    // row block k of C x - c
             const T ci = p.c[(size_t)k * S + i];
             T cx = xn;

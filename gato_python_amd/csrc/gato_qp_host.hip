@@ -238,14 +238,16 @@ extern "C" int gato_box_qp_polish(gato_solver *s, const void *d_G_blocks, const 
 // ---- primal-dual active-set iteration: the polish iterated (gato_pdas.hip, DESIGN.md sections 3.9, 3.10) ----------------
 // Per solve: add rho, the masked inversion and shifted right-hand side, the stage path of the whole solve (all as in the
 // polish), then the step and the decision and one read of the live count.  d_soft_w: the weights of soft bounds (NULL: all
-// hard), read by the check, the prepare and the step.  `who` names the entry in errors; soft: its texts speak of the weights.
-static int pdas_loop(gato_solver *s, const char *who, bool soft, const void *d_G_blocks, const void *d_C_blocks, const void *d_g,
-                     const void *d_c, const void *d_lo, const void *d_hi, const void *d_soft_w, signed char *d_act,
+// hard), read by the check, the prepare and the step; d_soft_cap: the caps of their forces (section 3.11; NULL: none, and not
+// read without weights).  `who` names the entry in errors; soft: its texts speak of the weights (2: and of the caps).
+static int pdas_loop(gato_solver *s, const char *who, int soft, const void *d_G_blocks, const void *d_C_blocks, const void *d_g,
+                     const void *d_c, const void *d_lo, const void *d_hi, const void *d_soft_w, const void *d_soft_cap,
+                     signed char *d_act,
                      const gato_box_qp_params *p, int max_pdas_iters, void *d_x, void *d_z, void *d_y, void *d_lambda, int *d_iters,
                      int *d_status, double *d_res, void *stream)
 {
     if (check_pointers(s, who, p, d_C_blocks, {d_G_blocks, d_g, d_c, d_lo, d_hi, d_act, d_x, d_z, d_y, d_lambda, d_iters, d_status, d_res},
-                       soft ? ", d_soft_w for no soft bound" : ""))
+                       soft == 2 ? ", d_soft_w for no soft bound, d_soft_cap for no cap" : (soft ? ", d_soft_w for no soft bound" : "")))
         return GATO_EINVAL;
     if (!reduced_params_ok(*p) || max_pdas_iters < 1) {
         set_error("%s: parameters out of range (want finite values, rho, eps_abs, eps_rel, exit_tol >= 0, max_iters, "
@@ -268,6 +270,7 @@ static int pdas_loop(gato_solver *s, const char *who, bool soft, const void *d_G
     PolishArgs &q = a.p;
     q = polish_args(s, w, o, p);
     q.G = d_G_blocks; q.Cd = d_C_blocks; q.g = d_g; q.c = d_c; q.lo = d_lo; q.hi = d_hi; q.act = d_act; q.w = d_soft_w;
+    q.cap = d_soft_w ? d_soft_cap : nullptr;
     q.x = d_x; q.z = d_z; q.y = d_y; q.lam = d_lambda; q.status = d_status; q.polish = (int *)(w + o.pol); q.res = d_res;
     q.bad = ctr + 3;
     a.act = d_act; a.act2 = (signed char *)(w + o.a2); a.round = (int *)(w + o.rn); a.ctr = ctr; a.iters = d_iters;
@@ -287,9 +290,13 @@ static int pdas_loop(gato_solver *s, const char *who, bool soft, const void *d_G
             GATO_HIP_CHECK(hipStreamSynchronize(st));
             if (h[1] > 0 || h[2] > 0) {
                 set_error("%s:%s%s; d_status marks the systems", who,
-                          h[1] > 0 ? (soft ? " a bound is NaN, lo > hi or a weight is NaN, negative or infinite (BAD_BOUNDS)"
-                                           : " a bound is NaN or lo > hi (BAD_BOUNDS)") : "",
-                          h[2] > 0 ? " a start act is not -1, 0 or 1, names an infinite bound or a state of x_0 (BAD_ACTIVE)" : "");
+                          h[1] > 0 ? (soft == 2 ? " a bound is NaN, lo > hi, a weight is NaN, negative or infinite or a cap is NaN or "
+                                                  "negative (BAD_BOUNDS)"
+                                      : soft ? " a bound is NaN, lo > hi or a weight is NaN, negative or infinite (BAD_BOUNDS)"
+                                             : " a bound is NaN or lo > hi (BAD_BOUNDS)") : "",
+                          h[2] > 0 ? (soft == 2 ? " a start act is not -2 .. 2, names an infinite bound or a state of x_0, or is +-2 "
+                                                  "without a weight and a finite cap (BAD_ACTIVE)"
+                                                : " a start act is not -1, 0 or 1, names an infinite bound or a state of x_0 (BAD_ACTIVE)") : "");
                 return GATO_EINVAL;
             }
         }
@@ -314,7 +321,7 @@ extern "C" int gato_box_qp_pdas(gato_solver *s, const void *d_G_blocks, const vo
                                 int max_pdas_iters, void *d_x, void *d_z, void *d_y, void *d_lambda, int *d_iters, int *d_status,
                                 double *d_res, void *stream)
 {
-    return pdas_loop(s, "box_qp_pdas", false, d_G_blocks, d_C_blocks, d_g, d_c, d_lo, d_hi, nullptr, d_act, p, max_pdas_iters, d_x,
+    return pdas_loop(s, "box_qp_pdas", 0, d_G_blocks, d_C_blocks, d_g, d_c, d_lo, d_hi, nullptr, nullptr, d_act, p, max_pdas_iters, d_x,
                      d_z, d_y, d_lambda, d_iters, d_status, d_res, stream);
 }
 
@@ -324,7 +331,7 @@ extern "C" int gato_box_qp_pdas_soft(gato_solver *s, const void *d_G_blocks, con
                                      const gato_box_qp_params *p, int max_pdas_iters, void *d_x, void *d_z, void *d_y,
                                      void *d_lambda, int *d_iters, int *d_status, double *d_res, void *stream)
 {
-    return pdas_loop(s, "box_qp_pdas_soft", true, d_G_blocks, d_C_blocks, d_g, d_c, d_lo, d_hi, d_soft_w, d_act, p, max_pdas_iters,
+    return pdas_loop(s, "box_qp_pdas_soft", 1, d_G_blocks, d_C_blocks, d_g, d_c, d_lo, d_hi, d_soft_w, nullptr, d_act, p, max_pdas_iters,
                      d_x, d_z, d_y, d_lambda, d_iters, d_status, d_res, stream);
 }
 
@@ -361,3 +368,33 @@ extern "C" int gato_box_qp_bound_grad(gato_solver *s, const void *d_G_blocks, co
     return s->ops->qp_bound_grad(d, a, (hipStream_t)stream);
 }
 
+
+// ---- capped (Huber) soft bounds in the active-set iteration -------------------------------------------
+extern "C" int gato_box_qp_pdas_huber(gato_solver *s, const void *d_G_blocks, const void *d_C_blocks, const void *d_g,
+                                      const void *d_c, const void *d_lo, const void *d_hi, const void *d_soft_w,
+                                      const void *d_soft_cap, signed char *d_act, const gato_box_qp_params *p, int max_pdas_iters,
+                                      void *d_x, void *d_z, void *d_y, void *d_lambda, int *d_iters, int *d_status, double *d_res,
+                                      void *stream)
+{
+    return pdas_loop(s, "box_qp_pdas_huber", 2, d_G_blocks, d_C_blocks, d_g, d_c, d_lo, d_hi, d_soft_w, d_soft_cap, d_act, p,
+                     max_pdas_iters, d_x, d_z, d_y, d_lambda, d_iters, d_status, d_res, stream);
+}
+
+extern "C" int gato_box_qp_huber_grad(gato_solver *s, const void *d_G_blocks, const void *d_C_blocks, const signed char *d_act,
+                                      const void *d_soft_w, const void *d_soft_cap, const void *d_lo, const void *d_hi,
+                                      const void *d_x, const void *d_xbar, const void *d_a, const void *d_beta, void *d_lo_bar,
+                                      void *d_hi_bar, void *d_w_bar, void *d_cap_bar, void *stream)
+{
+    if (!solver_usable(s, "box_qp_huber_grad", "gradients")) return GATO_EINVAL;
+    if (!d_G_blocks || (!d_C_blocks && s->d.K > 1) || !d_act || !d_lo || !d_hi || !d_x || !d_xbar || !d_a || !d_beta || !d_lo_bar ||
+        !d_hi_bar || !d_w_bar || !d_cap_bar) {
+        set_error("box_qp_huber_grad: every pointer is required (d_C_blocks may be NULL only for K = 1, d_soft_w for no soft bound, "
+                  "d_soft_cap for no cap)");
+        return GATO_EINVAL;
+    }
+    Dims d = s->d;
+    d.k_lo = d.k_hi = 0; d.rhs = 0;
+    const BoundGradArgs a{d_G_blocks, d_C_blocks, d_act, d_soft_w, d_lo, d_hi, d_x, d_xbar, d_a, d_beta, d_lo_bar, d_hi_bar, d_w_bar,
+                          d_soft_w ? d_soft_cap : nullptr, d_cap_bar};
+    return s->ops->qp_bound_grad(d, a, (hipStream_t)stream);
+}

@@ -5,7 +5,8 @@
 solves  min 1/2 x^T (G + rho I) x - g^T x  s.t.  C x = c,  lo <= x <= hi  - the KKT system of autograd.kkt_solve plus bounds on
 the states and controls - by ADMM over the device re-solve (Solver.box_qp, gato_box_qp_solve), optionally polished on the ADMM
 result's active set (polish=True), or by the primal-dual active-set iteration alone (method="pdas",
-Solver.box_qp_pdas; x_soft / u_soft turn bounds into quadratic penalties, section 3.10).  It is NOT differentiable: the inputs are read detached and the outputs carry no
+Solver.box_qp_pdas; x_soft / u_soft turn bounds into quadratic penalties, section 3.10, and x_soft_max /
+u_soft_max cap their forces, section 3.11).  It is NOT differentiable: the inputs are read detached and the outputs carry no
 grad_fn.
 
     box_qp_layer(Q, R, A, B, q, r, c, x_lo, x_hi, u_lo, u_hi, *, rho, exit_tol, max_iters, **admm) -> (x, lam, info)
@@ -38,10 +39,11 @@ def _bound(v, shape, name, ref, what):
         raise ValueError(f"{what}: {name} of shape {tuple(v.shape)} does not broadcast to {shape}") from None
 
 
-def _prepare(what, blocks, x_lo, x_hi, u_lo, u_hi, x_soft, u_soft):
+def _prepare(what, blocks, x_lo, x_hi, u_lo, u_hi, x_soft, u_soft, x_soft_max=None, u_soft_max=None):
     """Everything of box_qp and box_qp_layer (`what`) up to the solver call: the checks of the blocks (Q, R, A, B, q, r, c) and
-    the bounds, then (Gb, Cb, g, c) packed, lo, hi and the soft weights w (None unless x_soft or u_soft is given) in the dz
-    layout [Bt, N], and Bt, batched and the cached solver.  In torch ops, which torch differentiates."""
+    the bounds, then (Gb, Cb, g, c) packed, lo, hi, the soft weights w (None unless x_soft or u_soft is given) and the caps m
+    (None unless x_soft_max or u_soft_max is given; +inf where only the other is) in the dz layout [Bt, N], and Bt, batched
+    and the cached solver.  In torch ops, which torch differentiates."""
     args = dict(zip("Q R A B q r c".split(), blocks))
     batched, lead, K, S, C = _check_blocks(args, what, qp=True)
     device, dtype = _common(args, what)
@@ -58,12 +60,27 @@ def _prepare(what, blocks, x_lo, x_hi, u_lo, u_hi, x_soft, u_soft):
         xw = lift(_bound(0.0 if x_soft is None else x_soft, xs, "x_soft", q, what))
         uw = lift(_bound(0.0 if u_soft is None else u_soft, us, "u_soft", q, what))
         w = _dz_layout(xw, uw)
-    return Gb, Cb, g, cc, lo, hi, w, Bt, batched, sol
+    m = None
+    if x_soft_max is not None or u_soft_max is not None:
+        xm = lift(_bound(float("inf") if x_soft_max is None else x_soft_max, xs, "x_soft_max", q, what))
+        um = lift(_bound(float("inf") if u_soft_max is None else u_soft_max, us, "u_soft_max", q, what))
+        m = _dz_layout(xm, um)
+    return Gb, Cb, g, cc, lo, hi, w, m, Bt, batched, sol
+
+
+def _check_caps(what, method, polish, soft, capped):
+    """The refusals of x_soft_max / u_soft_max: they need the active-set iteration and a weight to cap."""
+    if not capped:
+        return
+    if method != "pdas" or polish:
+        raise ValueError(f"{what}: x_soft_max and u_soft_max need method='pdas' without polish (ADMM and the polish have no soft bounds)")
+    if not soft:
+        raise ValueError(f"{what}: x_soft_max and u_soft_max cap the force of a soft bound: give x_soft or u_soft too")
 
 
 def box_qp(Q, R, A, B, q, r, c, x_lo, x_hi, u_lo, u_hi, *, rho, exit_tol, max_iters, admm_rho=0.1, sigma=1e-6, alpha=1.6,
            eps_abs=1e-6, eps_rel=1e-6, max_admm_iters=4000, check_every=25, warm=None, polish=False, method="admm",
-           polish_iters=1, max_pdas_iters=30, x_soft=None, u_soft=None):
+           polish_iters=1, max_pdas_iters=30, x_soft=None, u_soft=None, x_soft_max=None, u_soft_max=None):
     """Box-constrained QP from math-shaped blocks, at most one leading batch dimension:
     Q [*,K,S,S], R [*,K-1,C,C], A [*,K-1,S,S], B [*,K-1,S,C], q [*,K,S], r [*,K-1,C], c [*,K,S] as kkt_solve takes them (A, B
     the raw values stored in C: -A and -B of the dynamics), and the bounds x_lo, x_hi [*,K,S], u_lo, u_hi [*,K-1,C] - numbers
@@ -80,17 +97,23 @@ def box_qp(Q, R, A, B, q, r, c, x_lo, x_hi, u_lo, u_hi, *, rho, exit_tol, max_it
     x_soft [*,K,S], u_soft [*,K-1,C] (method="pdas" only; numbers or tensors that broadcast like the bounds; None: 0): soft
     bounds.  A weight w > 0 replaces the bound of its variable by the penalty (w / 2) dist(x, [lo,
     hi])^2, a weight 0 keeps the hard bound.  For a soft variable outside its bounds result.y is the penalty force w (x - b)
-    and result.z = x.  ValueError for method="admm" or polish=True, and for a NaN, negative or infinite weight."""
+    and result.z = x.  ValueError for method="admm" or polish=True, and for a NaN, negative or infinite weight.
+    x_soft_max [*,K,S], u_soft_max [*,K-1,C] (with x_soft / u_soft; numbers or tensors that broadcast like the weights; None: no
+    cap): caps m >= 0 on the penalty forces.  The penalty becomes the Huber function - quadratic while
+    w dist <= m, linear with slope m beyond - and the force clamp(w (x - clip(x)), -m, m).  A saturated variable has
+    result.act = +-2 and result.y = +-m; warm.act may carry +-2.  ValueError for method="admm" or polish=True, without any
+    weight, and for a NaN or negative cap."""
     if method not in ("admm", "pdas"):
         raise ValueError(f"box_qp: method must be 'admm' or 'pdas', got {method!r}")
     soft = x_soft is not None or u_soft is not None
+    _check_caps("box_qp", method, polish, soft, x_soft_max is not None or u_soft_max is not None)
     if soft and (method != "pdas" or polish):
         raise ValueError("box_qp: x_soft and u_soft need method='pdas' without polish (ADMM and the polish have no soft bounds)")
     if int(polish_iters) < 1 or int(max_pdas_iters) < 1:
         raise ValueError("box_qp: polish_iters and max_pdas_iters must be at least 1")
     with torch.no_grad():
-        Gb, Cb, g, cc, lo, hi, wt, Bt, batched, sol = _prepare("box_qp", (Q, R, A, B, q, r, c), x_lo, x_hi, u_lo, u_hi,
-                                                               x_soft, u_soft)
+        Gb, Cb, g, cc, lo, hi, wt, mt, Bt, batched, sol = _prepare("box_qp", (Q, R, A, B, q, r, c), x_lo, x_hi, u_lo, u_hi,
+                                                                   x_soft, u_soft, x_soft_max, u_soft_max)
         if method == "pdas":
             act = None
             if warm is not None:
@@ -100,7 +123,8 @@ def box_qp(Q, R, A, B, q, r, c, x_lo, x_hi, u_lo, u_hi, *, rho, exit_tol, max_it
                                      "method='pdas' starts from the act of a previous method='pdas' result")
                 act = act.reshape(-1).contiguous()
             res = sol.box_qp_pdas(Gb, Cb, g, cc, lo, hi, rho=rho, exit_tol=exit_tol, max_iters=max_iters, eps_abs=eps_abs,
-                                  eps_rel=eps_rel, max_pdas_iters=max_pdas_iters, act=act, soft_weight=wt)
+                                  eps_rel=eps_rel, max_pdas_iters=max_pdas_iters, act=act, soft_weight=wt,
+                                  soft_cap=None if mt is None else mt.contiguous())
             return _shaped(res, sol, Bt, batched)
         out = {}
         if warm is not None:
@@ -147,19 +171,20 @@ def _shaped(res, sol, Bt, batched):
 
 # ---- the differentiable layer -----------------------------------------------------------------------------------------
 class _BoxQPLayer(torch.autograd.Function):
-    """(G_blocks [B, G_dense], C_blocks [B, C_dense], g [B, N], c [B, S K], lo, hi [B, N], w [B, N] or None) -> (x [B, N],
-    lam [B, S K]) of the polished solution; box[0] receives the BoxQPResult.  w: the soft-bound weights, which make the
-    forward pass the active-set iteration; None: hard bounds, by ADMM and the polish or (opts has max_pdas_iters) by the
-    active-set iteration.  The backward pass is one re-solve of the last assembly (the reduced system; with w, the weights of
-    the soft-active variables on its diagonal) plus the gradient launches."""
+    """(G_blocks [B, G_dense], C_blocks [B, C_dense], g [B, N], c [B, S K], lo, hi [B, N], w [B, N] or None, m [B, N] or None)
+    -> (x [B, N], lam [B, S K]) of the polished solution; box[0] receives the BoxQPResult.  w: the soft-bound weights, which
+    make the forward pass the active-set iteration; None: hard bounds, by ADMM and the polish or (opts has max_pdas_iters) by
+    the active-set iteration.  m (with w): the caps of the penalty forces.  The backward pass is one re-solve of the last
+    assembly (the reduced system; with w, the weights of the soft-active variables that are not saturated on its diagonal) plus
+    the gradient launches."""
 
     @staticmethod
-    def forward(ctx, Gb, Cb, g, c, lo, hi, w, sol, opts, box):
+    def forward(ctx, Gb, Cb, g, c, lo, hi, w, m, sol, opts, box):
         opts = dict(opts)
         pdas_iters = opts.pop("max_pdas_iters", None)      # set: the active-set iteration alone (method="pdas")
         pol = {k: opts[k] for k in ("rho", "exit_tol", "max_iters", "eps_abs", "eps_rel")}
         if w is not None or pdas_iters is not None:
-            res = sol.box_qp_pdas(Gb, Cb, g, c, lo, hi, max_pdas_iters=pdas_iters, soft_weight=w, **pol)
+            res = sol.box_qp_pdas(Gb, Cb, g, c, lo, hi, max_pdas_iters=pdas_iters, soft_weight=w, soft_cap=m, **pol)
             act = res.act
         else:
             res = sol.box_qp(Gb, Cb, g, c, lo, hi, **opts)
@@ -169,17 +194,17 @@ class _BoxQPLayer(torch.autograd.Function):
         ctx.sol, ctx.pol, ctx.gen = sol, pol, sol.get_option("assembly_gen")
         ctx.codes = res.polished.cpu()
         x, lam = res.x.view(sol.batch, sol.N), res.lam.view(sol.batch, sol.sizes["sk"])
-        ctx.save_for_backward(Gb, Cb, g, c, lo, hi, w, act, x, lam)
+        ctx.save_for_backward(Gb, Cb, g, c, lo, hi, w, m, act, x, lam)
         ctx.set_materialize_grads(False)
         return x.clone(), lam.clone()
 
     @staticmethod
     @once_differentiable
     def backward(ctx, x_bar, lam_bar):
-        Gb, Cb, g, c, lo, hi, w, act, x, lam = ctx.saved_tensors
+        Gb, Cb, g, c, lo, hi, w, m, act, x, lam = ctx.saved_tensors
         sol, pol, need = ctx.sol, ctx.pol, ctx.needs_input_grad
         if x_bar is None and lam_bar is None:
-            return (None,) * 10
+            return (None,) * 11
         xb = torch.zeros_like(x) if x_bar is None else x_bar.to(x.dtype).contiguous()
         lb = torch.zeros_like(lam) if lam_bar is None else lam_bar.to(lam.dtype).contiguous()
         live = (xb.ne(0).any(1) | lb.ne(0).any(1)).cpu()
@@ -190,9 +215,9 @@ class _BoxQPLayer(torch.autograd.Function):
                                f"(codes {ctx.codes[bad].tolist()}, _lib.POLISH_*): their x and lam are ADMM iterates (zeros "
                                "after method='pdas'), which have no gradient here")
         if not live.any():                   # every system's gradient is exactly zero: no re-solve (its PCG would form 0/0)
-            return tuple(torch.zeros_like(t) if need[i] else None for i, t in enumerate((Gb, Cb, g, c, lo, hi, w))) + (None,) * 3
+            return tuple(torch.zeros_like(t) if need[i] else None for i, t in enumerate((Gb, Cb, g, c, lo, hi, w, m))) + (None,) * 3
         if sol.get_option("assembly_gen") != ctx.gen or sol.get_option("assembly_valid") == 0:
-            _rebuild_assembly(sol, Gb, Cb, g, c, lo, hi, w, act, x, lam, pol)      # another forward replaced the assembly
+            _rebuild_assembly(sol, Gb, Cb, g, c, lo, hi, w, m, act, x, lam, pol)   # another forward replaced the assembly
         # the reduced system reads x_bar off the hard-active set only (Ginv' has zero rows there; a soft-active variable is in
         # the system): with those masked, a system whose upstream gradient lives on its hard-active set alone has a zero
         # right-hand side, and _adjoint's zero test gives it a = beta = 0 instead of the PCG's 0/0
@@ -205,25 +230,28 @@ class _BoxQPLayer(torch.autograd.Function):
         Cbar = torch.empty_like(Cb) if need[1] else None
         if Gbar is not None or Cbar is not None:
             sol.kkt_grad_blocks(x, lam, a, beta, Gbar, Cbar)
-        lo_bar = hi_bar = w_bar = None
-        if need[4] or need[5] or need[6]:
+        lo_bar = hi_bar = w_bar = m_bar = None
+        if need[4] or need[5] or need[6] or need[7]:
             if w is None:
                 lo_bar, hi_bar = sol.box_qp_bound_grad(Gb, Cb, act, xb, a, beta)
+            elif m is not None:
+                lo_bar, hi_bar, w_bar, m_bar = sol.box_qp_huber_grad(Gb, Cb, act, w.contiguous(), m.contiguous(), lo, hi,
+                                                                     x.contiguous(), xb, a.contiguous(), beta.contiguous())
             else:
                 lo_bar, hi_bar, w_bar = sol.box_qp_soft_grad(Gb, Cb, act, w.contiguous(), lo, hi, x.contiguous(), xb,
                                                              a.contiguous(), beta.contiguous())
         keep = live.to(x.device)[:, None]
         mask = lambda i, t: None if t is None or not need[i] else torch.where(keep, t.view(sol.batch, -1),
                                                                               torch.zeros((), dtype=t.dtype, device=t.device))
-        return tuple(mask(i, t) for i, t in enumerate((Gbar, Cbar, a, beta, lo_bar, hi_bar, w_bar))) + (None,) * 3
+        return tuple(mask(i, t) for i, t in enumerate((Gbar, Cbar, a, beta, lo_bar, hi_bar, w_bar, m_bar))) + (None,) * 3
 
 
-def _rebuild_assembly(sol, Gb, Cb, g, c, lo, hi, w, act, x, lam, pol):
+def _rebuild_assembly(sol, Gb, Cb, g, c, lo, hi, w, m, act, x, lam, pol):
     """The assembly a backward pass re-solves, from the saved active set (it is a function of the inputs, the weights and act
-    alone).  Hard bounds: the polish on act, its point into scratch copies; with weights w: one solve of the active-set
-    iteration from act, its point into tensors of its own."""
+    alone).  Hard bounds: the polish on act, its point into scratch copies; with weights w (and caps m: act may hold +-2): one
+    solve of the active-set iteration from act, its point into tensors of its own."""
     if w is not None:
-        sol.box_qp_pdas(Gb, Cb, g, c, lo, hi, max_pdas_iters=1, act=act, soft_weight=w, **pol)
+        sol.box_qp_pdas(Gb, Cb, g, c, lo, hi, max_pdas_iters=1, act=act, soft_weight=w, soft_cap=m, **pol)
         return
     res2 = torch.empty(sol.batch, 2, dtype=torch.float64, device=x.device)
     scratch = BoxQPResult(x.clone(), x.clone(), x.clone(), lam.clone(), None,
@@ -233,7 +261,7 @@ def _rebuild_assembly(sol, Gb, Cb, g, c, lo, hi, w, act, x, lam, pol):
 
 def box_qp_layer(Q, R, A, B, q, r, c, x_lo, x_hi, u_lo, u_hi, *, rho, exit_tol, max_iters, admm_rho=0.1, sigma=1e-6,
                  alpha=1.6, eps_abs=1e-6, eps_rel=1e-6, max_admm_iters=4000, check_every=25, method="admm", max_pdas_iters=30,
-                 x_soft=None, u_soft=None):
+                 x_soft=None, u_soft=None, x_soft_max=None, u_soft_max=None):
     """Differentiable box-constrained QP: the inputs of box_qp; returns (x [*, N], lam [*, S K], info) with x and lam those
     of the polished solution, differentiable with respect to every tensor input (the bounds included; Q and R as symmetric,
     DESIGN.md section 3.6), and info a detached BoxQPResult (info.polished: the polish codes).  A system whose polish was not
@@ -241,20 +269,24 @@ def box_qp_layer(Q, R, A, B, q, r, c, x_lo, x_hi, u_lo, u_hi, *, rho, exit_tol, 
     method="pdas": the forward pass is the active-set iteration alone (Solver.box_qp_pdas, cold start, at most max_pdas_iters
     reduced solves; the ADMM parameters are not read; a system that does not converge returns zeros); the backward pass is the
     same.  x_soft, u_soft (method="pdas" only): the soft-bound weights of box_qp; the layer is
-    differentiable with respect to them too.  rho is not differentiated and double backward is not supported."""
+    differentiable with respect to them too.  x_soft_max, u_soft_max (with x_soft / u_soft): the caps of box_qp (DESIGN.md section
+    3.11); differentiable with respect to them as well (a cap's gradient is nonzero only on a saturated variable).  rho is not differentiated and double backward is not supported."""
     if method not in ("admm", "pdas"):
         raise ValueError(f"box_qp_layer: method must be 'admm' or 'pdas', got {method!r}")
     soft = x_soft is not None or u_soft is not None
+    _check_caps("box_qp_layer", method, False, soft, x_soft_max is not None or u_soft_max is not None)
     if soft and method != "pdas":
         raise ValueError("box_qp_layer: x_soft and u_soft need method='pdas' (ADMM and the polish have no soft bounds)")
-    Gb, Cb, g, cc, lo, hi, wt, Bt, batched, sol = _prepare("box_qp_layer", (Q, R, A, B, q, r, c), x_lo, x_hi, u_lo, u_hi,
-                                                           x_soft, u_soft)
+    Gb, Cb, g, cc, lo, hi, wt, mt, Bt, batched, sol = _prepare("box_qp_layer", (Q, R, A, B, q, r, c), x_lo, x_hi, u_lo, u_hi,
+                                                               x_soft, u_soft, x_soft_max, u_soft_max)
+    if mt is not None:
+        mt = mt.contiguous()
     opts = dict(rho=float(rho), exit_tol=float(exit_tol), max_iters=int(max_iters), admm_rho=admm_rho, sigma=sigma, alpha=alpha,
                 eps_abs=eps_abs, eps_rel=eps_rel, max_admm_iters=max_admm_iters, check_every=check_every)
     if method == "pdas":
         opts["max_pdas_iters"] = int(max_pdas_iters)
     box = []
-    x, lam = _BoxQPLayer.apply(Gb, Cb, g, cc, lo, hi, wt, sol, opts, box)
+    x, lam = _BoxQPLayer.apply(Gb, Cb, g, cc, lo, hi, wt, mt, sol, opts, box)
     info = _shaped(box[0], sol, Bt, batched)
     info = BoxQPResult(*(t.detach().clone() for t in (info.x, info.z, info.y, info.lam, info.iters, info.status, info.res_prim,
                                                       info.res_dual, info.polished)),

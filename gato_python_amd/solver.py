@@ -282,7 +282,7 @@ class Solver:
         return codes
 
     def box_qp_pdas(self, Gb, Cb, g, c, lo, hi, *, rho, exit_tol, max_iters, eps_abs=1e-6, eps_rel=1e-6, max_pdas_iters=30,
-                    act=None, x=None, z=None, y=None, lam=None, soft_weight=None):
+                    act=None, x=None, z=None, y=None, lam=None, soft_weight=None, soft_cap=None):
         """The box QP of box_qp by the primal-dual active-set iteration (gato_box_qp_pdas): the polish
         iterated from the active set act [B N] int8 (None: nothing active, a cold start; the tensor is not written) until
         the polished point passes the polish's test.  No penalty parameter and no ADMM.  Returns a BoxQPResult: status
@@ -293,7 +293,13 @@ class Solver:
         soft_weight [B N] (gato_box_qp_pdas_soft): a weight w_i >= 0 per variable; w_i > 0 replaces the
         bound of variable i by the penalty (w_i / 2) dist(x_i, [lo_i, hi_i])^2 - where such a variable violates its bound it is
         active, x holds the reduced solution, z = x and y = w_i (x_i - b_i) - and w_i = 0 keeps the hard bound.  A weight that
-        is NaN, negative or infinite raises ValueError.  None: gato_box_qp_pdas."""
+        is NaN, negative or infinite raises ValueError.  None: gato_box_qp_pdas.
+        soft_cap [B N] (with soft_weight; gato_box_qp_pdas_huber): a cap m_i >= 0 on the penalty force of
+        variable i, read where w_i > 0; +inf: none.  The penalty is then the Huber function; where w_i (x_i - b_i) passes m_i the
+        variable is saturated - act = +2 above hi, -2 below lo - and y = +-m_i.  act may hold +-2 on such variables.  A cap that is
+        NaN or negative raises ValueError.  None: gato_box_qp_pdas_soft."""
+        if soft_cap is not None and soft_weight is None:
+            raise ValueError("box_qp_pdas: soft_cap needs soft_weight (a cap is read only where the weight is positive)")
         B, N, sk = self.batch, self.N, self.sizes["sk"]
         zeros = lambda n: torch.zeros(n, dtype=self.dtype, device=f"cuda:{self.device}")
         x = zeros(B * N) if x is None else x
@@ -308,6 +314,8 @@ class Solver:
         self._check_vecs("box_qp_pdas", Gb=Gb, Cb=Cb, g=g, c=c, lo=lo, hi=hi, x=x, z=z, y=y, lam=lam)
         if soft_weight is not None:
             self._check_vecs("box_qp_pdas", soft_weight=soft_weight)
+        if soft_cap is not None:
+            self._check_vecs("box_qp_pdas", soft_cap=soft_cap)
         iters = torch.zeros(B, dtype=torch.int32, device=act.device)
         status = self.new(B, torch.int32)
         res = torch.zeros(2 * B, dtype=torch.float64, device=act.device)
@@ -316,9 +324,12 @@ class Solver:
                 self._stream())
         if soft_weight is None:
             rc = _lib.lib().gato_box_qp_pdas(self._h, _ptr(Gb), _ptr(Cb), _ptr(g), _ptr(c), _ptr(lo), _ptr(hi), _ptr(act), *tail)
-        else:
+        elif soft_cap is None:
             rc = _lib.lib().gato_box_qp_pdas_soft(self._h, _ptr(Gb), _ptr(Cb), _ptr(g), _ptr(c), _ptr(lo), _ptr(hi),
                                                   _ptr(soft_weight), _ptr(act), *tail)
+        else:
+            rc = _lib.lib().gato_box_qp_pdas_huber(self._h, _ptr(Gb), _ptr(Cb), _ptr(g), _ptr(c), _ptr(lo), _ptr(hi),
+                                                   _ptr(soft_weight), _ptr(soft_cap), _ptr(act), *tail)
         msg = _lib.lib().gato_last_error().decode() if rc != 0 else ""
         if "BAD_BOUNDS" in msg or "BAD_ACTIVE" in msg:
             st = status.cpu()
@@ -333,9 +344,11 @@ class Solver:
     def _bound_grads(self, entry, what, Gb, Cb, act, soft, xbar, a, beta, **bars):
         """The body of the two bound-gradient methods: allocates the outputs bars (by name) that are None, checks every
         operand as `what`, calls the C entry and returns the outputs.  soft: the operands only the soft entry takes, in its
-        order (soft_weight, lo, hi, x; a soft_weight of None goes as a null pointer), or () for the entry without weights."""
+        order (soft_weight, lo, hi, x, or soft_weight, soft_cap, lo, hi, x for the capped entry; a soft_weight or soft_cap of
+        None goes as a null pointer), or () for the entry without weights."""
         bars = {name: self.new(self.batch * self.N) if t is None else t for name, t in bars.items()}
-        own = {name: t for name, t in zip(("soft_weight", "lo", "hi", "x"), soft) if name != "soft_weight" or t is not None}
+        names = ("soft_weight", "soft_cap", "lo", "hi", "x") if len(soft) == 5 else ("soft_weight", "lo", "hi", "x")
+        own = {name: t for name, t in zip(names, soft) if name not in ("soft_weight", "soft_cap") or t is not None}
         self._check_vecs(what, Gb=Gb, Cb=Cb, act=act, **own, xbar=xbar, a=a, beta=beta, **bars)
         _lib.check(entry(self._h, _ptr(Gb), _ptr(Cb), _ptr(act), *map(_ptr, soft), _ptr(xbar), _ptr(a), _ptr(beta),
                          *map(_ptr, bars.values()), self._stream()))
@@ -354,6 +367,15 @@ class Solver:
         soft_weight None: all hard."""
         return self._bound_grads(_lib.lib().gato_box_qp_soft_grad, "box_qp_soft_grad", Gb, Cb, act, (soft_weight, lo, hi, x),
                                  xbar, a, beta, lo_bar=lo_bar, hi_bar=hi_bar, w_bar=w_bar)
+
+    def box_qp_huber_grad(self, Gb, Cb, act, soft_weight, soft_cap, lo, hi, x, xbar, a, beta, lo_bar=None, hi_bar=None,
+                          w_bar=None, cap_bar=None):
+        """(lo_bar, hi_bar, w_bar, cap_bar) [B N] of a converged box_qp_pdas(soft_weight=, soft_cap=) point
+        (gato_box_qp_huber_grad): a saturated variable (act = +-2, s its sign) gets cap_bar_i = -s a_i and 0 in the other
+        three, every other variable what box_qp_soft_grad gives it and cap_bar_i = 0.  soft_cap None: no caps."""
+        return self._bound_grads(_lib.lib().gato_box_qp_huber_grad, "box_qp_huber_grad", Gb, Cb, act,
+                                 (soft_weight, soft_cap, lo, hi, x), xbar, a, beta, lo_bar=lo_bar, hi_bar=hi_bar, w_bar=w_bar,
+                                 cap_bar=cap_bar)
 
     def box_qp_pcg_iters(self):
         """PCG iterations of all x-steps of the latest box_qp call, per system (host int array)."""

@@ -455,6 +455,33 @@ int gato_box_qp_pdas_soft(gato_solver *s, const void *d_G_blocks, const void *d_
 int gato_box_qp_soft_grad(gato_solver *s, const void *d_G_blocks, const void *d_C_blocks, const signed char *d_act,
                           const void *d_soft_w, const void *d_lo, const void *d_hi, const void *d_x, const void *d_xbar,
                           const void *d_a, const void *d_beta, void *d_lo_bar, void *d_hi_bar, void *d_w_bar, void *stream);
+/* gato_box_qp_pdas_soft with capped penalty forces: d_soft_cap [B][N] holds a cap m_i >= 0 per variable (dz
+ * layout; +inf: no cap; NULL: every cap +inf), read only where w_i > 0.  The penalty of a soft variable becomes the Huber
+ * function h_i(d) = (w_i / 2) d^2 while w_i d <= m_i and m_i d - m_i^2 / (2 w_i) beyond, d = dist(x_i, [lo_i, hi_i]): the force
+ * is clamp(w_i (x_i - clip(x_i)), -m_i, m_i).  act takes two more values: +2 (-2) names a variable saturated above hi (below
+ * lo; where lo == hi the sign is that of the force).  A saturated variable is free in the reduced system - no diagonal term,
+ * g_i loses s m_i, s the sign of its act - and has d_x the reduced solution, d_z = d_x and d_y = s m_i bit for bit.  The
+ * acceptance test is that of gato_box_qp_pdas_soft, and also fails (within the dual tolerance) where |y_i| > m_i on a soft
+ * variable with act +-1 or where s w_i (x_i - b_i) < m_i on a saturated one.  The next act of a soft variable with a finite cap,
+ * from x alone with exact comparisons on the product f = w_i (x_i - hi_i): +2 where f > m_i, else +1 where x_i > hi_i; mirrored
+ * below lo_i; lo == hi: +2 where f > m_i, -2 where -f > m_i, else -1; every other variable as in gato_box_qp_pdas_soft.  A start
+ * act of +-2 is taken only on a variable with w_i > 0, a finite cap, a finite bound and off x_0 (else GATO_QP_BAD_ACTIVE); a
+ * cap that is NaN or negative marks its system GATO_QP_BAD_BOUNDS.  A cap of 0 removes the bound.  With d_soft_cap NULL or all
+ * +inf every output is bit for bit that of gato_box_qp_pdas_soft.  The iteration is still undamped: it may cycle and end in
+ * MAX_ITERS.  Refusals, blocking behaviour and side effects are those of gato_box_qp_pdas_soft; the last assembly is that of
+ * the returned d_act (saturated variables free), so gato_solve_rhs is the adjoint of the backward pass. */
+int gato_box_qp_pdas_huber(gato_solver *s, const void *d_G_blocks, const void *d_C_blocks, const void *d_g, const void *d_c,
+                           const void *d_lo, const void *d_hi, const void *d_soft_w /* [B][N], NULL = all hard */,
+                           const void *d_soft_cap /* [B][N], NULL = no cap */, signed char *d_act, const gato_box_qp_params *p,
+                           int max_pdas_iters, void *d_x, void *d_z, void *d_y, void *d_lambda, int *d_iters, int *d_status,
+                           double *d_res /* [B][2] */, void *stream);
+/* gato_box_qp_soft_grad for a converged gato_box_qp_pdas_huber point, one launch: a saturated variable i (act = +-2, s its
+ * sign, a finite cap) gets d_cap_bar_i = -s a_i and 0 in d_lo_bar, d_hi_bar and d_w_bar; every other variable gets what
+ * gato_box_qp_soft_grad gives it and d_cap_bar_i = 0.  d_soft_cap may be NULL (no caps: d_cap_bar = 0).  Asynchronous. */
+int gato_box_qp_huber_grad(gato_solver *s, const void *d_G_blocks, const void *d_C_blocks, const signed char *d_act,
+                           const void *d_soft_w, const void *d_soft_cap, const void *d_lo, const void *d_hi, const void *d_x,
+                           const void *d_xbar, const void *d_a, const void *d_beta, void *d_lo_bar, void *d_hi_bar, void *d_w_bar,
+                           void *d_cap_bar, void *stream);
 
 /* ---- direct block input (new): the caller already holds the per-knot blocks in the
  * reference's dense layouts - d_G_blocks as G_dense WITHOUT rho, d_C_blocks as C_dense - so the CSR scatter is
