@@ -3,10 +3,16 @@
 The problem is that of box_qp_ref:  min 1/2 x^T H x - g^T x  s.t.  C x = c,  lo <= x <= hi,  H = G + rho I  (dz layout).
 active_set() is OSQP's rule on (z, y) of an ADMM result; reduced_solve() is the exact KKT solution with the active variables
 fixed at their bounds, [[H_FF, C_F^T], [C_F, 0]] [x_F; lam] = [g_F - H_FA b_A; c - C_A b_A]; polish() adds the device's
-acceptance test; grads() is the backward pass of DESIGN.md section 3.6 applied to the reduced system.  H and C may be
+acceptance test; grads() is the backward pass of DESIGN.md section 3.6 applied to the reduced system.  The reduced system is
+also that of the active-set iteration (box_qp_active_ref), whose bounds may be soft (a weight vector
+w >= 0, w_i > 0 penalises the bound of variable i by (w_i / 2) dist^2; a soft-active variable stays in the system, its
+diagonal entry gains w_i, g gains w_i b_i, and its multiplier is the force y_i = w_i (x_i - b_i)) and capped (section 3.11: a
+cap m_i on that force; act = +-2 names a saturated variable, free in the system with g_i - s m_i and y_i = s m_i).  w=None
+means all hard, m=None no caps; every function here is one implementation for the three forms.  H and C may be
 scipy.sparse matrices (box_qp_ref.sparse_parts).  constructed_problem() builds QPs with a known active set (active states
 included) at any shape, constructed() walks its seeds by a rule on the reference alone, and reduced_stage_solve() restates
 the device's route to the reduced solution on the oracle's stages in a given dtype."""
+import dataclasses
 import os
 import sys
 
@@ -49,12 +55,37 @@ def _sub(M, rows, cols):
     return M[rows][:, cols] if ref.is_sparse(M) else M[np.ix_(rows, cols)]
 
 
-def _reduced_solver(H, Cm, act):
-    """(solve, F) of the reduced matrix [[H_FF, C_F^T], [C_F, 0]]; F the indices of the free variables.  solve(rhs) gives
-    NaN where the matrix is singular (LICQ fails).  Dense: np.linalg.solve; sparse: one splu factorisation."""
-    F = np.flatnonzero(np.asarray(act) == 0)
+def soft_set(act, w=None):
+    """The soft-active variables: active with a positive weight (the saturated ones included)."""
+    act = np.asarray(act)
+    return (act != 0) & (np.asarray(w) > 0) if w is not None else np.zeros(act.shape, bool)
+
+
+def sat_set(act):
+    """The saturated variables: act = +-2."""
+    return np.abs(np.asarray(act, np.int64)) == 2
+
+
+def hard_set(act, w=None):
+    """The hard-active variables: active, not soft, eliminated from the reduced system."""
+    return (np.asarray(act) != 0) & ~soft_set(act, w)
+
+
+def unsaturated(act):
+    """act with the saturated variables free: the act whose quadratic reduced system the saturated one shares."""
+    act = np.asarray(act, np.int8)
+    return np.where(sat_set(act), 0, act).astype(np.int8)
+
+
+def _reduced_solver(H, Cm, act, w=None):
+    """(solve, F) of the reduced matrix [[H_FF + diag(w) on the soft-active, C_F^T], [C_F, 0]]; F the indices of the variables
+    that are not hard-active.  solve(rhs) gives NaN where the matrix is singular (LICQ fails).  Dense: np.linalg.solve;
+    sparse: one splu factorisation."""
+    act = unsaturated(act)
+    soft = soft_set(act, w)
+    F = np.flatnonzero(~hard_set(act, w))
     if not ref.is_sparse(H):
-        M = reduced_matrix(H, Cm, act)
+        M = reduced_matrix(H, Cm, act, w)
 
         def solve(rhs):
             try:
@@ -63,35 +94,51 @@ def _reduced_solver(H, Cm, act):
                 return np.full(len(rhs), np.nan)
         return solve, F
     try:
-        solve = ref.kkt_solver(_sub(H, F, F), _cols(Cm, F))
+        solve = ref.kkt_solver(_sub(H, F, F), _cols(Cm, F), diag=np.where(soft, w, 0.0)[F] if soft.any() else None)
     except RuntimeError:                                  # splu: "Factor is exactly singular"
         solve = lambda rhs: np.full(len(rhs), np.nan)
     return solve, F
 
 
-def reduced_matrix(H, Cm, act):
-    """The dense reduced matrix [[H_FF, C_F^T], [C_F, 0]] (for its condition number; dense sizes only)."""
-    F = np.flatnonzero(np.asarray(act) == 0)
+def reduced_matrix(H, Cm, act, w=None):
+    """The dense reduced matrix [[H_FF, C_F^T], [C_F, 0]], w_i on the diagonal of the soft-active (for its condition number;
+    dense sizes only)."""
+    act = unsaturated(act)
+    soft = soft_set(act, w)
+    F = np.flatnonzero(~hard_set(act, w))
     m = Cm.shape[0]
     dense = lambda M: M.toarray() if ref.is_sparse(M) else M
-    return np.block([[dense(_sub(H, F, F)), dense(_cols(Cm, F)).T], [dense(_cols(Cm, F)), np.zeros((m, m))]])
+    M = np.block([[dense(_sub(H, F, F)), dense(_cols(Cm, F)).T], [dense(_cols(Cm, F)), np.zeros((m, m))]])
+    if soft.any():
+        M[np.arange(len(F)), np.arange(len(F))] += np.where(soft, w, 0.0)[F]
+    return M
 
 
-def reduced_solve(H, Cm, g, c, lo, hi, act):
-    """(x, y, lam) of the reduced KKT system: x_A = b_A exactly, y_A = (g - H x - C^T lam)_A, y_F = 0.  A singular reduced
-    system (LICQ fails) gives NaN.  H, Cm dense or scipy.sparse."""
+def reduced_solve(H, Cm, g, c, lo, hi, act, w=None, m=None):
+    """(x, y, lam) of the reduced KKT system: x_i = b_i exactly and y_i = (g - H x - C^T lam)_i on the hard-active set, y_i =
+    w_i (x_i - b_i) on the soft-active one, y_i = s m_i on the saturated one, y = 0 elsewhere.  A singular reduced system (LICQ
+    fails) gives NaN.  H, Cm dense or scipy.sparse."""
     act = np.asarray(act)
-    A = np.flatnonzero(act != 0)
+    sat = sat_set(act)
+    if sat.any():
+        push = np.where(sat, np.sign(act) * np.where(sat, m, 0.0), 0.0)
+        g, act = g - push, unsaturated(act)
+    soft = soft_set(act, w)
+    A = np.flatnonzero(hard_set(act, w))
     b = bound_values(act, lo, hi)
-    solve, F = _reduced_solver(H, Cm, act)
-    rhs = np.concatenate([g[F] - _sub(H, F, A) @ b[A], c - _cols(Cm, A) @ b[A]])
-    sol = solve(rhs)
+    solve, F = _reduced_solver(H, Cm, act, w)
+    top = g[F] + (np.where(soft, w, 0.0) * b)[F] if soft.any() else g[F]
+    sol = solve(np.concatenate([top - _sub(H, F, A) @ b[A], c - _cols(Cm, A) @ b[A]]))
     x = np.zeros(len(g))
     x[A] = b[A]
     x[F] = sol[:len(F)]
     lam = sol[len(F):]
     y = np.zeros(len(g))
     y[A] = (g - H @ x - Cm.T @ lam)[A]
+    if soft.any():
+        y[soft] = (w * (x - b))[soft]
+    if sat.any():
+        y = np.where(sat, push, y)
     return x, y, lam
 
 
@@ -115,33 +162,44 @@ def polish(H, Cm, g, c, lo, hi, z, y, S, eps_abs=1e-6, eps_rel=1e-6, act=None):
     return out
 
 
-def adjoint(H, Cm, act, xbar, lambar):
-    """[a; beta] of the reduced system for upstream gradients (xbar, lambar): a_A = 0."""
-    solve, F = _reduced_solver(H, Cm, act)
+def adjoint(H, Cm, act, xbar, lambar, w=None):
+    """[a; beta] of the reduced system for upstream gradients (xbar, lambar): a = 0 on the hard-active set."""
+    solve, F = _reduced_solver(H, Cm, act, w)
     sol = solve(np.concatenate([np.asarray(xbar, np.float64)[F], np.asarray(lambar, np.float64)]))
     a = np.zeros(H.shape[0])
     a[F] = sol[:len(F)]
     return a, sol[len(F):]
 
 
-def bound_grads(H, Cm, act, xbar, a, beta):
-    """(lo_bar, hi_bar) [N]: on A, xbar - (H a + C^T beta) goes to hi for act = +1 and to lo for act = -1 (lo == hi: to lo,
-    hi gets 0); free coordinates get 0 in both."""
+def bound_grads(H, Cm, act, xbar, a, beta, w=None, lo=None, hi=None, x=None):
+    """(lo_bar, hi_bar) [N], and with weights (lo_bar, hi_bar, w_bar): b_bar is xbar_i - (H a + C^T beta)_i on a hard-active i
+    and w_i a_i on a soft-active one, and goes to hi for act = +1 and to lo for act = -1 (lo == hi: to lo, hi gets 0); w_bar_i =
+    a_i (b_i - x_i) on the soft-active; 0 elsewhere."""
     act = np.asarray(act)
-    bb = np.where(act != 0, np.asarray(xbar, np.float64) - (H @ a + Cm.T @ beta), 0.0)
-    return np.where(act < 0, bb, 0.0), np.where(act > 0, bb, 0.0)
+    soft = soft_set(act, w)
+    bb = np.where(hard_set(act, w), np.asarray(xbar, np.float64) - (H @ a + Cm.T @ beta), 0.0)
+    if w is None:
+        return np.where(act < 0, bb, 0.0), np.where(act > 0, bb, 0.0)
+    bb = np.where(soft, w * a, bb)
+    return np.where(act < 0, bb, 0.0), np.where(act > 0, bb, 0.0), np.where(soft, a * (bound_values(act, lo, hi) - x), 0.0)
 
 
-def grads(H, Cm, act, x, lam, xbar, lambar, S, C, K):
-    """Gradients of L = xbar . x + lambar . lam through the polished solution with respect to all eleven inputs of
-    box_qp_layer: dict Q, R, A, B, q, r, c (kkt_grad_ref.grads_math on the reduced adjoint) and x_lo, x_hi [K, S], u_lo,
-    u_hi [K-1, C]; also a, beta, lo, hi (dz layout)."""
-    a, beta = adjoint(H, Cm, act, xbar, lambar)
+def grads(H, Cm, act, x, lam, xbar, lambar, S, C, K, w=None, m=None, lo=None, hi=None):
+    """Gradients of L = xbar . x + lambar . lam through a converged point with respect to the inputs of box_qp_layer: dict Q, R,
+    A, B, q, r, c (kkt_grad_ref.grads_math on the reduced adjoint) and x_lo, x_hi [K, S], u_lo, u_hi [K-1, C]; with w (and lo,
+    hi) also x_soft, u_soft; with m also x_soft_max, u_soft_max - the saturated variables are free, get 0 in lo, hi and w, and
+    m_bar_i = -s a_i.  Eleven, thirteen or fifteen inputs; also a, beta, lo, hi (and w, m) in the dz layout."""
+    sat, sign = sat_set(act), np.sign(np.asarray(act, np.int8))
+    act = unsaturated(act)
+    a, beta = adjoint(H, Cm, act, xbar, lambar, w)
     out = kgr.grads_math(x, lam, a, beta, S, C, K)
-    lo_bar, hi_bar = bound_grads(H, Cm, act, xbar, a, beta)
-    out["x_lo"], out["u_lo"] = split_states_controls(lo_bar, S, C, K)
-    out["x_hi"], out["u_hi"] = split_states_controls(hi_bar, S, C, K)
-    out.update(a=a, beta=beta, lo=lo_bar, hi=hi_bar)
+    bars = dict(zip(("lo", "hi", "w"), bound_grads(H, Cm, act, xbar, a, beta, w, lo, hi, x)))
+    if m is not None:
+        bars["m"] = np.where(sat, -sign * a, 0.0)
+    for k, name in (("lo", "lo"), ("hi", "hi"), ("w", "soft"), ("m", "soft_max")):
+        if k in bars:
+            out["x_" + name], out["u_" + name] = split_states_controls(bars[k], S, C, K)
+    out.update(a=a, beta=beta, **bars)
     return out
 
 
@@ -318,15 +376,16 @@ def meets_seed_rule(p, cond=True):
 
 
 def rounded(p):
-    """The constructed problem with every input rounded to fp32 (values held in fp64; rho rounded too) and its fp64 reduced
-    solution: the truth an fp32 polish is judged against."""
+    """The problem with every input rounded to fp32 (values held in fp64; rho rounded too, and the weights "w" and caps "m" where
+    it has them) and the fp64 reduced solution on its act: the truth an fp32 run is judged against."""
     s = p["s"].astype(np.float32).astype(np.float64)
     s.rho = float(np.float32(p["s"].rho))
     f32 = lambda a: np.asarray(a, np.float32).astype(np.float64)
     H, Cm, g, c = ref.parts(s)
     lo, hi = f32(p["lo"]), f32(p["hi"])
-    x, y, lam = reduced_solve(H, Cm, g, c, lo, hi, p["act"])
-    return dict(p, s=s, H=H, Cm=Cm, g=g, c=c, lo=lo, hi=hi, x=x, y=y, lam=lam)
+    wm = {k: f32(p[k]) for k in ("w", "m") if k in p}
+    x, y, lam = reduced_solve(H, Cm, g, c, lo, hi, p["act"], **wm)
+    return dict(p, s=s, H=H, Cm=Cm, g=g, c=c, lo=lo, hi=hi, x=x, y=y, lam=lam, **wm)
 
 
 def restatement_accepted(p, dtype, eps, max_iters=1000):
@@ -391,27 +450,41 @@ def wrong_sign(p):
 
 
 # ---- the reduced stage path restated in a given dtype ----------------------------------------------------------------------
-def reduced_stage_solve(s, lo, hi, act, dtype, exit_tol=1e-8, max_iters=1000):
-    """What the device's polish computes, restated in `dtype` on the oracle's stages: Q_k and R_k (rho added) with the active
-    rows and columns replaced by the identity, the oracle's Gauss-Jordan inverse, the active entries zeroed; g' = g - H_:A
-    b_A (0 on A), c' = c - C_:A b_A (C's identity blocks included); form_schur with those inverses, form_ss, pcg,
-    compute_dz; x = b on A, dz elsewhere.  -> (x, lam, pcg iterations)."""
+def reduced_stage_solve(s, lo, hi, act, dtype, exit_tol=1e-8, max_iters=1000, w=None, m=None):
+    """What the device's reduced solve computes, restated in `dtype` on the oracle's stages: Q_k and R_k (rho added) with the
+    hard-active rows and columns replaced by the identity, the oracle's Gauss-Jordan inverse, the hard-active entries zeroed;
+    g' = g - H_:A b_A (0 on A), c' = c - C_:A b_A (C's identity blocks included); form_schur with those inverses, form_ss, pcg,
+    compute_dz; x = b on A, dz elsewhere.  With weights the diagonal of Q_k, R_k gains w_i and g' gains w_i b_i on the
+    soft-active set (0 elsewhere: the terms are added whenever w is given, as the device adds them); with caps a saturated
+    variable is free, its g_i - s m_i formed in `dtype`.  -> (x, lam, pcg iterations)."""
     from oracle import gato_oracle as o
     dt = np.dtype(dtype).type
+    act = np.asarray(act, np.int8)
+    sat = sat_set(act)
+    if sat.any():
+        push = np.where(sat, np.sign(act) * np.where(sat, m, 0.0), 0.0).astype(dt)
+        s, act = dataclasses.replace(s, g=(np.asarray(s.g, dt) - push).astype(dt)), unsaturated(act)
     S, C, K, n = s.S, s.C, s.K, s.S + s.C
     Q, R, A, B, q, r, c = (np.asarray(t, dt) for t in kgr.blocks_of(s))
     rho = dt(s.rho)
     Q = Q + rho * np.eye(S, dtype=dt)
     R = R + rho * np.eye(C, dtype=dt)
-    act = np.asarray(act)
-    on = act != 0
-    b = bound_values(act, np.asarray(lo, dt), np.asarray(hi, dt)).astype(dt)
+    soft, on = soft_set(act, w), hard_set(act, w)
+    ball = bound_values(act, np.asarray(lo, dt), np.asarray(hi, dt)).astype(dt)
+    b = np.where(on, ball, dt(0)).astype(dt)
     xs, us = (np.arange(K)[:, None] * n + np.arange(S)), (np.arange(K - 1)[:, None] * n + S + np.arange(C))
     onx, onu, bx, bu = on[xs], on[us], b[xs], b[us]
-    eye = lambda m: np.eye(m, dtype=dt)[None]
+    eye = lambda k: np.eye(k, dtype=dt)[None]
     mx, mu = onx[:, :, None] | onx[:, None, :], onu[:, :, None] | onu[:, None, :]
-    Qi = np.where(mx, dt(0), o.gauss_jordan_inverse(np.where(mx, eye(S), Q)))
-    Ri = np.where(mu, dt(0), o.gauss_jordan_inverse(np.where(mu, eye(C), R)))
+    Qw, Rw = Q, R
+    if w is not None:
+        d = np.where(soft, np.asarray(w, dt), dt(0)).astype(dt)
+        db = (d * np.where(soft, ball, dt(0))).astype(dt)
+        Qw = Q + d[xs][:, :, None] * np.eye(S, dtype=dt)
+        Rw = R + d[us][:, :, None] * np.eye(C, dtype=dt)
+        q, r = q + db[xs], r + db[us]
+    Qi = np.where(mx, dt(0), o.gauss_jordan_inverse(np.where(mx, eye(S), Qw)))
+    Ri = np.where(mu, dt(0), o.gauss_jordan_inverse(np.where(mu, eye(C), Rw)))
     # g' and c': the kernel's fma chains are sums of a few products; numpy's matrix products in dt stand for them
     qp = np.where(onx, dt(0), q - np.einsum("kij,kj->ki", Q, bx))
     rp = np.where(onu, dt(0), r - np.einsum("kij,kj->ki", R, bu))

@@ -8,8 +8,8 @@ import re
 import numpy as np
 import pytest
 
+import box_qp_active_ref as AS
 import box_qp_huber_ref as R
-import box_qp_pdas_ref as D
 import box_qp_polish_ref as P
 import box_qp_ref as ref
 import box_qp_soft_ref as SR
@@ -30,13 +30,17 @@ def test_the_rule_on_capped_variables():
     act = np.array([0,   0,         2,          1,      0,          -1,        -1,      -1,      2,       0,       1,        0], np.int8)
     x = np.array([9.0,   1.5,       1.125,      0.5,    -1.125,     -1.5,      0.625,   1.0,     0.0,     9.0,     1.0,      1.25])
     y = np.array([0.0,   0.0,       0.0,        0.0,    0.0,        0.0,       0.0,     0.0,     0.0,     0.0,     0.3,      0.0])
-    assert R.next_act(act, x, y, lo, hi, w, m, S).tolist() == [0, 2, 1, 0, -1, -2, -1, 2, -2, 1, 1, 2]
+    assert AS.next_act(act, x, y, lo, hi, S, w, m).tolist() == [0, 2, 1, 0, -1, -2, -1, 2, -2, 1, 1, 2]
+    # a tie is not past the cap: at x = b +- m / w exactly the product equals m and the variable stays quadratic-active
+    one = lambda v: np.array([0.0, v])
+    tie = lambda xv: AS.next_act(np.zeros(2, np.int8), one(xv), np.zeros(2), one(-1.0), one(1.0), S, one(4.0), one(1.0))[1]
+    assert tie(1.25) == 1 and tie(-1.25) == -1
     # the switching points are b +- m / w = b +- 0.25: x = 1.125 is 0.125 from hi and 0.125 from hi + 0.25
-    assert R.decision_margin(act, x, y, lo, hi, w, np.where(np.arange(12) == 2, m, np.inf), S) == pytest.approx(0.125)
+    assert AS.decision_margin(act, x, y, lo, hi, S, w, np.where(np.arange(12) == 2, m, np.inf)) == pytest.approx(0.125)
     only = lambda j, cap: np.where(np.arange(12) == j, cap, np.inf)
-    assert R.decision_margin(act, x, y, lo, hi, w, only(1, 1.9), S) == pytest.approx(0.025)     # x = 1.5 against hi + 1.9 / 4
-    assert R.sat_set(act).tolist() == [j in (2, 8) for j in range(12)]
-    assert R.quad_set(act, w).tolist() == [j in (3, 5, 6, 7) for j in range(12)]
+    assert AS.decision_margin(act, x, y, lo, hi, S, w, only(1, 1.9)) == pytest.approx(0.025)     # x = 1.5 against hi + 1.9 / 4
+    assert P.sat_set(act).tolist() == [j in (2, 8) for j in range(12)]
+    assert AS.quad_set(act, w).tolist() == [j in (3, 5, 6, 7) for j in range(12)]
 
 
 def test_point_of_a_saturated_variable():
@@ -44,12 +48,12 @@ def test_point_of_a_saturated_variable():
     quadratic-active set; the converged point satisfies the Huber KKT system."""
     p = R.huber_box(6, 3, 9)[0]
     run, w, m, lo, hi = p["run"], p["w"], p["m"], p["lo"], p["hi"]
-    sat, quad = R.sat_set(run["act"]), R.quad_set(run["act"], w)
+    sat, quad = P.sat_set(run["act"]), AS.quad_set(run["act"], w)
     assert sat.any() and quad.any()
     assert np.array_equal(run["y"][sat], np.sign(run["act"])[sat] * m[sat]) and np.array_equal(run["z"][sat], run["x"][sat])
     b = P.bound_values(run["act"], lo, hi)
     assert np.all((np.sign(run["act"]) * w * (run["x"] - b))[sat] > m[sat]) and np.all(np.abs(run["y"])[quad] <= m[quad])
-    kk = R.kkt_residuals(p["H"], p["Cm"], p["g"], p["c"], lo, hi, w, m, run["x"], run["y"], run["lam"])
+    kk = AS.kkt_residuals(p["H"], p["Cm"], p["g"], p["c"], lo, hi, run["x"], run["y"], run["lam"], w, m)
     print(kk)
     assert max(kk.values()) <= 1e-9
 
@@ -60,15 +64,15 @@ def test_an_act_that_disagrees_with_its_point_fails_the_test():
     p = R.huber_box(6, 3, 9)[0]
     run, w, m = p["run"], p["w"], p["m"]
     args = tuple(p[k] for k in ("H", "Cm", "g", "c", "lo", "hi"))
-    assert R.point(*args, w, m, run["act"], run["x"], run["y"], run["lam"], 1e-6, 1e-6)[4]
-    for frm in (R.sat_set(run["act"]), R.quad_set(run["act"], w) & (p["lo"] != p["hi"])):
+    assert AS.point(*args, run["act"], run["x"], run["y"], run["lam"], 1e-6, 1e-6, w, m)[4]
+    for frm in (P.sat_set(run["act"]), AS.quad_set(run["act"], w) & (p["lo"] != p["hi"])):
         j = np.flatnonzero(frm)[0]
         act = run["act"].copy()
         act[j] = np.sign(act[j]) * (1 if abs(act[j]) == 2 else 2)
-        x, y, lam = R.reduced_solve(*args, w, m, act)
-        exc = R.cap_excess(act, x, y, p["lo"], p["hi"], w, m)
+        x, y, lam = P.reduced_solve(*args, act, w, m)
+        exc = AS.cap_excess(act, x, y, p["lo"], p["hi"], w, m)
         print(j, "act", run["act"][j], "->", act[j], "excess", exc[j])
-        assert exc[j] > 1e-3 and not R.point(*args, w, m, act, x, y, lam, 1e-6, 1e-6)[4]
+        assert exc[j] > 1e-3 and not AS.point(*args, act, x, y, lam, 1e-6, 1e-6, w, m)[4]
 
 
 NOCAP = [(6, 3, 9, 1e2), (14, 7, 3, 1e2), (4, 2, 9, 1e4), (2, 1, 20, 1e2)]
@@ -81,8 +85,8 @@ def test_infinite_caps_are_the_soft_reference(S, C, K, weight):
         s, H, Cm, g, c, lo, hi, w = SR.double_integrator_soft()
     else:
         s, H, Cm, g, c, lo, hi, w = SR.soft_problem(S, C, K, 0, weight=weight)
-    a = SR.pdas_soft(H, Cm, g, c, lo, hi, w, S)
-    b = R.pdas_huber(H, Cm, g, c, lo, hi, w, np.full(len(g), np.inf), S)
+    a = AS.iterate(H, Cm, g, c, lo, hi, S, w)
+    b = AS.iterate(H, Cm, g, c, lo, hi, S, w, np.full(len(g), np.inf))
     print(a["status"], a["iters"])
     assert (a["status"], a["iters"]) == (b["status"], b["iters"]) and len(a["trace"]) == len(b["trace"])
     for ta, tb in zip(a["trace"], b["trace"]):
@@ -93,10 +97,10 @@ def test_infinite_caps_are_the_soft_reference(S, C, K, weight):
 
 def _slsqp_seed(S, C, K):
     """The first huber_problem seed whose cold run converges on a final act with a saturated variable."""
-    for seed in range(D.WALK_SEEDS):
+    for seed in range(AS.WALK_SEEDS):
         s, H, Cm, g, c, lo, hi, w, m = R.huber_problem(S, C, K, seed)
-        run = R.pdas_huber(H, Cm, g, c, lo, hi, w, m, S)
-        if run["status"] == R.CONVERGED and R.sat_set(run["act"]).any():
+        run = AS.iterate(H, Cm, g, c, lo, hi, S, w, m)
+        if run["status"] == AS.CONVERGED and P.sat_set(run["act"]).any():
             return (H, Cm, g, c, lo, hi, w, m), run, seed
     raise AssertionError("no seed")
 
@@ -111,7 +115,7 @@ def test_converged_point_is_the_slsqp_minimum(S, C, K):
     inf = np.full(len(g), np.inf)
     bounds = [(None if not np.isfinite(l) else l, None if not np.isfinite(h) else h)
               for l, h in zip(np.where(sv, -inf, lo), np.where(sv, inf, hi))]
-    f = lambda x: R.penalised_objective(H, g, lo, hi, w, m, x)
+    f = lambda x: AS.penalised_objective(H, g, lo, hi, x, w, m)
     out = minimize(f, np.zeros(len(g)), jac=True, method="SLSQP", bounds=bounds,
                    constraints=[dict(type="eq", fun=lambda x: Cm @ x - c, jac=lambda x: Cm)], options=dict(ftol=1e-16, maxiter=2000))
     err = np.abs(out.x - run["x"]).max()
@@ -132,7 +136,7 @@ def _solve(inp, rho, act, S):
     hi = ref.dz_layout(inp["x_hi"], inp["u_hi"], S, C, K)
     w = ref.dz_layout(inp["x_soft"], inp["u_soft"], S, C, K)
     m = ref.dz_layout(inp["x_soft_max"], inp["u_soft_max"], S, C, K)
-    run = R.pdas_huber(H, Cm, g, c, lo, hi, w, m, S, act0=act, eps_abs=1e-9, eps_rel=1e-9)
+    run = AS.iterate(H, Cm, g, c, lo, hi, S, w, m, act0=act, eps_abs=1e-9, eps_rel=1e-9)
     return run, (H, Cm, g, c, lo, hi, w, m)
 
 
@@ -141,18 +145,18 @@ def _fd_problem(S, C, K):
     whose final point has every margin >= 1e-3, a saturated state and a saturated control off lo == hi, a soft
     quadratic-active variable and a hard-active one, and a final reduced matrix with cond <= 1e7."""
     n = S + C
-    for seed in range(4 * D.WALK_SEEDS):
+    for seed in range(4 * AS.WALK_SEEDS):
         s, H, Cm, g, c, lo, hi, w, m = R.huber_problem(S, C, K, seed, weight=30.0, cap=0.3)
         idx = np.arange(s.N)
         uc = (idx % n >= S) & ((idx // n) % 2 == 1)
         w[uc], m[uc] = 5.0, 0.1
-        run = R.pdas_huber(H, Cm, g, c, lo, hi, w, m, S)
-        if run["status"] != R.CONVERGED or run["trace"][-1]["margin"] < 1e-3:
+        run = AS.iterate(H, Cm, g, c, lo, hi, S, w, m)
+        if run["status"] != AS.CONVERGED or run["trace"][-1]["margin"] < 1e-3:
             continue
-        sat, quad = R.sat_set(run["act"]) & (lo != hi), R.quad_set(run["act"], w)
-        hard = (run["act"] != 0) & ~SR.soft_set(run["act"], w) & (lo != hi)
+        sat, quad = P.sat_set(run["act"]) & (lo != hi), AS.quad_set(run["act"], w)
+        hard = (run["act"] != 0) & ~P.soft_set(run["act"], w) & (lo != hi)
         if (sat & (idx % n < S)).any() and (sat & (idx % n >= S)).any() and quad.any() and hard.any() \
-                and np.linalg.cond(R.reduced_matrix(H, Cm, run["act"], w)) <= 1e7:
+                and np.linalg.cond(P.reduced_matrix(H, Cm, run["act"], w)) <= 1e7:
             return s, lo, hi, w, m, run
     raise AssertionError("no seed")
 
@@ -171,12 +175,12 @@ def test_gradients_match_finite_differences(S, C, K):
         inp["x_" + name], inp["u_" + name] = split(v)
     act = run0["act"]
     run, (H, Cm, g, cc, lo2, hi2, w2, m2) = _solve(inp, s.rho, act, S)
-    assert run["status"] == R.CONVERGED and run["iters"] == 1 and np.array_equal(lo2, lo) and np.array_equal(m2, m)
+    assert run["status"] == AS.CONVERGED and run["iters"] == 1 and np.array_equal(lo2, lo) and np.array_equal(m2, m)
     x, lam = run["x"], run["lam"]
     rng = np.random.default_rng(7)
     xbar, lambar = rng.standard_normal(len(x)), rng.standard_normal(len(lam))
-    gr = R.huber_grads(H, Cm, act, w, m, lo, hi, x, lam, xbar, lambar, S, C, K)
-    sat = R.sat_set(act)
+    gr = P.grads(H, Cm, act, x, lam, xbar, lambar, S, C, K, w=w, m=m, lo=lo, hi=hi)
+    sat = P.sat_set(act)
     assert gr["a"][sat].all() and not gr["lo"][sat].any() and not gr["hi"][sat].any() and not gr["w"][sat].any()
     assert np.array_equal(gr["m"] != 0, sat)
     L = lambda rr: float(xbar @ rr["x"] + lambar @ rr["lam"])
@@ -204,7 +208,7 @@ def test_gradients_match_finite_differences(S, C, K):
             if partner is not None:
                 pert[partner[0]] = inp[partner[0]] + sgn * FD_STEP * partner[1]
             rp, _ = _solve(pert, s.rho, act, S)
-            assert rp["status"] == R.CONVERGED and rp["iters"] == 1, (key, sgn)
+            assert rp["status"] == AS.CONVERGED and rp["iters"] == 1, (key, sgn)
             vals.append(L(rp))
         fd = (vals[0] - vals[1]) / (2 * FD_STEP)
         an = float(np.sum(gr[key] * V))
@@ -221,16 +225,16 @@ def test_stage_path_is_the_reduced_solve(S, C, K):
     """stage_solve in fp64 - a saturated variable free with g - s m in its row - against the dense solve of the reduced matrix on
     every act of a walked run; the fp64 restatement walks the reference's acts.  Bar: test_box_qp_polish_cpu.py's 1e-9."""
     p = R.huber_box(S, C, K)[0]
-    assert any(R.sat_set(t["act"]).any() for t in p["run"]["trace"])
+    assert any(P.sat_set(t["act"]).any() for t in p["run"]["trace"])
     for t in p["run"]["trace"]:
-        xr, _, lr = R.reduced_solve(p["H"], p["Cm"], p["g"], p["c"], p["lo"], p["hi"], p["w"], p["m"], t["act"])
-        x, lam, iters = R.stage_solve(p["s"], p["lo"], p["hi"], p["w"], p["m"], t["act"], np.float64, exit_tol=1e-30)
+        xr, _, lr = P.reduced_solve(p["H"], p["Cm"], p["g"], p["c"], p["lo"], p["hi"], t["act"], p["w"], p["m"])
+        x, lam, iters = P.reduced_stage_solve(p["s"], p["lo"], p["hi"], t["act"], np.float64, exit_tol=1e-30, w=p["w"], m=p["m"])
         ex = np.abs(x - xr).max() / max(1.0, np.abs(xr).max())
         el = np.abs(lam - lr).max() / max(1.0, np.abs(lr).max())
         print("pcg iterations", iters, "x", ex, "lam", el)
         assert ex <= 1e-9 and el <= 1e-9
-    status, acts = R.huber_stage(p["s"], p["lo"], p["hi"], p["w"], p["m"], np.float64, 1e-6, exit_tol=1e-30)
-    assert status == R.CONVERGED and len(acts) == p["run"]["iters"]
+    status, acts = AS.stage_iterate(p["s"], p["lo"], p["hi"], np.float64, 1e-6, p["w"], p["m"], exit_tol=1e-30)
+    assert status == AS.CONVERGED and len(acts) == p["run"]["iters"]
     assert all(np.array_equal(a, t["act"]) for a, t in zip(acts, p["run"]["trace"]))
 
 
@@ -248,15 +252,15 @@ def test_walk_finds_an_fp64_seed(S, C, K):
     if not ps:
         assert (S, C, K) in R.MAY_BE_EMPTY, "no seed at %d/%d/%d" % (S, C, K)
         pytest.fail("%d/%d/%d: the walk finds no seed below %d with a saturated variable (a cell that may be empty)"
-                    % (S, C, K, D.WALK_SEEDS))
+                    % (S, C, K, AS.WALK_SEEDS))
     p = ps[0]
     run = p["run"]
     sat, quad = R.final_kinds(run, p["w"], p["lo"], p["hi"])
-    print("seed", p["seed"], "solves", run["iters"], "margin", D.min_margin(run), "cond", R.max_cond(run, p["H"], p["Cm"], p["w"]),
+    print("seed", p["seed"], "solves", run["iters"], "margin", AS.min_margin(run), "cond", AS.max_cond(run, p["H"], p["Cm"], p["w"]),
           "saturated", sat, "quadratic", quad)
-    assert p["seed"] < D.WALK_SEEDS and sat and (quad or (S, C, K) in R.MAY_BE_EMPTY)
-    assert R.walk_ok(run, p["lo"], p["hi"], p["w"], p["H"], p["Cm"], both=(S, C, K) not in R.MAY_BE_EMPTY)
-    kk = R.kkt_residuals(p["H"], p["Cm"], p["g"], p["c"], p["lo"], p["hi"], p["w"], p["m"], run["x"], run["y"], run["lam"])
+    assert p["seed"] < AS.WALK_SEEDS and sat and (quad or (S, C, K) in R.MAY_BE_EMPTY)
+    assert AS.walk_ok(run, p["H"], p["Cm"], p["w"])
+    kk = AS.kkt_residuals(p["H"], p["Cm"], p["g"], p["c"], p["lo"], p["hi"], run["x"], run["y"], run["lam"], p["w"], p["m"])
     assert max(kk.values()) <= 1e-9, kk
 
 
@@ -265,9 +269,9 @@ def test_walk_finds_an_fp32_seed(S, C, K):
     """The fp32 restatement, the products w (x - b) formed in float32, walks the reference's acts - and again with every PCG
     stopped one iteration sooner."""
     ps = R.huber_box(S, C, K, f32=True)
-    assert ps and ps[0]["seed"] < D.WALK_SEEDS
+    assert ps and ps[0]["seed"] < AS.WALK_SEEDS
     print("seed", ps[0]["seed"], "solves", ps[0]["run"]["iters"])
-    assert R.f32_ok(ps[0]) and R.sat_set(ps[0]["run"]["act"]).any()
+    assert AS.f32_ok(ps[0]) and P.sat_set(ps[0]["run"]["act"]).any()
 
 
 def test_the_other_gpu_cases_exist():
@@ -280,18 +284,18 @@ def test_the_other_gpu_cases_exist():
         w, m, run = p["w"], p["m"], p["run"]
         ctl = np.arange(p["s"].N) % (S + C) >= S
         assert (np.isfinite(m) & (w > 0)).any() and (np.isinf(m) & (w > 0)).any() and np.all((m >= 0.1) & ((m <= 10.0) | np.isinf(m)))
-        assert (R.sat_set(run["act"]) & ctl & (p["lo"] != p["hi"])).any()
-        kk = R.kkt_residuals(p["H"], p["Cm"], p["g"], p["c"], p["lo"], p["hi"], w, m, run["x"], run["y"], run["lam"])
-        print((S, C, K), "mixed seed", p["seed"], "solves", run["iters"], "margin", D.min_margin(run), kk)
+        assert (P.sat_set(run["act"]) & ctl & (p["lo"] != p["hi"])).any()
+        kk = AS.kkt_residuals(p["H"], p["Cm"], p["g"], p["c"], p["lo"], p["hi"], run["x"], run["y"], run["lam"], w, m)
+        print((S, C, K), "mixed seed", p["seed"], "solves", run["iters"], "margin", AS.min_margin(run), kk)
         assert max(kk.values()) <= 1e-9
     p = R.huber_long()
     run = p["run"]
-    print("long: solves", run["iters"], "margin", D.min_margin(run))
-    assert run["status"] == R.CONVERGED and (np.flatnonzero(R.sat_set(run["act"])) // 3 >= 8192).any()
+    print("long: solves", run["iters"], "margin", AS.min_margin(run))
+    assert run["status"] == AS.CONVERGED and (np.flatnonzero(P.sat_set(run["act"])) // 3 >= 8192).any()
     s, H, Cm, g, c, lo, hi, w = SR.double_integrator_soft(weight=1e6)
-    run = R.pdas_huber(H, Cm, g, c, lo, hi, w, np.where(w > 0, 0.1, np.inf), 2)
+    run = AS.iterate(H, Cm, g, c, lo, hi, 2, w, np.where(w > 0, 0.1, np.inf))
     print("double integrator, w = 1e6, cap 0.1: solves", run["iters"], "violation", np.abs(run["x"] - np.clip(run["x"], lo, hi)).max())
-    assert run["status"] == R.CONVERGED
+    assert run["status"] == AS.CONVERGED
 
 
 def test_entries_declared_and_exported():

@@ -5,6 +5,7 @@ reference gradient summed - against central differences of the reference solutio
 import numpy as np
 import pytest
 
+import box_qp_active_ref as AS
 import box_qp_pdas_ref as D
 import box_qp_polish_ref as P
 import box_qp_ref as ref
@@ -15,9 +16,7 @@ SOLVES = dict(control=[8, 11, 17, 13, 8], constructed=[4, 4, 5, 3, 5], soft=[6, 
 
 def ok(p):
     run = p["run"]
-    if "w" in p:
-        return R.walk_ok(run, p["lo"], p["hi"], p["w"], p["H"], p["Cm"])
-    return D.walk_ok(run, p["H"], p["Cm"])
+    return AS.walk_ok(run, p["H"], p["Cm"], p.get("w"), R.soft_active_on_the_way(p) if "w" in p else None)
 
 
 @pytest.mark.parametrize("kind", R.LAYER_BATCHES)
@@ -35,7 +34,7 @@ def test_batches_hold_systems_with_different_solve_counts(kind):
         assert all((p["run"]["act"] != 0).any() for p in ps)
     if kind == "mixed":
         for p in ps[:3]:
-            sa = R.soft_set(p["run"]["act"], p["w"])
+            sa = P.soft_set(p["run"]["act"], p["w"])
             assert sa.any() and ((p["run"]["act"] != 0) & ~sa).any()        # soft-active and hard-active at the end
 
 
@@ -67,26 +66,26 @@ def test_sum_to():
 
 def test_hard_trio_outcomes():
     good0, bad, good1 = D.di_trio()
-    assert bad["run"]["status"] == D.NONFINITE and bad["run"]["iters"] == 2
+    assert bad["run"]["status"] == AS.NONFINITE and bad["run"]["iters"] == 2
     for p in (good0, good1):
-        assert D.walk_ok(p["run"], p["H"], p["Cm"]) and p["run"]["iters"] <= 30 and (p["run"]["act"] != 0).any()
+        assert AS.walk_ok(p["run"], p["H"], p["Cm"]) and p["run"]["iters"] <= 30 and (p["run"]["act"] != 0).any()
     assert not np.array_equal(good0["c"], good1["c"]) and len({p["s"].rho for p in (good0, bad, good1)}) == 1
 
 
 def test_soft_trio_outcomes():
     soft, bad, good = R.di_soft_trio()
     run = soft["run"]
-    sa = R.soft_set(run["act"], soft["w"])
+    sa = P.soft_set(run["act"], soft["w"])
     n = soft["s"].S + soft["s"].C
     ctl = np.arange(soft["s"].N) % n >= soft["s"].S
-    assert run["status"] == R.CONVERGED and run["iters"] == 11 and ok(soft)
+    assert run["status"] == AS.CONVERGED and run["iters"] == 11 and ok(soft)
     assert int(sa.sum()) == 6 and not sa[ctl].any() and int(((run["act"] != 0) & ~sa).sum()) == 14 and ctl[(run["act"] != 0) & ~sa].all()
     assert np.array_equal(soft["w"], R.state_weights(soft["s"], 100.0))
     hard_bad, hard_good = D.di_trio()[1], D.di_trio()[2]
-    assert not bad["w"].any() and bad["run"]["status"] == R.NONFINITE and bad["run"]["iters"] == 2
+    assert not bad["w"].any() and bad["run"]["status"] == AS.NONFINITE and bad["run"]["iters"] == 2
     assert np.array_equal(bad["run"]["act"], hard_bad["run"]["act"])
-    assert not good["w"].any() and good["run"]["status"] == R.CONVERGED and good["run"]["iters"] == hard_good["run"]["iters"] <= 30
-    assert np.array_equal(good["run"]["act"], hard_good["run"]["act"]) and D.walk_ok(good["run"], good["H"], good["Cm"])
+    assert not good["w"].any() and good["run"]["status"] == AS.CONVERGED and good["run"]["iters"] == hard_good["run"]["iters"] <= 30
+    assert np.array_equal(good["run"]["act"], hard_good["run"]["act"]) and AS.walk_ok(good["run"], good["H"], good["Cm"])
 
 
 def loss_on_act(p, xbar, lbar, lo=None, hi=None, w=None):
@@ -94,7 +93,7 @@ def loss_on_act(p, xbar, lbar, lo=None, hi=None, w=None):
     lo, hi = p["lo"] if lo is None else lo, p["hi"] if hi is None else hi
     act = p["run"]["act"]
     if "w" in p:
-        x, _, lam = R.reduced_solve(p["H"], p["Cm"], p["g"], p["c"], lo, hi, p["w"] if w is None else w, act)
+        x, _, lam = P.reduced_solve(p["H"], p["Cm"], p["g"], p["c"], lo, hi, act, p["w"] if w is None else w)
     else:
         x, _, lam = P.reduced_solve(p["H"], p["Cm"], p["g"], p["c"], lo, hi, act)
     return float(xbar @ x + lbar @ lam)
@@ -107,8 +106,8 @@ def test_hard_broadcast_case_and_the_summed_gradient_of_a_0d_bound():
     s, run = p["s"], p["run"]
     n = s.S + s.C
     ctl = np.arange(s.N) % n >= s.S
-    assert run["status"] == D.CONVERGED and run["iters"] == 7 and D.walk_ok(run, p["H"], p["Cm"])
-    assert int((run["act"] != 0).sum()) == 7 and ctl[run["act"] != 0].all() and 0.038 < D.min_margin(run) < 0.040
+    assert run["status"] == AS.CONVERGED and run["iters"] == 7 and AS.walk_ok(run, p["H"], p["Cm"])
+    assert int((run["act"] != 0).sum()) == 7 and ctl[run["act"] != 0].all() and 0.038 < AS.min_margin(run) < 0.040
     assert np.all(p["hi"][ctl] == 0.5) and np.all(p["lo"][ctl] == -0.5) and np.all(np.isinf(p["lo"][~ctl])) and np.all(np.isinf(p["hi"][~ctl]))
     assert (run["act"] > 0).any()
     rng = np.random.default_rng(61)
@@ -146,7 +145,7 @@ def test_soft_broadcast_cases_and_the_summed_gradient_of_a_0d_weight():
     assert an != 0 and abs(fd - an) <= 1e-6 * max(1.0, abs(an)), (fd, an)
     pair = R.di_soft_pair()
     for q in pair:
-        assert ok(q) and q["run"]["iters"] <= 30 and R.soft_set(q["run"]["act"], q["w"]).any()
+        assert ok(q) and q["run"]["iters"] <= 30 and P.soft_set(q["run"]["act"], q["w"]).any()
     a, b = pair
     assert all(np.array_equal(a[k], b[k]) for k in ("lo", "hi", "w")) and not np.array_equal(a["c"], b["c"])
     assert not np.array_equal(a["run"]["act"], b["run"]["act"])

@@ -5,6 +5,7 @@ converge."""
 import numpy as np
 import pytest
 
+import box_qp_active_ref as AS
 import box_qp_pdas_ref as D
 import box_qp_polish_ref as P
 import box_qp_ref as ref
@@ -22,8 +23,8 @@ def test_walk_finds_control_box_seeds(shape):
         ps = D.control_box(S, C, K)
         assert len(ps) == 1, (S, C, K)
         run = ps[0]["run"]
-        print((S, C, K), "seed", ps[0]["seed"], "solves", run["iters"], "margin", D.min_margin(run), "active", int((run["act"] != 0).sum()))
-        assert run["status"] == D.CONVERGED and D.min_margin(run) >= D.MARGIN and (run["act"] != 0).any()
+        print((S, C, K), "seed", ps[0]["seed"], "solves", run["iters"], "margin", AS.min_margin(run), "active", int((run["act"] != 0).sum()))
+        assert run["status"] == AS.CONVERGED and AS.min_margin(run) >= AS.MARGIN and (run["act"] != 0).any()
         kkt_ok(ps[0], run)
 
 
@@ -42,8 +43,8 @@ def test_constructed_problems_end_on_their_active_set(shape):
         ps = D.constructed_cold(S, C, K)
         assert len(ps) == 1, (S, C, K)
         p, run = ps[0], ps[0]["run"]
-        print((S, C, K), "seed", p["seed"], "solves", run["iters"], "margin", D.min_margin(run))
-        assert run["status"] == D.CONVERGED and np.array_equal(run["act"], p["act"])
+        print((S, C, K), "seed", p["seed"], "solves", run["iters"], "margin", AS.min_margin(run))
+        assert run["status"] == AS.CONVERGED and np.array_equal(run["act"], p["act"])
         assert np.abs(run["x"] - p["x"]).max() <= 1e-9 * max(1.0, np.abs(p["x"]).max())
         kkt_ok(p, run)
 
@@ -53,8 +54,8 @@ def test_every_constructed_problem_of_the_polish_sweep_converges():
     for S, C in D.SHAPES:
         for K in P.SWEEP_SHORT_K:
             p = P.constructed(S, C, K)[0]
-            run = D.pdas(p["H"], p["Cm"], p["g"], p["c"], p["lo"], p["hi"], S)
-            assert run["status"] == D.CONVERGED and np.array_equal(run["act"], p["act"]), (S, C, K, run["status"], run["iters"])
+            run = AS.iterate(p["H"], p["Cm"], p["g"], p["c"], p["lo"], p["hi"], S)
+            assert run["status"] == AS.CONVERGED and np.array_equal(run["act"], p["act"]), (S, C, K, run["status"], run["iters"])
             assert np.abs(run["x"] - p["x"]).max() <= 1e-9 * max(1.0, np.abs(p["x"]).max())
 
 
@@ -67,9 +68,9 @@ def test_batch_and_named_cases():
     assert len(set(iters)) >= 2                   # systems that need different numbers of solves
     for name in ("pendulum", "14_7_50"):
         s, H, Cm, g, c, lo, hi = D.named(name)
-        run = D.pdas(H, Cm, g, c, lo, hi, s.S)
-        print(name, "solves", run["iters"], "margin", D.min_margin(run))
-        assert run["status"] == D.CONVERGED
+        run = AS.iterate(H, Cm, g, c, lo, hi, s.S)
+        print(name, "solves", run["iters"], "margin", AS.min_margin(run))
+        assert run["status"] == AS.CONVERGED
         kkt_ok(dict(H=H, Cm=Cm, g=g, c=c, lo=lo, hi=hi), run)
     act, *_ = P.exact_active("14_7_50")
     assert np.array_equal(run["act"], act)       # the active set ADMM reaches
@@ -81,7 +82,7 @@ def test_walk_finds_the_long_horizon_seed():
     ps = D.control_box(S, C, K, sparse=True)
     assert len(ps) == 1
     run = ps[0]["run"]
-    print("seed", ps[0]["seed"], "solves", run["iters"], "margin", D.min_margin(run), "active", int((run["act"] != 0).sum()))
+    print("seed", ps[0]["seed"], "solves", run["iters"], "margin", AS.min_margin(run), "active", int((run["act"] != 0).sum()))
     assert (np.flatnonzero(run["act"]) // (S + C) >= 8192).any()
     kkt_ok(ps[0], run)
 
@@ -95,21 +96,21 @@ def test_polish_iterated_closes_6_3_20_from_50_admm_steps():
     assert out["status"] == ref.MAX_ITERS
     act = P.active_set(out["z"], out["y"], lo, hi, s.S)
     assert P.polish(H, Cm, g, c, lo, hi, None, None, s.S, act=act)["decision"] == P.REJECTED
-    run = D.pdas(H, Cm, g, c, lo, hi, s.S, act0=act, max_pdas_iters=10)
-    print("solves", run["iters"], "margin", D.min_margin(run))
-    assert run["status"] == D.CONVERGED and 1 < run["iters"] <= 10
+    run = AS.iterate(H, Cm, g, c, lo, hi, s.S, act0=act, max_pdas_iters=10)
+    print("solves", run["iters"], "margin", AS.min_margin(run))
+    assert run["status"] == AS.CONVERGED and 1 < run["iters"] <= 10
     kkt_ok(dict(H=H, Cm=Cm, g=g, c=c, lo=lo, hi=hi), run)
 
 
 def test_velocity_bounded_double_integrator_does_not_converge():
     s, lo, hi, _ = P.problem("double_integrator")                   # v_max = 0.57
     H, Cm, g, c = ref.parts(s)
-    run = D.pdas(H, Cm, g, c, lo, hi, s.S)
+    run = AS.iterate(H, Cm, g, c, lo, hi, s.S)
     print("status", run["status"], "solves", run["iters"])
-    assert run["status"] in (D.MAX_ITERS, D.NONFINITE)
+    assert run["status"] in (AS.MAX_ITERS, AS.NONFINITE)
     free = ref.double_integrator(K=20, u_max=0.5, v_max=None)       # the control-only box of the same system converges
     Hf, Cf, gf, cf = ref.parts(free[0])
-    assert D.pdas(Hf, Cf, gf, cf, free[1], free[2], 2)["status"] == D.CONVERGED
+    assert AS.iterate(Hf, Cf, gf, cf, free[1], free[2], 2)["status"] == AS.CONVERGED
 
 
 def test_rule_edges():
@@ -121,4 +122,4 @@ def test_rule_edges():
     x = np.array([9, 9, 1.5, 1.0, 1, 1, 0.5, 1e30, 1e30, -1.0])
     y = np.array([0, 0, 0.0, 0.0, 2, 0, 7.0, 0, 0, -3.0])
     want = np.array([0, 0, 1, 0, 1, 0, -1, 0, 0, -1], np.int8)
-    assert np.array_equal(D.next_act(act, x, y, lo, hi, 2), want)
+    assert np.array_equal(AS.next_act(act, x, y, lo, hi, 2), want)

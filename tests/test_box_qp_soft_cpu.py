@@ -9,6 +9,7 @@ import re
 import numpy as np
 import pytest
 
+import box_qp_active_ref as AS
 import box_qp_pdas_ref as D
 import box_qp_polish_ref as P
 import box_qp_ref as ref
@@ -30,24 +31,24 @@ def test_the_rule_on_soft_variables():
     act = np.array([0,   0,          1,                       1,          0,       1,               1,                0], np.int8)
     x = np.array([3.0,   1.25,       0.75,                    -1.5,       0.7,     1.0,             1.0,              9.0])
     y = np.array([0.0,   0.0,        -1.25,                   -12.5,      0.0,     0.3,             -0.2,             0.0])
-    assert R.next_act(act, x, y, lo, hi, w, S).tolist() == [0, 1, 0, -1, -1, 1, 0, 0]
-    assert R.decision_margin(act, x, y, lo, hi, w, S) == pytest.approx(0.2)      # the hard multiplier -0.2
-    assert R.decision_margin(act, x, np.where(w > 0, y, 1.0), lo, hi, w, S) == pytest.approx(0.25)   # x = 1.25 / 0.75 against hi = 1
-    assert R.soft_set(act, w).tolist() == [False, False, True, True, False, False, False, False]
+    assert AS.next_act(act, x, y, lo, hi, S, w).tolist() == [0, 1, 0, -1, -1, 1, 0, 0]
+    assert AS.decision_margin(act, x, y, lo, hi, S, w) == pytest.approx(0.2)      # the hard multiplier -0.2
+    assert AS.decision_margin(act, x, np.where(w > 0, y, 1.0), lo, hi, S, w) == pytest.approx(0.25)   # x = 1.25 / 0.75 against hi = 1
+    assert P.soft_set(act, w).tolist() == [False, False, True, True, False, False, False, False]
 
 
 def test_point_of_a_soft_active_variable():
     """y = w (x - b), z = x on a soft-active variable, and the reduced solve is the minimiser of the penalised objective with
     the active set held."""
     s, H, Cm, g, c, lo, hi, w = R.soft_problem(4, 2, 5, 0)
-    run = R.pdas_soft(H, Cm, g, c, lo, hi, w, 4)
-    assert run["status"] == R.CONVERGED
-    sa = R.soft_set(run["act"], w)
+    run = AS.iterate(H, Cm, g, c, lo, hi, 4, w)
+    assert run["status"] == AS.CONVERGED
+    sa = P.soft_set(run["act"], w)
     assert sa.any()
     b = P.bound_values(run["act"], lo, hi)
     assert np.array_equal(run["y"][sa], (w * (run["x"] - b))[sa]) and np.array_equal(run["z"][sa], run["x"][sa])
     assert np.all((run["x"] > hi)[sa & (run["act"] > 0)]) and np.all((run["x"] < lo)[sa & (run["act"] < 0) & (lo != hi)])
-    kk = R.kkt_residuals(H, Cm, g, c, lo, hi, w, run["x"], run["y"], run["lam"])
+    kk = AS.kkt_residuals(H, Cm, g, c, lo, hi, run["x"], run["y"], run["lam"], w)
     print(kk)
     assert max(kk.values()) <= 1e-9
 
@@ -70,8 +71,8 @@ def test_zero_weights_are_the_hard_reference(kind, S, C, K):
         s, H, Cm, g, c, lo, hi, _ = R.soft_problem(S, C, K, 0)
         p = dict(H=H, Cm=Cm, g=g, c=c, lo=lo, hi=hi)
     args = tuple(p[k] for k in ("H", "Cm", "g", "c", "lo", "hi"))
-    a = D.pdas(*args, S)
-    b = R.pdas_soft(*args, np.zeros(len(p["g"])), S)
+    a = AS.iterate(*args, S)
+    b = AS.iterate(*args, S, np.zeros(len(p["g"])))
     print(kind, a["status"], a["iters"])
     assert (a["status"], a["iters"]) == (b["status"], b["iters"])
     assert len(a["trace"]) == len(b["trace"])
@@ -80,7 +81,7 @@ def test_zero_weights_are_the_hard_reference(kind, S, C, K):
         assert ta["margin"] == tb["margin"] or (np.isnan(ta["margin"]) and np.isnan(tb["margin"]))
     assert np.array_equal(a["x"], b["x"], equal_nan=True) and np.array_equal(a["lam"], b["lam"], equal_nan=True)
     if kind == "states":
-        assert a["status"] != D.CONVERGED
+        assert a["status"] != AS.CONVERGED
 
 
 @pytest.mark.parametrize("S,C,K", [(2, 1, 5), (4, 2, 3)])
@@ -94,7 +95,7 @@ def test_converged_point_is_the_slsqp_minimum(S, C, K):
     inf = np.full(len(g), np.inf)
     bounds = list(zip(np.where(sv, -inf, lo), np.where(sv, inf, hi)))
     bounds = [(None if not np.isfinite(l) else l, None if not np.isfinite(h) else h) for l, h in bounds]
-    f = lambda x: R.penalised_objective(H, g, lo, hi, w, x)
+    f = lambda x: AS.penalised_objective(H, g, lo, hi, x, w)
     out = minimize(f, np.zeros(len(g)), jac=True, method="SLSQP", bounds=bounds,
                    constraints=[dict(type="eq", fun=lambda x: Cm @ x - c, jac=lambda x: Cm)], options=dict(ftol=1e-16, maxiter=2000))
     err = np.abs(out.x - p["run"]["x"]).max()
@@ -121,8 +122,8 @@ def test_solution_approaches_the_hard_one_as_one_over_w():
     d = x1 - p["x"]
     errs, devs = [], []
     for wt in (1e2, 1e3, 1e4):
-        run = R.pdas_soft(H, Cm, g, c, lo, hi, np.full(N, wt), S, act0=act)
-        assert run["status"] == R.CONVERGED and np.array_equal(run["act"], act), wt
+        run = AS.iterate(H, Cm, g, c, lo, hi, S, np.full(N, wt), act0=act)
+        assert run["status"] == AS.CONVERGED and np.array_equal(run["act"], act), wt
         errs.append(np.abs(run["x"] - p["x"]).max())
         devs.append(np.abs(wt * (run["x"] - p["x"]) - d).max() / np.abs(d).max())
         print("w", wt, "|x(w) - x_hard|", errs[-1], "deviation from d / w", devs[-1], "bar", 2 * kappa / wt)
@@ -141,21 +142,21 @@ def _solve(inp, rho, act, S):
     lo = ref.dz_layout(inp["x_lo"], inp["u_lo"], S, C, K)
     hi = ref.dz_layout(inp["x_hi"], inp["u_hi"], S, C, K)
     w = ref.dz_layout(inp["x_soft"], inp["u_soft"], S, C, K)
-    run = R.pdas_soft(H, Cm, g, c, lo, hi, w, S, act0=act, eps_abs=1e-9, eps_rel=1e-9)
+    run = AS.iterate(H, Cm, g, c, lo, hi, S, w, act0=act, eps_abs=1e-9, eps_rel=1e-9)
     return run, (H, Cm, g, c, lo, hi, w)
 
 
 def _fd_problem(S, C, K):
     """The first walked-style seed (weights 3 on the states, 0.5 on every other control: soft controls too) whose final
     point has every margin >= 1e-3 and both a hard-active and a soft-active non-equality variable."""
-    for seed in range(D.WALK_SEEDS):
+    for seed in range(AS.WALK_SEEDS):
         s, H, Cm, g, c, lo, hi, w = R.soft_problem(S, C, K, seed, weight=3.0)
         n = S + C
         idx = np.arange(s.N)
         w[(idx % n >= S) & ((idx // n) % 2 == 1)] = 0.5
-        run = R.pdas_soft(H, Cm, g, c, lo, hi, w, S)
-        sa = R.soft_set(run["act"], w)
-        if (run["status"] == R.CONVERGED and run["trace"][-1]["margin"] >= 1e-3 and (sa & (lo != hi)).any()
+        run = AS.iterate(H, Cm, g, c, lo, hi, S, w)
+        sa = P.soft_set(run["act"], w)
+        if (run["status"] == AS.CONVERGED and run["trace"][-1]["margin"] >= 1e-3 and (sa & (lo != hi)).any()
                 and ((run["act"] != 0) & ~sa & (lo != hi)).any()):
             return s, lo, hi, w, run
     raise AssertionError("no seed")
@@ -174,12 +175,12 @@ def _fd_check(s, lo, hi, w, run0):
         inp["x_" + name], inp["u_" + name] = split(v)
     act = run0["act"]
     run, (H, Cm, g, cc, lo2, hi2, w2) = _solve(inp, s.rho, act, S)
-    assert run["status"] == R.CONVERGED and run["iters"] == 1 and np.array_equal(lo2, lo) and np.array_equal(w2, w)
+    assert run["status"] == AS.CONVERGED and run["iters"] == 1 and np.array_equal(lo2, lo) and np.array_equal(w2, w)
     x, lam = run["x"], run["lam"]
     rng = np.random.default_rng(7)
     xbar, lambar = rng.standard_normal(len(x)), rng.standard_normal(len(lam))
-    gr = R.soft_grads(H, Cm, act, w, lo, hi, x, lam, xbar, lambar, S, C, K)
-    sa = R.soft_set(act, w)
+    gr = P.grads(H, Cm, act, x, lam, xbar, lambar, S, C, K, w=w, lo=lo, hi=hi)
+    sa = P.soft_set(act, w)
     assert not gr["a"][(act != 0) & ~sa].any() and gr["a"][sa].any()
     L = lambda rr: float(xbar @ rr["x"] + lambar @ rr["lam"])
     lmag = float(np.abs(xbar) @ np.abs(x) + np.abs(lambar) @ np.abs(lam))
@@ -204,7 +205,7 @@ def _fd_check(s, lo, hi, w, run0):
             if partner is not None:
                 pert[partner[0]] = inp[partner[0]] + sgn * FD_STEP * partner[1]
             rp, _ = _solve(pert, s.rho, act, S)
-            assert rp["status"] == R.CONVERGED and rp["iters"] == 1, (key, sgn)
+            assert rp["status"] == AS.CONVERGED and rp["iters"] == 1, (key, sgn)
             vals.append(L(rp))
         fd = (vals[0] - vals[1]) / (2 * FD_STEP)
         an = float(np.sum(gr[key] * V))
@@ -226,13 +227,13 @@ def _fd_mixed_problem(S, C, K):
     rounding of two dense solves by the step, and FD_ROUND allows them 1e-13: _fd_problem's matrices have cond 6e5 and keep
     it; 6/3/4 seed 0, next to an active set without LICQ (cond 7e9, |lam| 2e3), is 2e-2 off in R for that reason alone."""
     n = S + C
-    for seed in range(D.WALK_SEEDS):
+    for seed in range(AS.WALK_SEEDS):
         s, H, Cm, g, c, lo, hi, w = R.mixed_problem(S, C, K, seed)
-        run = R.pdas_soft(H, Cm, g, c, lo, hi, w, S)
-        sa = R.soft_set(run["act"], w)
-        if (run["status"] == R.CONVERGED and run["trace"][-1]["margin"] >= 1e-3
+        run = AS.iterate(H, Cm, g, c, lo, hi, S, w)
+        sa = P.soft_set(run["act"], w)
+        if (run["status"] == AS.CONVERGED and run["trace"][-1]["margin"] >= 1e-3
                 and (sa & (lo != hi) & (np.arange(s.N) % n >= S)).any() and ((run["act"] != 0) & ~sa & (lo != hi)).any()
-                and (sa & (np.arange(s.N) % n < S)).any() and np.linalg.cond(R.reduced_matrix(H, Cm, run["act"], w)) <= 1e7):
+                and (sa & (np.arange(s.N) % n < S)).any() and np.linalg.cond(P.reduced_matrix(H, Cm, run["act"], w)) <= 1e7):
             return s, lo, hi, w, run
     raise AssertionError("no seed")
 
@@ -243,7 +244,7 @@ def test_gradients_match_finite_differences_mixed(S, C, K):
     and bound gradients are nonzero."""
     s, lo, hi, w, run = _fd_mixed_problem(S, C, K)
     gr = _fd_check(s, lo, hi, w, run)
-    sc = P.split_states_controls(R.soft_set(run["act"], w) & (lo != hi), S, C, K)[1] > 0
+    sc = P.split_states_controls(P.soft_set(run["act"], w) & (lo != hi), S, C, K)[1] > 0
     assert sc.any() and np.abs(gr["u_soft"][sc]).max() > 0
     assert np.abs(gr["u_lo"][sc]).max() + np.abs(gr["u_hi"][sc]).max() > 0
     assert np.abs(gr["x_soft"]).max() > 0
@@ -256,22 +257,22 @@ def test_stage_path_is_the_reduced_solve(S, C, K):
     against the dense solve of the reduced matrix on every act of a walked run.  Bar: test_box_qp_polish_cpu.py's 1e-9."""
     p = R.soft_box(S, C, K)[0]
     for t in p["run"]["trace"]:
-        xr, _, lr = R.reduced_solve(p["H"], p["Cm"], p["g"], p["c"], p["lo"], p["hi"], p["w"], t["act"])
-        x, lam, iters = R.stage_solve(p["s"], p["lo"], p["hi"], p["w"], t["act"], np.float64, exit_tol=1e-30)
+        xr, _, lr = P.reduced_solve(p["H"], p["Cm"], p["g"], p["c"], p["lo"], p["hi"], t["act"], p["w"])
+        x, lam, iters = P.reduced_stage_solve(p["s"], p["lo"], p["hi"], t["act"], np.float64, exit_tol=1e-30, w=p["w"])
         ex = np.abs(x - xr).max() / max(1.0, np.abs(xr).max())
         el = np.abs(lam - lr).max() / max(1.0, np.abs(lr).max())
         print("pcg iterations", iters, "x", ex, "lam", el)
         assert ex <= 1e-9 and el <= 1e-9
-    status, acts = R.soft_stage(p["s"], p["lo"], p["hi"], p["w"], np.float64, 1e-6, exit_tol=1e-30)
-    assert status == R.CONVERGED and len(acts) == p["run"]["iters"]
+    status, acts = AS.stage_iterate(p["s"], p["lo"], p["hi"], np.float64, 1e-6, p["w"], exit_tol=1e-30)
+    assert status == AS.CONVERGED and len(acts) == p["run"]["iters"]
 
 
 def test_sparse_reference_equals_dense():
     s, H, Cm, g, c, lo, hi, w = R.soft_problem(4, 2, 9, 1)
     Hs, Cs, gs, cs = ref.sparse_parts(s)
-    a = R.pdas_soft(H, Cm, g, c, lo, hi, w, 4)
-    b = R.pdas_soft(Hs, Cs, gs, cs, lo, hi, w, 4)
-    assert a["status"] == b["status"] == R.CONVERGED and a["iters"] == b["iters"] and np.array_equal(a["act"], b["act"])
+    a = AS.iterate(H, Cm, g, c, lo, hi, 4, w)
+    b = AS.iterate(Hs, Cs, gs, cs, lo, hi, 4, w)
+    assert a["status"] == b["status"] == AS.CONVERGED and a["iters"] == b["iters"] and np.array_equal(a["act"], b["act"])
     assert np.abs(a["x"] - b["x"]).max() <= 1e-9 and np.abs(a["lam"] - b["lam"]).max() <= 1e-9
     assert all(abs(ta["margin"] - tb["margin"]) <= 1e-9 for ta, tb in zip(a["trace"], b["trace"]))
 
@@ -283,7 +284,7 @@ COLD = [(S, C, K) for S, C in R.SHAPES for K in R.COLD_K]
 @pytest.mark.parametrize("S,C,K", COLD, ids=["%d-%d-%d" % c for c in COLD])
 def test_walk_finds_an_fp64_seed(S, C, K):
     ps = R.soft_box(S, C, K)
-    assert ps and ps[0]["seed"] < D.WALK_SEEDS
+    assert ps and ps[0]["seed"] < AS.WALK_SEEDS
     p = ps[0]
     run = p["run"]
     n = S + C
@@ -292,16 +293,16 @@ def test_walk_finds_an_fp64_seed(S, C, K):
     if K >= 3:
         j = (K - 1) * n
         assert p["lo"][j] == p["hi"][j] and p["w"][j] > 0 and run["act"][j] == -1
-    print("seed", p["seed"], "solves", run["iters"], "margin", D.min_margin(run), "cond", R.max_cond(run, p["H"], p["Cm"], p["w"]))
-    assert R.walk_ok(run, p["lo"], p["hi"], p["w"], p["H"], p["Cm"])
+    print("seed", p["seed"], "solves", run["iters"], "margin", AS.min_margin(run), "cond", AS.max_cond(run, p["H"], p["Cm"], p["w"]))
+    assert AS.walk_ok(run, p["H"], p["Cm"], p["w"], R.soft_active_on_the_way(p))
 
 
 @pytest.mark.parametrize("S,C,K", R.F32_CASES, ids=["%d-%d-%d" % c for c in R.F32_CASES])
 def test_walk_finds_an_fp32_seed(S, C, K):
     ps = R.soft_box(S, C, K, f32=True)
-    assert ps and ps[0]["seed"] < D.WALK_SEEDS
+    assert ps and ps[0]["seed"] < AS.WALK_SEEDS
     print("seed", ps[0]["seed"], "solves", ps[0]["run"]["iters"])
-    assert R.f32_ok(ps[0])
+    assert AS.f32_ok(ps[0])
 
 
 def test_the_other_gpu_cases_exist():
@@ -313,18 +314,18 @@ def test_the_other_gpu_cases_exist():
     s = synth.make_system(S, C, K, seed=0)
     H, Cm, g, c = ref.parts(s)
     lo, hi = P.boxes(s, 1, eq=True, states=True)
-    assert D.pdas(H, Cm, g, c, lo, hi, S)["status"] != D.CONVERGED
+    assert AS.iterate(H, Cm, g, c, lo, hi, S)["status"] != AS.CONVERGED
     s, H, Cm, g, c, lo, hi, w = R.double_integrator_soft()
-    assert D.pdas(H, Cm, g, c, lo, hi, 2)["status"] in (D.MAX_ITERS, D.NONFINITE)
-    run = R.pdas_soft(H, Cm, g, c, lo, hi, w, 2)
-    print("double integrator: solves", run["iters"], "margin", D.min_margin(run), "cond", R.max_cond(run, H, Cm, w))
-    assert run["status"] == R.CONVERGED and D.min_margin(run) >= D.MARGIN and R.soft_set(run["act"], w).any()
+    assert AS.iterate(H, Cm, g, c, lo, hi, 2)["status"] in (AS.MAX_ITERS, AS.NONFINITE)
+    run = AS.iterate(H, Cm, g, c, lo, hi, 2, w)
+    print("double integrator: solves", run["iters"], "margin", AS.min_margin(run), "cond", AS.max_cond(run, H, Cm, w))
+    assert run["status"] == AS.CONVERGED and AS.min_margin(run) >= AS.MARGIN and P.soft_set(run["act"], w).any()
     p = R.soft_long()
     run = p["run"]
     n = 3
-    sa = R.soft_set(run["act"], p["w"])
-    print("long: solves", run["iters"], "margin", D.min_margin(run), "|x|", np.abs(run["x"]).max())
-    assert run["status"] == R.CONVERGED
+    sa = P.soft_set(run["act"], p["w"])
+    print("long: solves", run["iters"], "margin", AS.min_margin(run), "|x|", np.abs(run["x"]).max())
+    assert run["status"] == AS.CONVERGED
     assert (np.flatnonzero(sa) // n >= 8192).any() and (np.flatnonzero((run["act"] != 0) & ~sa) // n >= 8192).any()
 
 
@@ -342,7 +343,7 @@ def test_mixed_walk_finds_an_fp64_seed(S, C, K):
     seed rule and cover(), recomputed here, meets cover_need and the least this file demands; the final point satisfies the
     penalised KKT system."""
     ps = R.mixed_box(S, C, K)
-    assert ps and ps[0]["seed"] < D.WALK_SEEDS
+    assert ps and ps[0]["seed"] < AS.WALK_SEEDS
     p = ps[0]
     run, w, lo, hi = p["run"], p["w"], p["lo"], p["hi"]
     ctl = np.arange(p["s"].N) % (S + C) >= S
@@ -350,12 +351,12 @@ def test_mixed_walk_finds_an_fp64_seed(S, C, K):
     if S >= 4:                                                                   # 2/1/2 has a single control
         assert all((w[part] > 0).any() and (w[part] == 0).any() for part in (ctl, ~ctl))
     assert len(np.unique(w[w > 0])) == (w > 0).sum()
-    assert R.walk_ok(run, lo, hi, w, p["H"], p["Cm"])
+    assert AS.walk_ok(run, p["H"], p["Cm"], w, R.soft_active_on_the_way(p))
     cov = R.cover(run, w, lo, hi, S, C, K)
-    print("seed", p["seed"], "solves", run["iters"], "margin", D.min_margin(run), "cond", R.max_cond(run, p["H"], p["Cm"], w), "cover", cov)
+    print("seed", p["seed"], "solves", run["iters"], "margin", AS.min_margin(run), "cond", AS.max_cond(run, p["H"], p["Cm"], w), "cover", cov)
     assert cov == p["cover"] and R.covers(cov, R.cover_need(S, C, K)) and R.covers(cov, _issue_need(S, C, K))
     assert R.covers(R.cover_need(S, C, K), _issue_need(S, C, K))
-    kk = R.kkt_residuals(p["H"], p["Cm"], p["g"], p["c"], lo, hi, w, run["x"], run["y"], run["lam"])
+    kk = AS.kkt_residuals(p["H"], p["Cm"], p["g"], p["c"], lo, hi, run["x"], run["y"], run["lam"], w)
     print(kk)
     assert max(kk.values()) <= 1e-9
 
@@ -387,19 +388,19 @@ def test_mixed_walks_find_their_other_seeds():
     last = False
     for S, C in R.SHAPES:
         ps = R.mixed_box(S, C, R.MIXED_F32_K, f32=True)
-        assert ps and ps[0]["seed"] < D.WALK_SEEDS
+        assert ps and ps[0]["seed"] < AS.WALK_SEEDS
         p = ps[0]
         print((S, C), "fp32 seed", p["seed"], "solves", p["run"]["iters"], "cover", p["cover"])
-        assert R.f32_ok(p) and p["cover"] == R.cover(p["run"], p["w"], p["lo"], p["hi"], S, C, R.MIXED_F32_K)
+        assert AS.f32_ok(p) and p["cover"] == R.cover(p["run"], p["w"], p["lo"], p["hi"], S, C, R.MIXED_F32_K)
         assert p["cover"][0] and (S < 4 or p["cover"][2]) and (S < 6 or p["cover"][1])
         for K in R.COLD_K:
             q = R.mixed_box(S, C, K)[0]
-            last |= bool(R.soft_set(q["run"]["act"], q["w"])[(K - 1) * (S + C):].any())
+            last |= bool(P.soft_set(q["run"]["act"], q["w"])[(K - 1) * (S + C):].any())
     assert last
     for S, C, K in R.LAYER_CASES:
         p = R.mixed_layer_box(S, C, K)
         assert p is not None
-        sa = R.soft_set(p["run"]["act"], p["w"])
+        sa = P.soft_set(p["run"]["act"], p["w"])
         assert (sa & (np.arange(len(sa)) % (S + C) >= S) & (p["lo"] != p["hi"])).any()
         print((S, C, K), "layer seed", p["seed"])
 
@@ -414,9 +415,9 @@ def test_mixed_point_is_a_minimum_over_feasible_perturbations(S, C, K):
     p = R.mixed_box(S, C, K)[0]
     H, Cm, g, lo, hi, w, run = (p[k] for k in ("H", "Cm", "g", "lo", "hi", "w", "run"))
     x = run["x"]
-    f0, grad = R.penalised_objective(H, g, lo, hi, w, x)
+    f0, grad = AS.penalised_objective(H, g, lo, hi, x, w)
     assert np.abs(grad + Cm.T @ run["lam"] + np.where(w > 0, 0.0, run["y"])).max() <= 1e-9
-    hard = (run["act"] != 0) & ~R.soft_set(run["act"], w)
+    hard = (run["act"] != 0) & ~P.soft_set(run["act"], w)
     Z = null_space(np.vstack([Cm, np.eye(len(x))[hard]]))
     assert Z.shape[1] > 0
     hv = ~(w > 0)
@@ -433,7 +434,7 @@ def test_mixed_point_is_a_minimum_over_feasible_perturbations(S, C, K):
             d *= min(t, 0.5 * room) / np.abs(d).max()
             xp = x + d
             assert np.abs(Cm @ d).max() <= 1e-15 and np.all((xp >= lo)[hv & ~hard]) and np.all((xp <= hi)[hv & ~hard])
-            worst = min(worst, R.penalised_objective(H, g, lo, hi, w, xp)[0] - f0)
+            worst = min(worst, AS.penalised_objective(H, g, lo, hi, xp, w)[0] - f0)
     print("smallest f(x + d) - f(x)", worst, "rounding bar", 1e-12 * mag)
     assert worst >= -1e-12 * mag
 
@@ -447,7 +448,7 @@ def test_mixed_converged_point_is_the_slsqp_minimum():
     inf = np.full(len(g), np.inf)
     bounds = [(None if not np.isfinite(l) else l, None if not np.isfinite(h) else h)
               for l, h in zip(np.where(sv, -inf, lo), np.where(sv, inf, hi))]
-    f = lambda x: R.penalised_objective(H, g, lo, hi, w, x)
+    f = lambda x: AS.penalised_objective(H, g, lo, hi, x, w)
     out = minimize(f, np.zeros(len(g)), jac=True, method="SLSQP", bounds=bounds,
                    constraints=[dict(type="eq", fun=lambda x: Cm @ x - c, jac=lambda x: Cm)], options=dict(ftol=1e-16, maxiter=2000))
     err = np.abs(out.x - p["run"]["x"]).max()
@@ -465,13 +466,13 @@ def test_zero_weights_on_a_mixed_box_are_the_hard_reference(S, C, K):
     zero = np.zeros(len(g))
     for t in p["run"]["trace"]:
         act = t["act"]
-        assert np.array_equal(R.reduced_matrix(H, Cm, act, zero), P.reduced_matrix(H, Cm, act))
+        assert np.array_equal(P.reduced_matrix(H, Cm, act, zero), P.reduced_matrix(H, Cm, act))
         with np.errstate(all="ignore"):
-            got, want = R.reduced_solve(H, Cm, g, c, lo, hi, zero, act), P.reduced_solve(H, Cm, g, c, lo, hi, act)
+            got, want = P.reduced_solve(H, Cm, g, c, lo, hi, act, zero), P.reduced_solve(H, Cm, g, c, lo, hi, act)
         assert all(np.array_equal(a, b, equal_nan=True) for a, b in zip(got, want))
         x, y = np.nan_to_num(want[0]), np.nan_to_num(want[1])
-        assert np.array_equal(R.next_act(act, x, y, lo, hi, zero, S), D.next_act(act, x, y, lo, hi, S))
-    a, b = D.pdas(H, Cm, g, c, lo, hi, S), R.pdas_soft(H, Cm, g, c, lo, hi, zero, S)
+        assert np.array_equal(AS.next_act(act, x, y, lo, hi, S, zero), AS.next_act(act, x, y, lo, hi, S))
+    a, b = AS.iterate(H, Cm, g, c, lo, hi, S), AS.iterate(H, Cm, g, c, lo, hi, S, zero)
     assert (a["status"], a["iters"]) == (b["status"], b["iters"]) and len(a["trace"]) == len(b["trace"])
     assert all(np.array_equal(ta["act"], tb["act"]) and ta["changed"] == tb["changed"] for ta, tb in zip(a["trace"], b["trace"]))
     assert np.array_equal(a["x"], b["x"], equal_nan=True) and np.array_equal(a["lam"], b["lam"], equal_nan=True)
@@ -482,26 +483,26 @@ def test_the_batch_of_weights_and_the_mixed_long_horizon_exist():
     weight_batch_ok, the vectors as named, the mixed and the scaled run on different points.  mixed_long: CONVERGED, with a
     soft-active control off lo == hi and a hard-active variable among the knots >= 8192."""
     got = R.weight_batch_box()
-    assert got is not None and got[0] < D.WALK_SEEDS
+    assert got is not None and got[0] < AS.WALK_SEEDS
     seed, prob, ws, runs = got
     s, H, Cm, g, c, lo, hi, w = prob
-    print("batch seed", seed, [(r["iters"], D.min_margin(r), R.max_cond(r, H, Cm, wi)) for wi, r in zip(ws, runs)])
-    assert all(r["status"] == R.CONVERGED for r in runs) and R.weight_batch_ok(prob, ws, runs)
+    print("batch seed", seed, [(r["iters"], AS.min_margin(r), AS.max_cond(r, H, Cm, wi)) for wi, r in zip(ws, runs)])
+    assert all(r["status"] == AS.CONVERGED for r in runs) and R.weight_batch_ok(prob, ws, runs)
     assert np.array_equal(ws[0], w) and np.array_equal(ws[1], 10.0 * w) and not ws[2].any() and np.array_equal(ws[3], R.state_weights(s))
     ctl = np.arange(s.N) % (s.S + s.C) >= s.S
     assert (w[ctl] > 0).any() and (w[~ctl] > 0).any() and (w == 0).any()
     assert np.abs(runs[0]["x"] - runs[1]["x"]).max() > 1e-3
-    assert any(R.soft_set(t["act"], w)[ctl].any() for t in runs[0]["trace"])
+    assert any(P.soft_set(t["act"], w)[ctl].any() for t in runs[0]["trace"])
     for wi, r in zip(ws, runs):
-        kk = R.kkt_residuals(H, Cm, g, c, lo, hi, wi, r["x"], r["y"], r["lam"])
+        kk = AS.kkt_residuals(H, Cm, g, c, lo, hi, r["x"], r["y"], r["lam"], wi)
         assert max(kk.values()) <= 1e-9, kk
     p = R.mixed_long()
     run = p["run"]
     n = 3
     idx = np.arange(p["s"].N)
-    sa = R.soft_set(run["act"], p["w"])
-    print("long: seed", p["seed"], "solves", run["iters"], "margin", D.min_margin(run), "|x|", np.abs(run["x"]).max())
-    assert run["status"] == R.CONVERGED
+    sa = P.soft_set(run["act"], p["w"])
+    print("long: seed", p["seed"], "solves", run["iters"], "margin", AS.min_margin(run), "|x|", np.abs(run["x"]).max())
+    assert run["status"] == AS.CONVERGED
     assert (sa & (idx // n >= 8192) & (idx % n >= 2) & (p["lo"] != p["hi"])).any()
     assert ((run["act"] != 0) & ~sa & (idx // n >= 8192)).any()
     ctl = idx % n >= 2

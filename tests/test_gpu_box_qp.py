@@ -10,10 +10,10 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import box_qp_ref as ref                          # noqa: E402
+from box_qp_device import PARITY, admm_host, admm_run, bits, dev_inputs, rel, solver   # noqa: E402
+from box_qp_polish_ref import boxes               # noqa: E402
 from gato_python_amd import _lib, synth           # noqa: E402
-from oracle import gato_oracle as o               # noqa: E402
 
-PARITY = dict(eps_abs=0.0, eps_rel=0.0, max_admm_iters=25, exit_tol=1e-22, max_iters=500)
 SYN = dict(admm_rho=10.0)          # the synthetic systems' scale (Q up to 1e3) wants a stiffer penalty than the default 0.1
 
 
@@ -21,61 +21,6 @@ SYN = dict(admm_rho=10.0)          # the synthetic systems' scale (Q up to 1e3) 
 def _need_gpu():
     assert torch.cuda.is_available(), "GPU suite needs a GPU"
     _lib.lib()
-
-
-def solver(S, C, K, dt, batch=1):
-    from gato_python_amd.solver import Solver
-    return Solver(S, C, K, dt, batch=batch)
-
-
-def boxes(s, seed, eq=True):
-    """A box that cuts into the unconstrained solution: the controls and every other state bounded around half its
-    unconstrained value, x_0 free (it is pinned by c_0), one control fixed (lo == hi) when eq."""
-    rng = np.random.default_rng(seed)
-    dz, _ = synth.dense_kkt_solve(s)
-    n, N = s.S + s.C, s.N
-    w = 0.5 * np.abs(dz) + 0.05 * rng.uniform(0.5, 1.5, N)
-    lo, hi = -w, w.copy()
-    idx = np.arange(N)
-    state = (idx % n) < s.S
-    free = (idx < s.S) | (state & (idx % 2 == 1))
-    lo[free], hi[free] = -np.inf, np.inf
-    if eq:
-        j = s.S + n * (s.K // 2)
-        lo[j] = hi[j] = 0.25 * dz[j]
-    return lo, hi
-
-
-def dev_inputs(sol, systems, bounds):
-    """Stacked device inputs of the systems (G without rho, C raw, g, c, lo, hi) in the solver's dtype."""
-    dt = sol.np_dtype
-    Gs, Cs = zip(*(o.convert(s.G_row, s.G_col, s.G_val, s.C_row, s.C_col, s.C_val, s.S, s.C, s.K, 0.0) for s in systems))
-    cat = lambda arrs: sol.to_device(np.concatenate([np.asarray(a, np.float64) for a in arrs]).astype(dt))
-    return (cat(Gs), cat(Cs), cat([s.g for s in systems]), cat([s.c for s in systems]),
-            cat([b[0] for b in bounds]), cat([b[1] for b in bounds]))
-
-
-def run(sol, inputs, rho, **kw):
-    kw.setdefault("exit_tol", 1e-16 if sol.np_dtype == np.float64 else 1e-8)
-    kw.setdefault("max_iters", 500)
-    r = sol.box_qp(*inputs, rho=rho, **kw)
-    torch.cuda.synchronize()
-    return r
-
-
-def host(r, b, sol):
-    N, sk = sol.N, sol.sizes["sk"]
-    g = lambda t, n: t.cpu().numpy().astype(np.float64).reshape(-1, n)[b]
-    return dict(x=g(r.x, N), z=g(r.z, N), y=g(r.y, N), lam=g(r.lam, sk), iters=int(r.iters[b]), status=int(r.status[b]),
-                res_prim=float(r.res_prim[b]), res_dual=float(r.res_dual[b]))
-
-
-def bits(r):
-    return [t.cpu().numpy().tobytes() for t in (r.x, r.z, r.y, r.lam, r.iters, r.status, r.res_prim, r.res_dual)]
-
-
-def rel(a, b):
-    return float(np.abs(np.asarray(a) - np.asarray(b)).max() / max(np.abs(b).max(), 1.0))
 
 
 # ---- 1. free bounds --------------------------------------------------------------------------------------------------
@@ -89,7 +34,7 @@ def test_free_bounds_is_the_whole_solve(shape, dt):
     lam, dz = a.new(S * K), a.new(a.N)
     tol, eps = (1e-20, 1e-6) if dt == np.float64 else (1e-9, 1e-3)
     a.linsys_blocks(inp[0], inp[1], inp[2], inp[3], tol, 500, s.rho, lam, dz)
-    r = run(b, inp, s.rho, sigma=0.0, alpha=1.0, exit_tol=tol, eps_abs=eps, eps_rel=eps)
+    r = admm_run(b, inp, s.rho, sigma=0.0, alpha=1.0, exit_tol=tol, eps_abs=eps, eps_rel=eps)
     assert int(r.iters[0]) == 1 and int(r.status[0]) == _lib.QP_CONVERGED
     assert r.x.cpu().numpy().tobytes() == dz.cpu().numpy().tobytes()
     assert r.lam.cpu().numpy().tobytes() == lam.cpu().numpy().tobytes()
@@ -103,8 +48,8 @@ def test_iterates_match_reference(shape):
     s = synth.make_system(S, C, K, seed=2) if shape != (2, 1, 5) else synth.pendulum_system()
     lo, hi = boxes(s, 3)
     sol = solver(S, C, K, np.float64)
-    r = run(sol, dev_inputs(sol, [s], [(lo, hi)]), s.rho, **PARITY)
-    got = host(r, 0, sol)
+    r = admm_run(sol, dev_inputs(sol, [s], [(lo, hi)]), s.rho, **PARITY)
+    got = admm_host(r, 0, sol)
     H, Cm, g, c = ref.parts(s)
     want = ref.admm(H, Cm, g, c, lo, hi, eps_abs=0.0, eps_rel=0.0, max_admm_iters=25)
     assert got["status"] == want["status"] == ref.MAX_ITERS and got["iters"] == want["iters"] == 25
@@ -117,11 +62,11 @@ def test_iterates_match_reference_batch():
     systems = [synth.make_system(S, C, K, seed=40 + b) for b in range(B)]
     bounds = [boxes(s, 50 + b, eq=b % 2 == 0) for b, s in enumerate(systems)]
     sol = solver(S, C, K, np.float64, batch=B)
-    r = run(sol, dev_inputs(sol, systems, bounds), systems[0].rho, **PARITY)
+    r = admm_run(sol, dev_inputs(sol, systems, bounds), systems[0].rho, **PARITY)
     for b, s in enumerate(systems):
         H, Cm, g, c = ref.parts(s)
         want = ref.admm(H, Cm, g, c, *bounds[b], eps_abs=0.0, eps_rel=0.0, max_admm_iters=25)
-        got = host(r, b, sol)
+        got = admm_host(r, b, sol)
         assert got["iters"] == 25 and got["status"] == ref.MAX_ITERS
         for k in ("x", "z", "y", "lam"):
             assert rel(got[k], want[k]) <= 1e-8, (b, k, rel(got[k], want[k]))
@@ -129,7 +74,7 @@ def test_iterates_match_reference_batch():
 
 # ---- 3. converged solves ---------------------------------------------------------------------------------------------
 def check_converged(sol, r, b, s, lo, hi, eps):
-    got = host(r, b, sol)
+    got = admm_host(r, b, sol)
     assert got["status"] == _lib.QP_CONVERGED, got
     H, Cm, g, c = ref.parts(s)
     rp, rd, sp, sd = ref.residuals(H, Cm, g, c, got["x"], got["z"], got["y"], got["lam"])
@@ -152,13 +97,13 @@ def check_converged(sol, r, b, s, lo, hi, eps):
 def test_converged_solves(dt, eps):
     s, lo, hi, _ = ref.double_integrator(K=20, u_max=0.5, v_max=0.6)
     sol = solver(2, 1, 20, dt)
-    r = run(sol, dev_inputs(sol, [s], [(lo, hi)]), s.rho, eps_abs=eps, eps_rel=eps)
+    r = admm_run(sol, dev_inputs(sol, [s], [(lo, hi)]), s.rho, eps_abs=eps, eps_rel=eps)
     got = check_converged(sol, r, 0, s, lo, hi, eps)
     assert np.any(got["y"] != 0)
     s = synth.make_system(14, 7, 50, seed=5)
     lo, hi = boxes(s, 6)
     sol = solver(14, 7, 50, dt)
-    r = run(sol, dev_inputs(sol, [s], [(lo, hi)]), s.rho, eps_abs=eps, eps_rel=eps, **SYN)
+    r = admm_run(sol, dev_inputs(sol, [s], [(lo, hi)]), s.rho, eps_abs=eps, eps_rel=eps, **SYN)
     check_converged(sol, r, 0, s, lo, hi, eps)
 
 
@@ -170,13 +115,13 @@ def test_check_every_and_batch_order_do_not_change_bits():
     sol = solver(S, C, K, np.float64, batch=B)
     inp = dev_inputs(sol, systems, bounds)
     kw = dict(SYN, max_admm_iters=1000)
-    r1 = run(sol, inp, systems[0].rho, check_every=1, **kw)
-    r25 = run(sol, inp, systems[0].rho, check_every=25, **kw)
+    r1 = admm_run(sol, inp, systems[0].rho, check_every=1, **kw)
+    r25 = admm_run(sol, inp, systems[0].rho, check_every=25, **kw)
     assert bits(r1) == bits(r25)
     conv = r1.iters[r1.status == _lib.QP_CONVERGED].tolist()
     assert len(conv) >= 4 and len(set(conv)) > 1               # systems froze at different iterations
     perm = np.random.default_rng(0).permutation(B)
-    rp = run(sol, dev_inputs(sol, [systems[i] for i in perm], [bounds[i] for i in perm]), systems[0].rho, check_every=7, **kw)
+    rp = admm_run(sol, dev_inputs(sol, [systems[i] for i in perm], [bounds[i] for i in perm]), systems[0].rho, check_every=7, **kw)
     N, sk = sol.N, sol.sizes["sk"]
     for j, i in enumerate(perm):
         for a, b, n in ((r1.x, rp.x, N), (r1.z, rp.z, N), (r1.y, rp.y, N), (r1.lam, rp.lam, sk)):
@@ -189,16 +134,16 @@ def test_warm_start():
     s, lo, hi, blocks = ref.double_integrator(K=30, u_max=0.5)
     sol = solver(2, 1, 30, np.float64)
     inp = dev_inputs(sol, [s], [(lo, hi)])
-    r = run(sol, inp, s.rho)
+    r = admm_run(sol, inp, s.rho)
     assert int(r.status[0]) == _lib.QP_CONVERGED
     cold_iters = int(r.iters[0])
-    again = run(sol, inp, s.rho, z=r.z.clone(), y=r.y.clone(), lam=r.lam.clone(), warm=True)
+    again = admm_run(sol, inp, s.rho, z=r.z.clone(), y=r.y.clone(), lam=r.lam.clone(), warm=True)
     assert int(again.status[0]) == _lib.QP_CONVERGED and int(again.iters[0]) <= 5, int(again.iters[0])
     # an MPC step: the initial state moves a little
     s2, _, _, _ = ref.double_integrator(K=30, u_max=0.5, x0=(0.97, -0.05))
     inp2 = dev_inputs(sol, [s2], [(lo, hi)])
-    cold = run(sol, inp2, s.rho)
-    warm = run(sol, inp2, s.rho, z=r.z.clone(), y=r.y.clone(), lam=r.lam.clone(), warm=True)
+    cold = admm_run(sol, inp2, s.rho)
+    warm = admm_run(sol, inp2, s.rho, z=r.z.clone(), y=r.y.clone(), lam=r.lam.clone(), warm=True)
     assert int(cold.status[0]) == int(warm.status[0]) == _lib.QP_CONVERGED
     assert int(warm.iters[0]) < int(cold.iters[0]), (int(warm.iters[0]), int(cold.iters[0]), cold_iters)
 
@@ -213,7 +158,7 @@ def test_math_shaped_entry_and_warm_result():
     assert int(res.status) == _lib.QP_CONVERGED and res.x.shape == (s.N,) and res.lam.shape == (s.S * s.K,)
     assert res.x.grad_fn is None and not res.x.requires_grad
     sol = solver(2, 1, 20, np.float64)
-    direct = run(sol, dev_inputs(sol, [s], [(lo, hi)]), s.rho, exit_tol=1e-12, eps_abs=1e-7, eps_rel=1e-7)
+    direct = admm_run(sol, dev_inputs(sol, [s], [(lo, hi)]), s.rho, exit_tol=1e-12, eps_abs=1e-7, eps_rel=1e-7)
     assert res.x.cpu().numpy().tobytes() == direct.x.cpu().numpy().tobytes()
     again = gato_python_amd.box_qp(t(Q)[None], t(R)[None], t(A)[None], t(B)[None], t(q)[None], t(r)[None], t(c)[None],
                                    t([-np.inf, -0.6]), t([np.inf, 0.6]), -0.5, 0.5, rho=s.rho, exit_tol=1e-12,
@@ -227,13 +172,13 @@ def test_infeasible_box_leaves_neighbours_alone():
     systems = [synth.make_system(S, C, K, seed=100 + b) for b in range(3)]
     bounds = [boxes(s, 110 + b) for b, s in enumerate(systems)]
     sol = solver(S, C, K, np.float64, batch=3)
-    ok = run(sol, dev_inputs(sol, systems, bounds), systems[0].rho, max_admm_iters=300, **SYN)
+    ok = admm_run(sol, dev_inputs(sol, systems, bounds), systems[0].rho, max_admm_iters=300, **SYN)
     bad = synth.KKTSystem(S, C, K, systems[1].G_row, systems[1].G_col, systems[1].G_val, systems[1].C_row,
                           systems[1].C_col, systems[1].C_val, systems[1].g, systems[1].c.copy(), systems[1].rho)
     bad.c[:S] = 5.0
     blo, bhi = bounds[1][0].copy(), bounds[1][1].copy()
     blo[:S], bhi[:S] = -1.0, 1.0                                    # x_0 = c_0 = 5 lies outside the box
-    r = run(sol, dev_inputs(sol, [systems[0], bad, systems[2]], [bounds[0], (blo, bhi), bounds[2]]), systems[0].rho,
+    r = admm_run(sol, dev_inputs(sol, [systems[0], bad, systems[2]], [bounds[0], (blo, bhi), bounds[2]]), systems[0].rho,
             max_admm_iters=300, **SYN)
     assert int(r.status[1]) == _lib.QP_MAX_ITERS and int(r.iters[1]) == 300
     N, sk = sol.N, sol.sizes["sk"]
@@ -253,14 +198,14 @@ def test_bad_bounds_raise_and_trivial_qp():
     lo2, hi2 = lo.copy(), hi.copy()
     lo2[s.S + 1], hi2[s.S + 1] = 1.0, -1.0
     with pytest.raises(ValueError, match=r"systems \[1\]"):
-        run(sol, dev_inputs(sol, [s, s], [(lo, hi), (lo2, hi2)]), s.rho)
+        admm_run(sol, dev_inputs(sol, [s, s], [(lo, hi), (lo2, hi2)]), s.rho)
     lo3 = lo.copy()
     lo3[s.S + 2] = np.nan
     with pytest.raises(ValueError, match=r"systems \[0\]"):
-        run(sol, dev_inputs(sol, [s, s], [(lo3, hi), (lo, hi)]), s.rho)
+        admm_run(sol, dev_inputs(sol, [s, s], [(lo3, hi), (lo, hi)]), s.rho)
     zero = synth.KKTSystem(s.S, s.C, s.K, s.G_row, s.G_col, s.G_val, s.C_row, s.C_col, s.C_val, np.zeros_like(s.g),
                            np.zeros_like(s.c), s.rho)
-    r = run(sol, dev_inputs(sol, [zero, s], [boxes(s, 8, eq=False), (lo, hi)]), s.rho, **SYN)   # 0 inside the box
+    r = admm_run(sol, dev_inputs(sol, [zero, s], [boxes(s, 8, eq=False), (lo, hi)]), s.rho, **SYN)   # 0 inside the box
     assert int(r.status[0]) == _lib.QP_CONVERGED and int(r.iters[0]) == 1
     N, sk = sol.N, sol.sizes["sk"]
     for t, n in ((r.x, N), (r.z, N), (r.y, N), (r.lam, sk)):
@@ -277,7 +222,7 @@ def test_solver_state_and_refusals():
     for tws in (0, 1):
         sol.set_option("true_warm_start", tws)
         gen = sol.get_option("assembly_gen")
-        r = run(sol, inp, s.rho, max_admm_iters=50)
+        r = admm_run(sol, inp, s.rho, max_admm_iters=50)
         assert int(r.iters[0]) > 1
         assert sol.get_option("assembly_gen") == gen + 1
         assert sol.get_option("true_warm_start") == tws
@@ -324,6 +269,6 @@ def test_multi_workgroup_system_fp32():
     s = synth.make_system(14, 7, 512, seed=11)
     lo, hi = boxes(s, 12)
     sol = solver(14, 7, 512, np.float32)
-    r = run(sol, dev_inputs(sol, [s], [(lo, hi)]), s.rho, eps_abs=1e-4, eps_rel=1e-4, **SYN)
+    r = admm_run(sol, dev_inputs(sol, [s], [(lo, hi)]), s.rho, eps_abs=1e-4, eps_rel=1e-4, **SYN)
     assert sol.get_option("last_groups") > 1
     check_converged(sol, r, 0, s, lo, hi, 1e-4)

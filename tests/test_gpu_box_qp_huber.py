@@ -1,25 +1,23 @@
 """Capped (Huber) soft bounds in the active-set iteration on the device (gato_box_qp_pdas_huber, gato_box_qp_huber_grad,
 Solver.box_qp_pdas(soft_cap=), Solver.box_qp_huber_grad, box_qp / box_qp_layer(method="pdas", x_soft_max=, u_soft_max=)) against
-the numpy reference of tests/box_qp_huber_ref.py: the reference's number of solves and final act, +-2 included, on walked
+the numpy reference of tests/box_qp_active_ref.py: the reference's number of solves and final act, +-2 included, on walked
 problems (tests/test_box_qp_huber_cpu.py asserts that the walks find them), no caps equal to gato_box_qp_pdas_soft bit for bit,
 batches, warm starts, the grid cap, fp32, gradients.  Bars: those of tests/test_gpu_box_qp_soft.py - fp64 parity 1e-6 in the
 infinity norm, Huber KKT residuals <= 1e-7."""
-import ctypes as ct
-
 import numpy as np
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
 
+import box_qp_active_ref as AS                    # noqa: E402
 import box_qp_huber_ref as R                      # noqa: E402
 import box_qp_pdas_ref as D                       # noqa: E402
 import box_qp_polish_ref as P                     # noqa: E402
 import box_qp_soft_ref as SR                      # noqa: E402
 from gato_python_amd import _lib                  # noqa: E402
-from test_gpu_box_qp_pdas import CAP, SENTINEL, math_inputs, pdas, point_bits, sentinels, untouched   # noqa: E402
-from test_gpu_box_qp_polish import F64, dev_inputs, host, solver   # noqa: E402
-from test_gpu_box_qp_soft import dev_w, hard_state_box_that_fails, raw_soft, soft   # noqa: E402
+from box_qp_device import (CAP, F64, SENTINEL, check_point, cold_case, dev_inputs, dev_w, host, math_inputs, pdas, point_bits,  # noqa: E402
+                           raw_pdas, sentinels, solver, untouched)
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -29,32 +27,8 @@ def _need_gpu():
 
 
 def huber(sol, inp, w, m, rho, **kw):
-    """Solver.box_qp_pdas with the weights w and the caps m (device tensors; m None: no caps) through test_gpu_box_qp_pdas.pdas."""
+    """Solver.box_qp_pdas with the weights w and the caps m (device tensors; m None: no caps) through box_qp_device.pdas."""
     return pdas(sol, inp, rho, soft_weight=w, soft_cap=m, **kw)
-
-
-def check_huber(sol, r, b, p, run):
-    """System b: CONVERGED after the reference's solves on the reference's act, +-2 included; x, lam within 1e-6 of the
-    reference; the residuals of the Huber KKT system <= 1e-7; x on the hard-active set equal to the bounds and y on the saturated
-    set equal to +-m, bit for bit."""
-    H, Cm, g, c, lo, hi, w, m = (p[k] for k in ("H", "Cm", "g", "c", "lo", "hi", "w", "m"))
-    B = sol.batch
-    print("iters", int(r.iters[b]), "want", run["iters"], "status", int(r.status[b]))
-    assert int(r.status[b]) == _lib.QP_CONVERGED and int(r.polished[b]) == _lib.POLISH_ACCEPTED
-    assert int(r.iters[b]) == run["iters"]
-    act = r.act.cpu().numpy().reshape(B, -1)[b]
-    assert np.array_equal(act, run["act"]), np.flatnonzero(act != run["act"])[:5]
-    x, z, y, lam = host(r.x, B, sol.N)[b], host(r.z, B, sol.N)[b], host(r.y, B, sol.N)[b], host(r.lam, B, sol.sizes["sk"])[b]
-    ex, el = np.abs(x - run["x"]).max(), np.abs(lam - run["lam"]).max()
-    kk = R.kkt_residuals(H, Cm, g, c, lo, hi, w, m, x, y, lam)
-    print("x err", ex, "lam err", el, "kkt", kk)
-    assert ex < 1e-6 and el < 1e-6, (ex, el)
-    assert max(kk.values()) <= 1e-7, kk
-    sa, sat = SR.soft_set(act, w), R.sat_set(act)
-    hard = (act != 0) & ~sa
-    assert np.array_equal(x[hard], P.bound_values(act, lo, hi)[hard])
-    assert np.array_equal(y[sat], np.sign(act)[sat] * m[sat])
-    assert np.array_equal(z[sa], x[sa]) and np.array_equal(z[~sa], np.clip(x, lo, hi)[~sa])
 
 
 # ---- 1. cold starts: capped soft state boxes, hard control boxes ----------------------------------------------------------------
@@ -66,18 +40,10 @@ def test_cold_capped_state_box(S, C, K):
     ps = R.huber_box(S, C, K)
     assert ps, "the walk finds no seed at %d/%d/%d" % (S, C, K)
     p = ps[0]
-    s, run = p["s"], p["run"]
-    print("seed", p["seed"], "solves", run["iters"], "margin", D.min_margin(run), "kinds", R.final_kinds(run, p["w"], p["lo"], p["hi"]))
-    assert R.sat_set(run["act"]).any()
-    sol = solver(S, C, K, np.float64)
-    inp = dev_inputs(sol, [s], [(p["lo"], p["hi"])])
-    w, m = dev_w(sol, [p["w"]]), dev_w(sol, [p["m"]])
-    gen = sol.get_option("assembly_gen")
-    r = huber(sol, inp, w, m, s.rho)
-    assert sol.get_option("assembly_gen") == gen + run["iters"] and sol.get_option("assembly_valid") == 1
-    check_huber(sol, r, 0, p, run)
-    again = huber(sol, inp, w, m, s.rho)
-    assert point_bits(again, 0, sol) == point_bits(r, 0, sol)
+    run = p["run"]
+    print("seed", p["seed"], "solves", run["iters"], "margin", AS.min_margin(run), "kinds", R.final_kinds(run, p["w"], p["lo"], p["hi"]))
+    assert P.sat_set(run["act"]).any()
+    cold_case(p)
 
 
 @pytest.mark.parametrize("S,C,K", [(6, 3, 9), (14, 7, 3)], ids=["6-3-9", "14-7-3"])
@@ -85,10 +51,10 @@ def test_cold_mixed_weights_and_caps(S, C, K):
     """A weight and a cap per variable, on states and controls: the final act holds a saturated control."""
     p = R.mixed_box(S, C, K)
     s, run = p["s"], p["run"]
-    assert (R.sat_set(run["act"]) & (np.arange(s.N) % (S + C) >= S) & (p["lo"] != p["hi"])).any()
+    assert (P.sat_set(run["act"]) & (np.arange(s.N) % (S + C) >= S) & (p["lo"] != p["hi"])).any()
     sol = solver(S, C, K, np.float64)
     r = huber(sol, dev_inputs(sol, [s], [(p["lo"], p["hi"])]), dev_w(sol, [p["w"]]), dev_w(sol, [p["m"]]), s.rho)
-    check_huber(sol, r, 0, p, run)
+    check_point(sol, r, 0, p, run)
 
 
 # ---- 2. fp32 ------------------------------------------------------------------------------------------------------------------
@@ -97,42 +63,21 @@ def test_fp32_ends_on_the_reference_act(S, C, K):
     """fp32 under the fp32 seed rule at eps = F32_EPS, PCG exit tolerance F32_EXIT_TOL (box_qp_soft_ref): the reference's solves
     and act, the hard bounds and y = +-m on the saturated set bit for bit."""
     p = R.huber_box(S, C, K, f32=True)[0]
-    q = R.rounded(p)
+    q = P.rounded(p)
     sol = solver(S, C, K, np.float32)
     r = huber(sol, dev_inputs(sol, [q["s"]], [(q["lo"], q["hi"])]), dev_w(sol, [q["w"]]), dev_w(sol, [q["m"]]), q["s"].rho,
-              eps=P.F32_EPS, exit_tol=R.F32_EXIT_TOL, max_iters=1000)
+              eps=P.F32_EPS, exit_tol=AS.F32_EXIT_TOL, max_iters=1000)
     print("seed", p["seed"], "solves", int(r.iters[0]), "reference", p["run"]["iters"])
     assert int(r.status[0]) == _lib.QP_CONVERGED and int(r.iters[0]) == p["run"]["iters"]
     act = p["run"]["act"]
-    assert np.array_equal(r.act.cpu().numpy(), act) and R.sat_set(act).any()
-    hard = (act != 0) & ~SR.soft_set(act, p["w"])
+    assert np.array_equal(r.act.cpu().numpy(), act) and P.sat_set(act).any()
+    hard = (act != 0) & ~P.soft_set(act, p["w"])
     assert np.array_equal(r.x.cpu().numpy()[hard], P.bound_values(act, q["lo"], q["hi"])[hard].astype(np.float32))
-    sat = R.sat_set(act)
+    sat = P.sat_set(act)
     assert np.array_equal(r.y.cpu().numpy()[sat], (np.sign(act)[sat] * q["m"][sat]).astype(np.float32))
 
 
 # ---- 3. no caps: gato_box_qp_pdas_soft, bit for bit -----------------------------------------------------------------------------
-def raw_huber(sol, inp, w, m, rho, act0=None, max_pdas_iters=30):
-    """gato_box_qp_pdas_huber itself (w, m None: NULL pointers) -> (return code, the outputs' bytes in point_bits's order)."""
-    B, N, sk = sol.batch, sol.N, sol.sizes["sk"]
-    L = _lib.lib()
-    prm = _lib.BoxQpParams()
-    L.gato_box_qp_default_params(prm)
-    prm.rho, prm.exit_tol, prm.max_iters = rho, F64["exit_tol"], F64["max_iters"]
-    x, z, y, lam = (torch.zeros(n, dtype=sol.dtype, device="cuda") for n in (B * N, B * N, B * N, B * sk))
-    act = torch.zeros(B * N, dtype=torch.int8, device="cuda")
-    if act0 is not None:
-        act.copy_(torch.from_numpy(np.ascontiguousarray(act0, np.int8).reshape(-1)))
-    iters, status = torch.zeros(B, dtype=torch.int32, device="cuda"), sol.new(B, torch.int32)
-    res = torch.zeros(2 * B, dtype=torch.float64, device="cuda")
-    ptr = lambda t: None if t is None else ct.c_void_p(t.data_ptr())
-    rc = L.gato_box_qp_pdas_huber(sol._h, *(ptr(t) for t in inp), ptr(w), ptr(m), ptr(act), ct.byref(prm), max_pdas_iters, ptr(x),
-                                  ptr(z), ptr(y), ptr(lam), ptr(iters), ptr(status), ptr(res), sol._stream())
-    torch.cuda.synchronize()
-    res = res.view(B, 2)
-    return rc, [t.cpu().numpy().tobytes() for t in (x, z, y, lam, iters, status, res[:, 0].contiguous(), res[:, 1].contiguous(), act)]
-
-
 @pytest.mark.parametrize("shape", R.SHAPES, ids=lambda sh: "%d-%d" % sh)
 def test_no_caps_is_box_qp_pdas_soft(shape):
     """A walked soft problem: a NULL cap pointer, a tensor of +inf, finite caps on the variables with w = 0 (the controls) and
@@ -143,20 +88,20 @@ def test_no_caps_is_box_qp_pdas_soft(shape):
     sol = solver(S, C, 9, np.float64)
     inp = dev_inputs(sol, [s], [(p["lo"], p["hi"])])
     wd = dev_w(sol, [w])
-    want = raw_soft(sol, inp, wd, s.rho)
-    assert want == point_bits(soft(sol, inp, wd, s.rho), 0, sol)
-    assert raw_huber(sol, inp, wd, None, s.rho) == (0, want)
-    assert raw_huber(sol, inp, wd, dev_w(sol, [np.inf]), s.rho) == (0, want)
+    want = raw_pdas(sol, inp, wd, None, "gato_box_qp_pdas_soft", s.rho)[1]
+    assert want == point_bits(pdas(sol, inp, s.rho, soft_weight=wd), 0, sol)
+    assert raw_pdas(sol, inp, wd, None, "gato_box_qp_pdas_huber", s.rho) == (0, want)
+    assert raw_pdas(sol, inp, wd, dev_w(sol, [np.inf]), "gato_box_qp_pdas_huber", s.rho) == (0, want)
     assert point_bits(huber(sol, inp, wd, dev_w(sol, [np.inf]), s.rho), 0, sol) == want
     inside = (w > 0) & ~np.any([t["act"] != 0 for t in p["run"]["trace"]], axis=0)
     bounded = inside & (np.isfinite(p["lo"]) | np.isfinite(p["hi"])) & (np.arange(s.N) >= S + C)
     print("caps on", int((w == 0).sum()), "hard variables and", int(bounded.sum()), "bounded soft variables that stay inside")
     assert bounded.any() or S == 2                  # 2/1/9: each of its eight bounded states is active on some solve
     idle = np.where((w == 0) | inside, 0.5, np.inf)
-    assert raw_huber(sol, inp, wd, dev_w(sol, [idle]), s.rho) == (0, want)
+    assert raw_pdas(sol, inp, wd, dev_w(sol, [idle]), "gato_box_qp_pdas_huber", s.rho) == (0, want)
     # without weights the caps are not read at all: gato_box_qp_pdas
-    hard = raw_soft(sol, inp, None, s.rho)
-    assert raw_huber(sol, inp, None, dev_w(sol, [np.nan]), s.rho) == (0, hard)
+    hard = raw_pdas(sol, inp, None, None, "gato_box_qp_pdas_soft", s.rho)[1]
+    assert raw_pdas(sol, inp, None, dev_w(sol, [np.nan]), "gato_box_qp_pdas_huber", s.rho) == (0, hard)
 
 
 # ---- 4. batches -------------------------------------------------------------------------------------------------------------
@@ -170,7 +115,7 @@ def test_batch_of_capped_soft_hard_frozen_and_bad_systems():
     inf = np.full(a["s"].N, np.inf)
     unc = dict(SR.soft_box(S, C, K)[0], m=inf)
     ctl = dict(D.control_box(S, C, K)[0], w=np.zeros(a["s"].N), m=inf)
-    ps = [a, unc, ctl, dict(hard_state_box_that_fails(S, C, K), m=inf), b]
+    ps = [a, unc, ctl, dict(SR.hard_state_box_that_fails(S, C, K), m=inf), b]
     sol = solver(S, C, K, np.float64, batch=B)
     inp = dev_inputs(sol, [p["s"] for p in ps], [(p["lo"], p["hi"]) for p in ps])
     rho = a["s"].rho
@@ -194,9 +139,9 @@ def test_batch_of_capped_soft_hard_frozen_and_bad_systems():
         assert int(r.status[i]) == _lib.QP_CONVERGED and int(r.iters[i]) == p["run"]["iters"]
         assert point_bits(r, i, sol) == point_bits(solo, 0, one), i
         if i == 1:
-            assert point_bits(soft(one, one_inp, dev_w(one, [p["w"]]), rho), 0, one) == point_bits(solo, 0, one)
-    check_huber(sol, r, 0, a, a["run"])
-    check_huber(sol, r, 4, b, b["run"])
+            assert point_bits(pdas(one, one_inp, rho, soft_weight=dev_w(one, [p["w"]])), 0, one) == point_bits(solo, 0, one)
+    check_point(sol, r, 0, a, a["run"])
+    check_point(sol, r, 4, b, b["run"])
     assert a["run"]["iters"] != b["run"]["iters"] or a["run"]["iters"] != unc["run"]["iters"]      # the systems freeze at different solves
 
 
@@ -209,15 +154,15 @@ def test_warm_start_from_a_saturated_act_and_refusals():
     inp = dev_inputs(sol, [s], [(lo, hi)])
     wd, md = dev_w(sol, [w]), dev_w(sol, [m])
     cold = huber(sol, inp, wd, md, s.rho)
-    assert R.sat_set(cold.act.cpu().numpy()).any()
+    assert P.sat_set(cold.act.cpu().numpy()).any()
     warm = huber(sol, inp, wd, md, s.rho, act=cold.act.cpu().numpy())
     assert int(warm.status[0]) == _lib.QP_CONVERGED and int(warm.iters[0]) == 1
-    check_huber(sol, warm, 0, p, dict(run, iters=1))
+    check_point(sol, warm, 0, p, dict(run, iters=1))
     outs = sentinels(sol)
     # +-2 through gato_box_qp_pdas_soft, on a variable without a weight, without a finite cap, with an infinite bound, on x_0
     with pytest.raises(ValueError, match="BAD_ACTIVE"):
-        soft(sol, inp, wd, s.rho, act=run["act"], outs=outs)
-    sat = int(np.flatnonzero(R.sat_set(run["act"]))[0])
+        pdas(sol, inp, s.rho, soft_weight=wd, act=run["act"], outs=outs)
+    sat = int(np.flatnonzero(P.sat_set(run["act"]))[0])
     control = int(np.flatnonzero((w == 0) & np.isfinite(hi) & (np.arange(s.N) >= n))[0])
     free_state = int(np.flatnonzero(~np.isfinite(hi) & (np.arange(s.N) >= n) & (w > 0))[0])
     for j, v, caps in ((control, 2, m), (sat, 2, np.where(np.arange(s.N) == sat, np.inf, m)), (free_state, 2, m), (0, 2, m),
@@ -239,9 +184,9 @@ def test_warm_start_from_a_saturated_act_and_refusals():
     assert point_bits(ok, 0, sol) == point_bits(cold, 0, sol)
     zero = huber(sol, inp, wd, dev_w(sol, [0.0]), s.rho)
     H, Cm, g, c = (p[k] for k in ("H", "Cm", "g", "c"))
-    want = R.pdas_huber(H, Cm, g, c, lo, hi, w, np.zeros(s.N), s.S)
-    free = SR.pdas_soft(H, Cm, g, c, np.where(w > 0, -np.inf, lo), np.where(w > 0, np.inf, hi), w, s.S)
-    assert want["status"] == free["status"] == R.CONVERGED and np.abs(want["x"] - free["x"]).max() < 1e-9
+    want = AS.iterate(H, Cm, g, c, lo, hi, s.S, w, np.zeros(s.N))
+    free = AS.iterate(H, Cm, g, c, np.where(w > 0, -np.inf, lo), np.where(w > 0, np.inf, hi), s.S, w)
+    assert want["status"] == free["status"] == AS.CONVERGED and np.abs(want["x"] - free["x"]).max() < 1e-9
     assert int(zero.status[0]) == _lib.QP_CONVERGED and np.abs(host(zero.x, 1, sol.N)[0] - want["x"]).max() < 1e-6
     assert not host(zero.y, 1, sol.N)[0][w > 0].any()
 
@@ -255,8 +200,8 @@ def test_long_horizon_second_grid_pass():
     s, run = p["s"], p["run"]
     S, C, K = D.LONG
     n = S + C
-    assert run["status"] == R.CONVERGED
-    sat = R.sat_set(run["act"])
+    assert run["status"] == AS.CONVERGED
+    sat = P.sat_set(run["act"])
     assert (np.flatnonzero(sat) // n >= CAP).any()
     sol = solver(S, C, K, np.float64)
     r = huber(sol, dev_inputs(sol, [s], [(p["lo"], p["hi"])]), dev_w(sol, [p["w"]]), dev_w(sol, [p["m"]]), s.rho, act=run["act"],
@@ -266,7 +211,7 @@ def test_long_horizon_second_grid_pass():
     assert np.array_equal(r.act.cpu().numpy(), run["act"])
     x, y, lam = host(r.x, 1, sol.N)[0], host(r.y, 1, sol.N)[0], host(r.lam, 1, sol.sizes["sk"])[0]
     whole, tail = np.abs(x - run["x"]).max(), np.abs(x[CAP * n:] - run["x"][CAP * n:]).max()
-    kk = R.kkt_residuals(p["H"], p["Cm"], p["g"], p["c"], p["lo"], p["hi"], p["w"], p["m"], x, y, lam)
+    kk = AS.kkt_residuals(p["H"], p["Cm"], p["g"], p["c"], p["lo"], p["hi"], x, y, lam, p["w"], p["m"])
     print("x err whole", whole, "knots >= 8192", tail, "kkt", kk)
     assert whole < 1e-6 and tail < 1e-6
     assert max(kk.values()) <= 1e-7, kk
@@ -296,7 +241,7 @@ def test_huber_grad_kernel(K, dt):
     rnd = lambda v: np.asarray(v, dt).astype(np.float64)
     w, m, lo, hi, x = [rnd(p[k]) for k in ("w", "m", "lo", "hi")] + [rnd(p["run"]["x"])]
     rng = np.random.default_rng(5)
-    sa, sat = SR.soft_set(act, w), R.sat_set(act)
+    sa, sat = P.soft_set(act, w), P.sat_set(act)
     hard = (act != 0) & ~sa
     xbar, a, beta = rnd(rng.standard_normal(s.N)), rnd(np.where(hard, 0.0, rng.standard_normal(s.N))), rnd(rng.standard_normal(S * K))
     sol = solver(S, C, K, dt)
@@ -304,7 +249,7 @@ def test_huber_grad_kernel(K, dt):
     Gh, Ch = host(Gb, 1, Gb.numel())[0], host(Cb, 1, Cb.numel())[0]               # the blocks as the device holds them
     dev = lambda v: sol.to_device(np.ascontiguousarray(v, np.float64).astype(dt))
     # H = G + rho I serves for G: rho multiplies a_i, which is 0 wherever the hard formula is evaluated
-    want = SR.bound_grads(p["H"], p["Cm"], R.unsaturated(act), w, lo, hi, x, xbar, a, beta)
+    want = P.bound_grads(p["H"], p["Cm"], P.unsaturated(act), xbar, a, beta, w, lo, hi, x)
     want = list(want) + [np.where(sat, -np.sign(act) * a, 0.0)]
     outs = [sol.new(s.N + 1).fill_(SENTINEL)[1:] for _ in range(4)]
     got = sol.box_qp_huber_grad(Gb, Cb, torch.from_numpy(act).cuda(), dev(w), dev(m), dev(lo), dev(hi), dev(x), dev(xbar), dev(a),
@@ -322,17 +267,10 @@ def test_huber_grad_kernel(K, dt):
     for t in got[:3]:
         assert not np.any(t.cpu().numpy()[sat])                                  # exactly 0 on the saturated set
     # no caps (a NULL cap pointer) on the act without +-2: box_qp_soft_grad's outputs bit for bit, cap_bar zero
-    a1 = torch.from_numpy(R.unsaturated(act)).cuda()
+    a1 = torch.from_numpy(P.unsaturated(act)).cuda()
     l1, h1, w1 = sol.box_qp_soft_grad(Gb, Cb, a1, dev(w), dev(lo), dev(hi), dev(x), dev(xbar), dev(a), dev(beta))
     l2, h2, w2, c2 = sol.box_qp_huber_grad(Gb, Cb, a1, dev(w), None, dev(lo), dev(hi), dev(x), dev(xbar), dev(a), dev(beta))
     assert torch.equal(l1, l2) and torch.equal(h1, h2) and torch.equal(w1, w2) and not c2.any()
-
-
-def huber_math_inputs(p, requires_grad=False):
-    ts = math_inputs(p["s"], p["lo"], p["hi"], requires_grad=requires_grad)
-    split = lambda v: P.split_states_controls(v, p["s"].S, p["s"].C, p["s"].K)
-    ws = [torch.from_numpy(np.ascontiguousarray(t)).cuda().requires_grad_(requires_grad) for t in split(p["w"]) + split(p["m"])]
-    return ts, ws
 
 
 LAYER = [(6, 3, 9, False), (6, 3, 9, True), (14, 7, 3, False), (14, 7, 3, True)]
@@ -346,17 +284,18 @@ def test_layer_gradients_caps_included(S, C, K, stale):
     import gato_python_amd
     p = R.mixed_box(S, C, K)
     s, run = p["s"], p["run"]
-    ts, ws = huber_math_inputs(p, requires_grad=True)
-    x, lam, info = gato_python_amd.box_qp_layer(*ts, rho=s.rho, method="pdas", x_soft=ws[0], u_soft=ws[1], x_soft_max=ws[2],
+    ts = math_inputs(p, requires_grad=True)
+    ws = ts[11:]
+    x, lam, info = gato_python_amd.box_qp_layer(*ts[:11], rho=s.rho, method="pdas", x_soft=ws[0], u_soft=ws[1], x_soft_max=ws[2],
                                                 u_soft_max=ws[3], **F64)
     assert int(info.polished) == _lib.POLISH_ACCEPTED and int(info.iters) == run["iters"]
-    assert np.array_equal(info.act.cpu().numpy(), run["act"]) and R.sat_set(run["act"]).any()
+    assert np.array_equal(info.act.cpu().numpy(), run["act"]) and P.sat_set(run["act"]).any()
     if stale:
         from gato_python_amd import autograd
         sol = autograd._SOLVERS[(S, C, K, 1, torch.float64, torch.cuda.current_device())]     # the layer's cached solver
         gen = sol.get_option("assembly_gen")
         q = D.control_box(S, C, K)[0]
-        other = gato_python_amd.box_qp(*math_inputs(q["s"], q["lo"], q["hi"]), rho=q["s"].rho, method="pdas", **F64)
+        other = gato_python_amd.box_qp(*math_inputs(q), rho=q["s"].rho, method="pdas", **F64)
         assert int(other.status) == _lib.QP_CONVERGED and sol.get_option("assembly_gen") == gen + q["run"]["iters"]
         gen = sol.get_option("assembly_gen")
     rng = np.random.default_rng(7)
@@ -364,9 +303,9 @@ def test_layer_gradients_caps_included(S, C, K, stale):
     ((x * torch.from_numpy(xbar).cuda()).sum() + (lam * torch.from_numpy(lbar).cuda()).sum()).backward()
     if stale:
         assert sol.get_option("assembly_gen") == gen + 1 and sol.get_option("assembly_valid") == 1
-    want = R.huber_grads(p["H"], p["Cm"], run["act"], p["w"], p["m"], p["lo"], p["hi"], x.detach().cpu().numpy(),
-                         lam.detach().cpu().numpy(), xbar, lbar, S, C, K)
-    for k, t in zip(R.HUBER_KEYS, ts + ws):
+    want = P.grads(p["H"], p["Cm"], run["act"], x.detach().cpu().numpy(), lam.detach().cpu().numpy(), xbar, lbar, S, C, K,
+                   w=p["w"], m=p["m"], lo=p["lo"], hi=p["hi"])
+    for k, t in zip(R.HUBER_KEYS, ts):
         err = np.abs(t.grad.cpu().numpy() - want[k]).max()
         print(k, err, np.abs(want[k]).max())
         assert err < 1e-6 * max(1.0, np.abs(want[k]).max()), (k, err)
@@ -378,7 +317,8 @@ def test_box_qp_caps_are_the_solver_call():
     import gato_python_amd
     p = R.huber_box(6, 3, 9)[0]
     s = p["s"]
-    ts, ws = huber_math_inputs(p)
+    ts = math_inputs(p)
+    ts, ws = ts[:11], ts[11:]
     kw = dict(x_soft=ws[0], u_soft=ws[1], x_soft_max=ws[2], u_soft_max=ws[3])
     res = gato_python_amd.box_qp(*ts, rho=s.rho, method="pdas", **kw, **F64)
     assert int(res.status) == _lib.QP_CONVERGED and int(res.iters) == p["run"]["iters"] and res.x.shape == (s.N,)

@@ -16,7 +16,7 @@ import box_qp_pdas_ref as D                       # noqa: E402
 import box_qp_soft_ref as R                       # noqa: E402
 import kkt_grad_ref as kgr                        # noqa: E402
 from gato_python_amd import _lib                  # noqa: E402
-from test_gpu_box_qp_polish import F64            # noqa: E402
+from box_qp_device import F64                     # noqa: E402
 
 BAR = 1e-6
 WORST = {}                                        # section -> (largest err, its bar, input): printed when the module ends

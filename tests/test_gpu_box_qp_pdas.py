@@ -1,5 +1,5 @@
 """The primal-dual active-set iteration on the device (gato_box_qp_pdas, Solver.box_qp_pdas, box_qp(method="pdas"),
-box_qp(polish_iters=), box_qp_layer(method="pdas")) against the numpy reference of tests/box_qp_pdas_ref.py: the same number of
+box_qp(polish_iters=), box_qp_layer(method="pdas")) against the numpy reference of tests/box_qp_active_ref.py: the same number of
 reduced solves and the same final active set on problems whose every decision has a margin (the seed walks,
 tests/test_box_qp_pdas_cpu.py), one solve equal to the polish bit for bit, frozen systems, batches, the grid cap, fp32.
 Bars: those of tests/test_gpu_box_qp_polish.py - fp64 parity 1e-6 in the infinity norm, qp_kkt_residuals <= 1e-7."""
@@ -11,74 +11,19 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import box_qp_active_ref as AS                    # noqa: E402
 import box_qp_pdas_ref as D                       # noqa: E402
 import box_qp_polish_ref as P                     # noqa: E402
 import box_qp_ref as ref                          # noqa: E402
-import kkt_grad_ref as kgr                        # noqa: E402
+from box_qp_device import (CAP, F64, SENTINEL, admm, check_point, cold_case, dev_inputs, host, math_inputs, pdas, point_bits,  # noqa: E402
+                           polish, sentinels, solver, untouched)
 from gato_python_amd import _lib                  # noqa: E402
-from test_gpu_box_qp_polish import F64, admm, check_polished, dev_inputs, host, polish, solver   # noqa: E402
-
-CAP = 8192
-SENTINEL = -7.25
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _need_gpu():
     assert torch.cuda.is_available(), "GPU suite needs a GPU"
     _lib.lib()
-
-
-def parts_of(p):
-    return (None, p["H"], p["Cm"], p["g"], p["c"], p["lo"], p["hi"])
-
-
-def pdas(sol, inp, rho, eps=1e-6, act=None, outs=None, **kw):
-    kw.setdefault("exit_tol", F64["exit_tol"] if sol.np_dtype == np.float64 else 1e-8)
-    kw.setdefault("max_iters", F64["max_iters"])
-    if act is not None:
-        act = torch.from_numpy(np.ascontiguousarray(act, np.int8).reshape(-1)).cuda()
-    r = sol.box_qp_pdas(*inp, rho=rho, eps_abs=eps, eps_rel=eps, act=act, **(outs or {}), **kw)
-    torch.cuda.synchronize()
-    return r
-
-
-def sentinels(sol):
-    B, N, sk = sol.batch, sol.N, sol.sizes["sk"]
-    return dict(x=sol.new(B * N).fill_(SENTINEL), z=sol.new(B * N).fill_(SENTINEL), y=sol.new(B * N).fill_(SENTINEL),
-                lam=sol.new(B * sk).fill_(SENTINEL))
-
-
-def point_bits(r, b, sol):
-    B = sol.batch
-    return [t.cpu().numpy().reshape(B, -1)[b].tobytes() for t in (r.x, r.z, r.y, r.lam, r.iters, r.status, r.res_prim, r.res_dual, r.act)]
-
-
-def untouched(r, b, sol):
-    B = sol.batch
-    return all((t.cpu().numpy().reshape(B, -1)[b] == SENTINEL).all() for t in (r.x, r.z, r.y, r.lam))
-
-
-def check_converged(sol, r, b, p, run):
-    """System b: CONVERGED after the reference's number of solves on the reference's final act, and check_polished's bars."""
-    print("iters", int(r.iters[b]), "want", run["iters"], "status", int(r.status[b]))
-    assert int(r.status[b]) == _lib.QP_CONVERGED and int(r.polished[b]) == _lib.POLISH_ACCEPTED
-    assert int(r.iters[b]) == run["iters"]
-    act = r.act.cpu().numpy().reshape(sol.batch, -1)[b]
-    assert np.array_equal(act, run["act"]), np.flatnonzero(act != run["act"])[:5]
-    check_polished(sol, r, b, parts_of(p), run["act"])
-
-
-def cold_case(p):
-    """A cold fp64 run of problem p, twice: the reference's solves and act, the polish bars, and the same bits again."""
-    s, run = p["s"], p["run"]
-    sol = solver(s.S, s.C, s.K, np.float64)
-    inp = dev_inputs(sol, [s], [(p["lo"], p["hi"])])
-    gen = sol.get_option("assembly_gen")
-    r = pdas(sol, inp, s.rho)
-    assert sol.get_option("assembly_gen") == gen + run["iters"] and sol.get_option("assembly_valid") == 1
-    check_converged(sol, r, 0, p, run)
-    again = pdas(sol, inp, s.rho)
-    assert point_bits(again, 0, sol) == point_bits(r, 0, sol)
 
 
 # ---- 1. cold starts on control-only boxes -------------------------------------------------------------------------------
@@ -88,16 +33,16 @@ COLD = [(S, C, K) for S, C in D.SHAPES for K in D.COLD_K]
 @pytest.mark.parametrize("S,C,K", COLD, ids=["%d-%d-%d" % c for c in COLD])
 def test_cold_control_box(S, C, K):
     p = D.control_box(S, C, K)[0]
-    print("seed", p["seed"], "solves", p["run"]["iters"], "margin", D.min_margin(p["run"]))
+    print("seed", p["seed"], "solves", p["run"]["iters"], "margin", AS.min_margin(p["run"]))
     cold_case(p)
 
 
 @pytest.mark.parametrize("name", ["pendulum", "14_7_50"])
 def test_cold_named_problem(name):
     s, H, Cm, g, c, lo, hi = D.named(name)
-    run = D.pdas(H, Cm, g, c, lo, hi, s.S)
-    assert run["status"] == D.CONVERGED
-    cold_case(D.as_problem(s, H, Cm, g, c, lo, hi, run, None))
+    run = AS.iterate(H, Cm, g, c, lo, hi, s.S)
+    assert run["status"] == AS.CONVERGED
+    cold_case(AS.as_problem(s, H, Cm, g, c, lo, hi, run, None))
 
 
 # ---- 2. constructed problems: active states, dense Q and R ----------------------------------------------------------------
@@ -156,7 +101,7 @@ def test_batch_systems_equal_their_solo_runs():
     r = pdas(sol, dev_inputs(sol, [p["s"] for p in ps], [(p["lo"], p["hi"]) for p in ps]), ps[0]["s"].rho)
     assert r.iters.tolist() == want and r.status.tolist() == [_lib.QP_CONVERGED] * B
     for b, p in enumerate(ps):
-        check_converged(sol, r, b, p, p["run"])
+        check_point(sol, r, b, p, p["run"])
         assert point_bits(r, b, sol) == solo_bits(p["s"], (p["lo"], p["hi"]), p["s"].rho), b
 
 
@@ -170,7 +115,7 @@ def test_batch_with_a_system_that_does_not_converge():
     trio = [good0, bad, good1]
     for sy in (good0, good1):
         H, Cm, g, c = ref.parts(sy[0])
-        assert D.pdas(H, Cm, g, c, sy[1], sy[2], 2)["status"] == D.CONVERGED
+        assert AS.iterate(H, Cm, g, c, sy[1], sy[2], 2)["status"] == AS.CONVERGED
     sol = solver(2, 1, 20, np.float64, batch=3)
     r = pdas(sol, dev_inputs(sol, [t[0] for t in trio], [(t[1], t[2]) for t in trio]), good0[0].rho, outs=sentinels(sol))
     print("status", r.status.tolist(), "iters", r.iters.tolist())
@@ -217,22 +162,11 @@ def test_fp32_ends_on_the_reference_act(shape):
 
 
 # ---- 7. the Python surface ----------------------------------------------------------------------------------------------------
-def math_inputs(s, lo, hi, requires_grad=False):
-    """Q, R, A, B, q, r, c, x_lo, x_hi, u_lo, u_hi as box_qp takes them."""
-    blocks = [torch.from_numpy(np.ascontiguousarray(t)).cuda() for t in kgr.blocks_of(s)]
-    xl, ul = P.split_states_controls(lo, s.S, s.C, s.K)
-    xh, uh = P.split_states_controls(hi, s.S, s.C, s.K)
-    ts = blocks + [torch.from_numpy(np.ascontiguousarray(t)).cuda() for t in (xl, xh, ul, uh)]
-    for t in ts:
-        t.requires_grad_(requires_grad)
-    return ts
-
-
 def test_box_qp_method_pdas_is_the_solver_call():
     import gato_python_amd
     p = D.control_box(6, 3, 9)[0]
     s = p["s"]
-    ts = math_inputs(s, p["lo"], p["hi"])
+    ts = math_inputs(p)
     res = gato_python_amd.box_qp(*ts, rho=s.rho, method="pdas", **F64)
     assert int(res.status) == _lib.QP_CONVERGED and int(res.iters) == p["run"]["iters"] and res.x.shape == (s.N,)
     assert res.act.shape == (s.N,) and np.array_equal(res.act.cpu().numpy(), p["run"]["act"])
@@ -252,7 +186,7 @@ def test_polish_iters_closes_what_one_polish_rejects():
     import gato_python_amd
     s, lo, hi, arho = P.problem("6_3_20")
     H, Cm, g, c = ref.parts(s)
-    ts = math_inputs(s, lo, hi)
+    ts = math_inputs(dict(s=s, lo=lo, hi=hi))
     kw = dict(rho=s.rho, admm_rho=arho, max_admm_iters=50, polish=True, **F64)
     one = gato_python_amd.box_qp(*ts, **kw)
     assert int(one.polished) == _lib.POLISH_REJECTED and int(one.status) == _lib.QP_MAX_ITERS and one.act is None
@@ -270,7 +204,7 @@ def test_layer_method_pdas_gradients():
     S, C, K = 6, 3, 9
     p = D.constructed_cold(S, C, K)[0]
     s = p["s"]
-    ts = math_inputs(s, p["lo"], p["hi"], requires_grad=True)
+    ts = math_inputs(p, requires_grad=True)
     x, lam, info = gato_python_amd.box_qp_layer(*ts, rho=s.rho, method="pdas", **F64)
     assert int(info.polished) == _lib.POLISH_ACCEPTED and int(info.iters) == p["run"]["iters"]
     assert np.array_equal(info.act.cpu().numpy(), p["act"])

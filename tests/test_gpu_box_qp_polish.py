@@ -13,11 +13,11 @@ pytestmark = pytest.mark.gpu
 import box_qp_polish_ref as P                     # noqa: E402
 import box_qp_ref as ref                          # noqa: E402
 import kkt_grad_ref as kgr                        # noqa: E402
+from box_qp_device import F64, admm, bits, check_polished, dev_inputs, host, polish, solver   # noqa: E402
 from f32_parity import check_f32                  # noqa: E402
 from gato_python_amd import _lib, synth           # noqa: E402
 from oracle import gato_oracle as o               # noqa: E402
 
-F64 = dict(exit_tol=1e-20, max_iters=1000)
 _EXACT = {}
 
 
@@ -31,62 +31,6 @@ def exact(name):
     if name not in _EXACT:
         _EXACT[name] = P.exact_active(name)
     return _EXACT[name]
-
-
-def solver(S, C, K, dt, batch=1):
-    from gato_python_amd.solver import Solver
-    return Solver(S, C, K, dt, batch=batch)
-
-
-def dev_inputs(sol, systems, bounds):
-    """Stacked device inputs of the systems (G without rho, C raw, g, c, lo, hi) in the solver's dtype."""
-    dt = sol.np_dtype
-    Gs, Cs = zip(*(o.convert(s.G_row, s.G_col, s.G_val, s.C_row, s.C_col, s.C_val, s.S, s.C, s.K, 0.0) for s in systems))
-    cat = lambda arrs: sol.to_device(np.concatenate([np.asarray(a, np.float64) for a in arrs]).astype(dt))
-    return (cat(Gs), cat(Cs), cat([s.g for s in systems]), cat([s.c for s in systems]),
-            cat([b[0] for b in bounds]), cat([b[1] for b in bounds]))
-
-
-def admm(sol, inp, rho, **kw):
-    kw.setdefault("exit_tol", F64["exit_tol"] if sol.np_dtype == np.float64 else 1e-8)
-    kw.setdefault("max_iters", F64["max_iters"])
-    r = sol.box_qp(*inp, rho=rho, **kw)
-    torch.cuda.synchronize()
-    return r
-
-
-def polish(sol, inp, act, r, rho, eps=1e-6, **kw):
-    kw.setdefault("exit_tol", F64["exit_tol"] if sol.np_dtype == np.float64 else 1e-8)
-    kw.setdefault("max_iters", F64["max_iters"])
-    act_d = act if isinstance(act, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(act, np.int8)).cuda()
-    codes = sol.box_qp_polish(*inp, act_d.reshape(-1), r, rho=rho, eps_abs=eps, eps_rel=eps, **kw)
-    torch.cuda.synchronize()
-    return codes.cpu().numpy()
-
-
-def host(t, B, n):
-    return t.cpu().numpy().astype(np.float64).reshape(B, n)
-
-
-def bits(r):
-    return [t.cpu().numpy().tobytes() for t in (r.x, r.z, r.y, r.lam, r.iters, r.status, r.res_prim, r.res_dual)]
-
-
-def check_polished(sol, r, b, name_or_parts, act):
-    """Polished system b against the dense reduced solve: x, lam within 1e-6 (inf norm), qp_kkt_residuals <= 1e-7, x on the
-    active set equal to the bounds bit for bit."""
-    _, H, Cm, g, c, lo, hi = name_or_parts
-    xr, yr, lr = P.reduced_solve(H, Cm, g, c, lo, hi, act)
-    B = sol.batch
-    x, y, lam = host(r.x, B, sol.N)[b], host(r.y, B, sol.N)[b], host(r.lam, B, sol.sizes["sk"])[b]
-    ex, el = np.abs(x - xr).max(), np.abs(lam - lr).max()
-    kk = ref.qp_kkt_residuals(H, Cm, g, c, lo, hi, x, y, lam)
-    print("x err", ex, "lam err", el, "kkt", kk)
-    assert ex < 1e-6 and el < 1e-6, (ex, el)
-    assert max(kk.values()) <= 1e-7, kk
-    A = act != 0
-    assert np.array_equal(x[A], P.bound_values(act, lo, hi)[A])
-    assert int(r.status[b]) == _lib.QP_CONVERGED
 
 
 # ---- 1. the exact active set given ------------------------------------------------------------------------------------

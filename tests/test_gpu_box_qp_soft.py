@@ -1,6 +1,6 @@
 """Soft bounds in the active-set iteration on the device (gato_box_qp_pdas_soft, gato_box_qp_soft_grad, Solver.box_qp_pdas(
 soft_weight=), Solver.box_qp_soft_grad, box_qp / box_qp_layer(method="pdas", x_soft=, u_soft=)) against the numpy reference of
-tests/box_qp_soft_ref.py: the reference's number of solves and final act on walked problems (tests/test_box_qp_soft_cpu.py
+tests/box_qp_active_ref.py: the reference's number of solves and final act on walked problems (tests/test_box_qp_soft_cpu.py
 asserts that the walks find them), no weights equal to gato_box_qp_pdas bit for bit, batches, the grid cap, fp32, gradients.
 Bars: those of tests/test_gpu_box_qp_pdas.py - fp64 parity 1e-6 in the infinity norm, penalised KKT residuals <= 1e-7."""
 import ctypes as ct
@@ -11,13 +11,13 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import box_qp_active_ref as AS                    # noqa: E402
 import box_qp_pdas_ref as D                       # noqa: E402
 import box_qp_polish_ref as P                     # noqa: E402
-import box_qp_ref as ref                          # noqa: E402
 import box_qp_soft_ref as R                       # noqa: E402
 from gato_python_amd import _lib                  # noqa: E402
-from test_gpu_box_qp_pdas import CAP, SENTINEL, math_inputs, pdas, point_bits, sentinels, untouched   # noqa: E402
-from test_gpu_box_qp_polish import F64, dev_inputs, host, solver   # noqa: E402
+from box_qp_device import (CAP, F64, SENTINEL, check_point, cold_case, dev_inputs, dev_w, host, math_inputs, pdas, point_bits,  # noqa: E402
+                           raw_pdas, sentinels, solver, untouched)
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -26,48 +26,9 @@ def _need_gpu():
     _lib.lib()
 
 
-def dev_w(sol, ws):
-    return sol.to_device(np.concatenate([np.broadcast_to(np.asarray(w, np.float64), (sol.N,)) for w in ws]).astype(sol.np_dtype))
-
-
 def soft(sol, inp, w, rho, **kw):
-    """Solver.box_qp_pdas with the weights w (a device tensor or None) through test_gpu_box_qp_pdas.pdas."""
+    """Solver.box_qp_pdas with the weights w (a device tensor or None) through box_qp_device.pdas."""
     return pdas(sol, inp, rho, soft_weight=w, **kw)
-
-
-def check_soft(sol, r, b, p, run):
-    """System b: CONVERGED after the reference's solves on the reference's act; x, lam within 1e-6 of the reference; the
-    residuals of the penalised KKT system <= 1e-7; x on the hard-active set equal to the bounds bit for bit."""
-    H, Cm, g, c, lo, hi, w = (p[k] for k in ("H", "Cm", "g", "c", "lo", "hi", "w"))
-    B = sol.batch
-    print("iters", int(r.iters[b]), "want", run["iters"], "status", int(r.status[b]))
-    assert int(r.status[b]) == _lib.QP_CONVERGED and int(r.polished[b]) == _lib.POLISH_ACCEPTED
-    assert int(r.iters[b]) == run["iters"]
-    act = r.act.cpu().numpy().reshape(B, -1)[b]
-    assert np.array_equal(act, run["act"]), np.flatnonzero(act != run["act"])[:5]
-    x, z, y, lam = host(r.x, B, sol.N)[b], host(r.z, B, sol.N)[b], host(r.y, B, sol.N)[b], host(r.lam, B, sol.sizes["sk"])[b]
-    ex, el = np.abs(x - run["x"]).max(), np.abs(lam - run["lam"]).max()
-    kk = R.kkt_residuals(H, Cm, g, c, lo, hi, w, x, y, lam)
-    print("x err", ex, "lam err", el, "kkt", kk)
-    assert ex < 1e-6 and el < 1e-6, (ex, el)
-    assert max(kk.values()) <= 1e-7, kk
-    sa = R.soft_set(act, w)
-    hard = (act != 0) & ~sa
-    assert np.array_equal(x[hard], P.bound_values(act, lo, hi)[hard])
-    assert np.array_equal(z[sa], x[sa]) and np.array_equal(z[~sa], np.clip(x, lo, hi)[~sa])
-
-
-def cold_case(p):
-    s, run = p["s"], p["run"]
-    sol = solver(s.S, s.C, s.K, np.float64)
-    inp = dev_inputs(sol, [s], [(p["lo"], p["hi"])])
-    w = dev_w(sol, [p["w"]])
-    gen = sol.get_option("assembly_gen")
-    r = soft(sol, inp, w, s.rho)
-    assert sol.get_option("assembly_gen") == gen + run["iters"] and sol.get_option("assembly_valid") == 1
-    check_soft(sol, r, 0, p, run)
-    again = soft(sol, inp, w, s.rho)
-    assert point_bits(again, 0, sol) == point_bits(r, 0, sol)
 
 
 # ---- 1. cold starts: soft state boxes, hard control boxes ---------------------------------------------------------------------
@@ -77,7 +38,7 @@ COLD = [(S, C, K) for S, C in R.SHAPES for K in R.COLD_K]
 @pytest.mark.parametrize("S,C,K", COLD, ids=["%d-%d-%d" % c for c in COLD])
 def test_cold_soft_state_box(S, C, K):
     p = R.soft_box(S, C, K)[0]
-    print("seed", p["seed"], "solves", p["run"]["iters"], "margin", D.min_margin(p["run"]))
+    print("seed", p["seed"], "solves", p["run"]["iters"], "margin", AS.min_margin(p["run"]))
     cold_case(p)
 
 
@@ -85,16 +46,16 @@ def test_soft_bounds_converge_where_hard_bounds_do_not():
     """double_integrator(v_max=0.57): the hard iteration meets a singular reduced system (reference and device: MAX_ITERS or
     NONFINITE, nothing written); with the velocity bound soft the device converges as the reference does."""
     s, H, Cm, g, c, lo, hi, w = R.double_integrator_soft()
-    assert D.pdas(H, Cm, g, c, lo, hi, s.S)["status"] in (D.MAX_ITERS, D.NONFINITE)
-    run = R.pdas_soft(H, Cm, g, c, lo, hi, w, s.S)
-    assert run["status"] == R.CONVERGED and D.min_margin(run) >= D.MARGIN
+    assert AS.iterate(H, Cm, g, c, lo, hi, s.S)["status"] in (AS.MAX_ITERS, AS.NONFINITE)
+    run = AS.iterate(H, Cm, g, c, lo, hi, s.S, w)
+    assert run["status"] == AS.CONVERGED and AS.min_margin(run) >= AS.MARGIN
     sol = solver(s.S, s.C, s.K, np.float64)
     inp = dev_inputs(sol, [s], [(lo, hi)])
     hard = pdas(sol, inp, s.rho, outs=sentinels(sol))
     assert int(hard.status[0]) in (_lib.QP_MAX_ITERS, _lib.QP_NONFINITE) and untouched(hard, 0, sol)
     r = soft(sol, inp, dev_w(sol, [w]), s.rho)
-    check_soft(sol, r, 0, dict(H=H, Cm=Cm, g=g, c=c, lo=lo, hi=hi, w=w), run)
-    assert R.soft_set(run["act"], w).any()
+    check_point(sol, r, 0, dict(H=H, Cm=Cm, g=g, c=c, lo=lo, hi=hi, w=w), run)
+    assert P.soft_set(run["act"], w).any()
 
 
 # ---- 2. fp32 ------------------------------------------------------------------------------------------------------------------
@@ -103,39 +64,19 @@ def test_fp32_ends_on_the_reference_act(S, C, K):
     """fp32 under the fp32 seed rule at eps = F32_EPS, PCG exit tolerance box_qp_soft_ref.F32_EXIT_TOL (see there: at 1e-8
     the device takes the reference's nine acts at 14/7/9 and then misses the primal bar on the last one, 3.8e-4 against 3.0e-4)."""
     p = R.soft_box(S, C, K, f32=True)[0]
-    q = R.rounded(p)
+    q = P.rounded(p)
     sol = solver(S, C, K, np.float32)
     r = soft(sol, dev_inputs(sol, [q["s"]], [(q["lo"], q["hi"])]), dev_w(sol, [q["w"]]), q["s"].rho, eps=P.F32_EPS,
-             exit_tol=R.F32_EXIT_TOL, max_iters=1000)
+             exit_tol=AS.F32_EXIT_TOL, max_iters=1000)
     print("seed", p["seed"], "solves", int(r.iters[0]), "reference", p["run"]["iters"])
     assert int(r.status[0]) == _lib.QP_CONVERGED and int(r.iters[0]) == p["run"]["iters"]
     act = p["run"]["act"]
     assert np.array_equal(r.act.cpu().numpy(), act)
-    hard = (act != 0) & ~R.soft_set(act, p["w"])
+    hard = (act != 0) & ~P.soft_set(act, p["w"])
     assert np.array_equal(r.x.cpu().numpy()[hard], P.bound_values(act, q["lo"], q["hi"])[hard].astype(np.float32))
 
 
 # ---- 3. no weights: gato_box_qp_pdas, bit for bit ---------------------------------------------------------------------------
-def raw_soft(sol, inp, w, rho, max_pdas_iters=30):
-    """gato_box_qp_pdas_soft itself (w None: a NULL d_soft_w) -> a list of the outputs' bytes, in point_bits's order."""
-    B, N, sk = sol.batch, sol.N, sol.sizes["sk"]
-    L = _lib.lib()
-    prm = _lib.BoxQpParams()
-    L.gato_box_qp_default_params(prm)
-    prm.rho, prm.exit_tol, prm.max_iters = rho, F64["exit_tol"], F64["max_iters"]
-    x, z, y, lam = (torch.zeros(n, dtype=sol.dtype, device="cuda") for n in (B * N, B * N, B * N, B * sk))
-    act = torch.zeros(B * N, dtype=torch.int8, device="cuda")
-    iters, status = torch.zeros(B, dtype=torch.int32, device="cuda"), sol.new(B, torch.int32)
-    res = torch.zeros(2 * B, dtype=torch.float64, device="cuda")
-    ptr = lambda t: None if t is None else ct.c_void_p(t.data_ptr())
-    rc = L.gato_box_qp_pdas_soft(sol._h, *(ptr(t) for t in inp), ptr(w), ptr(act), ct.byref(prm), max_pdas_iters, ptr(x), ptr(z),
-                                 ptr(y), ptr(lam), ptr(iters), ptr(status), ptr(res), sol._stream())
-    _lib.check(rc)
-    torch.cuda.synchronize()
-    res = res.view(B, 2)
-    return [t.cpu().numpy().tobytes() for t in (x, z, y, lam, iters, status, res[:, 0].contiguous(), res[:, 1].contiguous(), act)]
-
-
 @pytest.mark.parametrize("shape", R.SHAPES, ids=lambda sh: "%d-%d" % sh)
 def test_no_weights_is_box_qp_pdas(shape):
     """A control-only walked problem: a NULL weight pointer, a tensor of zeros, and positive weights on variables that can never
@@ -146,26 +87,14 @@ def test_no_weights_is_box_qp_pdas(shape):
     sol = solver(S, C, 9, np.float64)
     inp = dev_inputs(sol, [s], [(p["lo"], p["hi"])])
     want = point_bits(pdas(sol, inp, s.rho), 0, sol)
-    assert raw_soft(sol, inp, None, s.rho) == want
-    assert raw_soft(sol, inp, dev_w(sol, [0.0]), s.rho) == want
+    assert raw_pdas(sol, inp, None, None, "gato_box_qp_pdas_soft", s.rho) == (0, want)
+    assert raw_pdas(sol, inp, dev_w(sol, [0.0]), None, "gato_box_qp_pdas_soft", s.rho) == (0, want)
     assert point_bits(soft(sol, inp, dev_w(sol, [0.0]), s.rho), 0, sol) == want
     assert not np.isfinite(p["lo"][R.state_weights(s) > 0]).any()
     assert point_bits(soft(sol, inp, dev_w(sol, [R.state_weights(s, 50.0)]), s.rho), 0, sol) == want
 
 
 # ---- 4. batches -------------------------------------------------------------------------------------------------------------
-def hard_state_box_that_fails(S, C, K):
-    """The first seed whose hard state box (box_qp_polish_ref.boxes(states=True), no weights) does not converge in the reference."""
-    from gato_python_amd import synth
-    for seed in range(D.WALK_SEEDS):
-        s = synth.make_system(S, C, K, seed=seed)
-        H, Cm, g, c = ref.parts(s)
-        lo, hi = P.boxes(s, seed + 1, eq=True, states=True)
-        if D.pdas(H, Cm, g, c, lo, hi, S)["status"] != D.CONVERGED:
-            return dict(s=s, H=H, Cm=Cm, g=g, c=c, lo=lo, hi=hi, w=np.zeros(s.N))
-    raise AssertionError("no such seed")
-
-
 def test_batch_of_soft_hard_frozen_and_bad_systems():
     """Five 14/7/9 systems: soft state boxes (0, 3, 4), an all-hard control box (1) and a hard state box that does not converge
     (2).  With a NaN weight in system 4 the call raises and writes nothing; with good weights every converged system has the
@@ -173,7 +102,7 @@ def test_batch_of_soft_hard_frozen_and_bad_systems():
     S, C, K, B = R.BATCH
     a, b = R.soft_box(S, C, K, count=2)
     ctl = dict(D.control_box(S, C, K)[0], w=np.zeros(a["s"].N))
-    ps = [a, ctl, hard_state_box_that_fails(S, C, K), b, a]
+    ps = [a, ctl, R.hard_state_box_that_fails(S, C, K), b, a]
     sol = solver(S, C, K, np.float64, batch=B)
     inp = dev_inputs(sol, [p["s"] for p in ps], [(p["lo"], p["hi"]) for p in ps])
     rho = a["s"].rho
@@ -193,7 +122,7 @@ def test_batch_of_soft_hard_frozen_and_bad_systems():
         solo = soft(one, dev_inputs(one, [p["s"]], [(p["lo"], p["hi"])]), dev_w(one, [p["w"]]), rho, outs=sentinels(one))
         assert int(r.status[i]) == _lib.QP_CONVERGED and int(r.iters[i]) == p["run"]["iters"]
         assert point_bits(r, i, sol) == point_bits(solo, 0, one), i
-    check_soft(sol, r, 3, b, b["run"])
+    check_point(sol, r, 3, b, b["run"])
 
 
 # ---- 5. K past the grid cap -------------------------------------------------------------------------------------------------
@@ -205,8 +134,8 @@ def test_long_horizon_second_grid_pass():
     s, run = p["s"], p["run"]
     S, C, K = D.LONG
     n = S + C
-    assert run["status"] == R.CONVERGED
-    sa = R.soft_set(run["act"], p["w"])
+    assert run["status"] == AS.CONVERGED
+    sa = P.soft_set(run["act"], p["w"])
     assert (np.flatnonzero(sa) // n >= CAP).any() and (np.flatnonzero((run["act"] != 0) & ~sa) // n >= CAP).any()
     sol = solver(S, C, K, np.float64)
     r = soft(sol, dev_inputs(sol, [s], [(p["lo"], p["hi"])]), dev_w(sol, [p["w"]]), s.rho, act=run["act"], max_iters=20000)
@@ -215,7 +144,7 @@ def test_long_horizon_second_grid_pass():
     assert np.array_equal(r.act.cpu().numpy(), run["act"])
     x, y, lam = host(r.x, 1, sol.N)[0], host(r.y, 1, sol.N)[0], host(r.lam, 1, sol.sizes["sk"])[0]
     whole, tail = np.abs(x - run["x"]).max(), np.abs(x[CAP * n:] - run["x"][CAP * n:]).max()
-    kk = R.kkt_residuals(p["H"], p["Cm"], p["g"], p["c"], p["lo"], p["hi"], p["w"], x, y, lam)
+    kk = AS.kkt_residuals(p["H"], p["Cm"], p["g"], p["c"], p["lo"], p["hi"], x, y, lam, p["w"])
     print("x err whole", whole, "knots >= 8192", tail, "kkt", kk)
     assert whole < 1e-6 and tail < 1e-6
     assert max(kk.values()) <= 1e-7, kk
@@ -233,10 +162,10 @@ def test_soft_grad_kernel(S, C, K):
     p = R.soft_box(S, C, K)[0]
     s, act, w, lo, hi, x = p["s"], p["run"]["act"], p["w"], p["lo"], p["hi"], p["run"]["x"]
     rng = np.random.default_rng(5)
-    sa = R.soft_set(act, w)
+    sa = P.soft_set(act, w)
     hard = (act != 0) & ~sa
     xbar, a, beta = rng.standard_normal(s.N), np.where(hard, 0.0, rng.standard_normal(s.N)), rng.standard_normal(S * K)
-    want = R.bound_grads(p["H"], p["Cm"], act, w, lo, hi, x, xbar, a, beta)
+    want = P.bound_grads(p["H"], p["Cm"], act, xbar, a, beta, w, lo, hi, x)
     sol = solver(S, C, K, np.float64)
     Gb, Cb = dev_inputs(sol, [s], [(lo, hi)])[:2]
     dev = lambda v: sol.to_device(np.ascontiguousarray(v, np.float64))
@@ -256,29 +185,23 @@ def test_soft_grad_kernel(S, C, K):
     assert torch.equal(lb, l2) and torch.equal(hb, h2) and not w2.any()
 
 
-def soft_math_inputs(p, requires_grad=False):
-    ts = math_inputs(p["s"], p["lo"], p["hi"], requires_grad=requires_grad)
-    xw, uw = P.split_states_controls(p["w"], p["s"].S, p["s"].C, p["s"].K)
-    ws = [torch.from_numpy(np.ascontiguousarray(t)).cuda().requires_grad_(requires_grad) for t in (xw, uw)]
-    return ts, ws
-
-
 @pytest.mark.parametrize("S,C,K", R.LAYER_CASES, ids=["%d-%d-%d" % c for c in R.LAYER_CASES])
 def test_layer_gradients_weights_included(S, C, K):
     import gato_python_amd
     p = R.soft_box(S, C, K)[0]
     s, run = p["s"], p["run"]
-    ts, ws = soft_math_inputs(p, requires_grad=True)
-    x, lam, info = gato_python_amd.box_qp_layer(*ts, rho=s.rho, method="pdas", x_soft=ws[0], u_soft=ws[1], **F64)
+    ts = math_inputs(p, requires_grad=True)
+    ws = ts[11:]
+    x, lam, info = gato_python_amd.box_qp_layer(*ts[:11], rho=s.rho, method="pdas", x_soft=ws[0], u_soft=ws[1], **F64)
     assert int(info.polished) == _lib.POLISH_ACCEPTED and int(info.iters) == run["iters"]
     assert np.array_equal(info.act.cpu().numpy(), run["act"])
     rng = np.random.default_rng(7)
     xbar, lbar = rng.standard_normal(s.N), rng.standard_normal(S * K)
     ((x * torch.from_numpy(xbar).cuda()).sum() + (lam * torch.from_numpy(lbar).cuda()).sum()).backward()
-    want = R.soft_grads(p["H"], p["Cm"], run["act"], p["w"], p["lo"], p["hi"], x.detach().cpu().numpy(), lam.detach().cpu().numpy(),
-                        xbar, lbar, S, C, K)
+    want = P.grads(p["H"], p["Cm"], run["act"], x.detach().cpu().numpy(), lam.detach().cpu().numpy(), xbar, lbar, S, C, K,
+                   w=p["w"], lo=p["lo"], hi=p["hi"])
     names = ("Q", "R", "A", "B", "q", "r", "c", "x_lo", "x_hi", "u_lo", "u_hi", "x_soft", "u_soft")
-    for k, t in zip(names, ts + ws):
+    for k, t in zip(names, ts):
         err = np.abs(t.grad.cpu().numpy() - want[k]).max()
         print(k, err, np.abs(want[k]).max())
         assert err < 1e-6 * max(1.0, np.abs(want[k]).max()), (k, err)
@@ -290,7 +213,8 @@ def test_box_qp_soft_is_the_solver_call():
     import gato_python_amd
     p = R.soft_box(6, 3, 9)[0]
     s = p["s"]
-    ts, ws = soft_math_inputs(p)
+    ts = math_inputs(p)
+    ts, ws = ts[:11], ts[11:]
     res = gato_python_amd.box_qp(*ts, rho=s.rho, method="pdas", x_soft=ws[0], u_soft=ws[1], **F64)
     assert int(res.status) == _lib.QP_CONVERGED and int(res.iters) == p["run"]["iters"] and res.x.shape == (s.N,)
     sol = solver(s.S, s.C, s.K, np.float64)

@@ -12,15 +12,14 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import box_qp_active_ref as AS                    # noqa: E402
 import box_qp_pdas_ref as D                       # noqa: E402
 import box_qp_polish_ref as P                     # noqa: E402
 import box_qp_soft_ref as R                       # noqa: E402
 from f32_parity import check_f32                  # noqa: E402
 from gato_python_amd import _lib                  # noqa: E402
-from test_gpu_box_qp_pdas import CAP, SENTINEL, point_bits   # noqa: E402
-from test_gpu_box_qp_polish import F64, dev_inputs, host, solver   # noqa: E402
-from test_gpu_box_qp_soft import check_soft, cold_case, dev_w, soft, soft_math_inputs   # noqa: E402
-from test_gpu_qp_kernel_sweep import g_and_c      # noqa: E402
+from box_qp_device import (CAP, F64, SENTINEL, check_point, cold_case, dev_inputs, dev_w, g_and_c, host, math_inputs, pdas,  # noqa: E402
+                           point_bits, solver)
 
 SHAPES = R.SHAPES
 NAMES = ("lo_bar", "hi_bar", "w_bar")
@@ -34,7 +33,7 @@ def _need_gpu():
 
 def describe(p):
     run = p["run"]
-    print("seed", p["seed"], "solves", run["iters"], "margin", D.min_margin(run), "cover (a, b, c)", p["cover"])
+    print("seed", p["seed"], "solves", run["iters"], "margin", AS.min_margin(run), "cover (a, b, c)", p["cover"])
 
 
 # ---- 1. cold starts on mixed problems -----------------------------------------------------------------------------------------
@@ -57,15 +56,15 @@ def test_fp32_mixed_ends_on_the_reference_act(shape):
     K = R.MIXED_F32_K
     p = R.mixed_box(S, C, K, f32=True)[0]
     describe(p)
-    q = R.rounded(p)
+    q = P.rounded(p)
     sol = solver(S, C, K, np.float32)
-    r = soft(sol, dev_inputs(sol, [q["s"]], [(q["lo"], q["hi"])]), dev_w(sol, [q["w"]]), q["s"].rho, eps=P.F32_EPS,
-             exit_tol=R.F32_EXIT_TOL, max_iters=1000)
+    r = pdas(sol, dev_inputs(sol, [q["s"]], [(q["lo"], q["hi"])]), q["s"].rho, soft_weight=dev_w(sol, [q["w"]]), eps=P.F32_EPS,
+             exit_tol=AS.F32_EXIT_TOL, max_iters=1000)
     print("solves", int(r.iters[0]), "reference", p["run"]["iters"])
     assert int(r.status[0]) == _lib.QP_CONVERGED and int(r.iters[0]) == p["run"]["iters"]
     act = p["run"]["act"]
     assert np.array_equal(r.act.cpu().numpy(), act)
-    hard = (act != 0) & ~R.soft_set(act, p["w"])
+    hard = (act != 0) & ~P.soft_set(act, p["w"])
     assert np.array_equal(r.x.cpu().numpy()[hard], P.bound_values(act, q["lo"], q["hi"])[hard].astype(np.float32))
 
 
@@ -121,7 +120,7 @@ def grad_case_cover(case, S, C, K):
     for act, w in zip(case["act"], case["w"]):
         idx = np.arange(len(act))
         knot, ctl = idx // n, idx % n >= S
-        sa = R.soft_set(act, w)
+        sa = P.soft_set(act, w)
         hard = (act != 0) & ~sa
         mixed = lambda part: np.intersect1d(knot[sa & part], knot[hard & part])
         out.append((mixed(~ctl).size > 0, mixed(ctl).size > 0, K - 1 in mixed(~ctl)))
@@ -147,7 +146,7 @@ def run_soft_grad(sol, case):
 
 
 def off_the_active_set_is_zero(got, act, w):
-    sa = R.soft_set(act, w)
+    sa = P.soft_set(act, w)
     assert not got[0][act >= 0].any() and not got[1][act <= 0].any() and not got[2][~sa].any()
 
 
@@ -156,7 +155,7 @@ def grad_oracle32(H, Cm, case, b):
     f = lambda v: np.asarray(v, np.float32)
     act, w, lo, hi = case["act"][b], f(case["w"][b]), f(case["lo"][b]), f(case["hi"][b])
     x, xbar, a, beta = (f(case[k][b]) for k in ("x", "xbar", "a", "beta"))
-    sa = R.soft_set(act, w)
+    sa = P.soft_set(act, w)
     hard = (act != 0) & ~sa
     bnd = np.where(act > 0, hi, np.where(act < 0, lo, np.float32(0)))
     zero = np.float32(0)
@@ -180,11 +179,11 @@ def test_batch_of_weight_vectors_on_one_system():
     sol = solver(S, C, K, np.float64, batch=B)
     inp = dev_inputs(sol, [s] * B, [(lo, hi)] * B)
     wd = dev_w(sol, ws)
-    r = soft(sol, inp, wd, s.rho)
+    r = pdas(sol, inp, s.rho, soft_weight=wd)
     acts = r.act.cpu().numpy().reshape(B, -1)
     for i, (w, run) in enumerate(zip(ws, runs)):
         one = solver(S, C, K, np.float64)
-        solo = soft(one, dev_inputs(one, [s], [(lo, hi)]), dev_w(one, [w]), s.rho)
+        solo = pdas(one, dev_inputs(one, [s], [(lo, hi)]), s.rho, soft_weight=dev_w(one, [w]))
         assert int(r.status[i]) == _lib.QP_CONVERGED and int(r.iters[i]) == run["iters"], (i, r.status.tolist(), r.iters.tolist())
         assert np.array_equal(acts[i], run["act"]), i
         assert point_bits(r, i, sol) == point_bits(solo, 0, one), i
@@ -193,7 +192,7 @@ def test_batch_of_weight_vectors_on_one_system():
     gap = np.abs(x[0] - x[1]).max()
     print("mixed against scaled: |x - x'|", gap, "reference", want_gap)
     assert want_gap > 1e-3 and gap > 1e-3
-    check_soft(sol, r, 0, dict(H=H, Cm=Cm, g=g, c=c, lo=lo, hi=hi, w=ws[0]), runs[0])
+    check_point(sol, r, 0, dict(H=H, Cm=Cm, g=g, c=c, lo=lo, hi=hi, w=ws[0]), runs[0])
     # the gradient kernel over the batch: one act, one weight vector and one point per system
     rng = np.random.default_rng(11)
     W = np.stack(ws)
@@ -206,7 +205,7 @@ def test_batch_of_weight_vectors_on_one_system():
     got = [host(t, B, sol.N) for t in got]
     Hg, Cg = (m.toarray() for m in g_and_c(s))
     for i in range(B):
-        want = R.bound_grads(Hg, Cg, acts[i], ws[i], lo, hi, x[i], xbar[i], a[i], beta[i])
+        want = P.bound_grads(Hg, Cg, acts[i], xbar[i], a[i], beta[i], ws[i], lo, hi, x[i])
         bar = 1e-12 * grad_scale(Hg, Cg, ws[i], a[i], beta[i]) * (2 * S + C)
         for name, t, wt in zip(NAMES, got, want):
             err = np.abs(t[i] - wt).max()
@@ -237,7 +236,7 @@ def test_soft_grad_direct(shape, K, dt):
         H, Cm = (m.toarray() for m in g_and_c(s))
         act, w = case["act"][b], case["w"][b]
         off_the_active_set_is_zero([t[b] for t in got], act, w)
-        want = R.bound_grads(H, Cm, act, w, case["lo"][b], case["hi"][b], case["x"][b], case["xbar"][b], case["a"][b], case["beta"][b])
+        want = P.bound_grads(H, Cm, act, case["xbar"][b], case["a"][b], case["beta"][b], w, case["lo"][b], case["hi"][b], case["x"][b])
         assert all(np.abs(t).max() > 0 for t in want)
         if dt == np.float64:
             bar = 1e-12 * grad_scale(H, Cm, w, case["a"][b], case["beta"][b]) * (2 * S + C)
@@ -260,7 +259,7 @@ def test_soft_grad_long_horizon():
     act, w = case["act"][0], case["w"][0]
     off_the_active_set_is_zero([t[0] for t in got], act, w)
     H, Cm = g_and_c(case["systems"][0])
-    want = R.bound_grads(H, Cm, act, w, case["lo"][0], case["hi"][0], case["x"][0], case["xbar"][0], case["a"][0], case["beta"][0])
+    want = P.bound_grads(H, Cm, act, case["xbar"][0], case["a"][0], case["beta"][0], w, case["lo"][0], case["hi"][0], case["x"][0])
     bar = 1e-12 * grad_scale(H, Cm, w, case["a"][0], case["beta"][0]) * (2 * S + C)
     tail = slice(CAP * n, None)
     for name, t, wt in zip(NAMES, got, want):
@@ -279,19 +278,19 @@ def test_long_horizon_mixed_second_grid_pass():
     s, run = p["s"], p["run"]
     S, C, K = D.LONG
     n = S + C
-    assert run["status"] == R.CONVERGED
-    sa = R.soft_set(run["act"], p["w"])
+    assert run["status"] == AS.CONVERGED
+    sa = P.soft_set(run["act"], p["w"])
     idx = np.arange(s.N)
     tail = idx // n >= CAP
     assert (sa & tail & (idx % n >= S) & (p["lo"] != p["hi"])).any() and ((run["act"] != 0) & ~sa & tail).any()
     sol = solver(S, C, K, np.float64)
-    r = soft(sol, dev_inputs(sol, [s], [(p["lo"], p["hi"])]), dev_w(sol, [p["w"]]), s.rho, act=run["act"], max_iters=20000)
+    r = pdas(sol, dev_inputs(sol, [s], [(p["lo"], p["hi"])]), s.rho, soft_weight=dev_w(sol, [p["w"]]), act=run["act"], max_iters=20000)
     print("seed", p["seed"], "solves", int(r.iters[0]), "reference", run["iters"])
     assert int(r.status[0]) == _lib.QP_CONVERGED and int(r.iters[0]) == 1
     assert np.array_equal(r.act.cpu().numpy(), run["act"])
     x, y, lam = host(r.x, 1, sol.N)[0], host(r.y, 1, sol.N)[0], host(r.lam, 1, sol.sizes["sk"])[0]
     whole, end = np.abs(x - run["x"]).max(), np.abs(x[CAP * n:] - run["x"][CAP * n:]).max()
-    kk = R.kkt_residuals(p["H"], p["Cm"], p["g"], p["c"], p["lo"], p["hi"], p["w"], x, y, lam)
+    kk = AS.kkt_residuals(p["H"], p["Cm"], p["g"], p["c"], p["lo"], p["hi"], x, y, lam, p["w"])
     print("x err whole", whole, "knots >= 8192", end, "kkt", kk)
     assert whole < 1e-6 and end < 1e-6
     assert max(kk.values()) <= 1e-7, kk
@@ -302,10 +301,11 @@ def test_box_qp_u_soft_is_the_solver_call():
     import gato_python_amd
     p = R.mixed_box(6, 3, 9)[0]
     s = p["s"]
-    ts, ws = soft_math_inputs(p)
+    ts = math_inputs(p)
+    ts, ws = ts[:11], ts[11:]
     assert ws[1].shape == (s.K - 1, s.C) and (ws[1] > 0).any() and (ws[1] == 0).any() and (ws[0] > 0).any()
     sol = solver(s.S, s.C, s.K, np.float64)
-    direct = soft(sol, dev_inputs(sol, [s], [(p["lo"], p["hi"])]), dev_w(sol, [p["w"]]), s.rho)
+    direct = pdas(sol, dev_inputs(sol, [s], [(p["lo"], p["hi"])]), s.rho, soft_weight=dev_w(sol, [p["w"]]))
     assert int(direct.status[0]) == _lib.QP_CONVERGED and int(direct.iters[0]) == p["run"]["iters"]
     names = ("x", "z", "y", "lam", "res_prim", "res_dual", "act")
     res = gato_python_amd.box_qp(*ts, rho=s.rho, method="pdas", x_soft=ws[0], u_soft=ws[1], **F64)
@@ -327,20 +327,21 @@ def test_layer_gradients_with_soft_controls(S, C, K):
     p = R.mixed_layer_box(S, C, K)
     describe(p)
     s, run = p["s"], p["run"]
-    ts, ws = soft_math_inputs(p, requires_grad=True)
-    x, lam, info = gato_python_amd.box_qp_layer(*ts, rho=s.rho, method="pdas", x_soft=ws[0], u_soft=ws[1], **F64)
+    ts = math_inputs(p, requires_grad=True)
+    ws = ts[11:]
+    x, lam, info = gato_python_amd.box_qp_layer(*ts[:11], rho=s.rho, method="pdas", x_soft=ws[0], u_soft=ws[1], **F64)
     assert int(info.polished) == _lib.POLISH_ACCEPTED and int(info.iters) == run["iters"]
     assert np.array_equal(info.act.cpu().numpy(), run["act"])
     rng = np.random.default_rng(7)
     xbar, lbar = rng.standard_normal(s.N), rng.standard_normal(S * K)
     ((x * torch.from_numpy(xbar).cuda()).sum() + (lam * torch.from_numpy(lbar).cuda()).sum()).backward()
-    want = R.soft_grads(p["H"], p["Cm"], run["act"], p["w"], p["lo"], p["hi"], x.detach().cpu().numpy(), lam.detach().cpu().numpy(),
-                        xbar, lbar, S, C, K)
+    want = P.grads(p["H"], p["Cm"], run["act"], x.detach().cpu().numpy(), lam.detach().cpu().numpy(), xbar, lbar, S, C, K,
+                   w=p["w"], lo=p["lo"], hi=p["hi"])
     names = ("Q", "R", "A", "B", "q", "r", "c", "x_lo", "x_hi", "u_lo", "u_hi", "x_soft", "u_soft")
-    for k, t in zip(names, ts + ws):
+    for k, t in zip(names, ts):
         err = np.abs(t.grad.cpu().numpy() - want[k]).max()
         print(k, err, np.abs(want[k]).max())
         assert err < 1e-6 * max(1.0, np.abs(want[k]).max()), (k, err)
-    sc = P.split_states_controls(R.soft_set(run["act"], p["w"]) & (p["lo"] != p["hi"]), S, C, K)[1] > 0
+    sc = P.split_states_controls(P.soft_set(run["act"], p["w"]) & (p["lo"] != p["hi"]), S, C, K)[1] > 0
     assert sc.any() and np.abs(want["u_lo"][sc]).max() + np.abs(want["u_hi"][sc]).max() > 0
     assert np.abs(want["u_soft"]).max() > 0 and np.abs(want["x_soft"]).max() > 0 and np.abs(want["R"]).max() > 0

@@ -15,14 +15,12 @@ import box_qp_polish_ref as P                     # noqa: E402
 import box_qp_ref as ref                          # noqa: E402
 from f32_parity import check_f32                  # noqa: E402
 from gato_python_amd import _lib, synth           # noqa: E402
-from test_gpu_box_qp import PARITY, boxes, rel    # noqa: E402
-from test_gpu_box_qp import host as admm_host, run as admm_run   # noqa: E402
-from test_gpu_box_qp_polish import admm, bits, check_polished, dev_inputs, host, polish, solver   # noqa: E402
+from box_qp_device import (CAP, PARITY, admm, admm_host, admm_run, bits, check_polished, dev_inputs, g_and_c, host, polish,   # noqa: E402
+                           rel, solver)
 
 SHAPES = P.SWEEP_SHAPES
 SHORT_K = P.SWEEP_SHORT_K
 LONG = P.SWEEP_LONG
-CAP = 8192                                        # knot_grid(): workgroups per system; knots >= CAP run in a second pass
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -175,13 +173,6 @@ def bound_grad_case(S, C, K, B, dt, sparse=False):
     return systems, act, xbar, a, beta
 
 
-def g_and_c(s):
-    """(G, C) of a system as scipy.sparse CSR matrices, rho not added: the kernel reads G's rows at rho 0 (a_A = 0)."""
-    from scipy import sparse
-    return (sparse.csr_matrix((s.G_val, s.G_col, s.G_row), shape=(s.N, s.N)),
-            sparse.csr_matrix((s.C_val, s.C_col, s.C_row), shape=(s.S * s.K, s.N)))
-
-
 def run_bound_grad(sol, systems, act, xbar, a, beta):
     inf = np.full(systems[0].N, np.inf)
     inp = dev_inputs(sol, systems, [(-inf, inf)] * len(systems))
@@ -241,11 +232,11 @@ ADMM_CASES = [((6, 3), 9), ((12, 6), 9), ((32, 16), 9)] + [(sh, K) for sh in SHA
 
 @pytest.mark.parametrize("shape,K", ADMM_CASES, ids=["%d-%d-%d" % (sh + (K,)) for sh, K in ADMM_CASES])
 def test_admm_iterates_every_shape(shape, K):
-    """K = 2, 3: every knot is a first or a last one.  boxes() fixes a control of knot K // 2, which K = 2 does not have:
+    """K = 2, 3: every knot is a first or a last one.  P.boxes() fixes a control of knot K // 2, which K = 2 does not have:
     there the box comes without the lo == hi control."""
     S, C = shape
     s = synth.make_system(S, C, K, seed=2)
-    lo, hi = boxes(s, 3, eq=K > 2)
+    lo, hi = P.boxes(s, 3, eq=K > 2)
     sol = solver(S, C, K, np.float64)
     r = admm_run(sol, dev_inputs(sol, [s], [(lo, hi)]), s.rho, **PARITY)
     got = admm_host(r, 0, sol)
