@@ -6,10 +6,13 @@ Public surface:
   gato_python_amd.Solver                 device-resident stage-level API over include/gato_hip.h
   gato_python_amd.kkt_solve(...)         differentiable solve from math-shaped blocks (torch autograd, autograd.py)
   gato_python_amd.kkt_solve_csr(...)     differentiable solve on device CSR input
-  gato_python_amd.box_qp(...)            box-constrained QP (bounds on states and controls) by ADMM over the re-solve
+  gato_python_amd.box_qp(...)            box-constrained QP (bounds on states and controls) by ADMM over the re-solve, or
+                                         by the active-set iteration (method="pdas": hard, soft and capped soft bounds;
+                                         line_search=True: the exact line search that makes the all-soft iteration converge)
   gato_python_amd.box_qp_layer(...)      differentiable box-constrained QP: ADMM, then the polish on its active set, or the
                                          active-set iteration alone, with hard or soft bounds (one autograd Function,
-                                         qp._BoxQPLayer, whose backward branches on "weights present")
+                                         qp._BoxQPLayer, whose backward branches on "weights present"); line_search=True
+                                         changes the forward pass only
   gato_python_amd.synth                  synthetic OCP inputs (the reference ships pendulum data only)
 """
 from .linsys import (clear_problem_size, last_stats, linsys_resolve, linsys_solve, set_precision,  # noqa: F401

@@ -391,6 +391,33 @@ int launch_pdas_step(const Dims &d, const PdasArgs &a, int it, hipStream_t st);
 // the decision of solve `it` (pdas_decide_kernel); last: no solve follows
 template <typename T, int S, int C>
 int launch_pdas_decide(const Dims &d, const PdasArgs &a, int it, int last, hipStream_t st);
+// Exact line search of the soft active-set iteration (gato_pdas_ls.hip): along d = x+ - xc the slope
+// phi'(alpha) = d^T (H (xc + alpha d) - g + f(xc + alpha d)), H = G + rho I, f the capped penalty force of section 3.11.
+struct LineSearchArgs {
+    const void *G, *g, *lo, *hi, *w, *cap;  // the caller's blocks (G without rho) and vectors [B][N]; cap may be nullptr (none)
+    const void *xc, *xp;                    // the current iterate and the Newton point x+ [B][N]
+    void *xout;                             // the stepped iterate [B][N] (the loop: xc itself); nullptr: not written
+    double *part;                           // [B][K][2] per knot: d_k^T (H_k xc_k - g_k), d_k^T H_k d_k
+    double *alpha;                          // step lengths, system sys at alpha[sys * alpha_stride]; nullptr: not written
+    size_t alpha_stride;
+    double *slope;                          // [B][2] phi'(0), phi'(1); nullptr: not written
+    // the loop only (status == nullptr: the kernels alone, no system is skipped and no act is written)
+    const int *status;                      // a system frozen before this solve (status >= 0) is skipped
+    const unsigned long long *slots;        // the solve's maxima [B][2][GATO_POLISH_NSLOT]: an accepted or non-finite point takes no step
+    const signed char *act;                 // the act of the solve
+    signed char *act2;                      // act' from the stepped iterate
+    int *round;                             // PdasArgs::round: the changed count of act' replaces the step kernel's
+    int *bad;                               // the scope check: waves that saw a finite hard bound
+    int *status_out;                        // the scope check marks BAD_BOUNDS here
+    double rho, eps_abs, eps_rel;
+    int it;                                 // the solve (1: the first of a call, xc <- x+ and alpha = 1)
+};
+// the scope of the option: a finite bound off x_0 without a weight marks the system BAD_BOUNDS (after launch_pdas_check)
+template <typename T, int S, int C>
+int launch_ls_scope(const Dims &d, const LineSearchArgs &a, hipStream_t st);
+// the per-knot partial sums, then the per-system step length, stepped iterate and (the loop) act' and its changed count
+template <typename T, int S, int C>
+int launch_line_search(const Dims &d, const LineSearchArgs &a, hipStream_t st);
 template <typename T, int S>
 int pcg_resident_plan(PcgPlan *plan);
 template <typename T, int S>
@@ -480,6 +507,8 @@ struct Ops {
     int (*pdas_check)(const Dims &, const PdasArgs &, hipStream_t);
     int (*pdas_step)(const Dims &, const PdasArgs &, int, hipStream_t);
     int (*pdas_decide)(const Dims &, const PdasArgs &, int, int, hipStream_t);
+    int (*ls_scope)(const Dims &, const LineSearchArgs &, hipStream_t);
+    int (*line_search)(const Dims &, const LineSearchArgs &, hipStream_t);
     int (*pcg_plan)(PcgPlan *);
     int (*pcg_resident)(const PcgLaunch &, hipStream_t);
     int (*pcg_dma_max_knots)();

@@ -150,22 +150,26 @@ extern "C" int gato_box_qp_active_set(gato_solver *s, const void *d_z, const voi
 
 // The work area of the polish and of the active-set iteration (pol_ws), as offsets: the reduced system's right-hand side, the
 // reduced solve and the polished point, then what only the iteration has (act', a second set of maxima, the round counts, polish
-// flags of its own) around the maxima and the counters.  Everything from sl on is zeroed at the start of a call.
+// flags of its own) around the maxima and the counters, and what only its line search has (the iterate, the knots' partial sums).
+// Everything from sl on is zeroed at the start of a call.
 struct PolishWs {
     size_t gp, cp, xt, lt, xp, zp, yp;      // [B][N] each, cp and lt [B][S K]
     size_t a2;                              // iteration: act' [B][N] int8
+    size_t xc, part;                        // line search: LineSearchArgs::xc [B][N], part [B][K][2] doubles
     size_t sl;                              // the maxima, [B][GATO_POLISH_NSLOT]; iteration: [B][2][GATO_POLISH_NSLOT]
     size_t rn, pol;                         // iteration: PdasArgs::round [B][2][2], PolishArgs::polish [B]
     size_t ctr;                             // polish: the BAD_ACTIVE count; iteration: PdasArgs::ctr and the count after it
     size_t bytes;
 };
-static PolishWs polish_ws(const Dims &d, size_t e, bool pdas)
+static PolishWs polish_ws(const Dims &d, size_t e, bool pdas, bool ls = false)
 {
     const size_t B = d.B, vN = align_up(B * d.N() * e), vK = align_up(B * d.sk() * e);
     PolishWs o;
     o.gp = 0; o.cp = o.gp + vN; o.xt = o.cp + vK; o.lt = o.xt + vN; o.xp = o.lt + vK; o.zp = o.xp + vN; o.yp = o.zp + vN;
     o.a2 = o.yp + vN;
-    o.sl = o.a2 + (pdas ? align_up(B * d.N()) : 0);
+    o.xc = o.a2 + (pdas ? align_up(B * d.N()) : 0);
+    o.part = o.xc + (ls ? vN : 0);
+    o.sl = o.part + (ls ? align_up(B * (size_t)d.K * 2 * sizeof(double)) : 0);
     o.rn = o.sl + align_up(B * (pdas ? 2 : 1) * GATO_POLISH_NSLOT * 8);
     o.pol = o.rn + (pdas ? align_up(B * 4 * sizeof(int)) : 0);
     o.ctr = o.pol + (pdas ? align_up(B * sizeof(int)) : 0);
@@ -240,11 +244,14 @@ extern "C" int gato_box_qp_polish(gato_solver *s, const void *d_G_blocks, const 
 // polish), then the step and the decision and one read of the live count.  d_soft_w: the weights of soft bounds (NULL: all
 // hard), read by the check, the prepare and the step; d_soft_cap: the caps of their forces (section 3.11; NULL: none, and not
 // read without weights).  `who` names the entry in errors; soft: its texts speak of the weights (2: and of the caps).
+// ls: the exact line search of section 3.12 - the scope check after the check launch, and between the step and the decision of
+// every solve the two launches that move the iterate xc and take act' and its changed count from it; d_alpha [B][max_pdas_iters]
+// (may be NULL) receives the step lengths.
 static int pdas_loop(gato_solver *s, const char *who, int soft, const void *d_G_blocks, const void *d_C_blocks, const void *d_g,
                      const void *d_c, const void *d_lo, const void *d_hi, const void *d_soft_w, const void *d_soft_cap,
                      signed char *d_act,
                      const gato_box_qp_params *p, int max_pdas_iters, void *d_x, void *d_z, void *d_y, void *d_lambda, int *d_iters,
-                     int *d_status, double *d_res, void *stream)
+                     int *d_status, double *d_res, void *stream, bool ls = false, double *d_alpha = nullptr)
 {
     if (check_pointers(s, who, p, d_C_blocks, {d_G_blocks, d_g, d_c, d_lo, d_hi, d_act, d_x, d_z, d_y, d_lambda, d_iters, d_status, d_res},
                        soft == 2 ? ", d_soft_w for no soft bound, d_soft_cap for no cap" : (soft ? ", d_soft_w for no soft bound" : "")))
@@ -258,13 +265,14 @@ static int pdas_loop(gato_solver *s, const char *who, int soft, const void *d_G_
     if (check_not_capturing(who, "the loop reads the live count", st)) return GATO_EINVAL;
     GATO_HIP_CHECK(hipSetDevice(s->device));
     const size_t B = s->d.B;
-    const PolishWs o = polish_ws(s->d, s->esz, true);
+    const PolishWs o = polish_ws(s->d, s->esz, true, ls);
     int rc;
     if ((rc = grow_ws(&s->pol_ws, &s->pol_ws_bytes, o.bytes, st))) return rc;
     char *w = s->pol_ws;
     int *ctr = (int *)(w + o.ctr);
     GATO_HIP_CHECK(hipMemsetAsync(w + o.sl, 0, o.bytes - o.sl, st));                 // both sets of maxima and counts, the counters
     GATO_HIP_CHECK(hipMemsetAsync(d_status, 0xff, B * sizeof(int), st));             // -1: running
+    if (d_alpha) GATO_HIP_CHECK(hipMemsetAsync(d_alpha, 0, B * max_pdas_iters * sizeof(double), st));   // 0: no step taken
     PdasArgs a;
     memset(&a, 0, sizeof(a));
     PolishArgs &q = a.p;
@@ -278,18 +286,30 @@ static int pdas_loop(gato_solver *s, const char *who, int soft, const void *d_G_
     s->as.valid = 0;
     s->lc.valid = 0;                        // G_dense and Ginv are rewritten: nothing earlier is left to recover
     if ((rc = s->ops->pdas_check(s->d, a, st))) return rc;
+    LineSearchArgs la;
+    memset(&la, 0, sizeof(la));
+    if (ls) {
+        la.G = d_G_blocks; la.g = d_g; la.lo = d_lo; la.hi = d_hi; la.w = d_soft_w; la.cap = q.cap;
+        la.xc = la.xout = w + o.xc; la.xp = q.xp; la.part = (double *)(w + o.part); la.alpha_stride = max_pdas_iters;
+        la.status = la.status_out = d_status; la.slots = q.slots; la.act = d_act; la.act2 = a.act2; la.round = a.round;
+        la.bad = ctr + 4;
+        la.rho = p->rho; la.eps_abs = p->eps_abs; la.eps_rel = p->eps_rel;
+        if ((rc = s->ops->ls_scope(s->d, la, st))) return rc;
+    }
     PcgOpts po = pcg_opts(*s);
     po.warm = 0;                            // every reduced solve is a cold start
     const AsmInput in{2, nullptr, nullptr, d_G_blocks, nullptr, nullptr, nullptr, d_C_blocks, true};
     for (int it = 1; it <= max_pdas_iters; ++it) {
         if ((rc = s->ops->add_rho(s->d, d_G_blocks, p->rho, s->G_dense, st))) return rc;
         if ((rc = s->ops->polish_prepare(s->d, q, st))) return rc;
-        int h[3] = {0, 0, 0};
+        int h[5] = {0, 0, 0, 0, 0};         // ctr[3] is the polish's own count, ctr[4] the line search's scope check
         if (it == 1) {                      // the caller's bounds and start act; later acts are the device's own: valid
-            GATO_HIP_CHECK(hipMemcpyAsync(h, ctr, sizeof(h), hipMemcpyDeviceToHost, st));
+            GATO_HIP_CHECK(hipMemcpyAsync(h, ctr, (ls ? 5 : 3) * sizeof(int), hipMemcpyDeviceToHost, st));
             GATO_HIP_CHECK(hipStreamSynchronize(st));
-            if (h[1] > 0 || h[2] > 0) {
-                set_error("%s:%s%s; d_status marks the systems", who,
+            if (h[1] > 0 || h[2] > 0 || h[4] > 0) {
+                set_error("%s:%s%s%s; d_status marks the systems", who,
+                          h[4] > 0 ? " a finite bound off x_0 has no weight: the line search takes soft bounds only, every variable "
+                                     "with a finite bound needs w_i > 0 (BAD_BOUNDS)" : "",
                           h[1] > 0 ? (soft == 2 ? " a bound is NaN, lo > hi, a weight is NaN, negative or infinite or a cap is NaN or "
                                                   "negative (BAD_BOUNDS)"
                                       : soft ? " a bound is NaN, lo > hi or a weight is NaN, negative or infinite (BAD_BOUNDS)"
@@ -302,6 +322,11 @@ static int pdas_loop(gato_solver *s, const char *who, int soft, const void *d_G_
         }
         if ((rc = whole_solve(s, po, in, w + o.gp, w + o.cp, p->exit_tol, p->max_iters, p->rho, w + o.lt, w + o.xt, st))) return rc;
         if ((rc = s->ops->pdas_step(s->d, a, it, st))) return rc;
+        if (ls) {
+            la.it = it;
+            la.alpha = d_alpha ? d_alpha + (it - 1) : nullptr;
+            if ((rc = s->ops->line_search(s->d, la, st))) return rc;
+        }
         if ((rc = s->ops->pdas_decide(s->d, a, it, it == max_pdas_iters, st))) return rc;
         if (it == max_pdas_iters) break;    // every system still live froze in that decision
         hipError_t he = hipMemcpyAsync(h, ctr, sizeof(int), hipMemcpyDeviceToHost, st);
@@ -397,4 +422,44 @@ extern "C" int gato_box_qp_huber_grad(gato_solver *s, const void *d_G_blocks, co
     const BoundGradArgs a{d_G_blocks, d_C_blocks, d_act, d_soft_w, d_lo, d_hi, d_x, d_xbar, d_a, d_beta, d_lo_bar, d_hi_bar, d_w_bar,
                           d_soft_w ? d_soft_cap : nullptr, d_cap_bar};
     return s->ops->qp_bound_grad(d, a, (hipStream_t)stream);
+}
+
+// ---- exact line search of the soft active-set iteration (gato_pdas_ls.hip) -----------------------------
+extern "C" int gato_box_qp_pdas_ls(gato_solver *s, const void *d_G_blocks, const void *d_C_blocks, const void *d_g, const void *d_c,
+                                   const void *d_lo, const void *d_hi, const void *d_soft_w, const void *d_soft_cap,
+                                   signed char *d_act, const gato_box_qp_params *p, int max_pdas_iters, void *d_x, void *d_z,
+                                   void *d_y, void *d_lambda, int *d_iters, int *d_status, double *d_res, double *d_alpha,
+                                   void *stream)
+{
+    if (!d_soft_w) {
+        set_error("box_qp_pdas_ls: d_soft_w is required (the line search takes soft bounds only; d_soft_cap and d_alpha may be NULL)");
+        return GATO_EINVAL;
+    }
+    return pdas_loop(s, "box_qp_pdas_ls", 2, d_G_blocks, d_C_blocks, d_g, d_c, d_lo, d_hi, d_soft_w, d_soft_cap, d_act, p,
+                     max_pdas_iters, d_x, d_z, d_y, d_lambda, d_iters, d_status, d_res, stream, true, d_alpha);
+}
+
+extern "C" int gato_box_qp_line_search(gato_solver *s, const void *d_G_blocks, const void *d_g, const void *d_lo, const void *d_hi,
+                                       const void *d_soft_w, const void *d_soft_cap, double rho, const void *d_xc, const void *d_xplus,
+                                       double *d_alpha, double *d_slope, void *d_x, void *stream)
+{
+    if (!solver_usable(s, "box_qp_line_search", "QP solves")) return GATO_EINVAL;
+    if (!d_G_blocks || !d_g || !d_lo || !d_hi || !d_soft_w || !d_xc || !d_xplus || !d_alpha || !d_slope) {
+        set_error("box_qp_line_search: every pointer is required (d_soft_cap may be NULL for no cap, d_x for no stepped point)");
+        return GATO_EINVAL;
+    }
+    if (!std::isfinite(rho) || rho < 0) { set_error("box_qp_line_search: rho must be finite and >= 0"); return GATO_EINVAL; }
+    hipStream_t st = (hipStream_t)stream;
+    GATO_HIP_CHECK(hipSetDevice(s->device));
+    const PolishWs o = polish_ws(s->d, s->esz, true, true);
+    int rc;
+    if ((rc = grow_ws(&s->pol_ws, &s->pol_ws_bytes, o.bytes, st))) return rc;
+    Dims d = s->d;
+    d.k_lo = d.k_hi = 0; d.rhs = 0;
+    LineSearchArgs la;
+    memset(&la, 0, sizeof(la));
+    la.G = d_G_blocks; la.g = d_g; la.lo = d_lo; la.hi = d_hi; la.w = d_soft_w; la.cap = d_soft_cap;
+    la.xc = d_xc; la.xp = d_xplus; la.xout = d_x; la.part = (double *)(s->pol_ws + o.part);
+    la.alpha = d_alpha; la.alpha_stride = 1; la.slope = d_slope; la.rho = rho; la.it = 2;
+    return s->ops->line_search(d, la, st);
 }

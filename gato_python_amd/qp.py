@@ -78,9 +78,21 @@ def _check_caps(what, method, polish, soft, capped):
         raise ValueError(f"{what}: x_soft_max and u_soft_max cap the force of a soft bound: give x_soft or u_soft too")
 
 
+def _check_line_search(what, method, polish, soft, line_search):
+    """The refusals of line_search=True that need no look at the bounds: it is an option of the active-set iteration on soft
+    bounds (a finite bound without a weight is refused by the solver, which reads the bounds on the device)."""
+    if not line_search:
+        return
+    if method != "pdas" or polish:
+        raise ValueError(f"{what}: line_search=True needs method='pdas' without polish (it is a step of the active-set iteration)")
+    if not soft:
+        raise ValueError(f"{what}: line_search=True takes soft bounds only: give x_soft or u_soft, a positive weight on every "
+                         "variable with a finite bound")
+
+
 def box_qp(Q, R, A, B, q, r, c, x_lo, x_hi, u_lo, u_hi, *, rho, exit_tol, max_iters, admm_rho=0.1, sigma=1e-6, alpha=1.6,
            eps_abs=1e-6, eps_rel=1e-6, max_admm_iters=4000, check_every=25, warm=None, polish=False, method="admm",
-           polish_iters=1, max_pdas_iters=30, x_soft=None, u_soft=None, x_soft_max=None, u_soft_max=None):
+           polish_iters=1, max_pdas_iters=30, x_soft=None, u_soft=None, x_soft_max=None, u_soft_max=None, line_search=False):
     """Box-constrained QP from math-shaped blocks, at most one leading batch dimension:
     Q [*,K,S,S], R [*,K-1,C,C], A [*,K-1,S,S], B [*,K-1,S,C], q [*,K,S], r [*,K-1,C], c [*,K,S] as kkt_solve takes them (A, B
     the raw values stored in C: -A and -B of the dynamics), and the bounds x_lo, x_hi [*,K,S], u_lo, u_hi [*,K-1,C] - numbers
@@ -102,11 +114,17 @@ def box_qp(Q, R, A, B, q, r, c, x_lo, x_hi, u_lo, u_hi, *, rho, exit_tol, max_it
     cap): caps m >= 0 on the penalty forces.  The penalty becomes the Huber function - quadratic while
     w dist <= m, linear with slope m beyond - and the force clamp(w (x - clip(x)), -m, m).  A saturated variable has
     result.act = +-2 and result.y = +-m; warm.act may carry +-2.  ValueError for method="admm" or polish=True, without any
-    weight, and for a NaN or negative cap."""
+    weight, and for a NaN or negative cap.
+    line_search=True (method="pdas" with x_soft / u_soft): the exact line search on the penalised
+    objective, which makes the iteration converge where the undamped one cycles (large weights, caps between the regimes), at
+    the price of more solves elsewhere.  Every variable with a finite bound (off x_0) must have a positive weight.
+    result.alpha [*, max_pdas_iters] holds the step length of every solve (1: a full step, 0: none taken).  ValueError for
+    method="admm", polish=True, without weights, and for a finite bound whose weight is 0."""
     if method not in ("admm", "pdas"):
         raise ValueError(f"box_qp: method must be 'admm' or 'pdas', got {method!r}")
     soft = x_soft is not None or u_soft is not None
     _check_caps("box_qp", method, polish, soft, x_soft_max is not None or u_soft_max is not None)
+    _check_line_search("box_qp", method, polish, soft, line_search)
     if soft and (method != "pdas" or polish):
         raise ValueError("box_qp: x_soft and u_soft need method='pdas' without polish (ADMM and the polish have no soft bounds)")
     if int(polish_iters) < 1 or int(max_pdas_iters) < 1:
@@ -124,7 +142,7 @@ def box_qp(Q, R, A, B, q, r, c, x_lo, x_hi, u_lo, u_hi, *, rho, exit_tol, max_it
                 act = act.reshape(-1).contiguous()
             res = sol.box_qp_pdas(Gb, Cb, g, cc, lo, hi, rho=rho, exit_tol=exit_tol, max_iters=max_iters, eps_abs=eps_abs,
                                   eps_rel=eps_rel, max_pdas_iters=max_pdas_iters, act=act, soft_weight=wt,
-                                  soft_cap=None if mt is None else mt.contiguous())
+                                  soft_cap=None if mt is None else mt.contiguous(), line_search=bool(line_search))
             return _shaped(res, sol, Bt, batched)
         out = {}
         if warm is not None:
@@ -166,7 +184,8 @@ def _shaped(res, sol, Bt, batched):
     first = (lambda t: t) if batched else (lambda t: t[0])
     return BoxQPResult(shp(res.x, N), shp(res.z, N), shp(res.y, N), shp(res.lam, sk), first(res.iters), first(res.status),
                        first(res.res_prim), first(res.res_dual), None if res.polished is None else first(res.polished),
-                       None if res.act is None else shp(res.act, N))
+                       None if res.act is None else shp(res.act, N),
+                       None if res.alpha is None else (res.alpha if batched else res.alpha[0]))
 
 
 # ---- the differentiable layer -----------------------------------------------------------------------------------------
@@ -182,9 +201,11 @@ class _BoxQPLayer(torch.autograd.Function):
     def forward(ctx, Gb, Cb, g, c, lo, hi, w, m, sol, opts, box):
         opts = dict(opts)
         pdas_iters = opts.pop("max_pdas_iters", None)      # set: the active-set iteration alone (method="pdas")
+        line_search = opts.pop("line_search", False)        # the forward pass only: the rebuild of a stale assembly is one solve
         pol = {k: opts[k] for k in ("rho", "exit_tol", "max_iters", "eps_abs", "eps_rel")}
         if w is not None or pdas_iters is not None:
-            res = sol.box_qp_pdas(Gb, Cb, g, c, lo, hi, max_pdas_iters=pdas_iters, soft_weight=w, soft_cap=m, **pol)
+            res = sol.box_qp_pdas(Gb, Cb, g, c, lo, hi, max_pdas_iters=pdas_iters, soft_weight=w, soft_cap=m,
+                                  line_search=line_search, **pol)
             act = res.act
         else:
             res = sol.box_qp(Gb, Cb, g, c, lo, hi, **opts)
@@ -261,7 +282,7 @@ def _rebuild_assembly(sol, Gb, Cb, g, c, lo, hi, w, m, act, x, lam, pol):
 
 def box_qp_layer(Q, R, A, B, q, r, c, x_lo, x_hi, u_lo, u_hi, *, rho, exit_tol, max_iters, admm_rho=0.1, sigma=1e-6,
                  alpha=1.6, eps_abs=1e-6, eps_rel=1e-6, max_admm_iters=4000, check_every=25, method="admm", max_pdas_iters=30,
-                 x_soft=None, u_soft=None, x_soft_max=None, u_soft_max=None):
+                 x_soft=None, u_soft=None, x_soft_max=None, u_soft_max=None, line_search=False):
     """Differentiable box-constrained QP: the inputs of box_qp; returns (x [*, N], lam [*, S K], info) with x and lam those
     of the polished solution, differentiable with respect to every tensor input (the bounds included; Q and R as symmetric,
     DESIGN.md section 3.6), and info a detached BoxQPResult (info.polished: the polish codes).  A system whose polish was not
@@ -270,11 +291,14 @@ def box_qp_layer(Q, R, A, B, q, r, c, x_lo, x_hi, u_lo, u_hi, *, rho, exit_tol, 
     reduced solves; the ADMM parameters are not read; a system that does not converge returns zeros); the backward pass is the
     same.  x_soft, u_soft (method="pdas" only): the soft-bound weights of box_qp; the layer is
     differentiable with respect to them too.  x_soft_max, u_soft_max (with x_soft / u_soft): the caps of box_qp (DESIGN.md section
-    3.11); differentiable with respect to them as well (a cap's gradient is nonzero only on a saturated variable).  rho is not differentiated and double backward is not supported."""
+    3.11); differentiable with respect to them as well (a cap's gradient is nonzero only on a saturated variable).
+    line_search=True: box_qp's line search in the forward pass; the backward pass is unchanged - a
+    converged point is the KKT point of its act.  rho is not differentiated and double backward is not supported."""
     if method not in ("admm", "pdas"):
         raise ValueError(f"box_qp_layer: method must be 'admm' or 'pdas', got {method!r}")
     soft = x_soft is not None or u_soft is not None
     _check_caps("box_qp_layer", method, False, soft, x_soft_max is not None or u_soft_max is not None)
+    _check_line_search("box_qp_layer", method, False, soft, line_search)
     if soft and method != "pdas":
         raise ValueError("box_qp_layer: x_soft and u_soft need method='pdas' (ADMM and the polish have no soft bounds)")
     Gb, Cb, g, cc, lo, hi, wt, mt, Bt, batched, sol = _prepare("box_qp_layer", (Q, R, A, B, q, r, c), x_lo, x_hi, u_lo, u_hi,
@@ -285,12 +309,14 @@ def box_qp_layer(Q, R, A, B, q, r, c, x_lo, x_hi, u_lo, u_hi, *, rho, exit_tol, 
                 eps_abs=eps_abs, eps_rel=eps_rel, max_admm_iters=max_admm_iters, check_every=check_every)
     if method == "pdas":
         opts["max_pdas_iters"] = int(max_pdas_iters)
+        if line_search:
+            opts["line_search"] = True
     box = []
     x, lam = _BoxQPLayer.apply(Gb, Cb, g, cc, lo, hi, wt, mt, sol, opts, box)
     info = _shaped(box[0], sol, Bt, batched)
     info = BoxQPResult(*(t.detach().clone() for t in (info.x, info.z, info.y, info.lam, info.iters, info.status, info.res_prim,
                                                       info.res_dual, info.polished)),
-                       act=None if info.act is None else info.act.clone())
+                       act=None if info.act is None else info.act.clone(), alpha=None if info.alpha is None else info.alpha.clone())
     return (x, lam, info) if batched else (x[0], lam[0], info)
 
 

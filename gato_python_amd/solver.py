@@ -21,13 +21,14 @@ class BoxQPResult:
     """Result of a box-constrained QP solve: x, z, y [.., N], lam [.., S K], iters, status [..] (int32: _lib.QP_*),
     res_prim, res_dual [..] (float64) - the true QP residuals of the returned iterate - and polished [..] (int32:
     _lib.POLISH_*; None unless a polish was asked for); act [.., N] (int8) the final active set of an active-set solve
-    (box_qp_pdas; None otherwise)."""
-    __slots__ = ("x", "z", "y", "lam", "iters", "status", "res_prim", "res_dual", "polished", "act")
+    (box_qp_pdas; None otherwise); alpha [.., max_pdas_iters] (float64) the step length of every reduced solve of an
+    active-set solve with line_search=True (None otherwise)."""
+    __slots__ = ("x", "z", "y", "lam", "iters", "status", "res_prim", "res_dual", "polished", "act", "alpha")
 
-    def __init__(self, x, z, y, lam, iters, status, res_prim, res_dual, polished=None, act=None):
+    def __init__(self, x, z, y, lam, iters, status, res_prim, res_dual, polished=None, act=None, alpha=None):
         self.x, self.z, self.y, self.lam = x, z, y, lam
         self.iters, self.status, self.res_prim, self.res_dual = iters, status, res_prim, res_dual
-        self.polished, self.act = polished, act
+        self.polished, self.act, self.alpha = polished, act, alpha
 
     def __repr__(self):
         pol = "" if self.polished is None else f", polished={self.polished.tolist()}"
@@ -282,7 +283,7 @@ class Solver:
         return codes
 
     def box_qp_pdas(self, Gb, Cb, g, c, lo, hi, *, rho, exit_tol, max_iters, eps_abs=1e-6, eps_rel=1e-6, max_pdas_iters=30,
-                    act=None, x=None, z=None, y=None, lam=None, soft_weight=None, soft_cap=None):
+                    act=None, x=None, z=None, y=None, lam=None, soft_weight=None, soft_cap=None, line_search=False):
         """The box QP of box_qp by the primal-dual active-set iteration (gato_box_qp_pdas): the polish
         iterated from the active set act [B N] int8 (None: nothing active, a cold start; the tensor is not written) until
         the polished point passes the polish's test.  No penalty parameter and no ADMM.  Returns a BoxQPResult: status
@@ -297,9 +298,16 @@ class Solver:
         soft_cap [B N] (with soft_weight; gato_box_qp_pdas_huber): a cap m_i >= 0 on the penalty force of
         variable i, read where w_i > 0; +inf: none.  The penalty is then the Huber function; where w_i (x_i - b_i) passes m_i the
         variable is saturated - act = +2 above hi, -2 below lo - and y = +-m_i.  act may hold +-2 on such variables.  A cap that is
-        NaN or negative raises ValueError.  None: gato_box_qp_pdas_soft."""
+        NaN or negative raises ValueError.  None: gato_box_qp_pdas_soft.
+        line_search=True (with soft_weight; gato_box_qp_pdas_ls): every solve after the first moves an
+        iterate xc to the exact minimiser of the penalised objective along the direction to the solve's point, and the next
+        act is that of xc; the result's alpha [B, max_pdas_iters] holds the step lengths (1: a full step, 0: no step taken).
+        Every variable off x_0 with a finite bound must have a positive weight: a finite hard bound raises ValueError."""
         if soft_cap is not None and soft_weight is None:
             raise ValueError("box_qp_pdas: soft_cap needs soft_weight (a cap is read only where the weight is positive)")
+        if line_search and soft_weight is None:
+            raise ValueError("box_qp_pdas: line_search=True needs soft_weight (the line search takes soft bounds only: every "
+                             "variable with a finite bound needs a positive weight)")
         B, N, sk = self.batch, self.N, self.sizes["sk"]
         zeros = lambda n: torch.zeros(n, dtype=self.dtype, device=f"cuda:{self.device}")
         x = zeros(B * N) if x is None else x
@@ -322,7 +330,12 @@ class Solver:
         p = self._qp_params(rho, exit_tol, max_iters, eps_abs, eps_rel)
         tail = (ct.byref(p), int(max_pdas_iters), _ptr(x), _ptr(z), _ptr(y), _ptr(lam), _ptr(iters), _ptr(status), _ptr(res),
                 self._stream())
-        if soft_weight is None:
+        alpha = None
+        if line_search:
+            alpha = torch.zeros(B, int(max_pdas_iters), dtype=torch.float64, device=act.device)
+            rc = _lib.lib().gato_box_qp_pdas_ls(self._h, _ptr(Gb), _ptr(Cb), _ptr(g), _ptr(c), _ptr(lo), _ptr(hi), _ptr(soft_weight),
+                                                _ptr(soft_cap), _ptr(act), *tail[:-1], _ptr(alpha), tail[-1])
+        elif soft_weight is None:
             rc = _lib.lib().gato_box_qp_pdas(self._h, _ptr(Gb), _ptr(Cb), _ptr(g), _ptr(c), _ptr(lo), _ptr(hi), _ptr(act), *tail)
         elif soft_cap is None:
             rc = _lib.lib().gato_box_qp_pdas_soft(self._h, _ptr(Gb), _ptr(Cb), _ptr(g), _ptr(c), _ptr(lo), _ptr(hi),
@@ -339,7 +352,23 @@ class Solver:
         res = res.view(B, 2)
         codes = torch.where(status == _lib.QP_CONVERGED, _lib.POLISH_ACCEPTED,
                             torch.where(status == _lib.QP_NONFINITE, _lib.POLISH_NONFINITE, _lib.POLISH_REJECTED)).to(torch.int32)
-        return BoxQPResult(x, z, y, lam, iters, status, res[:, 0], res[:, 1], codes, act)
+        return BoxQPResult(x, z, y, lam, iters, status, res[:, 0], res[:, 1], codes, act, alpha)
+
+    def box_qp_line_search(self, Gb, g, lo, hi, soft_weight, soft_cap, xc, xplus, *, rho, x=None):
+        """The line search of box_qp_pdas(line_search=True) alone (gato_box_qp_line_search): from the
+        iterate xc and the Newton point xplus [B N], along d = xplus - xc, -> (alpha [B], slope [B, 2], x): the slopes phi'(0)
+        and phi'(1) of the penalised objective with H = G + rho I (float64), the step length alpha (float64; 1 where phi'(1) <=
+        0 or phi'(0) >= 0, else the root of phi' in (0, 1)) and, where x [B N] is given, x = xc + alpha d (xplus bit for bit where
+        alpha = 1).  soft_cap None: no caps.  Asynchronous."""
+        own = dict(Gb=Gb, g=g, lo=lo, hi=hi, soft_weight=soft_weight, xc=xc, xplus=xplus)
+        own.update({k: v for k, v in (("soft_cap", soft_cap), ("x", x)) if v is not None})
+        self._check_vecs("box_qp_line_search", **own)
+        alpha = torch.zeros(self.batch, dtype=torch.float64, device=g.device)
+        slope = torch.zeros(self.batch, 2, dtype=torch.float64, device=g.device)
+        _lib.check(_lib.lib().gato_box_qp_line_search(self._h, _ptr(Gb), _ptr(g), _ptr(lo), _ptr(hi), _ptr(soft_weight), _ptr(soft_cap),
+                                                      float(rho), _ptr(xc), _ptr(xplus), _ptr(alpha), _ptr(slope), _ptr(x),
+                                                      self._stream()))
+        return alpha, slope, x
 
     def _bound_grads(self, entry, what, Gb, Cb, act, soft, xbar, a, beta, **bars):
         """The body of the two bound-gradient methods: allocates the outputs bars (by name) that are None, checks every

@@ -482,6 +482,31 @@ int gato_box_qp_huber_grad(gato_solver *s, const void *d_G_blocks, const void *d
                            const void *d_soft_w, const void *d_soft_cap, const void *d_lo, const void *d_hi, const void *d_x,
                            const void *d_xbar, const void *d_a, const void *d_beta, void *d_lo_bar, void *d_hi_bar, void *d_w_bar,
                            void *d_cap_bar, void *stream);
+/* gato_box_qp_pdas_huber with an exact line search, for problems whose every bound is soft: every variable off
+ * x_0 with a finite bound must have w_i > 0 (else d_status = GATO_QP_BAD_BOUNDS and GATO_EINVAL, found by the first host read);
+ * d_soft_w is required, d_soft_cap may be NULL.  The problem is then the minimisation of the C1, strongly convex, piecewise-
+ * quadratic phi(x) = 1/2 x^T H x - g^T x + sum h_i(dist(x_i, [lo_i, hi_i])) on C x = c, and the reduced solve on the act named by an
+ * iterate xc is the Newton point x+ of phi at xc.  Per system the loop keeps xc: the first solve of a call (on the start act)
+ * sets xc = x+; every later one moves xc to the exact minimiser of phi along d = x+ - xc, the root alpha in (0, 1) of the
+ * non-decreasing piecewise-linear slope phi'(alpha) = d^T (H (xc + alpha d) - g + f(xc + alpha d)), f the capped force of 3.11,
+ * or takes the full step xc = x+ (bit for bit) where phi'(1) <= 0 or phi'(0) >= 0.  The next act is that of the soft rule on
+ * xc, not on x+.  The acceptance test, the outcomes, the stall rule, max_pdas_iters and the outputs are those of
+ * gato_box_qp_pdas_huber: the accepted point is the x+ of its act.  In exact arithmetic the iteration ends after finitely many
+ * solves.  d_alpha [B][max_pdas_iters] (may be NULL): the step length of every solve - 1 for the first and for a full step, 0
+ * where no step was taken (the accepted or non-finite solve and the solves a system did not run).  Two more launches per solve;
+ * a run repeats bit for bit.  Refusals, blocking behaviour and side effects are those of gato_box_qp_pdas_huber. */
+int gato_box_qp_pdas_ls(gato_solver *s, const void *d_G_blocks, const void *d_C_blocks, const void *d_g, const void *d_c,
+                        const void *d_lo, const void *d_hi, const void *d_soft_w /* [B][N] */,
+                        const void *d_soft_cap /* [B][N], NULL = no cap */, signed char *d_act, const gato_box_qp_params *p,
+                        int max_pdas_iters, void *d_x, void *d_z, void *d_y, void *d_lambda, int *d_iters, int *d_status,
+                        double *d_res /* [B][2] */, double *d_alpha /* [B][max_pdas_iters], may be NULL */, void *stream);
+/* The line search of gato_box_qp_pdas_ls alone, two launches: from d_xc and the Newton point d_xplus [B][N], d_slope [B][2] =
+ * phi'(0), phi'(1), d_alpha [B] = the step length and, where d_x is given, d_x [B][N] = xc + alpha (x+ - xc) (x+ bit for bit
+ * where alpha = 1).  The weights on the states of x_0 are not read.  d_soft_cap may be NULL.  Asynchronous.  GATO_EINVAL for
+ * another NULL pointer, a rho that is negative or not finite, and on a cluster rank. */
+int gato_box_qp_line_search(gato_solver *s, const void *d_G_blocks, const void *d_g, const void *d_lo, const void *d_hi,
+                            const void *d_soft_w, const void *d_soft_cap, double rho, const void *d_xc, const void *d_xplus,
+                            double *d_alpha, double *d_slope, void *d_x, void *stream);
 
 /* ---- direct block input (new): the caller already holds the per-knot blocks in the
  * reference's dense layouts - d_G_blocks as G_dense WITHOUT rho, d_C_blocks as C_dense - so the CSR scatter is

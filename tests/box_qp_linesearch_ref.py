@@ -1,0 +1,284 @@
+"""numpy reference of the exact line search of the soft active-set iteration, fp64, on
+box_qp_active_ref (next_act, point, force, penalised_objective, decision_margin) and box_qp_polish_ref.reduced_solve.
+
+Every bounded variable is soft (weight w_i > 0, cap m_i, +inf: none; the weights on the S states of x_0 are not read), so the
+problem is the minimisation of the C1, strongly convex, piecewise-quadratic
+
+    phi(x) = 1/2 x^T H x - g^T x + sum_i h_i(dist(x_i, [lo_i, hi_i]))   on   C x = c,
+
+the reduced solve on the act that the iterate xc names is the Newton point x+ of phi at xc, and along d = x+ - xc the slope
+
+    phi'(alpha) = d^T (H (xc + alpha d) - g + f(xc + alpha d)),   f = clamp(w (x - clip(x, lo, hi)), -m, m),
+
+is continuous, piecewise linear and non-decreasing (C d = 0: the multipliers drop out).  exact_alpha() finds its root by
+sorting the breakpoints; iterate_ls() is box_qp_active_ref.iterate with that step; stage_iterate_ls() restates it on the oracle's
+stages in a given dtype.  The problems are box_qp_soft_ref.soft_problem's with the weight (and the cap) on every variable."""
+import os
+import sys
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+if HERE not in sys.path:
+    sys.path.insert(0, HERE)
+
+import box_qp_active_ref as AS                    # noqa: E402
+import box_qp_pdas_ref as D                       # noqa: E402
+import box_qp_polish_ref as P                     # noqa: E402
+import box_qp_ref as ref                          # noqa: E402
+import box_qp_soft_ref as SR                      # noqa: E402
+
+CONVERGED, MAX_ITERS, NONFINITE = AS.CONVERGED, AS.MAX_ITERS, AS.NONFINITE
+LS_SOLVES = 30                                    # a seed's damped run converges, and its undamped run does not, within these
+
+
+def off_x0(w, S):
+    """The weights the line search reads: w with the states of x_0 at 0 (the device ignores them, C pins those states)."""
+    w = np.array(w, np.float64)
+    w[:S] = 0.0
+    return w
+
+
+def caps(N, m):
+    return np.full(N, np.inf) if m is None else np.broadcast_to(np.asarray(m, np.float64), (N,))
+
+
+def slope(H, g, lo, hi, w, m, xc, d, alpha):
+    """phi'(alpha) along d from xc (w: the weights the search reads, off_x0's)."""
+    x = xc + alpha * d
+    return float(d @ (H @ x - g + AS.force(lo, hi, w, caps(len(x), m), x)))
+
+
+def slope_scale(H, g, lo, hi, w, m, xc, d, alpha):
+    """sum_i |d_i| (sum_j |H_ij x_j| + |g_i| + |f_i|) at x = xc + alpha d: N eps times it bounds the rounding of a slope summed in
+    a dtype of unit roundoff eps, whatever the order."""
+    x = xc + alpha * d
+    return float(np.abs(d) @ (abs(H) @ np.abs(x) + np.abs(g) + np.abs(AS.force(lo, hi, w, caps(len(x), m), x))))
+
+
+def breakpoints(lo, hi, w, m, xc, d):
+    """The alpha in (0, 1) at which some soft variable's force changes its piece - x_i crosses lo, hi, lo - m / w or hi + m / w -
+    sorted."""
+    m = caps(len(xc), m)
+    out = []
+    sv = (w > 0) & (d != 0)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        r = np.where(sv, m / np.where(sv, w, 1.0), np.inf)
+        for b in (lo, hi, lo - r, hi + r):
+            t = (b - xc) / np.where(sv, d, 1.0)
+            out.append(t[sv & np.isfinite(t) & (t > 0) & (t < 1)])
+    return np.unique(np.concatenate(out))
+
+
+def exact_alpha(H, g, lo, hi, w, m, xc, xp):
+    """The exact step length from xc towards xp: 1 where phi'(1) <= 0 (no root inside) or phi'(0) >= 0 (d is no descent
+    direction: the solve that gave xp was too loose), else the root of phi' in (0, 1) - sort the breakpoints, find the piece on
+    which phi' changes sign, interpolate.  -> dict alpha, piece (the ends of that linear piece; (1, 1) for a full step), s0, s1
+    (phi'(0), phi'(1)) and ends (|phi'| at the piece's ends)."""
+    d = xp - xc
+    f = lambda a: slope(H, g, lo, hi, w, m, xc, d, a)
+    s0, s1 = f(0.0), f(1.0)
+    if s1 <= 0 or s0 >= 0:
+        return dict(alpha=1.0, piece=(1.0, 1.0), s0=s0, s1=s1, ends=(abs(s1), abs(s1)))
+    ts = np.concatenate([[0.0], breakpoints(lo, hi, w, m, xc, d), [1.0]])
+    fs = np.array([f(t) for t in ts])
+    j = int(np.searchsorted(fs > 0, True))                # the first breakpoint with a positive slope: the root is before it
+    a, b, fa, fb = ts[j - 1], ts[j], fs[j - 1], fs[j]
+    alpha = float(a - fa * (b - a) / (fb - fa))
+    return dict(alpha=min(max(alpha, a), b), piece=(float(a), float(b)), s0=s0, s1=s1, ends=(abs(float(fa)), abs(float(fb))))
+
+
+def iterate_ls(H, Cm, g, c, lo, hi, S, w, m=None, act0=None, eps_abs=1e-6, eps_rel=1e-6, max_pdas_iters=LS_SOLVES, force_alpha=None):
+    """box_qp_active_ref.iterate with the line search: the first solve sets xc = x+; every later one moves xc by exact_alpha
+    along x+ - xc (x+ itself where alpha = 1), and act' is next_act of xc.  -> iterate's dict; every trace entry also holds alpha
+    (1 on the first solve, 0 on an accepted or non-finite one: no step), xc (the iterate before the step, None on the first
+    solve), xp (the solve's x+) and ls (exact_alpha's dict, None where there was no search), and its margin is taken on the
+    stepped xc, the point the rule reads.  force_alpha: that step length instead of the exact one (1: the undamped iteration)."""
+    N = len(g)
+    w = np.broadcast_to(np.asarray(w, np.float64), (N,))
+    m = None if m is None else np.broadcast_to(np.asarray(m, np.float64), (N,))
+    wl = off_x0(w, S)
+    act = np.zeros(N, np.int8) if act0 is None else np.asarray(act0, np.int8).copy()
+    trace, xc, status = [], None, MAX_ITERS
+    for it in range(1, max_pdas_iters + 1):
+        x, y, lam = P.reduced_solve(H, Cm, g, c, lo, hi, act, w, m)
+        z, rp, rd, finite, ok = AS.point(H, Cm, g, c, lo, hi, act, x, y, lam, eps_abs, eps_rel, w, m)
+        entry = dict(act=act.copy(), changed=None, margin=np.nan, alpha=0.0, xc=None if xc is None else xc.copy(), xp=x.copy(), ls=None)
+        trace.append(entry)
+        if not finite:
+            status = NONFINITE
+            break
+        if ok:
+            entry["margin"] = AS.decision_margin(act, x, y, lo, hi, S, w, m)
+            status = CONVERGED
+            break
+        if xc is None:
+            alpha, xn = 1.0, x
+        else:
+            entry["ls"] = exact_alpha(H, g, lo, hi, wl, m, xc, x)
+            alpha = entry["ls"]["alpha"] if force_alpha is None else float(force_alpha)
+            xn = x if alpha == 1.0 else xc + alpha * (x - xc)
+        new = AS.next_act(act, xn, y, lo, hi, S, w, m)
+        entry.update(alpha=alpha, changed=int((new != act).sum()), margin=AS.decision_margin(act, xn, y, lo, hi, S, w, m))
+        xc = xn
+        if entry["changed"] == 0 or it == max_pdas_iters:
+            break
+        act = new
+    return dict(status=status, iters=it, act=act, trace=trace, x=x, z=z, y=y, lam=lam, res_prim=rp, res_dual=rd,
+                alpha=[t["alpha"] for t in trace])
+
+
+def stage_iterate_ls(s, lo, hi, dtype, eps, w, m=None, max_pdas_iters=LS_SOLVES, exit_tol=1e-8, max_iters=1000, sooner=False):
+    """box_qp_active_ref.stage_iterate with the line search: every reduced solve in `dtype` on the oracle's stages, the search in
+    fp64 on its point, xc kept in `dtype`, the capped rule's products in `dtype`.  -> (status, acts solved on, alphas)."""
+    H, Cm, g, c = ref.parts(s)
+    wl = off_x0(w, s.S)
+    act = np.zeros(s.N, np.int8)
+    acts, alphas, xc = [], [], None
+    for it in range(1, max_pdas_iters + 1):
+        acts.append(act.copy())
+        x, lam, iters = P.reduced_stage_solve(s, lo, hi, act, dtype, exit_tol, max_iters, w, m)
+        if sooner and iters >= 1:
+            x, lam, _ = P.reduced_stage_solve(s, lo, hi, act, dtype, exit_tol, iters, w, m)
+        x, lam = np.asarray(x, np.float64), np.asarray(lam, np.float64)
+        if not (np.isfinite(x).all() and np.isfinite(lam).all()):
+            return NONFINITE, acts, alphas + [0.0]
+        y = np.where(P.soft_set(act, w), w * (x - P.bound_values(act, lo, hi)), 0.0)
+        if m is not None:
+            sat = P.sat_set(act)
+            y = np.where(sat, np.sign(act) * np.where(sat, m, 0.0), y)
+        if AS.point(H, Cm, g, c, lo, hi, act, x, y, lam, eps, eps, w, m)[4]:
+            return CONVERGED, acts, alphas + [0.0]
+        alpha = 1.0 if xc is None else exact_alpha(H, g, lo, hi, wl, m, xc, x)["alpha"]
+        xc = x if alpha == 1.0 else np.asarray(xc + alpha * (x - xc), dtype).astype(np.float64)
+        alphas.append(alpha)
+        new = AS.next_act(act, xc, y, lo, hi, s.S, w, m, dtype)
+        if np.array_equal(new, act):
+            return MAX_ITERS, acts, alphas
+        act = new
+    return MAX_ITERS, acts, alphas
+
+
+# ---- the problems and the seed rule ------------------------------------------------------------------------------------------
+CAPPED = (100.0, 1.0)                             # weight, cap on every variable: the undamped iteration cycles at every shape
+UNCAPPED = (1e4, None)
+SHAPES = D.SHAPES
+CAPPED_CASES = [(S, C, K) for S, C in SHAPES for K in (3, 9)]
+UNCAPPED_CASES = [(2, 1, 9), (4, 2, 9), (6, 3, 9), (14, 7, 9)]      # the cells of 3 and 9 knots in which the rule leaves a seed
+F32_CASES = [(S, C, 3) for S, C in SHAPES]
+LAYER_CASES = SR.LAYER_CASES
+LONG = D.LONG
+LONG_SOLVES = 2                                   # of the sparse reference at LONG (seconds each): the first search of a run
+
+
+def ls_problem(S, C, K, seed, weight, cap, sparse=False, eps=1e-6, undamped=True, max_pdas_iters=LS_SOLVES):
+    """soft_problem(S, C, K, seed) with `weight` on every variable (and `cap`, None: no caps), as a problem dict with "w" (and
+    "m"), its damped reference run under "run" and - undamped - box_qp_active_ref.iterate's run of LS_SOLVES solves under
+    "undamped"."""
+    s, H, Cm, g, c, lo, hi, _ = SR.soft_problem(S, C, K, seed, sparse=sparse, weight=weight)
+    w = np.full(s.N, float(weight))
+    wm = dict(w=w) if cap is None else dict(w=w, m=np.full(s.N, float(cap)))
+    run = iterate_ls(H, Cm, g, c, lo, hi, S, w, wm.get("m"), eps_abs=eps, eps_rel=eps, max_pdas_iters=max_pdas_iters)
+    p = AS.as_problem(s, H, Cm, g, c, lo, hi, run, seed, **wm)
+    if undamped:
+        p["undamped"] = AS.iterate(H, Cm, g, c, lo, hi, S, w, wm.get("m"), eps_abs=eps, eps_rel=eps, max_pdas_iters=LS_SOLVES)
+    return p
+
+
+def cond_cap(weight):
+    """The cap on the condition number of a run's dense reduced matrices: box_qp_polish_ref.COND_CAP, 1e8, at the weight it was
+    set for, box_qp_soft_ref.WEIGHT = 100, and in proportion to the weight above it.  The weights sit on the reduced matrix's
+    diagonal, so its condition number grows with them by scaling alone: at weight 1e4 it is 1.0e9 to 2.0e9 on every solve of
+    every seed and shape, against 1e6 to 1e8 at weight 100, and a fixed cap of 1e8 leaves the uncapped cells no seed at all.
+    What the cap protects is the margin: cond * eps(fp64) bounds the relative rounding of a solve, and at the scaled cap of
+    1e10 that is 2.2e-6, still below MARGIN = 1e-5."""
+    return P.COND_CAP * max(1.0, float(weight) / SR.WEIGHT)
+
+
+def damped_on_the_way(run):
+    return any(0.0 < t["alpha"] < 1.0 for t in run["trace"])
+
+
+def ls_ok(p):
+    """The seed rule (section 3.9's, the margins on xc): the damped run CONVERGED within LS_SOLVES solves, every margin at least
+    MARGIN, every dense reduced matrix with cond <= COND_CAP, a step 0 < alpha < 1 on the way, and the undamped run not
+    CONVERGED within LS_SOLVES solves."""
+    run = p["run"]
+    if not (run["status"] == CONVERGED and run["iters"] <= LS_SOLVES and AS.min_margin(run) >= AS.MARGIN and damped_on_the_way(run)):
+        return False
+    if p["undamped"]["status"] == CONVERGED:
+        return False
+    return ref.is_sparse(p["H"]) or AS.max_cond(run, p["H"], p["Cm"], p["w"]) <= cond_cap(p["w"].max())
+
+
+def f32_ok(p):
+    """box_qp_active_ref.f32_ok's pattern: on the problem rounded to fp32 the fp32 restatement ends CONVERGED over the reference's
+    act sequence, and does so again with every PCG stopped one iteration sooner."""
+    q = P.rounded(p)
+    want = [t["act"] for t in p["run"]["trace"]]
+    for sooner in (False, True):
+        status, acts, _ = stage_iterate_ls(q["s"], q["lo"], q["hi"], np.float32, P.F32_EPS, q["w"], q.get("m"),
+                                           exit_tol=AS.F32_EXIT_TOL, sooner=sooner)
+        if status != CONVERGED or len(acts) != len(want) or not all(np.array_equal(a, b) for a, b in zip(acts, want)):
+            return False
+    return True
+
+
+def ls_box(S, C, K, form=CAPPED, f32=False, count=1):
+    """The first `count` problems ls_problem(S, C, K, seed, *form) of seeds < WALK_SEEDS that meet ls_ok (f32: at eps = F32_EPS,
+    and f32_ok)."""
+    return AS.walk(("ls", S, C, K, form, f32), lambda seed: ls_problem(S, C, K, seed, *form, eps=P.F32_EPS if f32 else 1e-6),
+                  lambda p: ls_ok(p) and (not f32 or f32_ok(p)), count)
+
+
+def full_step_box(S, C, K):
+    """The first ls_problem at weight 1, uncapped, whose damped run converges with alpha = 1 on every step (it is the undamped
+    run) in at least three solves, within the margins."""
+    ps = AS.walk(("ls full", S, C, K), lambda seed: ls_problem(S, C, K, seed, 1.0, None, undamped=False),
+                lambda p: AS.walk_ok(p["run"], p["H"], p["Cm"], p["w"]) and p["run"]["iters"] >= 3 and not damped_on_the_way(p["run"]))
+    return ps[0] if ps else None
+
+
+# ---- the inputs of the kernel tests --------------------------------------------------------------------------------------------
+SLACK = 64.0                                      # the kernel tests' bar: |phi'(alpha)| <= SLACK N eps scale
+
+
+def search_inputs(p, dtype, damped, margin=False):
+    """(xc, xp, exact_alpha's dict) of a solve of problem p's damped run, inputs rounded to `dtype`: damped - the first solve
+    with 0 < alpha < 1 whose root no error within the kernel's bar can move off its linear piece (|phi'| at both ends of the
+    piece at least 2 SLACK N eps scale); else the first later solve that takes the full step.  margin: only a solve whose
+    decision margin is at least MARGIN.  None if the run has none."""
+    eps = float(np.finfo(dtype).eps)
+    q = P.rounded(p) if np.dtype(dtype) == np.float32 else p
+    H, g, lo, hi, m = q["H"], q["g"], q["lo"], q["hi"], q.get("m")
+    w = off_x0(q["w"], p["s"].S)
+    rnd = lambda v: np.asarray(v, dtype).astype(np.float64)
+    for t in p["run"]["trace"]:
+        if t["ls"] is None or (margin and not t["margin"] >= AS.MARGIN):
+            continue
+        xc, xp = rnd(t["xc"]), rnd(t["xp"])
+        e = exact_alpha(H, g, lo, hi, w, m, xc, xp)
+        if not damped and e["alpha"] == 1.0:
+            return xc, xp, e
+        if damped and 0.0 < e["alpha"] < 1.0:
+            bar = 2 * SLACK * len(g) * eps * slope_scale(H, g, lo, hi, w, m, xc, xp - xc, e["alpha"])
+            if min(e["ends"]) >= bar and min(-e["s0"], e["s1"]) >= bar:
+                return xc, xp, e
+    return None
+
+
+def kernel_inputs(S, C, K, form, dtype, damped, count=1, sparse=False, margin=False):
+    """The first `count` seeds < WALK_SEEDS whose damped run (it need not converge) holds a solve that search_inputs takes, as a
+    list of (p, xc, xp, exact_alpha's dict)."""
+    def make(seed):
+        p = ls_problem(S, C, K, seed, *form, sparse=sparse, undamped=False, max_pdas_iters=LONG_SOLVES if sparse else LS_SOLVES)
+        return dict(p, inputs=search_inputs(p, dtype, damped, margin))
+    ps = AS.walk(("ls kernel", S, C, K, form, np.dtype(dtype).name, damped, sparse, margin), make, lambda p: p["inputs"] is not None, count)
+    return [(p,) + p["inputs"] for p in ps]
+
+
+def kernel_batch(S, C, K, form, dtype):
+    """The systems of a kernel test: two damped searches and one full step between them, of different seeds where the walks
+    allow (the first one alone is the B = 1 case)."""
+    d, f = kernel_inputs(S, C, K, form, dtype, True, 2), kernel_inputs(S, C, K, form, dtype, False, 1)
+    return [d[0], f[0], d[1]] if len(d) == 2 and f else None
