@@ -13,6 +13,9 @@ Public surface:
                                          active-set iteration alone, with hard or soft bounds (one autograd Function,
                                          qp._BoxQPLayer, whose backward branches on "weights present"); line_search=True
                                          changes the forward pass only
+  gato_python_amd.kkt_solve_tangents(...)      kkt_solve and its forward-mode sensitivities along R directions (one re-solve)
+  gato_python_amd.box_qp_layer_tangents(...)   box_qp_layer and its forward-mode sensitivities; both also take
+                                         torch.autograd.forward_ad dual tensors (one direction per pass)
   gato_python_amd.synth                  synthetic OCP inputs (the reference ships pendulum data only)
 """
 from .linsys import (clear_problem_size, last_stats, linsys_resolve, linsys_solve, set_precision,  # noqa: F401
@@ -23,10 +26,10 @@ def __getattr__(name):
     if name == "Solver":              # torch import deferred: linsys_solve itself needs only ctypes
         from .solver import Solver
         return Solver
-    if name in ("kkt_solve", "kkt_solve_csr"):
+    if name in ("kkt_solve", "kkt_solve_csr", "kkt_solve_tangents"):
         from . import autograd
         return getattr(autograd, name)
-    if name in ("box_qp", "box_qp_layer"):
+    if name in ("box_qp", "box_qp_layer", "box_qp_layer_tangents"):
         from . import qp
         return getattr(qp, name)
     raise AttributeError(name)

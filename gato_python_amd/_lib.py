@@ -35,7 +35,7 @@ SYMBOLS = [
     "gato_kkt_grad_blocks", "gato_kkt_grad_csr", "gato_box_qp_default_params", "gato_box_qp_solve",
     "gato_box_qp_active_set", "gato_box_qp_polish", "gato_box_qp_bound_grad", "gato_box_qp_pdas",
     "gato_box_qp_pdas_soft", "gato_box_qp_soft_grad", "gato_box_qp_pdas_huber", "gato_box_qp_huber_grad",
-    "gato_box_qp_pdas_ls", "gato_box_qp_line_search",
+    "gato_box_qp_pdas_ls", "gato_box_qp_line_search", "gato_kkt_tangent_rhs",
 ]
 
 
@@ -134,6 +134,7 @@ def lib() -> ct.CDLL:
         L.gato_box_qp_huber_grad.argtypes = [vp] * 17
         L.gato_box_qp_pdas_ls.argtypes = [vp] * 10 + [ct.POINTER(BoxQpParams), i] + [vp] * 9
         L.gato_box_qp_line_search.argtypes = [vp] * 7 + [d] + [vp] * 6
+        L.gato_kkt_tangent_rhs.argtypes = [vp, i] + [vp] * 20
         f = ct.c_float
         L.gato_linsys_solve_f32.argtypes = [ip, i, ip, vp, i, ip, i, ip, vp, i, vp, i, vp, i, vp,
                                             i, i, i, i, f, i, i, f, vp, vp, vp, vp]

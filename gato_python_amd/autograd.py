@@ -2,10 +2,14 @@
 
     kkt_solve(Q, R, A, B, q, r, c, *, rho, exit_tol, max_iters) -> (lam, dz)
     kkt_solve_csr(G_row, G_col, G_val, C_row, C_col, C_val, g, c, *, rho, exit_tol, max_iters) -> (lam, dz)
+    kkt_solve_tangents(Q, R, A, B, q, r, c, tangents, *, rho, exit_tol, max_iters) -> (lam, dz, lam_dot, dz_dot)
 
 The forward is the device solve (Solver.linsys_blocks / linsys / linsys_batched).  The backward is one re-solve of the same
 assembly with the incoming gradients as right-hand side (the KKT matrix is symmetric, so the adjoint system has the forward's
 matrix: Solver.solve_rhs), then one launch that forms the matrix gradients from dz, lambda and the adjoint (gato_grad.hip).
+Forward mode: the tangent system has the same matrix, so a tangent is one launch for its right-hand side
+(gato_tangent.hip) and the same re-solve - through torch.autograd.forward_ad dual tensors (the jvp of the Function, one direction)
+or kkt_solve_tangents (R directions in one call).
 Only device tensors are taken; there is no CPU fallback.  rho is not differentiated, and double backward is not supported.
 """
 from __future__ import annotations
@@ -94,8 +98,21 @@ class _BlocksSolve(torch.autograd.Function):
         sol.check_status()
         ctx.sol, ctx.opts, ctx.gen = sol, (rho, exit_tol, max_iters), sol.get_option("assembly_gen")
         ctx.save_for_backward(Gb, Cb, g, c, lam, dz)      # Cb itself: the re-solve reads the caller's C blocks again
+        ctx.save_for_forward(lam, dz)
         ctx.set_materialize_grads(False)
         return lam, dz
+
+    @staticmethod
+    def jvp(ctx, Gb_dot, Cb_dot, g_dot, c_dot, *_):
+        """Forward mode, one direction: the tangent right-hand side and one re-solve.  It runs straight
+        after its forward, so the assembly is the forward's; a stale one raises."""
+        lam, dz = ctx.saved_tensors
+        sol = ctx.sol
+        _, exit_tol, max_iters = ctx.opts
+        _fresh(sol, ctx.gen, "kkt_solve")
+        dots = dict(G_dot=Gb_dot, C_dot=Cb_dot, g_dot=g_dot, c_dot=c_dot)
+        lam_dot, dz_dot = sol.tangents(1, dz, lam, exit_tol, max_iters, **_dots(dots, dz.dtype))
+        return lam_dot[:, 0], dz_dot[:, 0]
 
     @staticmethod
     @once_differentiable
@@ -115,6 +132,18 @@ class _BlocksSolve(torch.autograd.Function):
         if Gbar is not None or Cbar is not None:
             sol.kkt_grad_blocks(dz, lam, a, beta, Gbar, Cbar)
         return (Gbar, Cbar, a if need[2] else None, beta if need[3] else None) + (None,) * 4
+
+
+def _fresh(sol, gen, what):
+    """RuntimeError unless the solver's assembly is still that of generation gen: a tangent re-solves it and never rebuilds it."""
+    if sol.get_option("assembly_gen") != gen or sol.get_option("assembly_valid") == 0:
+        raise RuntimeError(f"{what}: another solve replaced this forward pass's assembly before its tangent was taken; forward "
+                           "mode re-solves the assembly of its own forward pass (take the tangent before the next solve of this shape)")
+
+
+def _dots(dots, dtype):
+    """The given tangents (None: zero, dropped) as contiguous tensors of dtype."""
+    return {k: t.to(dtype).contiguous() for k, t in dots.items() if t is not None}
 
 
 def _adjoint(sol, lam, dz, lam_bar, dz_bar, exit_tol, max_iters):
@@ -166,6 +195,72 @@ def kkt_solve(Q, R, A, B, q, r, c, *, rho, exit_tol, max_iters):
     sol = _solver(S, C, K, Bt, dtype, device)
     lam, dz = _BlocksSolve.apply(Gb, Cb, g, cc, sol, rho, exit_tol, max_iters)
     return (lam, dz) if batched else (lam[0], dz[0])
+
+
+def _tangent_dims(tangents, shapes, lead, what):
+    """R of the explicit tangents (a dict name -> tensor of its input's shape with one extra dimension R after the batch
+    dimension; all given ones share R); ValueError for an unknown name, a wrong shape or no tangent at all."""
+    if not isinstance(tangents, dict) or not tangents:
+        raise ValueError(f"{what}: tangents must be a non-empty dict of input name -> tensor")
+    unknown = sorted(set(tangents) - set(shapes))
+    if unknown:
+        raise ValueError(f"{what}: tangents names {unknown}; the inputs are {sorted(shapes)}")
+    R = None
+    for name, t in tangents.items():
+        if not isinstance(t, torch.Tensor):
+            continue                                                      # a number: broadcast (bounds only, checked by the caller)
+        nl = len(lead)
+        if t.dim() != nl + 1 + len(shapes[name]) or tuple(t.shape[:nl]) != lead or tuple(t.shape[nl + 1:]) != shapes[name]:
+            raise ValueError(f"{what}: the tangent of {name} has shape {tuple(t.shape)}, want {lead + ('R',) + shapes[name]}")
+        if R is not None and t.shape[nl] != R:
+            raise ValueError(f"{what}: the tangents do not share one R ({R} and {t.shape[nl]})")
+        R = t.shape[nl]
+    if R is None or R < 1:
+        raise ValueError(f"{what}: at least one tangent must be a tensor with R >= 1 directions")
+    return R
+
+
+def _pack_tangents(tangents, shapes, Bt, R, ref):
+    """The block tangents [Bt, R, ...] in the solver's layouts [Bt, R, G_dense] etc. by _pack on Bt R systems; a pair (Q, R),
+    (A, B) or (q, r) neither of which is given stays None, c likewise."""
+    def full(name):
+        t = tangents.get(name)
+        return torch.zeros((Bt * R,) + shapes[name], dtype=ref.dtype, device=ref.device) if t is None \
+            else t.detach().to(ref.dtype).reshape((Bt * R,) + shapes[name])
+    Gd, Cd, gd, cd = _pack(*(full(n) for n in "Q R A B q r c".split()))
+    have = lambda *names: any(n in tangents for n in names)
+    return dict(G_dot=Gd if have("Q", "R") else None, C_dot=Cd if have("A", "B") else None, g_dot=gd if have("q", "r") else None,
+                c_dot=cd if have("c") else None)
+
+
+def kkt_solve_tangents(Q, R, A, B, q, r, c, tangents, *, rho, exit_tol, max_iters):
+    """kkt_solve and its forward-mode sensitivities along R directions in one call:
+    -> (lam [*, S K], dz [*, N], lam_dot [*, R, S K], dz_dot [*, R, N]).  tangents: a dict from input name (Q, R, A, B, q, r,
+    c) to a tensor of that input's shape with one extra dimension R after the batch dimension; the given ones share R, a
+    missing name is a zero tangent.  Q and R tangents are used as given (symmetric perturbations).  One solve, one launch for the
+    R right-hand sides, one re-solve for all of them.  Nothing returned carries a grad_fn."""
+    what = "kkt_solve_tangents"
+    args = dict(Q=Q, R=R, A=A, B=B, q=q, r=r, c=c)
+    batched, lead, K, S, C = _check_blocks(args, what)
+    if K < 1 or S < 1 or C < 1:
+        raise ValueError(f"{what}: S = {S}, C = {C}, K = {K} must all be >= 1")
+    device, dtype = _common(args, what)
+    shapes = dict(Q=(K, S, S), R=(K - 1, C, C), A=(K - 1, S, S), B=(K - 1, S, C), q=(K, S), r=(K - 1, C), c=(K, S))
+    Rn = _tangent_dims(tangents, shapes, lead, what)
+    _common(dict(tangents, q=q), what)
+    rho, exit_tol, max_iters = _opts(rho, exit_tol, max_iters)
+    with torch.no_grad():
+        blocks = [t if batched else t.unsqueeze(0) for t in (Q, R, A, B, q, r, c)]
+        Bt = blocks[0].shape[0]
+        Gb, Cb, g, cc = _pack(*blocks)
+        sol = _solver(S, C, K, Bt, dtype, device)
+        lam = torch.empty(Bt, sol.sizes["sk"], dtype=dtype, device=g.device)
+        dz = torch.empty(Bt, sol.N, dtype=dtype, device=g.device)
+        sol.linsys_blocks(Gb, Cb, g, cc, exit_tol, max_iters, rho, lam, dz)
+        sol.check_status()
+        dots = _pack_tangents(tangents, shapes, Bt, Rn, q)
+        lam_dot, dz_dot = sol.tangents(Rn, dz, lam, exit_tol, max_iters, **_dots(dots, dtype))
+    return (lam, dz, lam_dot, dz_dot) if batched else (lam[0], dz[0], lam_dot[0], dz_dot[0])
 
 
 # ---- CSR form ----------------------------------------------------------------------------------------------------------

@@ -373,6 +373,20 @@ struct BoundGradArgs {
 };
 template <typename T, int S, int C>
 int launch_qp_bound_grad(const Dims &d, const BoundGradArgs &a, hipStream_t st);
+// Right-hand side of the tangent system of a solve or a converged box-QP point (gato_tangent.hip).
+// Tangents [B][R][...], shared inputs [B][...]; every tangent may be nullptr (zero).
+struct TangentArgs {
+    const void *G_dot, *C_dot;              // [B][R][G_dense], [B][R][C_dense]
+    const void *g_dot, *c_dot;              // [B][R][N], [B][R][S K]
+    const void *lo_dot, *hi_dot, *w_dot, *m_dot;    // [B][R][N]
+    const void *x, *lam;                    // the point [B][N], [B][S K]
+    const void *G, *Cd;                     // the caller's blocks (G without rho, C raw); read with an act only
+    const signed char *act;                 // nullptr: nothing active (a plain KKT solve)
+    const void *w, *cap, *lo, *hi;          // as BoundGradArgs: w nullptr = all hard, then lo and hi are not read
+    void *tg, *tc;                          // [B][R][N], [B][R][S K]
+};
+template <typename T, int S, int C>
+int launch_kkt_tangent_rhs(const Dims &d, int R, const TangentArgs &a, hipStream_t st);
 // Primal-dual active-set iteration over the polish path (gato_pdas.hip, DESIGN.md sections 3.9, 3.10).
 struct PdasArgs {
     PolishArgs p;                           // p.act: the current act; p.slots [B][2][GATO_POLISH_NSLOT], set it % 2 of solve it
@@ -504,6 +518,7 @@ struct Ops {
     int (*polish_prepare)(const Dims &, const PolishArgs &, hipStream_t);
     int (*polish_finish)(const Dims &, const PolishArgs &, hipStream_t);
     int (*qp_bound_grad)(const Dims &, const BoundGradArgs &, hipStream_t);
+    int (*kkt_tangent_rhs)(const Dims &, int, const TangentArgs &, hipStream_t);
     int (*pdas_check)(const Dims &, const PdasArgs &, hipStream_t);
     int (*pdas_step)(const Dims &, const PdasArgs &, int, hipStream_t);
     int (*pdas_decide)(const Dims &, const PdasArgs &, int, int, hipStream_t);

@@ -58,6 +58,7 @@ static Ops make_ops(int dtype)
     o.polish_prepare = [](const Dims &d, const PolishArgs &a, hipStream_t st) { return launch_polish_prepare<T, S, C>(d, a, st); };
     o.polish_finish = [](const Dims &d, const PolishArgs &a, hipStream_t st) { return launch_polish_finish<T, S, C>(d, a, st); };
     o.qp_bound_grad = [](const Dims &d, const BoundGradArgs &a, hipStream_t st) { return launch_qp_bound_grad<T, S, C>(d, a, st); };
+    o.kkt_tangent_rhs = [](const Dims &d, int R, const TangentArgs &a, hipStream_t st) { return launch_kkt_tangent_rhs<T, S, C>(d, R, a, st); };
     o.pdas_check = [](const Dims &d, const PdasArgs &a, hipStream_t st) { return launch_pdas_check<T, S, C>(d, a, st); };
     o.pdas_step = [](const Dims &d, const PdasArgs &a, int it, hipStream_t st) { return launch_pdas_step<T, S, C>(d, a, it, st); };
     o.pdas_decide = [](const Dims &d, const PdasArgs &a, int it, int last, hipStream_t st) {

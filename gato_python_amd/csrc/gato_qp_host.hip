@@ -424,6 +424,31 @@ extern "C" int gato_box_qp_huber_grad(gato_solver *s, const void *d_G_blocks, co
     return s->ops->qp_bound_grad(d, a, (hipStream_t)stream);
 }
 
+// ---- right-hand side of the tangent system (gato_tangent.hip) -------------------------------------------
+extern "C" int gato_kkt_tangent_rhs(gato_solver *s, int R, const void *d_G_dot, const void *d_C_dot, const void *d_g_dot,
+                                    const void *d_c_dot, const void *d_lo_dot, const void *d_hi_dot, const void *d_w_dot,
+                                    const void *d_m_dot, const void *d_x, const void *d_lambda, const void *d_G_blocks,
+                                    const void *d_C_blocks, const signed char *d_act, const void *d_soft_w, const void *d_soft_cap,
+                                    const void *d_lo, const void *d_hi, void *d_tg, void *d_tc, void *stream)
+{
+    if (!solver_usable(s, "kkt_tangent_rhs", "tangents")) return GATO_EINVAL;
+    if (R < 1) { set_error("kkt_tangent_rhs: R = %d: at least one direction", R); return GATO_EINVAL; }
+    if (!d_x || !d_lambda || !d_tg || !d_tc) { set_error("kkt_tangent_rhs: d_x, d_lambda, d_tg and d_tc are required"); return GATO_EINVAL; }
+    if (d_act && (!d_G_blocks || (!d_C_blocks && s->d.K > 1))) {
+        set_error("kkt_tangent_rhs: an act needs d_G_blocks and d_C_blocks (d_C_blocks may be NULL only for K = 1)");
+        return GATO_EINVAL;
+    }
+    if (d_act && d_soft_w && (!d_lo || !d_hi)) { set_error("kkt_tangent_rhs: soft weights need d_lo and d_hi"); return GATO_EINVAL; }
+    Dims d = s->d;
+    d.k_lo = d.k_hi = 0; d.rhs = 0;
+    // without an act nothing is active; without weights no cap and no tangent of a weight or a cap is read
+    const bool soft = d_act && d_soft_w;
+    const TangentArgs a{d_G_dot, d_C_dot, d_g_dot, d_c_dot, d_act ? d_lo_dot : nullptr, d_act ? d_hi_dot : nullptr,
+                        soft ? d_w_dot : nullptr, soft ? d_m_dot : nullptr, d_x, d_lambda, d_G_blocks, d_C_blocks, d_act,
+                        soft ? d_soft_w : nullptr, soft ? d_soft_cap : nullptr, d_lo, d_hi, d_tg, d_tc};
+    return s->ops->kkt_tangent_rhs(d, R, a, (hipStream_t)stream);
+}
+
 // ---- exact line search of the soft active-set iteration (gato_pdas_ls.hip) -----------------------------
 extern "C" int gato_box_qp_pdas_ls(gato_solver *s, const void *d_G_blocks, const void *d_C_blocks, const void *d_g, const void *d_c,
                                    const void *d_lo, const void *d_hi, const void *d_soft_w, const void *d_soft_cap,

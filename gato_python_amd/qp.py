@@ -12,8 +12,9 @@ grad_fn.
     box_qp_layer(Q, R, A, B, q, r, c, x_lo, x_hi, u_lo, u_hi, *, rho, exit_tol, max_iters, **admm) -> (x, lam, info)
 
 is the differentiable form: ADMM, the active set, the polish (or method="pdas": the active-set iteration alone); the backward
-pass is one re-solve of the polish assembly (the reduced KKT system) plus the gradient launches.  Only device tensors are
-taken; there is no CPU fallback.
+pass is one re-solve of the polish assembly (the reduced KKT system) plus the gradient launches; forward mode (dual tensors of
+torch.autograd.forward_ad, or box_qp_layer_tangents for R directions in one call) is the same re-solve
+behind one launch for the tangent right-hand sides.  Only device tensors are taken; there is no CPU fallback.
 """
 from __future__ import annotations
 
@@ -21,7 +22,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from .autograd import _adjoint, _check_blocks, _common, _dz_layout, _pack, _solver
+from .autograd import _adjoint, _check_blocks, _common, _dots, _dz_layout, _fresh, _pack, _pack_tangents, _solver, _tangent_dims
 from .solver import BoxQPResult
 
 
@@ -199,25 +200,25 @@ class _BoxQPLayer(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, Gb, Cb, g, c, lo, hi, w, m, sol, opts, box):
-        opts = dict(opts)
-        pdas_iters = opts.pop("max_pdas_iters", None)      # set: the active-set iteration alone (method="pdas")
-        line_search = opts.pop("line_search", False)        # the forward pass only: the rebuild of a stale assembly is one solve
-        pol = {k: opts[k] for k in ("rho", "exit_tol", "max_iters", "eps_abs", "eps_rel")}
-        if w is not None or pdas_iters is not None:
-            res = sol.box_qp_pdas(Gb, Cb, g, c, lo, hi, max_pdas_iters=pdas_iters, soft_weight=w, soft_cap=m,
-                                  line_search=line_search, **pol)
-            act = res.act
-        else:
-            res = sol.box_qp(Gb, Cb, g, c, lo, hi, **opts)
-            act = sol.box_qp_active_set(res.z, res.y, lo, hi)
-            sol.box_qp_polish(Gb, Cb, g, c, lo, hi, act, res, **pol)
+        res, act, pol = _layer_solve(sol, Gb, Cb, g, c, lo, hi, w, m, opts)
         box.append(res)
         ctx.sol, ctx.pol, ctx.gen = sol, pol, sol.get_option("assembly_gen")
         ctx.codes = res.polished.cpu()
         x, lam = res.x.view(sol.batch, sol.N), res.lam.view(sol.batch, sol.sizes["sk"])
         ctx.save_for_backward(Gb, Cb, g, c, lo, hi, w, m, act, x, lam)
+        ctx.save_for_forward(Gb, Cb, lo, hi, w, m, act, x, lam)
         ctx.set_materialize_grads(False)
         return x.clone(), lam.clone()
+
+    @staticmethod
+    def jvp(ctx, Gb_dot, Cb_dot, g_dot, c_dot, lo_dot, hi_dot, w_dot, m_dot, *_):
+        """Forward mode, one direction.  It runs straight after its forward, so the assembly is the
+        reduced system of the returned act; a stale one raises."""
+        Gb, Cb, lo, hi, w, m, act, x, lam = ctx.saved_tensors
+        _fresh(ctx.sol, ctx.gen, "box_qp_layer")
+        dots = dict(G_dot=Gb_dot, C_dot=Cb_dot, g_dot=g_dot, c_dot=c_dot, lo_dot=lo_dot, hi_dot=hi_dot, w_dot=w_dot, m_dot=m_dot)
+        x_dot, lam_dot = _layer_tangents(ctx.sol, 1, ctx.codes, ctx.pol, Gb, Cb, lo, hi, w, m, act, x, lam, _dots(dots, x.dtype))
+        return x_dot[:, 0], lam_dot[:, 0]
 
     @staticmethod
     @once_differentiable
@@ -265,6 +266,52 @@ class _BoxQPLayer(torch.autograd.Function):
         mask = lambda i, t: None if t is None or not need[i] else torch.where(keep, t.view(sol.batch, -1),
                                                                               torch.zeros((), dtype=t.dtype, device=t.device))
         return tuple(mask(i, t) for i, t in enumerate((Gbar, Cbar, a, beta, lo_bar, hi_bar, w_bar, m_bar))) + (None,) * 3
+
+
+def _layer_solve(sol, Gb, Cb, g, c, lo, hi, w, m, opts):
+    """The forward pass of the layer on packed inputs -> (BoxQPResult, act, the options of the polish); the solver's assembly is
+    the reduced system of act afterwards."""
+    opts = dict(opts)
+    pdas_iters = opts.pop("max_pdas_iters", None)      # set: the active-set iteration alone (method="pdas")
+    line_search = opts.pop("line_search", False)        # the forward pass only: the rebuild of a stale assembly is one solve
+    pol = {k: opts[k] for k in ("rho", "exit_tol", "max_iters", "eps_abs", "eps_rel")}
+    if w is not None or pdas_iters is not None:
+        res = sol.box_qp_pdas(Gb, Cb, g, c, lo, hi, max_pdas_iters=pdas_iters, soft_weight=w, soft_cap=m,
+                              line_search=line_search, **pol)
+        act = res.act
+    else:
+        res = sol.box_qp(Gb, Cb, g, c, lo, hi, **opts)
+        act = sol.box_qp_active_set(res.z, res.y, lo, hi)
+        sol.box_qp_polish(Gb, Cb, g, c, lo, hi, act, res, **pol)
+    return res, act, pol
+
+
+def _layer_tangents(sol, R, codes, pol, Gb, Cb, lo, hi, w, m, act, x, lam, dots):
+    """(x_dot [B, R, N], lam_dot [B, R, S K]) of the layer's point on the solver's current assembly (the reduced system of act)
+    for the tangents dots (Solver.kkt_tangent_rhs's names, [B, R, ...]).  A system whose polish was not accepted raises
+    RuntimeError if any of its tangents is nonzero, as the backward pass does for a nonzero upstream gradient, and gets zeros
+    otherwise."""
+    B = sol.batch
+    live = torch.zeros(B, dtype=torch.bool, device=x.device)
+    for t in dots.values():
+        live |= t.view(B, -1).ne(0).any(1)
+    live = live.cpu()
+    unpolished = live & (codes != _lib.POLISH_ACCEPTED)
+    if unpolished.any():
+        bad = unpolished.nonzero().flatten().tolist()
+        raise RuntimeError(f"box_qp_layer: systems {bad} have a nonzero input tangent but their polish was not accepted "
+                           f"(codes {codes[bad].tolist()}, _lib.POLISH_*): their x and lam are ADMM iterates (zeros after "
+                           "method='pdas'), which have no tangent here")
+    if not live.any():                       # every tangent is exactly zero: no re-solve (its PCG would form 0/0)
+        return (torch.zeros(B, R, sol.N, dtype=x.dtype, device=x.device),
+                torch.zeros(B, R, sol.sizes["sk"], dtype=x.dtype, device=x.device))
+    cont = lambda t: None if t is None else t.contiguous()
+    lam_dot, x_dot = sol.tangents(R, x.contiguous(), lam.contiguous(), pol["exit_tol"], pol["max_iters"], Gb=Gb, Cb=Cb,
+                                  act=act.reshape(-1), soft_weight=cont(w), soft_cap=cont(m), lo=lo.contiguous(),
+                                  hi=hi.contiguous(), **dots)
+    keep = (codes == _lib.POLISH_ACCEPTED).to(x.device)[:, None, None]
+    zero = torch.zeros((), dtype=x.dtype, device=x.device)
+    return torch.where(keep, x_dot, zero), torch.where(keep, lam_dot, zero)
 
 
 def _rebuild_assembly(sol, Gb, Cb, g, c, lo, hi, w, m, act, x, lam, pol):
@@ -318,6 +365,64 @@ def box_qp_layer(Q, R, A, B, q, r, c, x_lo, x_hi, u_lo, u_hi, *, rho, exit_tol, 
                                                       info.res_dual, info.polished)),
                        act=None if info.act is None else info.act.clone(), alpha=None if info.alpha is None else info.alpha.clone())
     return (x, lam, info) if batched else (x[0], lam[0], info)
+
+
+def box_qp_layer_tangents(Q, R, A, B, q, r, c, x_lo, x_hi, u_lo, u_hi, tangents, *, rho, exit_tol, max_iters, admm_rho=0.1,
+                          sigma=1e-6, alpha=1.6, eps_abs=1e-6, eps_rel=1e-6, max_admm_iters=4000, check_every=25, method="admm",
+                          max_pdas_iters=30, x_soft=None, u_soft=None, x_soft_max=None, u_soft_max=None, line_search=False):
+    """box_qp_layer and its forward-mode sensitivities along R directions in one call: the inputs of
+    box_qp_layer and tangents, a dict from input name (Q, R, A, B, q, r, c, x_lo, x_hi, u_lo, u_hi, x_soft, u_soft, x_soft_max,
+    u_soft_max) to a tensor of that input's full shape with one extra dimension R after the batch dimension (a bound's, weight's
+    or cap's tangent may also be a number or a tensor that broadcasts to that shape); the given ones share R, a missing name is
+    a zero tangent.  Returns (x [*, N], lam [*, S K], info, x_dot [*, R, N], lam_dot [*, R, S K]); nothing carries a grad_fn.
+    The tangents are those of the returned act: the solution is piecewise smooth in its inputs.  A system whose polish was not
+    accepted raises RuntimeError if one of its tangents is nonzero and gets zeros otherwise."""
+    what = "box_qp_layer_tangents"
+    if method not in ("admm", "pdas"):
+        raise ValueError(f"{what}: method must be 'admm' or 'pdas', got {method!r}")
+    soft = x_soft is not None or u_soft is not None
+    capped = x_soft_max is not None or u_soft_max is not None
+    _check_caps(what, method, False, soft, capped)
+    _check_line_search(what, method, False, soft, line_search)
+    if soft and method != "pdas":
+        raise ValueError(f"{what}: x_soft and u_soft need method='pdas' (ADMM and the polish have no soft bounds)")
+    with torch.no_grad():
+        Gb, Cb, g, cc, lo, hi, wt, mt, Bt, batched, sol = _prepare(what, (Q, R, A, B, q, r, c), x_lo, x_hi, u_lo, u_hi, x_soft,
+                                                                   u_soft, x_soft_max, u_soft_max)
+        K, S, C = sol.K, sol.S, sol.C
+        lead = (Bt,) if batched else ()
+        shapes = dict(Q=(K, S, S), R=(K - 1, C, C), A=(K - 1, S, S), B=(K - 1, S, C), q=(K, S), r=(K - 1, C), c=(K, S))
+        pairs = dict(lo=("x_lo", "u_lo"), hi=("x_hi", "u_hi"), w=("x_soft", "u_soft"), m=("x_soft_max", "u_soft_max"))
+        vec = {n: (K, S) if n.startswith("x") else (K - 1, C) for p in pairs.values() for n in p}
+        if not isinstance(tangents, dict):
+            raise ValueError(f"{what}: tangents must be a non-empty dict of input name -> tensor")
+        for name, have in (("x_soft", soft), ("u_soft", soft), ("x_soft_max", capped), ("u_soft_max", capped)):
+            if name in tangents and not have:
+                raise ValueError(f"{what}: a tangent of {name} needs the input itself")
+        for name in shapes:
+            if name in tangents and not isinstance(tangents[name], torch.Tensor):
+                raise ValueError(f"{what}: the tangent of {name} must be a torch.Tensor")
+        full = {n: t for n, t in tangents.items() if not (n in vec and (not isinstance(t, torch.Tensor) or t.dim() != len(lead) + 3))}
+        Rn = _tangent_dims(full, dict(shapes, **vec), lead, what)
+        dots = _pack_tangents({n: t for n, t in tangents.items() if n in shapes}, shapes, Bt, Rn, q)
+        for key, (xn, un) in pairs.items():
+            if xn in tangents or un in tangents:
+                xv, uv = (_bound(tangents.get(n, 0.0), lead + (Rn,) + vec[n], n + " tangent", q, what).reshape((Bt * Rn,) + vec[n])
+                          for n in (xn, un))
+                dots[key + "_dot"] = _dz_layout(xv, uv)
+        if mt is not None:
+            mt = mt.contiguous()
+        opts = dict(rho=float(rho), exit_tol=float(exit_tol), max_iters=int(max_iters), admm_rho=admm_rho, sigma=sigma, alpha=alpha,
+                    eps_abs=eps_abs, eps_rel=eps_rel, max_admm_iters=max_admm_iters, check_every=check_every)
+        if method == "pdas":
+            opts["max_pdas_iters"] = int(max_pdas_iters)
+            if line_search:
+                opts["line_search"] = True
+        res, act, pol = _layer_solve(sol, Gb, Cb, g, cc, lo, hi, wt, mt, opts)
+        x, lam = res.x.view(Bt, sol.N).clone(), res.lam.view(Bt, sol.sizes["sk"]).clone()
+        x_dot, lam_dot = _layer_tangents(sol, Rn, res.polished.cpu(), pol, Gb, Cb, lo, hi, wt, mt, act, x, lam, _dots(dots, x.dtype))
+        info = _shaped(res, sol, Bt, batched)
+    return (x, lam, info, x_dot, lam_dot) if batched else (x[0], lam[0], info, x_dot[0], lam_dot[0])
 
 
 STATUS = {_lib.QP_CONVERGED: "CONVERGED", _lib.QP_MAX_ITERS: "MAX_ITERS", _lib.QP_NONFINITE: "NONFINITE",

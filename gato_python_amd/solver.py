@@ -196,6 +196,75 @@ class Solver:
                                                 _ptr(Cbar_val), self._stream()))
         return Gbar_val, Cbar_val
 
+    # ---- forward-mode sensitivities (gato_kkt_tangent_rhs) ------------------------------------------
+    _TANGENTS = dict(G_dot="G_dense", C_dot="C_dense", g_dot=None, c_dot="sk", lo_dot=None, hi_dot=None, w_dot=None, m_dot=None)
+
+    def kkt_tangent_rhs(self, R, x, lam, *, G_dot=None, C_dot=None, g_dot=None, c_dot=None, lo_dot=None, hi_dot=None, w_dot=None,
+                        m_dot=None, Gb=None, Cb=None, act=None, soft_weight=None, soft_cap=None, lo=None, hi=None, tg=None, tc=None):
+        """The right-hand side (tg [B R N], tc [B R S K]) of the tangent system of the point x [B N], lam [B S K] for R directions
+        per system (gato_kkt_tangent_rhs): tangents G_dot [B R G_dense], C_dot [B R C_dense], g_dot, lo_dot, hi_dot, w_dot, m_dot
+        [B R N], c_dot [B R S K], None = zero.  act [B N] int8 with Gb, Cb (and soft_weight with lo, hi; soft_cap) names the
+        active set of a box-QP point; None: a plain KKT solve.  Asynchronous; touches no solver state."""
+        B, R = self.batch, int(R)
+        if R < 1:
+            raise ValueError(f"kkt_tangent_rhs: R = {R}: at least one direction")
+        dots = dict(G_dot=G_dot, C_dot=C_dot, g_dot=g_dot, c_dot=c_dot, lo_dot=lo_dot, hi_dot=hi_dot, w_dot=w_dot, m_dot=m_dot)
+        for name, t in dots.items():
+            if t is None:
+                continue
+            per = self.sizes[self._TANGENTS[name]] if self._TANGENTS[name] else self.N
+            if not isinstance(t, torch.Tensor) or t.numel() != B * R * per or t.dtype != self.dtype or not t.is_cuda or not t.is_contiguous():
+                got = f"{t.dtype} {tuple(t.shape)} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
+                raise ValueError(f"kkt_tangent_rhs: {name} must be a contiguous {self.dtype} CUDA tensor of {B * R * per} entries, got {got}")
+        shared = dict(x=x, lam=lam)
+        if act is not None:
+            shared.update(Gb=Gb, Cb=Cb, act=act)
+            if soft_weight is not None:
+                shared.update(soft_weight=soft_weight, lo=lo, hi=hi)
+                if soft_cap is not None:
+                    shared.update(soft_cap=soft_cap)
+        self._check_vecs("kkt_tangent_rhs", **shared)
+        tg = self.new(B * R * self.N) if tg is None else tg
+        tc = self.new(B * R * self.sizes["sk"]) if tc is None else tc
+        for name, t, per in (("tg", tg, self.N), ("tc", tc, self.sizes["sk"])):
+            if not isinstance(t, torch.Tensor) or t.numel() != B * R * per or t.dtype != self.dtype or not t.is_cuda or not t.is_contiguous():
+                raise ValueError(f"kkt_tangent_rhs: {name} must be a contiguous {self.dtype} CUDA tensor of {B * R * per} entries")
+        on = act is not None
+        soft = on and soft_weight is not None
+        _lib.check(_lib.lib().gato_kkt_tangent_rhs(
+            self._h, R, *map(_ptr, dots.values()), _ptr(x), _ptr(lam), _ptr(Gb if on else None), _ptr(Cb if on else None),
+            _ptr(act), _ptr(soft_weight if soft else None), _ptr(soft_cap if soft else None), _ptr(lo if soft else None),
+            _ptr(hi if soft else None), _ptr(tg), _ptr(tc), self._stream()))
+        return tg, tc
+
+    def tangents(self, R, x, lam, exit_tol, max_iters, **inputs):
+        """(lam_dot [B, R, S K], x_dot [B, R, N]): the tangents of the point (x, lam) of the solver's CURRENT assembly along R
+        directions per system: kkt_tangent_rhs(R, x, lam, **inputs), one re-solve of the assembly for
+        the B R right-hand sides, x_dot = b_dot on the hard-active set.  A (system, direction) pair whose right-hand side is all
+        zero (off the hard-active set) gets x_dot = b_dot there, 0 elsewhere and lam_dot = 0 without its PCG, which would form
+        0/0.  Blocking (reserve_rhs)."""
+        B, R, N, sk = self.batch, int(R), self.N, self.sizes["sk"]
+        tg, tc = self.kkt_tangent_rhs(R, x, lam, **inputs)
+        self.reserve_rhs(R)
+        lam_d, x_d, _ = self.solve_rhs(tg, tc, exit_tol, max_iters)
+        self.check_status()
+        tg, tc, lam_d, x_d = tg.view(B, R, N), tc.view(B, R, sk), lam_d.view(B, R, sk), x_d.view(B, R, N)
+        act, w = inputs.get("act"), inputs.get("soft_weight")
+        hard = None
+        if act is not None:
+            hard = act.view(B, 1, N) != 0
+            if w is not None:
+                hard = hard & ~(w.view(B, 1, N) > 0)
+            tg = torch.where(hard, 0, tg)
+        zero = ~(tg.ne(0).any(2) | tc.ne(0).any(2))[:, :, None]
+        lam_d, x_d = torch.where(zero, 0, lam_d), torch.where(zero, 0, x_d)
+        if hard is not None:
+            lo_d, hi_d = inputs.get("lo_dot"), inputs.get("hi_dot")
+            z = torch.zeros((), dtype=self.dtype, device=x_d.device)
+            b_dot = torch.where(act.view(B, 1, N) > 0, z if hi_d is None else hi_d.view(B, R, N), z if lo_d is None else lo_d.view(B, R, N))
+            x_d = torch.where(hard, b_dot, x_d)
+        return lam_d, x_d
+
     # ---- box-constrained QP by ADMM over the re-solve (gato_box_qp_solve, DESIGN.md section 3.7) ------------------------
     def box_qp(self, Gb, Cb, g, c, lo, hi, *, rho, exit_tol, max_iters, admm_rho=0.1, sigma=1e-6, alpha=1.6, eps_abs=1e-6,
                eps_rel=1e-6, max_admm_iters=4000, check_every=25, x=None, z=None, y=None, lam=None, warm=False):

@@ -508,6 +508,28 @@ int gato_box_qp_line_search(gato_solver *s, const void *d_G_blocks, const void *
                             const void *d_soft_w, const void *d_soft_cap, double rho, const void *d_xc, const void *d_xplus,
                             double *d_alpha, double *d_slope, void *d_x, void *stream);
 
+/* ---- forward-mode sensitivities (new): the right-hand side of the tangent system, one launch --------
+ * For R directions per system, from the returned point (d_x [B][N], d_lambda [B][S*K]) and the input tangents (a dot):
+ *     t_g = g. - G. x - C.^T lambda,   t_c = c. - C. x            (C's identity blocks carry no tangent; rho drops out)
+ *     soft-active i (act = +-1, w_i > 0):  t_g,i += w._i (b_i - x_i) + w_i b._i;   saturated i (act = +-2):  t_g,i -= sign(act_i) m._i
+ *     t_g -= G b._A,  t_c -= C b._A   (b._A = b. on the hard-active set A - act != 0 and w_i = 0 or no weights - and 0 elsewhere;
+ *                                      C's identity blocks included; b. = hi. where act > 0, lo. where act < 0)
+ * gato_solve_rhs(R, d_tg, d_tc) on the point's assembly (the whole solve's, or the last one of a box-QP call) then gives the
+ * tangent [x.'; lambda.]: x. = x.' off A and b. on A.  Rows of d_tg on A hold what the sums give; the reduced system ignores them.
+ * Tangents: d_G_dot [B][R][G_dense], d_C_dot [B][R][C_dense] (the layouts of d_G_blocks / d_C_blocks; Q. and R. are used as
+ * given: symmetric perturbations), d_g_dot, d_lo_dot, d_hi_dot, d_w_dot, d_m_dot [B][R][N], d_c_dot [B][R][S*K]; each may be NULL
+ * (zero), and a NULL one is not read.  Shared by the R directions: d_x, d_lambda, d_G_blocks (WITHOUT rho), d_C_blocks, d_act
+ * [B][N] int8 (NULL: nothing active, the tangent of a plain solve - then the blocks, bounds and weights are not read), d_soft_w,
+ * d_soft_cap (NULL as in gato_box_qp_huber_grad), d_lo, d_hi (read on the soft-active set only).  Outputs d_tg [B][R][N],
+ * d_tc [B][R][S*K], the layouts gato_solve_rhs takes.  No atomics and a fixed order of the sums: a run repeats bit for bit.
+ * Touches no solver state and no assembly.  Asynchronous.  GATO_EINVAL for R < 1, a NULL d_x, d_lambda, d_tg or d_tc, an act
+ * without its blocks (d_C_blocks may be NULL only for K = 1), weights without d_lo and d_hi, and on a cluster rank. */
+int gato_kkt_tangent_rhs(gato_solver *s, int R, const void *d_G_dot, const void *d_C_dot, const void *d_g_dot, const void *d_c_dot,
+                         const void *d_lo_dot, const void *d_hi_dot, const void *d_w_dot, const void *d_m_dot, const void *d_x,
+                         const void *d_lambda, const void *d_G_blocks, const void *d_C_blocks, const signed char *d_act,
+                         const void *d_soft_w, const void *d_soft_cap, const void *d_lo, const void *d_hi, void *d_tg, void *d_tc,
+                         void *stream);
+
 /* ---- direct block input (new): the caller already holds the per-knot blocks in the
  * reference's dense layouts - d_G_blocks as G_dense WITHOUT rho, d_C_blocks as C_dense - so the CSR scatter is
  * skipped; rho is added to the diagonals of Q_k, R_k on the way into the solver's workspace.  Otherwise identical
