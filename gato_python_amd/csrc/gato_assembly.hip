@@ -364,7 +364,8 @@ __global__ __launch_bounds__(WAVE) void ss_kernel(const T *__restrict__ Sbd, T *
 //  1. gather the CSR entries of knots k-2..k (rows are contiguous, so the entries are one contiguous index range:
 //     a thread per ENTRY, row found by bisection of the row pointers held in LDS - two dependent global loads deep,
 //     coalesced) into dense LDS blocks; knot k's blocks are written out once (no memset);
-//  2. invert Q_{k-2}, R_{k-2}, Q_{k-1}, R_{k-1}, Q_k, R_k on six wavefronts at the same time (register Gauss-Jordan);
+//  2. invert Q_{k-2}, R_{k-2}, Q_{k-1}, R_{k-1}, Q_k, R_k on six wavefronts at the same time (register Gauss-Jordan, one
+//     body of code per matrix size);
 //  3. phi/theta of knots k-1 and k with the MFMA tiles spread over the waves; gamma, S[k], Pinv[k].main;
 //  4. the two stair blocks.
 // Per block the instruction sequence is that of invert_G_kernel / schur_kernel / ss_kernel: results are bit-identical
@@ -579,17 +580,28 @@ __global__ __launch_bounds__(NT) void assemble_kernel(AsmArgs a, int K, BatchStr
         const size_t gk = (size_t)k * (SS + CC);
         const size_t cm = first ? 0 : (size_t)(k - 1) * ABS;
         T *Sk = Sbd + (size_t)k * 3 * SS, *Pk = Pbd + (size_t)k * 3 * SS;
+        // q_{k-1}, r_{k-1}, q_k (one contiguous range of g) and c_k do not depend on the CSR: their loads go out here, beside
+        // the row pointers, instead of as a further dependent round trip behind the scatter; a thread holds one element of each
+        static_assert(2 * S + C <= NT && S <= NT - 2 * WAVE, "one element of g and of c per thread");
+        const int n_gq = first ? S : n + S;
+        const int i_cq = first ? tid : tid - 2 * WAVE;                       // the lanes that form gamma below
+        const T gq = tid < n_gq ? g[(first ? 0 : (size_t)(k - 1) * n) + tid] : (T)0;
+        const T cq = i_cq >= 0 && i_cq < S ? c[(size_t)k * S + i_cq] : (T)0;
         __syncthreads();
         // ---- 1. blocks of knots k-2 .. k into LDS ----
         if (a.mode == 0) {
             const T *G_val = (const T *)a.G_val + sys * bs.nnzG, *C_val = (const T *)a.C_val + sys * bs.nnzC;
             const int r0 = (k >= 2 ? k - 2 : 0) * n, nrG = k * n + (last ? S : n) - r0;
             const int c0 = (k >= 2 ? k - 1 : 1) * S, nrC = first ? 0 : (k + 1) * S - c0;
-            for (int i = tid; i <= nrG; i += NT) sPtrG[i] = a.G_row[r0 + i];
-            if (nrC) for (int i = tid; i <= nrC; i += NT) sPtrC[i] = a.C_row[c0 + i];
+            // at most 3n + 1 and 2S + 1 row pointers: one per thread, in flight while the zero fill runs
+            static_assert(L::PTR_G <= NT && L::PTR_C <= NT, "one row pointer per thread");
+            const int pG = tid <= nrG ? a.G_row[r0 + tid] : 0;
+            const int pC = nrC && tid <= nrC ? a.C_row[c0 + tid] : 0;
             for (int i = tid; i < 3 * SS + 3 * CC + 2 * ABS; i += NT) lds[i] = (T)0;   // sQ, sR, sAB are contiguous
             for (int i = tid; i < (NSLOT + 31) / 32; i += NT) smask[i] = 0u;
             if (tid == 0) s_coll = 0;
+            if (tid <= nrG) sPtrG[tid] = pG;
+            if (nrC && tid <= nrC) sPtrC[tid] = pC;
             __syncthreads();
             const int eG0 = sPtrG[0], nG = sPtrG[nrG] - eG0;
             const int eC0 = nrC ? sPtrC[0] : 0, nC = nrC ? sPtrC[nrC] - eC0 : 0;
@@ -664,11 +676,7 @@ __global__ __launch_bounds__(NT) void assemble_kernel(AsmArgs a, int K, BatchStr
                 if (qi < 2 && knot < K - 1) copy_nt<NT>(sAB + qi * ABS, Cd + (size_t)knot * ABS, ABS, tid);
             }
         }
-        if (first) { for (int i = tid; i < S; i += NT) sq[i] = g[i]; }
-        else {
-            copy_nt<NT>(sq, g + (size_t)(k - 1) * n, n, tid);                // q_{k-1}, r_{k-1}
-            for (int i = tid; i < S; i += NT) sq[n + i] = g[(size_t)k * n + i];   // q_k
-        }
+        if (tid < n_gq) sq[tid] = gq;                                        // q_0, or q_{k-1}, r_{k-1}, q_k
         __syncthreads();
         stamp();                                                             // 1: gathered
         if (a.mode != 1) {                                                   // knot k's dense blocks, written once
@@ -680,12 +688,14 @@ __global__ __launch_bounds__(NT) void assemble_kernel(AsmArgs a, int K, BatchStr
         if (k == 1) for (int i = tid; i < SS; i += NT) sTh0[i] = -sQm[i];    // ... which is this knot's left neighbour
         __syncthreads();
         // ---- 2. six inversions side by side, in place ----
-        if (wave == 0) invert_to<T, S>(sQk, sQk, lane, (T)1);
-        else if (wave == 1) { if (!first) invert_to<T, S>(sQm, sQm, lane, (T)1); }
-        else if (wave == 2) { if (!first) invert_to<T, C>(sRm, sRm, lane, (T)1); }
-        else if (wave == 3) { if (full0) invert_to<T, S>(sQmm, sQmm, lane, (T)1); }
-        else if (wave == 4) { if (full0) invert_to<T, C>(sRmm, sRmm, lane, (T)1); }
-        else if (wave == 5) { if (!last) invert_to<T, C>(sRk, sRk, lane, (T)1); }
+        // (waves 0, 1, 3: Q_k, Q_{k-1}, Q_{k-2}; waves 5, 2, 4: R_k, R_{k-1}, R_{k-2}.)  Each wave picks its matrix and all of
+        // them run ONE elimination body per size: three waves fetch the same instructions instead of three cold copies
+        // (14/7 fp64: 56 KB of kernel code -> 32 KB; 0.5 us of the launch, profiles/asm_chain_stamps.txt)
+        {
+            T *mS = wave == 0 ? sQk : wave == 1 ? sQm : sQmm, *mC = wave == 5 ? sRk : wave == 2 ? sRm : sRmm;
+            if (wave == 0 || (wave == 1 && !first) || (wave == 3 && full0)) invert_to<T, S>(mS, mS, lane, (T)1);
+            else if ((wave == 5 && !last) || (wave == 2 && !first) || (wave == 4 && full0)) invert_to<T, C>(mC, mC, lane, (T)1);
+        }
         __syncthreads();
         stamp();                                                             // 2: inverted
         for (int i = tid; i < SS; i += NT) Ginv[gk + i] = sQk[i];
@@ -701,7 +711,7 @@ __global__ __launch_bounds__(NT) void assemble_kernel(AsmArgs a, int K, BatchStr
                 if (last) { imP(0, 2, i % S, i / S, (T)0); imS(0, 2, i % S, i / S, (T)0); }
             }
             __syncthreads();
-            for (int i = tid; i < S; i += NT) gamma[i] = c[i] - sv[i];       // :131-146, + c_0 (D4)
+            if (tid < S) gamma[tid] = cq - sv[tid];                          // :131-146, + c_0 (D4)
             continue;
         }
         // ---- 3. Schur blocks of knot k, theta of knot k-1 ----
@@ -749,11 +759,12 @@ __global__ __launch_bounds__(NT) void assemble_kernel(AsmArgs a, int K, BatchStr
                 },
                 [&](int r, int cc, T v) { sTh0[cc * S + r] = v + sQm[cc * S + r]; });
         __syncthreads();
-        if (wave == 0) invert_to<T, S>(sTh1, sTh1, lane, (T)-1);             // Pinv[k].main = -theta^-1  :407-422
-        else if (wave == 1) { if (full0) invert_to<T, S>(sTh0, sTh0, lane, (T)-1); }
-        else {
-            for (int i = tid - 2 * WAVE; i < S; i += NT - 2 * WAVE) {
-                T gt = sv[i] - c[(size_t)k * S + i];                         // :311-313
+        if (wave == 0 || (wave == 1 && full0)) {                             // Pinv[k].main = -theta^-1  :407-422
+            T *mT = wave == 0 ? sTh1 : sTh0;
+            invert_to<T, S>(mT, mT, lane, (T)-1);
+        } else if (wave >= 2) {
+            if (const int i = i_cq; i < S) {
+                T gt = sv[i] - cq;                                           // :311-313
                 gt += sv[2 * S + i] + sv[S + i];                             // :336-338
                 gamma[(size_t)k * S + i] = -gt;                              // :435-438
             }
