@@ -8,7 +8,9 @@ Public surface:
   gato_python_amd.kkt_solve_csr(...)     differentiable solve on device CSR input
   gato_python_amd.box_qp(...)            box-constrained QP (bounds on states and controls) by ADMM over the re-solve, or
                                          by the active-set iteration (method="pdas": hard, soft and capped soft bounds;
-                                         line_search=True: the exact line search that makes the all-soft iteration converge)
+                                         line_search=True: the exact line search that makes the all-soft iteration converge),
+                                         or by the method of multipliers over that iteration (method="alm": hard bounds on
+                                         states too, where ADMM is slow and the hard active-set iteration cycles)
   gato_python_amd.box_qp_layer(...)      differentiable box-constrained QP: ADMM, then the polish on its active set, or the
                                          active-set iteration alone, with hard or soft bounds (one autograd Function,
                                          qp._BoxQPLayer, whose backward branches on "weights present"); line_search=True

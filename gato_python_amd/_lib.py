@@ -35,11 +35,12 @@ SYMBOLS = [
     "gato_kkt_grad_blocks", "gato_kkt_grad_csr", "gato_box_qp_default_params", "gato_box_qp_solve",
     "gato_box_qp_active_set", "gato_box_qp_polish", "gato_box_qp_bound_grad", "gato_box_qp_pdas",
     "gato_box_qp_pdas_soft", "gato_box_qp_soft_grad", "gato_box_qp_pdas_huber", "gato_box_qp_huber_grad",
-    "gato_box_qp_pdas_ls", "gato_box_qp_line_search", "gato_kkt_tangent_rhs",
+    "gato_box_qp_pdas_ls", "gato_box_qp_line_search", "gato_kkt_tangent_rhs", "gato_box_qp_alm", "gato_box_qp_alm_update",
 ]
 
 
 QP_CONVERGED, QP_MAX_ITERS, QP_NONFINITE, QP_BAD_BOUNDS, QP_BAD_ACTIVE = 0, 1, 2, 3, 4
+ALM_ACCEPT, ALM_GROW, ALM_KEEP, ALM_LAST, ALM_INNER = 0, 1, 2, 3, 4      # Solver.box_qp_alm_update's decisions
 POLISH_ACCEPTED, POLISH_REJECTED, POLISH_NONFINITE, POLISH_BAD_ACTIVE = 0, 1, 2, 3
 
 
@@ -135,6 +136,8 @@ def lib() -> ct.CDLL:
         L.gato_box_qp_pdas_ls.argtypes = [vp] * 10 + [ct.POINTER(BoxQpParams), i] + [vp] * 9
         L.gato_box_qp_line_search.argtypes = [vp] * 7 + [d] + [vp] * 6
         L.gato_kkt_tangent_rhs.argtypes = [vp, i] + [vp] * 20
+        L.gato_box_qp_alm.argtypes = [vp] * 10 + [ct.POINTER(BoxQpParams), i, d, d, d, i] + [vp] * 11
+        L.gato_box_qp_alm_update.argtypes = [vp] * 10 + [d, d, d, d, i] + [vp] * 8
         f = ct.c_float
         L.gato_linsys_solve_f32.argtypes = [ip, i, ip, vp, i, ip, i, ip, vp, i, vp, i, vp, i, vp,
                                             i, i, i, i, f, i, i, f, vp, vp, vp, vp]

@@ -432,6 +432,36 @@ int launch_ls_scope(const Dims &d, const LineSearchArgs &a, hipStream_t st);
 // the per-knot partial sums, then the per-system step length, stepped iterate and (the loop) act' and its changed count
 template <typename T, int S, int C>
 int launch_line_search(const Dims &d, const LineSearchArgs &a, hipStream_t st);
+// Hard bounds by an augmented-Lagrangian outer loop over the line-search iteration (gato_alm.hip).
+// ALM variables: a finite bound, no user weight, off the states of x_0.  The inner run solves the all-soft problem on lo2, hi2,
+// w2 (cap2) from act; its point is xi, zi, yi, li with status_i, iters_i, res_i.
+struct AlmArgs {
+    const void *lo, *hi, *w, *cap;          // the caller's bounds, weights and caps [B][N]; w, cap may be nullptr
+    const void *mu0;                        // check: the start multiplier [B][N]; nullptr: 0
+    const signed char *act0;                // check: the caller's start act, copied to act; nullptr: act is not written
+    const void *xi, *zi, *yi, *li;          // the inner point [B][N], li [B][S K]
+    const int *status_i, *iters_i;          // the inner run's status and solves [B]
+    const double *res_i;                    // and residuals [B][2]
+    signed char *act;                       // the inner run's act [B][N] (in: its start, out: its last)
+    void *lo2, *hi2, *w2, *cap2, *mu;       // the inner bounds, weights, caps (nullptr without caps) and the multiplier [B][N]
+    double *state;                          // [B][2][2] per set {w, v_prev}: step k reads set k % 2 and writes the other
+    unsigned long long *slots;              // [B][2][2] per set {v, |x|_inf} of step k % 2, as bit patterns
+    int *flag;                              // [B] the system was frozen before this step (update writes, decide reads)
+    int *tot;                               // [B] reduced solves of all steps so far
+    int *ctr;                               // {live systems, waves that saw a bad bound, weight, cap or parameter}
+    void *x, *z, *y, *lam;                  // the caller's outputs, written on acceptance only
+    signed char *act_out;                   // the accepted act [B][N]; nullptr: not written
+    int *iters, *status, *outer, *dec;      // [B]; outer, dec (GATO_ALM_*) may be nullptr
+    double *res, *weight;                   // [B][2]; [B] the weight of the last step, may be nullptr
+    double alm_weight, growth, weight_max, eps_abs, eps_rel;
+};
+enum { GATO_ALM_ACCEPT = 0, GATO_ALM_GROW = 1, GATO_ALM_KEEP = 2, GATO_ALM_LAST = 3, GATO_ALM_INNER = 4 };
+// the checks of the parameters, bounds, weights and caps, and the inner inputs of the first step (first launch of a call)
+template <typename T, int S, int C>
+int launch_alm_check(const Dims &d, const AlmArgs &a, hipStream_t st);
+// after the inner run of outer step `it` (1, 2, ...): v, |x|_inf and mu <- y, then the decision (last: no step follows)
+template <typename T, int S, int C>
+int launch_alm_update(const Dims &d, const AlmArgs &a, int it, int last, hipStream_t st);
 template <typename T, int S>
 int pcg_resident_plan(PcgPlan *plan);
 template <typename T, int S>
@@ -524,6 +554,8 @@ struct Ops {
     int (*pdas_decide)(const Dims &, const PdasArgs &, int, int, hipStream_t);
     int (*ls_scope)(const Dims &, const LineSearchArgs &, hipStream_t);
     int (*line_search)(const Dims &, const LineSearchArgs &, hipStream_t);
+    int (*alm_check)(const Dims &, const AlmArgs &, hipStream_t);
+    int (*alm_update)(const Dims &, const AlmArgs &, int, int, hipStream_t);
     int (*pcg_plan)(PcgPlan *);
     int (*pcg_resident)(const PcgLaunch &, hipStream_t);
     int (*pcg_dma_max_knots)();

@@ -66,6 +66,10 @@ static Ops make_ops(int dtype)
     };
     o.ls_scope = [](const Dims &d, const LineSearchArgs &a, hipStream_t st) { return launch_ls_scope<T, S, C>(d, a, st); };
     o.line_search = [](const Dims &d, const LineSearchArgs &a, hipStream_t st) { return launch_line_search<T, S, C>(d, a, st); };
+    o.alm_check = [](const Dims &d, const AlmArgs &a, hipStream_t st) { return launch_alm_check<T, S, C>(d, a, st); };
+    o.alm_update = [](const Dims &d, const AlmArgs &a, int it, int last, hipStream_t st) {
+        return launch_alm_update<T, S, C>(d, a, it, last, st);
+    };
     o.pcg_plan = [](PcgPlan *p) { return pcg_resident_plan<T, S>(p); };
     o.pcg_resident = [](const PcgLaunch &a, hipStream_t st) { return launch_pcg_resident<T, S>(a, st); };   // incl. the DPP-row layout
     o.pcg_dma_max_knots = []() { return pcg_dma_max_knots<T, S>(); };

@@ -488,3 +488,165 @@ extern "C" int gato_box_qp_line_search(gato_solver *s, const void *d_G_blocks, c
     la.alpha = d_alpha; la.alpha_stride = 1; la.slope = d_slope; la.rho = rho; la.it = 2;
     return s->ops->line_search(d, la, st);
 }
+
+// ---- hard bounds by an augmented-Lagrangian outer loop (gato_alm.hip) ----------------------------------
+// The work area of the outer loop, behind the line-search iteration's in pol_ws (which the inner runs use and zero as they
+// always do): the inner run's inputs and point, the multiplier, then what a call zeroes - the maxima, the counts, the counters.
+struct AlmWs {
+    size_t lo2, hi2, w2, cap2, mu, xi, zi, yi;   // [B][N] each
+    size_t li;                              // [B][S K]
+    size_t act;                             // [B][N] int8
+    size_t res_i, state;                    // [B][2], [B][2][2] doubles
+    size_t sl;                              // [B][2][2] maxima; zeroed from here on
+    size_t st_i, it_i, flag, tot;           // [B] ints
+    size_t ctr;
+    size_t st_o, it_o, res_o;               // gato_box_qp_alm_update: the status, solves [B] and residuals [B][2] it has no caller for
+    size_t bytes;
+};
+static AlmWs alm_ws(const Dims &d, size_t e)
+{
+    const size_t B = d.B, vN = align_up(B * d.N() * e), vB = align_up(B * sizeof(int));
+    AlmWs o;
+    o.lo2 = polish_ws(d, e, true, true).bytes;
+    o.hi2 = o.lo2 + vN; o.w2 = o.hi2 + vN; o.cap2 = o.w2 + vN; o.mu = o.cap2 + vN; o.xi = o.mu + vN; o.zi = o.xi + vN; o.yi = o.zi + vN;
+    o.li = o.yi + vN;
+    o.act = o.li + align_up(B * d.sk() * e);
+    o.res_i = o.act + align_up(B * d.N());
+    o.state = o.res_i + align_up(B * 2 * sizeof(double));
+    o.sl = o.state + align_up(B * 4 * sizeof(double));
+    o.st_i = o.sl + align_up(B * 4 * 8);
+    o.it_i = o.st_i + vB; o.flag = o.it_i + vB; o.tot = o.flag + vB; o.ctr = o.tot + vB;
+    o.st_o = o.ctr + 256; o.it_o = o.st_o + vB; o.res_o = o.it_o + vB;
+    o.bytes = o.res_o + align_up(B * 2 * sizeof(double));
+    return o;
+}
+
+// The part of AlmArgs both entries fill alike: the work area at w.
+static AlmArgs alm_args(char *w, const AlmWs &o, bool caps)
+{
+    AlmArgs a;
+    memset(&a, 0, sizeof(a));
+    a.lo2 = w + o.lo2; a.hi2 = w + o.hi2; a.w2 = w + o.w2; a.cap2 = caps ? w + o.cap2 : nullptr; a.mu = w + o.mu;
+    a.xi = w + o.xi; a.zi = w + o.zi; a.yi = w + o.yi; a.li = w + o.li;
+    a.status_i = (const int *)(w + o.st_i); a.iters_i = (const int *)(w + o.it_i); a.res_i = (const double *)(w + o.res_i);
+    a.state = (double *)(w + o.state); a.slots = (unsigned long long *)(w + o.sl);
+    a.flag = (int *)(w + o.flag); a.tot = (int *)(w + o.tot); a.ctr = (int *)(w + o.ctr);
+    return a;
+}
+
+static bool alm_params_ok(double alm_weight, double alm_growth, double alm_weight_max)
+{
+    return std::isfinite(alm_weight) && alm_weight > 0 && alm_growth > 1 && alm_weight_max >= alm_weight;
+}
+
+// Per outer step: the inner run - gato_box_qp_pdas_ls's loop on the work area's bounds, weights and act, launch for launch - then
+// the update and the decision and one read of the live count.  Only the decision writes the caller's arrays.
+extern "C" int gato_box_qp_alm(gato_solver *s, const void *d_G_blocks, const void *d_C_blocks, const void *d_g, const void *d_c,
+                               const void *d_lo, const void *d_hi, const void *d_soft_w, const void *d_soft_cap, signed char *d_act,
+                               const gato_box_qp_params *p, int max_pdas_iters, double alm_weight, double alm_growth,
+                               double alm_weight_max, int max_alm_iters, const void *d_mu0, void *d_x, void *d_z, void *d_y,
+                               void *d_lambda, int *d_iters, int *d_status, double *d_res, int *d_outer, double *d_weight,
+                               void *stream)
+{
+    const char *who = "box_qp_alm";
+    if (check_pointers(s, who, p, d_C_blocks, {d_G_blocks, d_g, d_c, d_lo, d_hi, d_act, d_x, d_z, d_y, d_lambda, d_iters, d_status, d_res},
+                       ", d_soft_w for no soft bound, d_soft_cap for no cap, d_mu0 for a zero multiplier, d_outer and d_weight"))
+        return GATO_EINVAL;
+    if (!reduced_params_ok(*p) || max_pdas_iters < 1 || max_alm_iters < 1) {
+        set_error("%s: parameters out of range (want finite values, rho, eps_abs, eps_rel, exit_tol >= 0, max_iters, "
+                  "max_pdas_iters, max_alm_iters >= 1)", who);
+        return GATO_EINVAL;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (check_not_capturing(who, "the loop reads the live count", st)) return GATO_EINVAL;
+    GATO_HIP_CHECK(hipSetDevice(s->device));
+    const size_t B = s->d.B;
+    const bool caps = d_soft_w && d_soft_cap;
+    const AlmWs o = alm_ws(s->d, s->esz);
+    int rc;
+    if ((rc = grow_ws(&s->pol_ws, &s->pol_ws_bytes, o.bytes, st))) return rc;     // the inner runs find their part large enough
+    char *w = s->pol_ws;
+    GATO_HIP_CHECK(hipMemsetAsync(w + o.sl, 0, o.bytes - o.sl, st));
+    GATO_HIP_CHECK(hipMemsetAsync(d_status, 0xff, B * sizeof(int), st));             // -1: running
+    AlmArgs a = alm_args(w, o, caps);
+    a.lo = d_lo; a.hi = d_hi; a.w = d_soft_w; a.cap = caps ? d_soft_cap : nullptr; a.mu0 = d_mu0;
+    a.act0 = d_act; a.act = (signed char *)(w + o.act); a.act_out = d_act;
+    a.x = d_x; a.z = d_z; a.y = d_y; a.lam = d_lambda; a.iters = d_iters; a.status = d_status; a.outer = d_outer;
+    a.res = d_res; a.weight = d_weight;
+    a.alm_weight = alm_weight; a.growth = alm_growth; a.weight_max = alm_weight_max; a.eps_abs = p->eps_abs; a.eps_rel = p->eps_rel;
+    Dims d = s->d;
+    d.k_lo = d.k_hi = 0; d.rhs = 0;
+    if ((rc = s->ops->alm_check(d, a, st))) return rc;
+    int h[2] = {0, 0};
+    GATO_HIP_CHECK(hipMemcpyAsync(h, a.ctr, sizeof(h), hipMemcpyDeviceToHost, st));
+    GATO_HIP_CHECK(hipStreamSynchronize(st));
+    if (h[1] > 0) {
+        set_error("%s:%s a bound is NaN, lo > hi, a weight is NaN, negative or infinite or a cap is NaN or negative (BAD_BOUNDS); "
+                  "d_status marks the systems", who,
+                  alm_params_ok(alm_weight, alm_growth, alm_weight_max) ? "" : " want a finite alm_weight > 0, alm_growth > 1 and "
+                  "alm_weight_max >= alm_weight, or");
+        return GATO_EINVAL;
+    }
+    for (int it = 1; it <= max_alm_iters; ++it) {
+        rc = pdas_loop(s, who, 2, d_G_blocks, d_C_blocks, d_g, d_c, a.lo2, a.hi2, a.w2, a.cap2, a.act, p, max_pdas_iters, w + o.xi,
+                       w + o.zi, w + o.yi, w + o.li, (int *)(w + o.it_i), (int *)(w + o.st_i), (double *)(w + o.res_i), stream, true);
+        if (rc) {                           // step 1: a start act the inner run refuses, its marks to the caller; a later
+            if (it == 1) {                  // error (HIP, a hand-off time-out) leaves d_status -1 on the systems still running
+                GATO_HIP_CHECK(hipMemcpyAsync(d_status, w + o.st_i, B * sizeof(int), hipMemcpyDeviceToDevice, st));
+                GATO_HIP_CHECK(hipStreamSynchronize(st));
+            }
+            return rc;
+        }
+        if ((rc = s->ops->alm_update(d, a, it, it == max_alm_iters, st))) return rc;
+        if (it == max_alm_iters) break;     // every system still live froze in that decision
+        hipError_t he = hipMemcpyAsync(h, a.ctr, sizeof(int), hipMemcpyDeviceToHost, st);
+        if (he == hipSuccess) he = hipStreamSynchronize(st);
+        if (he != hipSuccess) {
+            set_error("%s: reading the live count failed: %s", who, hipGetErrorString(he));
+            return GATO_EHIP;
+        }
+        if (h[0] == 0) break;
+    }
+    GATO_HIP_CHECK(hipStreamSynchronize(st));
+    return gato_pcg_status(s, nullptr);
+}
+
+// The update and the decision alone, two launches, on a given inner point of converged inner runs.
+extern "C" int gato_box_qp_alm_update(gato_solver *s, const void *d_x, const void *d_y, const void *d_lambda, void *d_mu,
+                                      const double *d_w, const double *d_v_prev, const void *d_lo, const void *d_hi, const void *d_soft_w,
+                                      double eps_abs, double eps_rel, double alm_growth,
+                                      double alm_weight_max, int last, double *d_v, double *d_xinf, int *d_dec, void *d_lo2,
+                                      void *d_hi2, void *d_w2, void *d_z, void *stream)
+{
+    if (!solver_usable(s, "box_qp_alm_update", "QP solves")) return GATO_EINVAL;
+    if (!d_x || !d_y || !d_lambda || !d_mu || !d_w || !d_v_prev || !d_lo || !d_hi || !d_v || !d_xinf || !d_dec || !d_lo2 || !d_hi2 ||
+        !d_w2 || !d_z) {
+        set_error("box_qp_alm_update: every pointer is required (d_soft_w may be NULL for no soft bound)");
+        return GATO_EINVAL;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    GATO_HIP_CHECK(hipSetDevice(s->device));
+    const size_t B = s->d.B;
+    const AlmWs o = alm_ws(s->d, s->esz);
+    int rc;
+    if ((rc = grow_ws(&s->pol_ws, &s->pol_ws_bytes, o.bytes, st))) return rc;
+    char *w = s->pol_ws;
+    GATO_HIP_CHECK(hipMemsetAsync(w + o.res_i, 0, o.bytes - o.res_i, st));          // inner status CONVERGED, residuals and solves 0
+    AlmArgs a = alm_args(w, o, false);
+    a.lo = d_lo; a.hi = d_hi; a.w = d_soft_w;                    // the caps are not read: a capped variable has a weight and is no ALM variable
+    a.xi = d_x; a.zi = d_x; a.yi = d_y; a.li = d_lambda; a.mu = d_mu; a.lo2 = d_lo2; a.hi2 = d_hi2; a.w2 = d_w2;
+    a.x = w + o.xi; a.y = w + o.yi; a.lam = w + o.li; a.z = d_z;
+    a.status = (int *)(w + o.st_o); a.iters = (int *)(w + o.it_o); a.res = (double *)(w + o.res_o); a.dec = d_dec;
+    a.growth = alm_growth; a.weight_max = alm_weight_max; a.eps_abs = eps_abs; a.eps_rel = eps_rel;
+    GATO_HIP_CHECK(hipMemsetAsync(a.status, 0xff, B * sizeof(int), st));
+    // set 1 of the state is step 1's: {w, v_prev} interleaved from the caller's arrays
+    GATO_HIP_CHECK(hipMemcpy2DAsync(a.state + 2, 4 * sizeof(double), d_w, sizeof(double), sizeof(double), B, hipMemcpyDeviceToDevice, st));
+    GATO_HIP_CHECK(hipMemcpy2DAsync(a.state + 3, 4 * sizeof(double), d_v_prev, sizeof(double), sizeof(double), B, hipMemcpyDeviceToDevice, st));
+    Dims d = s->d;
+    d.k_lo = d.k_hi = 0; d.rhs = 0;
+    if ((rc = s->ops->alm_update(d, a, 1, last, st))) return rc;
+    // the maxima of set 1, step 1's
+    GATO_HIP_CHECK(hipMemcpy2DAsync(d_v, sizeof(double), a.slots + 2, 4 * 8, 8, B, hipMemcpyDeviceToDevice, st));
+    GATO_HIP_CHECK(hipMemcpy2DAsync(d_xinf, sizeof(double), a.slots + 3, 4 * 8, 8, B, hipMemcpyDeviceToDevice, st));
+    return GATO_OK;
+}

@@ -93,7 +93,8 @@ def _check_line_search(what, method, polish, soft, line_search):
 
 def box_qp(Q, R, A, B, q, r, c, x_lo, x_hi, u_lo, u_hi, *, rho, exit_tol, max_iters, admm_rho=0.1, sigma=1e-6, alpha=1.6,
            eps_abs=1e-6, eps_rel=1e-6, max_admm_iters=4000, check_every=25, warm=None, polish=False, method="admm",
-           polish_iters=1, max_pdas_iters=30, x_soft=None, u_soft=None, x_soft_max=None, u_soft_max=None, line_search=False):
+           polish_iters=1, max_pdas_iters=30, x_soft=None, u_soft=None, x_soft_max=None, u_soft_max=None, line_search=None,
+           alm_weight=100.0, alm_growth=10.0, alm_weight_max=None, max_alm_iters=50):
     """Box-constrained QP from math-shaped blocks, at most one leading batch dimension:
     Q [*,K,S,S], R [*,K-1,C,C], A [*,K-1,S,S], B [*,K-1,S,C], q [*,K,S], r [*,K-1,C], c [*,K,S] as kkt_solve takes them (A, B
     the raw values stored in C: -A and -B of the dynamics), and the bounds x_lo, x_hi [*,K,S], u_lo, u_hi [*,K-1,C] - numbers
@@ -120,9 +121,32 @@ def box_qp(Q, R, A, B, q, r, c, x_lo, x_hi, u_lo, u_hi, *, rho, exit_tol, max_it
     objective, which makes the iteration converge where the undamped one cycles (large weights, caps between the regimes), at
     the price of more solves elsewhere.  Every variable with a finite bound (off x_0) must have a positive weight.
     result.alpha [*, max_pdas_iters] holds the step length of every solve (1: a full step, 0: none taken).  ValueError for
-    method="admm", polish=True, without weights, and for a finite bound whose weight is 0."""
-    if method not in ("admm", "pdas"):
-        raise ValueError(f"box_qp: method must be 'admm' or 'pdas', got {method!r}")
+    method="admm", polish=True, without weights, and for a finite bound whose weight is 0.
+    method="alm" (DESIGN.md section 3.14): hard bounds on states and controls by the method of multipliers over the line-search
+    iteration - the method for hard state bounds, where ADMM needs thousands of x-steps and the hard active-set iteration
+    cycles or meets a singular system.  Every variable with a finite bound and no weight gets a multiplier and the penalty weight
+    w, from alm_weight; an outer step is one line-search iteration (at most max_pdas_iters solves) on the bounds shifted by
+    -mu / w, then mu <- its force, and w <- alm_growth w where the violation did not fall below a quarter of the step before
+    (while w < alm_weight_max; None: 1e8 in float64, 1e5 in float32), at most max_alm_iters steps.  CONVERGED: the violation
+    of the hard bounds is within eps_abs + eps_rel |x|_inf, result.z is x clipped to them and result.y holds their multipliers.
+    An infeasible box ends MAX_ITERS with result.res_prim the violation it stalls at.  x_soft / u_soft (and x_soft_max /
+    u_soft_max) keep their variables soft bounds: hard actuator limits with soft state limits.  result.iters counts the reduced
+    solves of all steps, result.outer the steps, result.weight the last w.  warm: a previous method="alm" result - its y starts
+    the multipliers and its act the active set.  polish=True: the point is then polished on its active set
+    (Solver.box_qp_polish) and replaced by the exact vertex where the polish is ACCEPTED (LICQ holds); no weights then.
+    ValueError for an ADMM parameter or polish_iters that is not its default, for line_search (it is implied) and for
+    alm_weight <= 0, alm_growth <= 1, alm_weight_max < alm_weight or max_alm_iters < 1."""
+    if method not in ("admm", "pdas", "alm"):
+        raise ValueError(f"box_qp: method must be 'admm', 'pdas' or 'alm', got {method!r}")
+    if method == "alm":
+        return _box_qp_alm((Q, R, A, B, q, r, c), (x_lo, x_hi, u_lo, u_hi), (x_soft, u_soft, x_soft_max, u_soft_max),
+                           dict(admm_rho=(admm_rho, 0.1), sigma=(sigma, 1e-6), alpha=(alpha, 1.6), max_admm_iters=(max_admm_iters, 4000),
+                                check_every=(check_every, 25), polish_iters=(polish_iters, 1)), line_search, warm, polish,
+                           dict(rho=rho, exit_tol=exit_tol, max_iters=max_iters, eps_abs=eps_abs, eps_rel=eps_rel),
+                           dict(max_pdas_iters=max_pdas_iters, alm_weight=alm_weight, alm_growth=alm_growth,
+                                alm_weight_max=alm_weight_max, max_alm_iters=max_alm_iters))
+    if (alm_weight, alm_growth, alm_weight_max, max_alm_iters) != (100.0, 10.0, None, 50):
+        raise ValueError("box_qp: alm_weight, alm_growth, alm_weight_max and max_alm_iters need method='alm'")
     soft = x_soft is not None or u_soft is not None
     _check_caps("box_qp", method, polish, soft, x_soft_max is not None or u_soft_max is not None)
     _check_line_search("box_qp", method, polish, soft, line_search)
@@ -186,7 +210,48 @@ def _shaped(res, sol, Bt, batched):
     return BoxQPResult(shp(res.x, N), shp(res.z, N), shp(res.y, N), shp(res.lam, sk), first(res.iters), first(res.status),
                        first(res.res_prim), first(res.res_dual), None if res.polished is None else first(res.polished),
                        None if res.act is None else shp(res.act, N),
-                       None if res.alpha is None else (res.alpha if batched else res.alpha[0]))
+                       None if res.alpha is None else (res.alpha if batched else res.alpha[0]),
+                       None if res.outer is None else first(res.outer), None if res.weight is None else first(res.weight))
+
+
+def _box_qp_alm(blocks, bounds, soft, admm_only, line_search, warm, polish, pol, alm):
+    """box_qp(method="alm"): the refusals, Solver.box_qp_alm and - polish - the active set of its point and one polish on it."""
+    given = [name for name, (v, default) in admm_only.items() if v != default]
+    if given:
+        raise ValueError(f"box_qp: {', '.join(given)} {'is' if len(given) == 1 else 'are'} not read by method='alm' (ADMM and "
+                         "its polish stage only)")
+    if line_search is not None:
+        raise ValueError("box_qp: line_search is implied by method='alm' (every inner iteration is the line-search one): leave it out")
+    weight, growth, weight_max = float(alm["alm_weight"]), float(alm["alm_growth"]), alm["alm_weight_max"]
+    if not (0 < weight < float("inf")) or not growth > 1 or (weight_max is not None and not float(weight_max) >= weight):
+        raise ValueError("box_qp: method='alm' needs a finite alm_weight > 0, alm_growth > 1 and alm_weight_max >= alm_weight")
+    if int(alm["max_alm_iters"]) < 1 or int(alm["max_pdas_iters"]) < 1:
+        raise ValueError("box_qp: max_alm_iters and max_pdas_iters must be at least 1")
+    x_soft, u_soft, x_soft_max, u_soft_max = soft
+    is_soft = x_soft is not None or u_soft is not None
+    if (x_soft_max is not None or u_soft_max is not None) and not is_soft:
+        raise ValueError("box_qp: x_soft_max and u_soft_max cap the force of a soft bound: give x_soft or u_soft too")
+    if polish and is_soft:
+        raise ValueError("box_qp: polish=True with method='alm' takes hard bounds only (the polish has no soft bounds)")
+    with torch.no_grad():
+        Gb, Cb, g, cc, lo, hi, wt, mt, Bt, batched, sol = _prepare("box_qp", blocks, *bounds, *soft)
+        act = mu = None
+        if warm is not None:
+            act, mu = getattr(warm, "act", None), getattr(warm, "y", None)
+            if not isinstance(act, torch.Tensor) or act.numel() != Bt * sol.N or act.dtype != torch.int8 or act.device != g.device:
+                raise ValueError(f"box_qp: warm.act does not match this problem ({Bt} x {sol.N} int8 on {g.device}); "
+                                 "method='alm' starts from the act and the y of a previous method='alm' result")
+            if not isinstance(mu, torch.Tensor) or mu.numel() != Bt * sol.N or mu.dtype != g.dtype or mu.device != g.device:
+                raise ValueError(f"box_qp: warm.y does not match this problem ({Bt} x {sol.N} {g.dtype} on {g.device})")
+            act, mu = act.reshape(-1).contiguous(), mu.detach().reshape(-1).contiguous()
+        res = sol.box_qp_alm(Gb, Cb, g, cc, lo, hi, act=act, mu=mu, soft_weight=None if wt is None else wt.contiguous(),
+                             soft_cap=None if mt is None else mt.contiguous(), **pol, **alm)
+        if polish:
+            act = res.act
+            pact = sol.box_qp_active_set(res.z, res.y, lo, hi)
+            sol.box_qp_polish(Gb, Cb, g, cc, lo, hi, pact, res, **pol)
+            res.act = torch.where((res.polished == _lib.POLISH_ACCEPTED).repeat_interleave(sol.N), pact, act)
+    return _shaped(res, sol, Bt, batched)
 
 
 # ---- the differentiable layer -----------------------------------------------------------------------------------------

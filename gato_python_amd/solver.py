@@ -15,6 +15,8 @@ import torch
 from . import _lib
 
 _TORCH_DT = {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64}
+# alm_weight_max=None of Solver.box_qp_alm (DESIGN.md section 3.14 says how the float32 value was chosen)
+ALM_WEIGHT_MAX = {np.dtype(np.float64): 1e8, np.dtype(np.float32): 1e5}
 
 
 class BoxQPResult:
@@ -22,13 +24,15 @@ class BoxQPResult:
     res_prim, res_dual [..] (float64) - the true QP residuals of the returned iterate - and polished [..] (int32:
     _lib.POLISH_*; None unless a polish was asked for); act [.., N] (int8) the final active set of an active-set solve
     (box_qp_pdas; None otherwise); alpha [.., max_pdas_iters] (float64) the step length of every reduced solve of an
-    active-set solve with line_search=True (None otherwise)."""
-    __slots__ = ("x", "z", "y", "lam", "iters", "status", "res_prim", "res_dual", "polished", "act", "alpha")
+    active-set solve with line_search=True (None otherwise); outer [..] (int32) and weight [..] (float64) the outer steps and
+    the last step's weight of an augmented-Lagrangian solve (box_qp_alm; None otherwise)."""
+    __slots__ = ("x", "z", "y", "lam", "iters", "status", "res_prim", "res_dual", "polished", "act", "alpha", "outer", "weight")
 
-    def __init__(self, x, z, y, lam, iters, status, res_prim, res_dual, polished=None, act=None, alpha=None):
+    def __init__(self, x, z, y, lam, iters, status, res_prim, res_dual, polished=None, act=None, alpha=None, outer=None,
+                 weight=None):
         self.x, self.z, self.y, self.lam = x, z, y, lam
         self.iters, self.status, self.res_prim, self.res_dual = iters, status, res_prim, res_dual
-        self.polished, self.act, self.alpha = polished, act, alpha
+        self.polished, self.act, self.alpha, self.outer, self.weight = polished, act, alpha, outer, weight
 
     def __repr__(self):
         pol = "" if self.polished is None else f", polished={self.polished.tolist()}"
@@ -438,6 +442,89 @@ class Solver:
                                                       float(rho), _ptr(xc), _ptr(xplus), _ptr(alpha), _ptr(slope), _ptr(x),
                                                       self._stream()))
         return alpha, slope, x
+
+    # ---- hard bounds by an augmented-Lagrangian outer loop (gato_box_qp_alm) ----------------------
+    def box_qp_alm(self, Gb, Cb, g, c, lo, hi, *, rho, exit_tol, max_iters, eps_abs=1e-6, eps_rel=1e-6, max_pdas_iters=30,
+                   alm_weight=100.0, alm_growth=10.0, alm_weight_max=None, max_alm_iters=50, act=None, mu=None, x=None, z=None,
+                   y=None, lam=None, soft_weight=None, soft_cap=None):
+        """The box QP of box_qp with hard bounds on states and controls, by the method of multipliers over
+        box_qp_pdas(line_search=True) (gato_box_qp_alm).  Every variable off x_0 with a finite bound and
+        no positive soft_weight gets a multiplier (start: mu [B N], None: 0) and the penalty weight w (start: alm_weight); each
+        outer step is one line-search iteration on the bounds shifted by -mu / w, from the act the step before ended on (start:
+        act, None: nothing active), then mu <- its force y, and w <- alm_growth w where the violation did not fall below a
+        quarter of the step before (while w < alm_weight_max; None: 1e8 in float64, 1e5 in float32).  A variable with
+        soft_weight > 0 stays the soft bound of box_qp_pdas (soft_cap: its cap).  Returns a BoxQPResult: status CONVERGED (x; z =
+        x clipped on the hard variables; y; lam; res_* written) where the violation is within eps_abs + eps_rel |x|_inf, MAX_ITERS
+        after max_alm_iters steps (res_prim = the last violation; an infeasible box ends so) or where an inner iteration did not
+        converge, NONFINITE; iters the reduced solves of all steps, outer the steps, weight the last step's w; act the accepted
+        act.  The optional output tensors keep what they held for a system that did not converge.  Blocking.  Raises ValueError
+        for bad bounds, weights, caps or parameters and for a start act the iteration cannot take."""
+        if soft_cap is not None and soft_weight is None:
+            raise ValueError("box_qp_alm: soft_cap needs soft_weight (a cap is read only where the weight is positive)")
+        if alm_weight_max is None:
+            alm_weight_max = max(ALM_WEIGHT_MAX[self.np_dtype], float(alm_weight))
+        B, N, sk = self.batch, self.N, self.sizes["sk"]
+        dev = f"cuda:{self.device}"
+        zeros = lambda n: torch.zeros(n, dtype=self.dtype, device=dev)
+        x = zeros(B * N) if x is None else x
+        z = zeros(B * N) if z is None else z
+        y = zeros(B * N) if y is None else y
+        lam = zeros(B * sk) if lam is None else lam
+        if act is None:
+            act = torch.zeros(B * N, dtype=torch.int8, device=dev)
+        else:
+            self._check_vecs("box_qp_alm", act=act)
+            act = act.detach().reshape(-1).clone()
+        own = dict(Gb=Gb, Cb=Cb, g=g, c=c, lo=lo, hi=hi, x=x, z=z, y=y, lam=lam)
+        own.update({k: v for k, v in (("soft_weight", soft_weight), ("soft_cap", soft_cap), ("mu", mu)) if v is not None})
+        self._check_vecs("box_qp_alm", **own)
+        iters = torch.zeros(B, dtype=torch.int32, device=dev)
+        outer = torch.zeros(B, dtype=torch.int32, device=dev)
+        weight = torch.zeros(B, dtype=torch.float64, device=dev)
+        status = self.new(B, torch.int32)
+        res = torch.zeros(2 * B, dtype=torch.float64, device=dev)
+        p = self._qp_params(rho, exit_tol, max_iters, eps_abs, eps_rel)
+        rc = _lib.lib().gato_box_qp_alm(self._h, _ptr(Gb), _ptr(Cb), _ptr(g), _ptr(c), _ptr(lo), _ptr(hi), _ptr(soft_weight),
+                                        _ptr(soft_cap), _ptr(act), ct.byref(p), int(max_pdas_iters), float(alm_weight),
+                                        float(alm_growth), float(alm_weight_max), int(max_alm_iters), _ptr(mu), _ptr(x), _ptr(z),
+                                        _ptr(y), _ptr(lam), _ptr(iters), _ptr(status), _ptr(res), _ptr(outer), _ptr(weight),
+                                        self._stream())
+        msg = _lib.lib().gato_last_error().decode() if rc != 0 else ""
+        if "BAD_BOUNDS" in msg or "BAD_ACTIVE" in msg:
+            st = status.cpu()
+            bad = ((st == _lib.QP_BAD_BOUNDS) | (st == _lib.QP_BAD_ACTIVE)).nonzero().flatten().tolist()
+            raise ValueError(f"box_qp_alm: systems {bad}: " + msg)
+        _lib.check(rc)
+        res = res.view(B, 2)
+        return BoxQPResult(x, z, y, lam, iters, status, res[:, 0], res[:, 1], None, act, None, outer, weight)
+
+    def box_qp_alm_update(self, x, y, lam, mu, w, v_prev, lo, hi, *, eps_abs=1e-6, eps_rel=1e-6, alm_growth=10.0, alm_weight_max=1e8,
+                          last=False, soft_weight=None, lo2=None, hi2=None, w2=None, z=None):
+        """The update and the decision of one outer step of box_qp_alm alone (gato_box_qp_alm_update), on converged inner points x,
+        y [B N], lam [B S K] with the multipliers mu [B N] (updated in place), the weights w [B] and the violations of the step
+        before v_prev [B] (float64; inf: the first step).  -> dict v, xinf [B] (float64), dec [B] (int32, _lib.ALM_*), mu, and
+        lo2, hi2, w2 [B N] - the next inner bounds and weights, written on the ALM variables of a system that goes on - and z [B N],
+        written for an accepted system (the four may be given; new ones start as NaN).  soft_weight [B N]: the variables with a
+        positive weight are soft bounds, not ALM variables (caps play no part in the update).  Asynchronous."""
+        B, N = self.batch, self.N
+        dev = f"cuda:{self.device}"
+        nans = lambda: torch.full((B * N,), float("nan"), dtype=self.dtype, device=dev)
+        lo2, hi2, w2, z = (nans() if t is None else t for t in (lo2, hi2, w2, z))
+        own = dict(x=x, y=y, lam=lam, mu=mu, lo=lo, hi=hi, lo2=lo2, hi2=hi2, w2=w2, z=z)
+        if soft_weight is not None:
+            own["soft_weight"] = soft_weight
+        self._check_vecs("box_qp_alm_update", **own)
+        for name, t in (("w", w), ("v_prev", v_prev)):
+            if not isinstance(t, torch.Tensor) or t.numel() != B or t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous():
+                raise ValueError(f"box_qp_alm_update: {name} must be a contiguous float64 CUDA tensor of {B} entries")
+        v = torch.zeros(B, dtype=torch.float64, device=dev)
+        xinf = torch.zeros(B, dtype=torch.float64, device=dev)
+        dec = torch.zeros(B, dtype=torch.int32, device=dev)
+        _lib.check(_lib.lib().gato_box_qp_alm_update(self._h, _ptr(x), _ptr(y), _ptr(lam), _ptr(mu), _ptr(w), _ptr(v_prev), _ptr(lo),
+                                                     _ptr(hi), _ptr(soft_weight), float(eps_abs), float(eps_rel),
+                                                     float(alm_growth), float(alm_weight_max), int(bool(last)), _ptr(v), _ptr(xinf),
+                                                     _ptr(dec), _ptr(lo2), _ptr(hi2), _ptr(w2), _ptr(z), self._stream()))
+        return dict(v=v, xinf=xinf, dec=dec, mu=mu, lo2=lo2, hi2=hi2, w2=w2, z=z)
 
     def _bound_grads(self, entry, what, Gb, Cb, act, soft, xbar, a, beta, **bars):
         """The body of the two bound-gradient methods: allocates the outputs bars (by name) that are None, checks every

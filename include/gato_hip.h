@@ -508,6 +508,42 @@ int gato_box_qp_line_search(gato_solver *s, const void *d_G_blocks, const void *
                             const void *d_soft_w, const void *d_soft_cap, double rho, const void *d_xc, const void *d_xplus,
                             double *d_alpha, double *d_slope, void *d_x, void *stream);
 
+/* ---- hard bounds by an augmented-Lagrangian outer loop (new) --------------------------------------------
+ * The box QP of gato_box_qp_solve with HARD bounds on states and controls, by the method of multipliers over
+ * gato_box_qp_pdas_ls.  An ALM variable is one off x_0 with a finite bound and no weight (d_soft_w NULL or w_i = 0); a variable
+ * with w_i > 0 stays the soft bound of gato_box_qp_pdas_huber (its weight, its cap, no multiplier).  Per system: a multiplier
+ * mu [N] (0, or d_mu0), a weight w (alm_weight) and an act (d_act: in the start act, out the accepted one).  Outer step k = 1 ..
+ * max_alm_iters: the inner run is gato_box_qp_pdas_ls's loop, launch for launch, on the bounds lo - mu / w, hi - mu / w with
+ * weight w and no cap on the ALM variables (the caller's elsewhere), from the act the step before ended on, at most
+ * max_pdas_iters solves.  An inner run that ends MAX_ITERS or NONFINITE ends the system with that status and nothing else
+ * written.  On its converged point: v = max over the ALM variables of dist(x_i, [lo_i, hi_i]), mu <- y on them, and the point is
+ * accepted iff v <= eps_abs + eps_rel |x|_inf: d_x; d_z = clip(x, lo, hi) on the ALM variables; d_y (mu on them, the soft force
+ * elsewhere); d_lambda; d_res = {max(v, |C x - c|_inf), the inner run's dual residual}; d_status CONVERGED; d_iters = the reduced
+ * solves of all steps; d_outer = k; d_weight = w.  Otherwise w <- alm_growth w where v > v_prev / 4 and w < alm_weight_max (never
+ * after the first step).  After max_alm_iters steps: MAX_ITERS with d_res[0] = the last v, d_iters, d_outer and d_weight - an
+ * infeasible box ends so.  d_soft_w, d_soft_cap, d_mu0, d_outer, d_weight may be NULL.  Systems the outer loop froze keep running
+ * in the batch's inner runs; nothing of theirs is written again and every system has the bits of its solo run.  Blocking; one
+ * host read per outer step beyond the inner loop's.  GATO_EINVAL as gato_box_qp_pdas_ls, and (d_status = GATO_QP_BAD_BOUNDS) for
+ * an alm_weight that is not finite and positive, alm_growth <= 1 or alm_weight_max < alm_weight.  After a start act the first
+ * inner run refuses d_status holds its marks; after an error at a later step (GATO_EHIP, GATO_ETIMEOUT) d_status is -1 on the
+ * systems that were still running, their outputs are not written, and the frozen systems keep theirs. */
+int gato_box_qp_alm(gato_solver *s, const void *d_G_blocks, const void *d_C_blocks, const void *d_g, const void *d_c,
+                    const void *d_lo, const void *d_hi, const void *d_soft_w, const void *d_soft_cap, signed char *d_act,
+                    const gato_box_qp_params *p, int max_pdas_iters, double alm_weight, double alm_growth, double alm_weight_max,
+                    int max_alm_iters, const void *d_mu0, void *d_x, void *d_z, void *d_y, void *d_lambda, int *d_iters,
+                    int *d_status, double *d_res /* [B][2] */, int *d_outer, double *d_weight, void *stream);
+/* The update and the decision of one outer step alone, two launches, on given converged inner points d_x, d_y [B][N], d_lambda
+ * [B][S*K] with the multipliers d_mu [B][N] (in, out), the weights d_w [B] and the violations of the step before d_v_prev [B]
+ * (doubles; +inf: the first step): d_v, d_xinf [B] = v and |x|_inf, d_dec [B] = the decision (0 accept, 1 the weight grows, 2 it
+ * stays, 3 the last step; 4, an inner run that did not converge, does not occur here), and for a system that goes on d_lo2, d_hi2, d_w2 [B][N] = the next inner bounds and weights on its ALM
+ * variables (other entries are not written); d_z [B][N] is written for an accepted system.  d_soft_w [B][N] (may be NULL) names
+ * the soft variables, which are no ALM variables; caps are not read.  Asynchronous. */
+int gato_box_qp_alm_update(gato_solver *s, const void *d_x, const void *d_y, const void *d_lambda, void *d_mu, const double *d_w,
+                           const double *d_v_prev, const void *d_lo, const void *d_hi, const void *d_soft_w,
+                           double eps_abs, double eps_rel, double alm_growth, double alm_weight_max,
+                           int last, double *d_v, double *d_xinf, int *d_dec, void *d_lo2, void *d_hi2, void *d_w2, void *d_z,
+                           void *stream);
+
 /* ---- forward-mode sensitivities (new): the right-hand side of the tangent system, one launch --------
  * For R directions per system, from the returned point (d_x [B][N], d_lambda [B][S*K]) and the input tangents (a dot):
  *     t_g = g. - G. x - C.^T lambda,   t_c = c. - C. x            (C's identity blocks carry no tangent; rho drops out)
