@@ -181,21 +181,14 @@ __global__ __launch_bounds__(WAVE) void alm_decide_kernel(AlmArgs a, int it, int
 template <typename T, int S, int C>
 int launch_alm_check(const Dims &d, const AlmArgs &a, hipStream_t st)
 {
-    if (d.B < 1 || d.B > 65535) { set_error("alm_check: B = %d", d.B); return GATO_EINVAL; }
-    hipLaunchKernelGGL((alm_check_kernel<T, S, C>), dim3(knot_grid(d.K), d.B), dim3(WAVE), 0, st, a, d.K, d.B, batch_stride(d));
-    GATO_HIP_CHECK(hipGetLastError());
-    return GATO_OK;
+    return launch_per_knot("alm_check", alm_check_kernel<T, S, C>, d, st, a, d.K, d.B, batch_stride(d));
 }
 
 template <typename T, int S, int C>
 int launch_alm_update(const Dims &d, const AlmArgs &a, int it, int last, hipStream_t st)
 {
-    if (d.B < 1 || d.B > 65535) { set_error("alm_update: B = %d", d.B); return GATO_EINVAL; }
-    hipLaunchKernelGGL((alm_update_kernel<T, S, C>), dim3(knot_grid(d.K), d.B), dim3(WAVE), 0, st, a, it, d.K, batch_stride(d));
-    GATO_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL((alm_decide_kernel<T, S, C>), dim3(knot_grid(d.K), d.B), dim3(WAVE), 0, st, a, it, last, d.K, batch_stride(d));
-    GATO_HIP_CHECK(hipGetLastError());
-    return GATO_OK;
+    const int rc = launch_per_knot("alm_update", alm_update_kernel<T, S, C>, d, st, a, it, d.K, batch_stride(d));
+    return rc ? rc : launch_per_knot("alm_update", alm_decide_kernel<T, S, C>, d, st, a, it, last, d.K, batch_stride(d));
 }
 
 #define X(S_, C_)                                                                                     \

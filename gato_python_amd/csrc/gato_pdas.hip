@@ -166,34 +166,21 @@ __global__ __launch_bounds__(WAVE) void pdas_decide_kernel(PdasArgs a, int it, i
 template <typename T, int S, int C>
 int launch_pdas_check(const Dims &d, const PdasArgs &a, hipStream_t st)
 {
-    if (d.B < 1 || d.B > 65535) { set_error("pdas_check: B = %d", d.B); return GATO_EINVAL; }
-    const int form = bounds_form(a.p.w, a.p.cap);
-    const auto kernel = form == BOUNDS_CAPPED ? pdas_check_kernel<T, S, C, BOUNDS_CAPPED>
-                        : form == BOUNDS_SOFT ? pdas_check_kernel<T, S, C, BOUNDS_SOFT> : pdas_check_kernel<T, S, C, BOUNDS_HARD>;
-    hipLaunchKernelGGL(kernel, dim3(knot_grid(d.K), d.B), dim3(WAVE), 0, st, a, d.K, d.B, batch_stride(d));
-    GATO_HIP_CHECK(hipGetLastError());
-    return GATO_OK;
+    return launch_per_knot("pdas_check", GATO_BOUNDS_KERNEL(pdas_check_kernel, bounds_form(a.p.w, a.p.cap)), d, st, a, d.K, d.B,
+                           batch_stride(d));
 }
 
 template <typename T, int S, int C>
 int launch_pdas_step(const Dims &d, const PdasArgs &a, int it, hipStream_t st)
 {
-    if (d.B < 1 || d.B > 65535) { set_error("pdas_step: B = %d", d.B); return GATO_EINVAL; }
-    const int form = bounds_form(a.p.w, a.p.cap);
-    const auto kernel = form == BOUNDS_CAPPED ? pdas_step_kernel<T, S, C, BOUNDS_CAPPED>
-                        : form == BOUNDS_SOFT ? pdas_step_kernel<T, S, C, BOUNDS_SOFT> : pdas_step_kernel<T, S, C, BOUNDS_HARD>;
-    hipLaunchKernelGGL(kernel, dim3(knot_grid(d.K), d.B), dim3(WAVE), 0, st, a, it, d.K, batch_stride(d));
-    GATO_HIP_CHECK(hipGetLastError());
-    return GATO_OK;
+    return launch_per_knot("pdas_step", GATO_BOUNDS_KERNEL(pdas_step_kernel, bounds_form(a.p.w, a.p.cap)), d, st, a, it, d.K,
+                           batch_stride(d));
 }
 
 template <typename T, int S, int C>
 int launch_pdas_decide(const Dims &d, const PdasArgs &a, int it, int last, hipStream_t st)
 {
-    if (d.B < 1 || d.B > 65535) { set_error("pdas_decide: B = %d", d.B); return GATO_EINVAL; }
-    hipLaunchKernelGGL((pdas_decide_kernel<T, S, C>), dim3(knot_grid(d.K), d.B), dim3(WAVE), 0, st, a, it, last, d.K, batch_stride(d));
-    GATO_HIP_CHECK(hipGetLastError());
-    return GATO_OK;
+    return launch_per_knot("pdas_decide", pdas_decide_kernel<T, S, C>, d, st, a, it, last, d.K, batch_stride(d));
 }
 
 #define X(S_, C_)                                                                                        \

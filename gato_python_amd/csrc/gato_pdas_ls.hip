@@ -228,10 +228,7 @@ __global__ __launch_bounds__(LS_THREADS) void ls_system_kernel(LineSearchArgs a,
 template <typename T, int S, int C>
 int launch_ls_scope(const Dims &d, const LineSearchArgs &a, hipStream_t st)
 {
-    if (d.B < 1 || d.B > 65535) { set_error("ls_scope: B = %d", d.B); return GATO_EINVAL; }
-    hipLaunchKernelGGL((ls_scope_kernel<T, S, C>), dim3(knot_grid(d.K), d.B), dim3(WAVE), 0, st, a, d.K, batch_stride(d));
-    GATO_HIP_CHECK(hipGetLastError());
-    return GATO_OK;
+    return launch_per_knot("ls_scope", ls_scope_kernel<T, S, C>, d, st, a, d.K, batch_stride(d));
 }
 
 template <typename T, int S, int C>
@@ -239,8 +236,8 @@ int launch_line_search(const Dims &d, const LineSearchArgs &a, hipStream_t st)
 {
     if (d.B < 1 || d.B > 65535) { set_error("line_search: B = %d", d.B); return GATO_EINVAL; }
     if (a.it > 1) {                                                     // the first solve of a call takes the full step
-        hipLaunchKernelGGL((ls_knot_kernel<T, S, C>), dim3(knot_grid(d.K), d.B), dim3(WAVE), 0, st, a, d.K, batch_stride(d));
-        GATO_HIP_CHECK(hipGetLastError());
+        const int rc = launch_per_knot("line_search", ls_knot_kernel<T, S, C>, d, st, a, d.K, batch_stride(d));
+        if (rc) return rc;
     }
     hipLaunchKernelGGL((ls_system_kernel<T, S, C>), dim3(d.B), dim3(LS_THREADS), 0, st, a, d.K, batch_stride(d));
     GATO_HIP_CHECK(hipGetLastError());

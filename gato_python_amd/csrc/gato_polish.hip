@@ -276,47 +276,31 @@ __global__ __launch_bounds__(WAVE) void qp_bound_grad_kernel(BoundGradArgs q, in
 template <typename T, int S, int C>
 int launch_qp_active(const Dims &d, const void *z, const void *y, const void *lo, const void *hi, signed char *act, hipStream_t st)
 {
-    if (d.B < 1 || d.B > 65535) { set_error("qp_active: B = %d", d.B); return GATO_EINVAL; }
-    hipLaunchKernelGGL((qp_active_kernel<T, S, C>), dim3(knot_grid(d.K), d.B), dim3(WAVE), 0, st, (const T *)z, (const T *)y,
-                       (const T *)lo, (const T *)hi, act, d.K, batch_stride(d));
-    GATO_HIP_CHECK(hipGetLastError());
-    return GATO_OK;
+    return launch_per_knot("qp_active", qp_active_kernel<T, S, C>, d, st, (const T *)z, (const T *)y, (const T *)lo, (const T *)hi,
+                           act, d.K, batch_stride(d));
 }
 
 template <typename T, int S, int C>
 int launch_polish_prepare(const Dims &d, const PolishArgs &a, hipStream_t st)
 {
-    if (d.B < 1 || d.B > 65535) { set_error("polish_prepare: B = %d", d.B); return GATO_EINVAL; }
-    const int form = bounds_form(a.w, a.cap);
-    const auto kernel = form == BOUNDS_CAPPED ? polish_prepare_kernel<T, S, C, BOUNDS_CAPPED>
-                        : form == BOUNDS_SOFT ? polish_prepare_kernel<T, S, C, BOUNDS_SOFT> : polish_prepare_kernel<T, S, C, BOUNDS_HARD>;
-    hipLaunchKernelGGL(kernel, dim3(knot_grid(d.K), d.B), dim3(WAVE), 0, st, a, d.K, batch_stride(d));
-    GATO_HIP_CHECK(hipGetLastError());
-    return GATO_OK;
+    return launch_per_knot("polish_prepare", GATO_BOUNDS_KERNEL(polish_prepare_kernel, bounds_form(a.w, a.cap)), d, st, a, d.K,
+                           batch_stride(d));
 }
 
 template <typename T, int S, int C>
 int launch_polish_finish(const Dims &d, const PolishArgs &a, hipStream_t st)
 {
-    if (d.B < 1 || d.B > 65535) { set_error("polish_finish: B = %d", d.B); return GATO_EINVAL; }
-    hipLaunchKernelGGL((polish_finish_kernel<T, S, C>), dim3(knot_grid(d.K), d.B), dim3(WAVE), 0, st, a, d.K, batch_stride(d));
-    GATO_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL((polish_writeback_kernel<T, S, C>), dim3(knot_grid(d.K), d.B), dim3(WAVE), 0, st, a, d.K, batch_stride(d));
-    GATO_HIP_CHECK(hipGetLastError());
-    return GATO_OK;
+    const int rc = launch_per_knot("polish_finish", polish_finish_kernel<T, S, C>, d, st, a, d.K, batch_stride(d));
+    return rc ? rc : launch_per_knot("polish_finish", polish_writeback_kernel<T, S, C>, d, st, a, d.K, batch_stride(d));
 }
 
 template <typename T, int S, int C>
 int launch_qp_bound_grad(const Dims &d, const BoundGradArgs &a, hipStream_t st)
 {
-    if (d.B < 1 || d.B > 65535) { set_error("qp_bound_grad: B = %d", d.B); return GATO_EINVAL; }
     // with w_bar alone (the soft entry without weights) the W kernel finds no weight at run time and writes w_bar = 0
     // with cap_bar alone (the capped entry without caps) the capped kernel finds no cap at run time and writes cap_bar = 0
-    const auto kernel = a.cap || a.cap_bar ? qp_bound_grad_kernel<T, S, C, BOUNDS_CAPPED>
-                        : a.w || a.w_bar ? qp_bound_grad_kernel<T, S, C, BOUNDS_SOFT> : qp_bound_grad_kernel<T, S, C, BOUNDS_HARD>;
-    hipLaunchKernelGGL(kernel, dim3(knot_grid(d.K), d.B), dim3(WAVE), 0, st, a, d.K, batch_stride(d));
-    GATO_HIP_CHECK(hipGetLastError());
-    return GATO_OK;
+    const int form = a.cap || a.cap_bar ? BOUNDS_CAPPED : (a.w || a.w_bar ? BOUNDS_SOFT : BOUNDS_HARD);
+    return launch_per_knot("qp_bound_grad", GATO_BOUNDS_KERNEL(qp_bound_grad_kernel, form), d, st, a, d.K, batch_stride(d));
 }
 
 #define X(S_, C_)                                                                                                            \

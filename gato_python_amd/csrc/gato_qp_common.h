@@ -270,5 +270,23 @@ __device__ __forceinline__ void write_point(const PolishArgs &a, size_t sys, con
     }
 }
 
+// ---- host side: what the units' launch wrappers share --------------------------------------------------------------------------
+// The one-wave-per-knot launch of `kernel` with args: knot_grid(d.K) workgroups of one wave for each of the d.B systems (the
+// grid's y, hence B <= 65535).  name: the wrapper's, in the refusal of a B out of range.
+constexpr int KNOT_THREADS = 64;            // one wave: the WAVE of every unit, the __launch_bounds__ of these kernels
+template <typename... P, typename... A>
+inline int launch_per_knot(const char *name, void (*kernel)(P...), const Dims &d, hipStream_t st, const A &...args)
+{
+    if (d.B < 1 || d.B > 65535) { set_error("%s: B = %d", name, d.B); return GATO_EINVAL; }
+    hipLaunchKernelGGL(kernel, dim3(knot_grid(d.K), d.B), dim3(KNOT_THREADS), 0, st, args...);
+    GATO_HIP_CHECK(hipGetLastError());
+    return GATO_OK;
+}
+
+// The instantiation of kernel template k<T, S, C, W> for a form of the bounds (BOUNDS_*).  For the units' launch wrappers only:
+// it names their template parameters T, S and C, and stays defined to the end of the unit.
+#define GATO_BOUNDS_KERNEL(k, form) \
+    ((form) == BOUNDS_CAPPED ? k<T, S, C, BOUNDS_CAPPED> : (form) == BOUNDS_SOFT ? k<T, S, C, BOUNDS_SOFT> : k<T, S, C, BOUNDS_HARD>)
+
 }  // namespace
 }  // namespace gato

@@ -1,5 +1,7 @@
-// Box-constrained QP (ADMM over the re-solve), its polish, the active-set iteration and bound gradients: the host side of
-// gato_qp.hip / gato_polish.hip / gato_pdas.hip.
+// Box-constrained QP (ADMM over the re-solve), its polish, the active-set iteration with its line search, the augmented-
+// Lagrangian outer loop, bound gradients and tangent right-hand sides: the host side of gato_qp.hip / gato_polish.hip /
+// gato_pdas.hip / gato_pdas_ls.hip / gato_alm.hip / gato_tangent.hip.  The active-set entries each fill a BoxProblem and share
+// pdas_loop; the bound-gradient entries share bound_grad.
 #include <cmath>
 #include <initializer_list>
 
@@ -36,6 +38,39 @@ static int check_not_capturing(const char *who, const char *reads, hipStream_t s
     if (!stream_is_capturing(st)) return GATO_OK;
     set_error("%s: the stream is being captured; %s on the host and cannot be captured", who, reads);
     return GATO_EINVAL;
+}
+
+// The solver's dimensions as the box-QP kernels take them: every knot, no shared right-hand sides.
+static Dims kernel_dims(const gato_solver *s)
+{
+    Dims d = s->d;
+    d.k_lo = d.k_hi = 0; d.rhs = 0;
+    return d;
+}
+
+// The start of a call: the work area zeroed from w + from to w + end (maxima, counts, counters), then the caller's status (the
+// polish: its codes) -1 = running (undecided).
+static int start_call(char *w, size_t from, size_t end, int *d_status, size_t B, hipStream_t st)
+{
+    GATO_HIP_CHECK(hipMemsetAsync(w + from, 0, end - from, st));
+    GATO_HIP_CHECK(hipMemsetAsync(d_status, 0xff, B * sizeof(int), st));
+    return GATO_OK;
+}
+
+// The systems still live (ctr[0]) to *live, once everything queued on st has run: what the loops wait for between rounds.
+static int read_live(const char *who, const int *ctr, int *live, hipStream_t st)
+{
+    hipError_t he = hipMemcpyAsync(live, ctr, sizeof(int), hipMemcpyDeviceToHost, st);
+    if (he == hipSuccess) he = hipStreamSynchronize(st);
+    if (he == hipSuccess) return GATO_OK;
+    set_error("%s: reading the live count failed: %s", who, hipGetErrorString(he));
+    return GATO_EHIP;
+}
+
+// What an entry that takes soft weights (and caps) adds to its pointer text: they may be NULL.
+static const char *soft_note(bool takes_w, bool takes_cap)
+{
+    return takes_cap ? ", d_soft_w for no soft bound, d_soft_cap for no cap" : (takes_w ? ", d_soft_w for no soft bound" : "");
 }
 
 // The parameters a reduced solve reads (polish, active-set iteration): finite and in range.
@@ -87,8 +122,7 @@ extern "C" int gato_box_qp_solve(gato_solver *s, const void *d_G_blocks, const v
     char *w = s->qp_ws;
     int *ctr = (int *)(w + o_ctr);
     s->qp_pcg_total = (int *)(w + o_tot);
-    GATO_HIP_CHECK(hipMemsetAsync(w + o_sl, 0, o_ctr + 256 - o_sl, st));              // slots, PCG totals, counters
-    GATO_HIP_CHECK(hipMemsetAsync(d_status, 0xff, B * sizeof(int), st));             // -1: running
+    if ((rc = start_call(w, o_sl, bytes, d_status, B, st))) return rc;                 // slots, PCG totals, counters
     if (p->warm) GATO_HIP_CHECK(hipMemcpyAsync(w + o_lt, d_lambda, B * d.sk() * e, hipMemcpyDeviceToDevice, st));
     QpArgs a;
     memset(&a, 0, sizeof(a));
@@ -123,12 +157,7 @@ extern "C" int gato_box_qp_solve(gato_solver *s, const void *d_G_blocks, const v
             break;
         }
         if ((it + 1) % p->check_every == 0) {               // systems still live, after the test of iterate it
-            hipError_t he = hipMemcpyAsync(h, ctr, sizeof(int), hipMemcpyDeviceToHost, st);
-            if (he == hipSuccess) he = hipStreamSynchronize(st);
-            if (he != hipSuccess) {
-                set_error("box_qp_solve: reading the live count failed: %s", hipGetErrorString(he));
-                return GATO_EHIP;
-            }
+            if ((rc = read_live("box_qp_solve", ctr, h, st))) return rc;
             if (h[0] == 0) break;
         }
         if ((rc = solve_rhs(s, o, 1, w + o_gt, d_c, p->exit_tol, p->max_iters, w + o_lt, w + o_dz, rhs_iters(s), st))) return rc;
@@ -143,9 +172,7 @@ extern "C" int gato_box_qp_active_set(gato_solver *s, const void *d_z, const voi
 {
     if (!solver_usable(s, "box_qp_active_set", "QP solves")) return GATO_EINVAL;
     if (!d_z || !d_y || !d_lo || !d_hi || !d_act) { set_error("box_qp_active_set: every pointer is required"); return GATO_EINVAL; }
-    Dims d = s->d;
-    d.k_lo = d.k_hi = 0; d.rhs = 0;
-    return s->ops->qp_active(d, d_z, d_y, d_lo, d_hi, d_act, (hipStream_t)stream);
+    return s->ops->qp_active(kernel_dims(s), d_z, d_y, d_lo, d_hi, d_act, (hipStream_t)stream);
 }
 
 // The work area of the polish and of the active-set iteration (pol_ws), as offsets: the reduced system's right-hand side, the
@@ -177,6 +204,23 @@ static PolishWs polish_ws(const Dims &d, size_t e, bool pdas, bool ls = false)
     return o;
 }
 
+// The problem of an active-set call, as its extern "C" entry (or gato_box_qp_alm, from its work area) fills it for pdas_loop.
+struct BoxPoint {
+    void *x, *z, *y, *lam;                  // [B][N], lam [B][S K]
+    int *iters, *status;                    // [B]
+    double *res;                            // [B][2]
+};
+struct BoxProblem {
+    const char *who;                        // names the entry in errors
+    bool takes_w, takes_cap;                // the entry has d_soft_w / d_soft_cap arguments: its texts speak of them
+    const void *G, *C, *g, *c, *lo, *hi;    // the caller's blocks (G without rho, C raw) and vectors
+    const void *w, *cap;                    // soft weights (NULL: all hard, section 3.10), caps of their forces (NULL: none, 3.11)
+    signed char *act;                       // in: the start act; the iteration writes the final one
+    BoxPoint pt;
+};
+// The exact line search of section 3.12, asked of pdas_loop: d_alpha [B][max_pdas_iters] (may be NULL) receives the step lengths.
+struct LineSearch { double *d_alpha; };
+
 // The part of PolishArgs both entries fill alike: the solver's buffers, the work area at w and the parameters.
 static PolishArgs polish_args(const gato_solver *s, char *w, const PolishWs &o, const gato_box_qp_params *p)
 {
@@ -205,14 +249,12 @@ extern "C" int gato_box_qp_polish(gato_solver *s, const void *d_G_blocks, const 
     hipStream_t st = (hipStream_t)stream;
     if (check_not_capturing("box_qp_polish", "the polish reads the active-set check", st)) return GATO_EINVAL;
     GATO_HIP_CHECK(hipSetDevice(s->device));
-    const size_t B = s->d.B;
     const PolishWs o = polish_ws(s->d, s->esz, false);
     int rc;
     if ((rc = grow_ws(&s->pol_ws, &s->pol_ws_bytes, o.bytes, st))) return rc;
     char *w = s->pol_ws;
     int *nbad = (int *)(w + o.ctr);
-    GATO_HIP_CHECK(hipMemsetAsync(w + o.sl, 0, o.bytes - o.sl, st));                 // slots, the BAD_ACTIVE count
-    GATO_HIP_CHECK(hipMemsetAsync(d_polish, 0xff, B * sizeof(int), st));             // -1 until decided
+    if ((rc = start_call(w, o.sl, o.bytes, d_polish, s->d.B, st))) return rc;         // slots, the BAD_ACTIVE count; -1 until decided
     PolishArgs a = polish_args(s, w, o, p);
     a.G = d_G_blocks; a.Cd = d_C_blocks; a.g = d_g; a.c = d_c; a.lo = d_lo; a.hi = d_hi; a.act = d_act; a.bad = nbad;
     a.x = d_x; a.z = d_z; a.y = d_y; a.lam = d_lambda; a.status = d_status; a.polish = d_polish; a.res = d_res;
@@ -241,47 +283,44 @@ extern "C" int gato_box_qp_polish(gato_solver *s, const void *d_G_blocks, const 
 
 // ---- primal-dual active-set iteration: the polish iterated (gato_pdas.hip, DESIGN.md sections 3.9, 3.10) ----------------
 // Per solve: add rho, the masked inversion and shifted right-hand side, the stage path of the whole solve (all as in the
-// polish), then the step and the decision and one read of the live count.  d_soft_w: the weights of soft bounds (NULL: all
-// hard), read by the check, the prepare and the step; d_soft_cap: the caps of their forces (section 3.11; NULL: none, and not
-// read without weights).  `who` names the entry in errors; soft: its texts speak of the weights (2: and of the caps).
-// ls: the exact line search of section 3.12 - the scope check after the check launch, and between the step and the decision of
-// every solve the two launches that move the iterate xc and take act' and its changed count from it; d_alpha [B][max_pdas_iters]
-// (may be NULL) receives the step lengths.
-static int pdas_loop(gato_solver *s, const char *who, int soft, const void *d_G_blocks, const void *d_C_blocks, const void *d_g,
-                     const void *d_c, const void *d_lo, const void *d_hi, const void *d_soft_w, const void *d_soft_cap,
-                     signed char *d_act,
-                     const gato_box_qp_params *p, int max_pdas_iters, void *d_x, void *d_z, void *d_y, void *d_lambda, int *d_iters,
-                     int *d_status, double *d_res, void *stream, bool ls = false, double *d_alpha = nullptr)
+// polish), then the step and the decision and one read of the live count.  b.w: the weights of soft bounds, read by the check,
+// the prepare and the step; b.cap: the caps of their forces (not read without weights).  The texts speak of weights and caps
+// where the entry takes them (b.takes_w, b.takes_cap), given or not.
+// ls (may be NULL): the exact line search of section 3.12 - the scope check after the check launch, and between the step and the
+// decision of every solve the two launches that move the iterate xc and take act' and its changed count from it.
+static int pdas_loop(gato_solver *s, const BoxProblem &b, const gato_box_qp_params *p, int max_pdas_iters, hipStream_t st,
+                     const LineSearch *ls)
 {
-    if (check_pointers(s, who, p, d_C_blocks, {d_G_blocks, d_g, d_c, d_lo, d_hi, d_act, d_x, d_z, d_y, d_lambda, d_iters, d_status, d_res},
-                       soft == 2 ? ", d_soft_w for no soft bound, d_soft_cap for no cap" : (soft ? ", d_soft_w for no soft bound" : "")))
+    const char *who = b.who;
+    const BoxPoint &pt = b.pt;
+    if (check_pointers(s, who, p, b.C, {b.G, b.g, b.c, b.lo, b.hi, b.act, pt.x, pt.z, pt.y, pt.lam, pt.iters, pt.status, pt.res},
+                       soft_note(b.takes_w, b.takes_cap)))
         return GATO_EINVAL;
     if (!reduced_params_ok(*p) || max_pdas_iters < 1) {
         set_error("%s: parameters out of range (want finite values, rho, eps_abs, eps_rel, exit_tol >= 0, max_iters, "
                   "max_pdas_iters >= 1)", who);
         return GATO_EINVAL;
     }
-    hipStream_t st = (hipStream_t)stream;
     if (check_not_capturing(who, "the loop reads the live count", st)) return GATO_EINVAL;
     GATO_HIP_CHECK(hipSetDevice(s->device));
     const size_t B = s->d.B;
-    const PolishWs o = polish_ws(s->d, s->esz, true, ls);
+    const PolishWs o = polish_ws(s->d, s->esz, true, ls != nullptr);
     int rc;
     if ((rc = grow_ws(&s->pol_ws, &s->pol_ws_bytes, o.bytes, st))) return rc;
     char *w = s->pol_ws;
     int *ctr = (int *)(w + o.ctr);
-    GATO_HIP_CHECK(hipMemsetAsync(w + o.sl, 0, o.bytes - o.sl, st));                 // both sets of maxima and counts, the counters
-    GATO_HIP_CHECK(hipMemsetAsync(d_status, 0xff, B * sizeof(int), st));             // -1: running
+    if ((rc = start_call(w, o.sl, o.bytes, pt.status, B, st))) return rc;             // both sets of maxima and counts, the counters
+    double *d_alpha = ls ? ls->d_alpha : nullptr;
     if (d_alpha) GATO_HIP_CHECK(hipMemsetAsync(d_alpha, 0, B * max_pdas_iters * sizeof(double), st));   // 0: no step taken
     PdasArgs a;
     memset(&a, 0, sizeof(a));
     PolishArgs &q = a.p;
     q = polish_args(s, w, o, p);
-    q.G = d_G_blocks; q.Cd = d_C_blocks; q.g = d_g; q.c = d_c; q.lo = d_lo; q.hi = d_hi; q.act = d_act; q.w = d_soft_w;
-    q.cap = d_soft_w ? d_soft_cap : nullptr;
-    q.x = d_x; q.z = d_z; q.y = d_y; q.lam = d_lambda; q.status = d_status; q.polish = (int *)(w + o.pol); q.res = d_res;
+    q.G = b.G; q.Cd = b.C; q.g = b.g; q.c = b.c; q.lo = b.lo; q.hi = b.hi; q.act = b.act; q.w = b.w;
+    q.cap = b.w ? b.cap : nullptr;
+    q.x = pt.x; q.z = pt.z; q.y = pt.y; q.lam = pt.lam; q.status = pt.status; q.polish = (int *)(w + o.pol); q.res = pt.res;
     q.bad = ctr + 3;
-    a.act = d_act; a.act2 = (signed char *)(w + o.a2); a.round = (int *)(w + o.rn); a.ctr = ctr; a.iters = d_iters;
+    a.act = b.act; a.act2 = (signed char *)(w + o.a2); a.round = (int *)(w + o.rn); a.ctr = ctr; a.iters = pt.iters;
     s->d.k_lo = s->d.k_hi = 0;
     s->as.valid = 0;
     s->lc.valid = 0;                        // G_dense and Ginv are rewritten: nothing earlier is left to recover
@@ -289,18 +328,18 @@ static int pdas_loop(gato_solver *s, const char *who, int soft, const void *d_G_
     LineSearchArgs la;
     memset(&la, 0, sizeof(la));
     if (ls) {
-        la.G = d_G_blocks; la.g = d_g; la.lo = d_lo; la.hi = d_hi; la.w = d_soft_w; la.cap = q.cap;
+        la.G = b.G; la.g = b.g; la.lo = b.lo; la.hi = b.hi; la.w = b.w; la.cap = q.cap;
         la.xc = la.xout = w + o.xc; la.xp = q.xp; la.part = (double *)(w + o.part); la.alpha_stride = max_pdas_iters;
-        la.status = la.status_out = d_status; la.slots = q.slots; la.act = d_act; la.act2 = a.act2; la.round = a.round;
+        la.status = la.status_out = pt.status; la.slots = q.slots; la.act = b.act; la.act2 = a.act2; la.round = a.round;
         la.bad = ctr + 4;
         la.rho = p->rho; la.eps_abs = p->eps_abs; la.eps_rel = p->eps_rel;
         if ((rc = s->ops->ls_scope(s->d, la, st))) return rc;
     }
     PcgOpts po = pcg_opts(*s);
     po.warm = 0;                            // every reduced solve is a cold start
-    const AsmInput in{2, nullptr, nullptr, d_G_blocks, nullptr, nullptr, nullptr, d_C_blocks, true};
+    const AsmInput in{2, nullptr, nullptr, b.G, nullptr, nullptr, nullptr, b.C, true};
     for (int it = 1; it <= max_pdas_iters; ++it) {
-        if ((rc = s->ops->add_rho(s->d, d_G_blocks, p->rho, s->G_dense, st))) return rc;
+        if ((rc = s->ops->add_rho(s->d, b.G, p->rho, s->G_dense, st))) return rc;
         if ((rc = s->ops->polish_prepare(s->d, q, st))) return rc;
         int h[5] = {0, 0, 0, 0, 0};         // ctr[3] is the polish's own count, ctr[4] the line search's scope check
         if (it == 1) {                      // the caller's bounds and start act; later acts are the device's own: valid
@@ -310,13 +349,15 @@ static int pdas_loop(gato_solver *s, const char *who, int soft, const void *d_G_
                 set_error("%s:%s%s%s; d_status marks the systems", who,
                           h[4] > 0 ? " a finite bound off x_0 has no weight: the line search takes soft bounds only, every variable "
                                      "with a finite bound needs w_i > 0 (BAD_BOUNDS)" : "",
-                          h[1] > 0 ? (soft == 2 ? " a bound is NaN, lo > hi, a weight is NaN, negative or infinite or a cap is NaN or "
-                                                  "negative (BAD_BOUNDS)"
-                                      : soft ? " a bound is NaN, lo > hi or a weight is NaN, negative or infinite (BAD_BOUNDS)"
-                                             : " a bound is NaN or lo > hi (BAD_BOUNDS)") : "",
-                          h[2] > 0 ? (soft == 2 ? " a start act is not -2 .. 2, names an infinite bound or a state of x_0, or is +-2 "
-                                                  "without a weight and a finite cap (BAD_ACTIVE)"
-                                                : " a start act is not -1, 0 or 1, names an infinite bound or a state of x_0 (BAD_ACTIVE)") : "");
+                          h[1] <= 0 ? ""
+                          : b.takes_cap ? " a bound is NaN, lo > hi, a weight is NaN, negative or infinite or a cap is NaN or negative "
+                                          "(BAD_BOUNDS)"
+                          : b.takes_w ? " a bound is NaN, lo > hi or a weight is NaN, negative or infinite (BAD_BOUNDS)"
+                                      : " a bound is NaN or lo > hi (BAD_BOUNDS)",
+                          h[2] <= 0 ? ""
+                          : b.takes_cap ? " a start act is not -2 .. 2, names an infinite bound or a state of x_0, or is +-2 without a "
+                                          "weight and a finite cap (BAD_ACTIVE)"
+                                        : " a start act is not -1, 0 or 1, names an infinite bound or a state of x_0 (BAD_ACTIVE)");
                 return GATO_EINVAL;
             }
         }
@@ -329,12 +370,7 @@ static int pdas_loop(gato_solver *s, const char *who, int soft, const void *d_G_
         }
         if ((rc = s->ops->pdas_decide(s->d, a, it, it == max_pdas_iters, st))) return rc;
         if (it == max_pdas_iters) break;    // every system still live froze in that decision
-        hipError_t he = hipMemcpyAsync(h, ctr, sizeof(int), hipMemcpyDeviceToHost, st);
-        if (he == hipSuccess) he = hipStreamSynchronize(st);
-        if (he != hipSuccess) {
-            set_error("%s: reading the live count failed: %s", who, hipGetErrorString(he));
-            return GATO_EHIP;
-        }
+        if ((rc = read_live(who, ctr, h, st))) return rc;
         if (h[0] == 0) break;
     }
     GATO_HIP_CHECK(hipStreamSynchronize(st));
@@ -346,8 +382,9 @@ extern "C" int gato_box_qp_pdas(gato_solver *s, const void *d_G_blocks, const vo
                                 int max_pdas_iters, void *d_x, void *d_z, void *d_y, void *d_lambda, int *d_iters, int *d_status,
                                 double *d_res, void *stream)
 {
-    return pdas_loop(s, "box_qp_pdas", 0, d_G_blocks, d_C_blocks, d_g, d_c, d_lo, d_hi, nullptr, nullptr, d_act, p, max_pdas_iters, d_x,
-                     d_z, d_y, d_lambda, d_iters, d_status, d_res, stream);
+    const BoxProblem b{"box_qp_pdas", false, false, d_G_blocks, d_C_blocks, d_g, d_c, d_lo, d_hi, nullptr, nullptr, d_act,
+                       {d_x, d_z, d_y, d_lambda, d_iters, d_status, d_res}};
+    return pdas_loop(s, b, p, max_pdas_iters, (hipStream_t)stream, nullptr);
 }
 
 // ---- soft bounds in the active-set iteration ------------------------------------------------------
@@ -356,8 +393,25 @@ extern "C" int gato_box_qp_pdas_soft(gato_solver *s, const void *d_G_blocks, con
                                      const gato_box_qp_params *p, int max_pdas_iters, void *d_x, void *d_z, void *d_y,
                                      void *d_lambda, int *d_iters, int *d_status, double *d_res, void *stream)
 {
-    return pdas_loop(s, "box_qp_pdas_soft", 1, d_G_blocks, d_C_blocks, d_g, d_c, d_lo, d_hi, d_soft_w, nullptr, d_act, p, max_pdas_iters,
-                     d_x, d_z, d_y, d_lambda, d_iters, d_status, d_res, stream);
+    const BoxProblem b{"box_qp_pdas_soft", true, false, d_G_blocks, d_C_blocks, d_g, d_c, d_lo, d_hi, d_soft_w, nullptr, d_act,
+                       {d_x, d_z, d_y, d_lambda, d_iters, d_status, d_res}};
+    return pdas_loop(s, b, p, max_pdas_iters, (hipStream_t)stream, nullptr);
+}
+
+// The three bound-gradient entries: the check of the pointers the entry takes (takes_w: lo, hi, x and w_bar too, takes_cap:
+// cap_bar too; a.w and a.cap may be NULL), then the launch.
+static int bound_grad(gato_solver *s, const char *who, bool takes_w, bool takes_cap, BoundGradArgs a, void *stream)
+{
+    if (!solver_usable(s, who, "gradients")) return GATO_EINVAL;
+    bool ok = a.G && (a.Cd || s->d.K <= 1) && a.act && a.xbar && a.adz && a.beta && a.lo_bar && a.hi_bar;
+    if (takes_w) ok = ok && a.lo && a.hi && a.x && a.w_bar;
+    if (takes_cap) ok = ok && a.cap_bar;
+    if (!ok) {
+        set_error("%s: every pointer is required (d_C_blocks may be NULL only for K = 1%s)", who, soft_note(takes_w, takes_cap));
+        return GATO_EINVAL;
+    }
+    if (!a.w) a.cap = nullptr;              // no cap is read without weights
+    return s->ops->qp_bound_grad(kernel_dims(s), a, (hipStream_t)stream);
 }
 
 extern "C" int gato_box_qp_soft_grad(gato_solver *s, const void *d_G_blocks, const void *d_C_blocks, const signed char *d_act,
@@ -365,34 +419,18 @@ extern "C" int gato_box_qp_soft_grad(gato_solver *s, const void *d_G_blocks, con
                                      const void *d_a, const void *d_beta, void *d_lo_bar, void *d_hi_bar, void *d_w_bar,
                                      void *stream)
 {
-    if (!solver_usable(s, "box_qp_soft_grad", "gradients")) return GATO_EINVAL;
-    if (!d_G_blocks || (!d_C_blocks && s->d.K > 1) || !d_act || !d_lo || !d_hi || !d_x || !d_xbar || !d_a || !d_beta || !d_lo_bar ||
-        !d_hi_bar || !d_w_bar) {
-        set_error("box_qp_soft_grad: every pointer is required (d_C_blocks may be NULL only for K = 1, d_soft_w for no soft bound)");
-        return GATO_EINVAL;
-    }
-    Dims d = s->d;
-    d.k_lo = d.k_hi = 0; d.rhs = 0;
-    const BoundGradArgs a{d_G_blocks, d_C_blocks, d_act, d_soft_w, d_lo, d_hi, d_x, d_xbar, d_a, d_beta, d_lo_bar, d_hi_bar, d_w_bar};
-    return s->ops->qp_bound_grad(d, a, (hipStream_t)stream);
+    return bound_grad(s, "box_qp_soft_grad", true, false,
+                      {d_G_blocks, d_C_blocks, d_act, d_soft_w, d_lo, d_hi, d_x, d_xbar, d_a, d_beta, d_lo_bar, d_hi_bar, d_w_bar}, stream);
 }
 
 extern "C" int gato_box_qp_bound_grad(gato_solver *s, const void *d_G_blocks, const void *d_C_blocks, const signed char *d_act,
                                       const void *d_xbar, const void *d_a, const void *d_beta, void *d_lo_bar, void *d_hi_bar,
                                       void *stream)
 {
-    if (!solver_usable(s, "box_qp_bound_grad", "gradients")) return GATO_EINVAL;
-    if (!d_G_blocks || (!d_C_blocks && s->d.K > 1) || !d_act || !d_xbar || !d_a || !d_beta || !d_lo_bar || !d_hi_bar) {
-        set_error("box_qp_bound_grad: every pointer is required (d_C_blocks may be NULL only for K = 1)");
-        return GATO_EINVAL;
-    }
-    Dims d = s->d;
-    d.k_lo = d.k_hi = 0; d.rhs = 0;
-    const BoundGradArgs a{d_G_blocks, d_C_blocks, d_act, nullptr, nullptr, nullptr, nullptr,      // no weights: no lo, hi, x
-                          d_xbar, d_a, d_beta, d_lo_bar, d_hi_bar, nullptr};
-    return s->ops->qp_bound_grad(d, a, (hipStream_t)stream);
+    return bound_grad(s, "box_qp_bound_grad", false, false,
+                      {d_G_blocks, d_C_blocks, d_act, nullptr, nullptr, nullptr, nullptr,      // no weights: no lo, hi, x
+                       d_xbar, d_a, d_beta, d_lo_bar, d_hi_bar, nullptr}, stream);
 }
-
 
 // ---- capped (Huber) soft bounds in the active-set iteration -------------------------------------------
 extern "C" int gato_box_qp_pdas_huber(gato_solver *s, const void *d_G_blocks, const void *d_C_blocks, const void *d_g,
@@ -401,8 +439,9 @@ extern "C" int gato_box_qp_pdas_huber(gato_solver *s, const void *d_G_blocks, co
                                       void *d_x, void *d_z, void *d_y, void *d_lambda, int *d_iters, int *d_status, double *d_res,
                                       void *stream)
 {
-    return pdas_loop(s, "box_qp_pdas_huber", 2, d_G_blocks, d_C_blocks, d_g, d_c, d_lo, d_hi, d_soft_w, d_soft_cap, d_act, p,
-                     max_pdas_iters, d_x, d_z, d_y, d_lambda, d_iters, d_status, d_res, stream);
+    const BoxProblem b{"box_qp_pdas_huber", true, true, d_G_blocks, d_C_blocks, d_g, d_c, d_lo, d_hi, d_soft_w, d_soft_cap, d_act,
+                       {d_x, d_z, d_y, d_lambda, d_iters, d_status, d_res}};
+    return pdas_loop(s, b, p, max_pdas_iters, (hipStream_t)stream, nullptr);
 }
 
 extern "C" int gato_box_qp_huber_grad(gato_solver *s, const void *d_G_blocks, const void *d_C_blocks, const signed char *d_act,
@@ -410,18 +449,9 @@ extern "C" int gato_box_qp_huber_grad(gato_solver *s, const void *d_G_blocks, co
                                       const void *d_x, const void *d_xbar, const void *d_a, const void *d_beta, void *d_lo_bar,
                                       void *d_hi_bar, void *d_w_bar, void *d_cap_bar, void *stream)
 {
-    if (!solver_usable(s, "box_qp_huber_grad", "gradients")) return GATO_EINVAL;
-    if (!d_G_blocks || (!d_C_blocks && s->d.K > 1) || !d_act || !d_lo || !d_hi || !d_x || !d_xbar || !d_a || !d_beta || !d_lo_bar ||
-        !d_hi_bar || !d_w_bar || !d_cap_bar) {
-        set_error("box_qp_huber_grad: every pointer is required (d_C_blocks may be NULL only for K = 1, d_soft_w for no soft bound, "
-                  "d_soft_cap for no cap)");
-        return GATO_EINVAL;
-    }
-    Dims d = s->d;
-    d.k_lo = d.k_hi = 0; d.rhs = 0;
-    const BoundGradArgs a{d_G_blocks, d_C_blocks, d_act, d_soft_w, d_lo, d_hi, d_x, d_xbar, d_a, d_beta, d_lo_bar, d_hi_bar, d_w_bar,
-                          d_soft_w ? d_soft_cap : nullptr, d_cap_bar};
-    return s->ops->qp_bound_grad(d, a, (hipStream_t)stream);
+    return bound_grad(s, "box_qp_huber_grad", true, true,
+                      {d_G_blocks, d_C_blocks, d_act, d_soft_w, d_lo, d_hi, d_x, d_xbar, d_a, d_beta, d_lo_bar, d_hi_bar, d_w_bar,
+                       d_soft_cap, d_cap_bar}, stream);
 }
 
 // ---- right-hand side of the tangent system (gato_tangent.hip) -------------------------------------------
@@ -439,14 +469,12 @@ extern "C" int gato_kkt_tangent_rhs(gato_solver *s, int R, const void *d_G_dot, 
         return GATO_EINVAL;
     }
     if (d_act && d_soft_w && (!d_lo || !d_hi)) { set_error("kkt_tangent_rhs: soft weights need d_lo and d_hi"); return GATO_EINVAL; }
-    Dims d = s->d;
-    d.k_lo = d.k_hi = 0; d.rhs = 0;
     // without an act nothing is active; without weights no cap and no tangent of a weight or a cap is read
     const bool soft = d_act && d_soft_w;
     const TangentArgs a{d_G_dot, d_C_dot, d_g_dot, d_c_dot, d_act ? d_lo_dot : nullptr, d_act ? d_hi_dot : nullptr,
                         soft ? d_w_dot : nullptr, soft ? d_m_dot : nullptr, d_x, d_lambda, d_G_blocks, d_C_blocks, d_act,
                         soft ? d_soft_w : nullptr, soft ? d_soft_cap : nullptr, d_lo, d_hi, d_tg, d_tc};
-    return s->ops->kkt_tangent_rhs(d, R, a, (hipStream_t)stream);
+    return s->ops->kkt_tangent_rhs(kernel_dims(s), R, a, (hipStream_t)stream);
 }
 
 // ---- exact line search of the soft active-set iteration (gato_pdas_ls.hip) -----------------------------
@@ -460,8 +488,10 @@ extern "C" int gato_box_qp_pdas_ls(gato_solver *s, const void *d_G_blocks, const
         set_error("box_qp_pdas_ls: d_soft_w is required (the line search takes soft bounds only; d_soft_cap and d_alpha may be NULL)");
         return GATO_EINVAL;
     }
-    return pdas_loop(s, "box_qp_pdas_ls", 2, d_G_blocks, d_C_blocks, d_g, d_c, d_lo, d_hi, d_soft_w, d_soft_cap, d_act, p,
-                     max_pdas_iters, d_x, d_z, d_y, d_lambda, d_iters, d_status, d_res, stream, true, d_alpha);
+    const BoxProblem b{"box_qp_pdas_ls", true, true, d_G_blocks, d_C_blocks, d_g, d_c, d_lo, d_hi, d_soft_w, d_soft_cap, d_act,
+                       {d_x, d_z, d_y, d_lambda, d_iters, d_status, d_res}};
+    const LineSearch ls{d_alpha};
+    return pdas_loop(s, b, p, max_pdas_iters, (hipStream_t)stream, &ls);
 }
 
 extern "C" int gato_box_qp_line_search(gato_solver *s, const void *d_G_blocks, const void *d_g, const void *d_lo, const void *d_hi,
@@ -479,14 +509,12 @@ extern "C" int gato_box_qp_line_search(gato_solver *s, const void *d_G_blocks, c
     const PolishWs o = polish_ws(s->d, s->esz, true, true);
     int rc;
     if ((rc = grow_ws(&s->pol_ws, &s->pol_ws_bytes, o.bytes, st))) return rc;
-    Dims d = s->d;
-    d.k_lo = d.k_hi = 0; d.rhs = 0;
     LineSearchArgs la;
     memset(&la, 0, sizeof(la));
     la.G = d_G_blocks; la.g = d_g; la.lo = d_lo; la.hi = d_hi; la.w = d_soft_w; la.cap = d_soft_cap;
     la.xc = d_xc; la.xp = d_xplus; la.xout = d_x; la.part = (double *)(s->pol_ws + o.part);
     la.alpha = d_alpha; la.alpha_stride = 1; la.slope = d_slope; la.rho = rho; la.it = 2;
-    return s->ops->line_search(d, la, st);
+    return s->ops->line_search(kernel_dims(s), la, st);
 }
 
 // ---- hard bounds by an augmented-Lagrangian outer loop (gato_alm.hip) ----------------------------------
@@ -566,16 +594,14 @@ extern "C" int gato_box_qp_alm(gato_solver *s, const void *d_G_blocks, const voi
     int rc;
     if ((rc = grow_ws(&s->pol_ws, &s->pol_ws_bytes, o.bytes, st))) return rc;     // the inner runs find their part large enough
     char *w = s->pol_ws;
-    GATO_HIP_CHECK(hipMemsetAsync(w + o.sl, 0, o.bytes - o.sl, st));
-    GATO_HIP_CHECK(hipMemsetAsync(d_status, 0xff, B * sizeof(int), st));             // -1: running
+    if ((rc = start_call(w, o.sl, o.bytes, d_status, B, st))) return rc;
     AlmArgs a = alm_args(w, o, caps);
     a.lo = d_lo; a.hi = d_hi; a.w = d_soft_w; a.cap = caps ? d_soft_cap : nullptr; a.mu0 = d_mu0;
     a.act0 = d_act; a.act = (signed char *)(w + o.act); a.act_out = d_act;
     a.x = d_x; a.z = d_z; a.y = d_y; a.lam = d_lambda; a.iters = d_iters; a.status = d_status; a.outer = d_outer;
     a.res = d_res; a.weight = d_weight;
     a.alm_weight = alm_weight; a.growth = alm_growth; a.weight_max = alm_weight_max; a.eps_abs = p->eps_abs; a.eps_rel = p->eps_rel;
-    Dims d = s->d;
-    d.k_lo = d.k_hi = 0; d.rhs = 0;
+    const Dims d = kernel_dims(s);
     if ((rc = s->ops->alm_check(d, a, st))) return rc;
     int h[2] = {0, 0};
     GATO_HIP_CHECK(hipMemcpyAsync(h, a.ctr, sizeof(h), hipMemcpyDeviceToHost, st));
@@ -587,9 +613,12 @@ extern "C" int gato_box_qp_alm(gato_solver *s, const void *d_G_blocks, const voi
                   "alm_weight_max >= alm_weight, or");
         return GATO_EINVAL;
     }
+    // the inner runs: the work area's bounds, weights and act, their point into it, the line search without a record of its steps
+    const BoxProblem inner{who, true, true, d_G_blocks, d_C_blocks, d_g, d_c, a.lo2, a.hi2, a.w2, a.cap2, a.act,
+                           {w + o.xi, w + o.zi, w + o.yi, w + o.li, (int *)(w + o.it_i), (int *)(w + o.st_i), (double *)(w + o.res_i)}};
+    const LineSearch ls{nullptr};
     for (int it = 1; it <= max_alm_iters; ++it) {
-        rc = pdas_loop(s, who, 2, d_G_blocks, d_C_blocks, d_g, d_c, a.lo2, a.hi2, a.w2, a.cap2, a.act, p, max_pdas_iters, w + o.xi,
-                       w + o.zi, w + o.yi, w + o.li, (int *)(w + o.it_i), (int *)(w + o.st_i), (double *)(w + o.res_i), stream, true);
+        rc = pdas_loop(s, inner, p, max_pdas_iters, st, &ls);
         if (rc) {                           // step 1: a start act the inner run refuses, its marks to the caller; a later
             if (it == 1) {                  // error (HIP, a hand-off time-out) leaves d_status -1 on the systems still running
                 GATO_HIP_CHECK(hipMemcpyAsync(d_status, w + o.st_i, B * sizeof(int), hipMemcpyDeviceToDevice, st));
@@ -599,12 +628,7 @@ extern "C" int gato_box_qp_alm(gato_solver *s, const void *d_G_blocks, const voi
         }
         if ((rc = s->ops->alm_update(d, a, it, it == max_alm_iters, st))) return rc;
         if (it == max_alm_iters) break;     // every system still live froze in that decision
-        hipError_t he = hipMemcpyAsync(h, a.ctr, sizeof(int), hipMemcpyDeviceToHost, st);
-        if (he == hipSuccess) he = hipStreamSynchronize(st);
-        if (he != hipSuccess) {
-            set_error("%s: reading the live count failed: %s", who, hipGetErrorString(he));
-            return GATO_EHIP;
-        }
+        if ((rc = read_live(who, a.ctr, h, st))) return rc;
         if (h[0] == 0) break;
     }
     GATO_HIP_CHECK(hipStreamSynchronize(st));
@@ -631,20 +655,18 @@ extern "C" int gato_box_qp_alm_update(gato_solver *s, const void *d_x, const voi
     int rc;
     if ((rc = grow_ws(&s->pol_ws, &s->pol_ws_bytes, o.bytes, st))) return rc;
     char *w = s->pol_ws;
-    GATO_HIP_CHECK(hipMemsetAsync(w + o.res_i, 0, o.bytes - o.res_i, st));          // inner status CONVERGED, residuals and solves 0
+    // inner status CONVERGED, residuals and solves 0; the status it has no caller for: running
+    if ((rc = start_call(w, o.res_i, o.bytes, (int *)(w + o.st_o), B, st))) return rc;
     AlmArgs a = alm_args(w, o, false);
     a.lo = d_lo; a.hi = d_hi; a.w = d_soft_w;                    // the caps are not read: a capped variable has a weight and is no ALM variable
     a.xi = d_x; a.zi = d_x; a.yi = d_y; a.li = d_lambda; a.mu = d_mu; a.lo2 = d_lo2; a.hi2 = d_hi2; a.w2 = d_w2;
     a.x = w + o.xi; a.y = w + o.yi; a.lam = w + o.li; a.z = d_z;
     a.status = (int *)(w + o.st_o); a.iters = (int *)(w + o.it_o); a.res = (double *)(w + o.res_o); a.dec = d_dec;
     a.growth = alm_growth; a.weight_max = alm_weight_max; a.eps_abs = eps_abs; a.eps_rel = eps_rel;
-    GATO_HIP_CHECK(hipMemsetAsync(a.status, 0xff, B * sizeof(int), st));
     // set 1 of the state is step 1's: {w, v_prev} interleaved from the caller's arrays
     GATO_HIP_CHECK(hipMemcpy2DAsync(a.state + 2, 4 * sizeof(double), d_w, sizeof(double), sizeof(double), B, hipMemcpyDeviceToDevice, st));
     GATO_HIP_CHECK(hipMemcpy2DAsync(a.state + 3, 4 * sizeof(double), d_v_prev, sizeof(double), sizeof(double), B, hipMemcpyDeviceToDevice, st));
-    Dims d = s->d;
-    d.k_lo = d.k_hi = 0; d.rhs = 0;
-    if ((rc = s->ops->alm_update(d, a, 1, last, st))) return rc;
+    if ((rc = s->ops->alm_update(kernel_dims(s), a, 1, last, st))) return rc;
     // the maxima of set 1, step 1's
     GATO_HIP_CHECK(hipMemcpy2DAsync(d_v, sizeof(double), a.slots + 2, 4 * 8, 8, B, hipMemcpyDeviceToDevice, st));
     GATO_HIP_CHECK(hipMemcpy2DAsync(d_xinf, sizeof(double), a.slots + 3, 4 * 8, 8, B, hipMemcpyDeviceToDevice, st));

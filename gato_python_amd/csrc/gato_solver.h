@@ -111,7 +111,7 @@ struct gato_solver {
     char *qp_ws;                      // box-QP work area (gato_box_qp_solve): G' | rho | x ping-pong | g~ | dz | lambda~ | slots | ...
     size_t qp_ws_bytes;               // only grows
     int *qp_pcg_total;                // in qp_ws: PCG iterations of every x-step of the latest QP solve, per system [B]
-    char *pol_ws;                     // polish work area (gato_box_qp_polish, gato_box_qp_pdas): g' | c' | dz' | lambda' | x, z, y polished | [act'] | [line search: xc | knot partials] | slots | counts | [gato_box_qp_alm: the inner runs' inputs and point, mu, its state and counts]
+    char *pol_ws;                     // polish work area (gato_box_qp_polish; pdas_loop for every active-set entry; layouts: PolishWs, AlmWs in gato_qp_host.hip): g' | c' | dz' | lambda' | x, z, y polished | [act'] | [line search: xc | knot partials] | slots | counts | [gato_box_qp_alm: the inner runs' inputs and point, mu, its state and counts]
     size_t pol_ws_bytes;              // only grows
 };
 

@@ -161,11 +161,7 @@ int launch_kkt_tangent_rhs(const Dims &d, int R, const TangentArgs &a, hipStream
 {
     if (R < 1 || d.B < 1 || d.B > 65535) { set_error("kkt_tangent_rhs: R = %d, B = %d", R, d.B); return GATO_EINVAL; }
     const int form = a.act ? bounds_form(a.w, a.w ? (a.cap ? a.cap : a.m_dot) : nullptr) : BOUNDS_HARD;
-    const auto kernel = form == BOUNDS_CAPPED ? kkt_tangent_rhs_kernel<T, S, C, BOUNDS_CAPPED>
-                        : form == BOUNDS_SOFT ? kkt_tangent_rhs_kernel<T, S, C, BOUNDS_SOFT> : kkt_tangent_rhs_kernel<T, S, C, BOUNDS_HARD>;
-    hipLaunchKernelGGL(kernel, dim3(knot_grid(d.K), d.B), dim3(WAVE), 0, st, a, d.K, R, batch_stride(d));
-    GATO_HIP_CHECK(hipGetLastError());
-    return GATO_OK;
+    return launch_per_knot("kkt_tangent_rhs", GATO_BOUNDS_KERNEL(kkt_tangent_rhs_kernel, form), d, st, a, d.K, R, batch_stride(d));
 }
 
 #define X(S_, C_)                                                                                                   \

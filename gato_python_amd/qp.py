@@ -91,6 +91,37 @@ def _check_line_search(what, method, polish, soft, line_search):
                          "variable with a finite bound")
 
 
+def _check_layer(what, method, soft, capped, line_search):
+    """The refusals box_qp_layer and box_qp_layer_tangents (`what`) share: the method, then what the soft bounds, their caps and
+    the line search need."""
+    if method not in ("admm", "pdas"):
+        raise ValueError(f"{what}: method must be 'admm' or 'pdas', got {method!r}")
+    _check_caps(what, method, False, soft, capped)
+    _check_line_search(what, method, False, soft, line_search)
+    if soft and method != "pdas":
+        raise ValueError(f"{what}: x_soft and u_soft need method='pdas' (ADMM and the polish have no soft bounds)")
+
+
+def _layer_opts(method, max_pdas_iters, line_search, rho, exit_tol, max_iters, admm_rho, sigma, alpha, eps_abs, eps_rel,
+                max_admm_iters, check_every):
+    """The options _layer_solve reads: those of Solver.box_qp, and for method="pdas" max_pdas_iters and the line search."""
+    opts = dict(rho=float(rho), exit_tol=float(exit_tol), max_iters=int(max_iters), admm_rho=admm_rho, sigma=sigma, alpha=alpha,
+                eps_abs=eps_abs, eps_rel=eps_rel, max_admm_iters=max_admm_iters, check_every=check_every)
+    if method == "pdas":
+        opts["max_pdas_iters"] = int(max_pdas_iters)
+        if line_search:
+            opts["line_search"] = True
+    return opts
+
+
+def _warm_act(warm, Bt, sol, device, starts):
+    """warm.act of box_qp, flat, for an active-set start; `starts` ends the refusal of one that does not match the problem."""
+    act = getattr(warm, "act", None)
+    if not isinstance(act, torch.Tensor) or act.numel() != Bt * sol.N or act.dtype != torch.int8 or act.device != device:
+        raise ValueError(f"box_qp: warm.act does not match this problem ({Bt} x {sol.N} int8 on {device}); {starts}")
+    return act.reshape(-1).contiguous()
+
+
 def box_qp(Q, R, A, B, q, r, c, x_lo, x_hi, u_lo, u_hi, *, rho, exit_tol, max_iters, admm_rho=0.1, sigma=1e-6, alpha=1.6,
            eps_abs=1e-6, eps_rel=1e-6, max_admm_iters=4000, check_every=25, warm=None, polish=False, method="admm",
            polish_iters=1, max_pdas_iters=30, x_soft=None, u_soft=None, x_soft_max=None, u_soft_max=None, line_search=None,
@@ -158,13 +189,8 @@ def box_qp(Q, R, A, B, q, r, c, x_lo, x_hi, u_lo, u_hi, *, rho, exit_tol, max_it
         Gb, Cb, g, cc, lo, hi, wt, mt, Bt, batched, sol = _prepare("box_qp", (Q, R, A, B, q, r, c), x_lo, x_hi, u_lo, u_hi,
                                                                    x_soft, u_soft, x_soft_max, u_soft_max)
         if method == "pdas":
-            act = None
-            if warm is not None:
-                act = getattr(warm, "act", None)
-                if not isinstance(act, torch.Tensor) or act.numel() != Bt * sol.N or act.dtype != torch.int8 or act.device != g.device:
-                    raise ValueError(f"box_qp: warm.act does not match this problem ({Bt} x {sol.N} int8 on {g.device}); "
-                                     "method='pdas' starts from the act of a previous method='pdas' result")
-                act = act.reshape(-1).contiguous()
+            act = None if warm is None else _warm_act(warm, Bt, sol, g.device,
+                                                      "method='pdas' starts from the act of a previous method='pdas' result")
             res = sol.box_qp_pdas(Gb, Cb, g, cc, lo, hi, rho=rho, exit_tol=exit_tol, max_iters=max_iters, eps_abs=eps_abs,
                                   eps_rel=eps_rel, max_pdas_iters=max_pdas_iters, act=act, soft_weight=wt,
                                   soft_cap=None if mt is None else mt.contiguous(), line_search=bool(line_search))
@@ -229,21 +255,18 @@ def _box_qp_alm(blocks, bounds, soft, admm_only, line_search, warm, polish, pol,
         raise ValueError("box_qp: max_alm_iters and max_pdas_iters must be at least 1")
     x_soft, u_soft, x_soft_max, u_soft_max = soft
     is_soft = x_soft is not None or u_soft is not None
-    if (x_soft_max is not None or u_soft_max is not None) and not is_soft:
-        raise ValueError("box_qp: x_soft_max and u_soft_max cap the force of a soft bound: give x_soft or u_soft too")
+    _check_caps("box_qp", "pdas", False, is_soft, x_soft_max is not None or u_soft_max is not None)   # the inner iteration takes caps
     if polish and is_soft:
         raise ValueError("box_qp: polish=True with method='alm' takes hard bounds only (the polish has no soft bounds)")
     with torch.no_grad():
         Gb, Cb, g, cc, lo, hi, wt, mt, Bt, batched, sol = _prepare("box_qp", blocks, *bounds, *soft)
         act = mu = None
         if warm is not None:
-            act, mu = getattr(warm, "act", None), getattr(warm, "y", None)
-            if not isinstance(act, torch.Tensor) or act.numel() != Bt * sol.N or act.dtype != torch.int8 or act.device != g.device:
-                raise ValueError(f"box_qp: warm.act does not match this problem ({Bt} x {sol.N} int8 on {g.device}); "
-                                 "method='alm' starts from the act and the y of a previous method='alm' result")
+            act = _warm_act(warm, Bt, sol, g.device, "method='alm' starts from the act and the y of a previous method='alm' result")
+            mu = getattr(warm, "y", None)
             if not isinstance(mu, torch.Tensor) or mu.numel() != Bt * sol.N or mu.dtype != g.dtype or mu.device != g.device:
                 raise ValueError(f"box_qp: warm.y does not match this problem ({Bt} x {sol.N} {g.dtype} on {g.device})")
-            act, mu = act.reshape(-1).contiguous(), mu.detach().reshape(-1).contiguous()
+            mu = mu.detach().reshape(-1).contiguous()
         res = sol.box_qp_alm(Gb, Cb, g, cc, lo, hi, act=act, mu=mu, soft_weight=None if wt is None else wt.contiguous(),
                              soft_cap=None if mt is None else mt.contiguous(), **pol, **alm)
         if polish:
@@ -406,23 +429,14 @@ def box_qp_layer(Q, R, A, B, q, r, c, x_lo, x_hi, u_lo, u_hi, *, rho, exit_tol, 
     3.11); differentiable with respect to them as well (a cap's gradient is nonzero only on a saturated variable).
     line_search=True: box_qp's line search in the forward pass; the backward pass is unchanged - a
     converged point is the KKT point of its act.  rho is not differentiated and double backward is not supported."""
-    if method not in ("admm", "pdas"):
-        raise ValueError(f"box_qp_layer: method must be 'admm' or 'pdas', got {method!r}")
-    soft = x_soft is not None or u_soft is not None
-    _check_caps("box_qp_layer", method, False, soft, x_soft_max is not None or u_soft_max is not None)
-    _check_line_search("box_qp_layer", method, False, soft, line_search)
-    if soft and method != "pdas":
-        raise ValueError("box_qp_layer: x_soft and u_soft need method='pdas' (ADMM and the polish have no soft bounds)")
+    _check_layer("box_qp_layer", method, x_soft is not None or u_soft is not None,
+                 x_soft_max is not None or u_soft_max is not None, line_search)
     Gb, Cb, g, cc, lo, hi, wt, mt, Bt, batched, sol = _prepare("box_qp_layer", (Q, R, A, B, q, r, c), x_lo, x_hi, u_lo, u_hi,
                                                                x_soft, u_soft, x_soft_max, u_soft_max)
     if mt is not None:
         mt = mt.contiguous()
-    opts = dict(rho=float(rho), exit_tol=float(exit_tol), max_iters=int(max_iters), admm_rho=admm_rho, sigma=sigma, alpha=alpha,
-                eps_abs=eps_abs, eps_rel=eps_rel, max_admm_iters=max_admm_iters, check_every=check_every)
-    if method == "pdas":
-        opts["max_pdas_iters"] = int(max_pdas_iters)
-        if line_search:
-            opts["line_search"] = True
+    opts = _layer_opts(method, max_pdas_iters, line_search, rho, exit_tol, max_iters, admm_rho, sigma, alpha, eps_abs, eps_rel,
+                       max_admm_iters, check_every)
     box = []
     x, lam = _BoxQPLayer.apply(Gb, Cb, g, cc, lo, hi, wt, mt, sol, opts, box)
     info = _shaped(box[0], sol, Bt, batched)
@@ -443,14 +457,9 @@ def box_qp_layer_tangents(Q, R, A, B, q, r, c, x_lo, x_hi, u_lo, u_hi, tangents,
     The tangents are those of the returned act: the solution is piecewise smooth in its inputs.  A system whose polish was not
     accepted raises RuntimeError if one of its tangents is nonzero and gets zeros otherwise."""
     what = "box_qp_layer_tangents"
-    if method not in ("admm", "pdas"):
-        raise ValueError(f"{what}: method must be 'admm' or 'pdas', got {method!r}")
     soft = x_soft is not None or u_soft is not None
     capped = x_soft_max is not None or u_soft_max is not None
-    _check_caps(what, method, False, soft, capped)
-    _check_line_search(what, method, False, soft, line_search)
-    if soft and method != "pdas":
-        raise ValueError(f"{what}: x_soft and u_soft need method='pdas' (ADMM and the polish have no soft bounds)")
+    _check_layer(what, method, soft, capped, line_search)
     with torch.no_grad():
         Gb, Cb, g, cc, lo, hi, wt, mt, Bt, batched, sol = _prepare(what, (Q, R, A, B, q, r, c), x_lo, x_hi, u_lo, u_hi, x_soft,
                                                                    u_soft, x_soft_max, u_soft_max)
@@ -477,12 +486,8 @@ def box_qp_layer_tangents(Q, R, A, B, q, r, c, x_lo, x_hi, u_lo, u_hi, tangents,
                 dots[key + "_dot"] = _dz_layout(xv, uv)
         if mt is not None:
             mt = mt.contiguous()
-        opts = dict(rho=float(rho), exit_tol=float(exit_tol), max_iters=int(max_iters), admm_rho=admm_rho, sigma=sigma, alpha=alpha,
-                    eps_abs=eps_abs, eps_rel=eps_rel, max_admm_iters=max_admm_iters, check_every=check_every)
-        if method == "pdas":
-            opts["max_pdas_iters"] = int(max_pdas_iters)
-            if line_search:
-                opts["line_search"] = True
+        opts = _layer_opts(method, max_pdas_iters, line_search, rho, exit_tol, max_iters, admm_rho, sigma, alpha, eps_abs, eps_rel,
+                           max_admm_iters, check_every)
         res, act, pol = _layer_solve(sol, Gb, Cb, g, cc, lo, hi, wt, mt, opts)
         x, lam = res.x.view(Bt, sol.N).clone(), res.lam.view(Bt, sol.sizes["sk"]).clone()
         x_dot, lam_dot = _layer_tangents(sol, Rn, res.polished.cpu(), pol, Gb, Cb, lo, hi, wt, mt, act, x, lam, _dots(dots, x.dtype))

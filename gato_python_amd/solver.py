@@ -292,10 +292,7 @@ class Solver:
         rc = _lib.lib().gato_box_qp_solve(self._h, _ptr(Gb), _ptr(Cb), _ptr(g), _ptr(c), _ptr(lo), _ptr(hi), ct.byref(p),
                                           _ptr(x), _ptr(z), _ptr(y), _ptr(lam), _ptr(iters), _ptr(status), _ptr(res),
                                           self._stream())
-        if rc != 0 and "BAD_BOUNDS" in _lib.lib().gato_last_error().decode():
-            bad = (status.cpu() == _lib.QP_BAD_BOUNDS).nonzero().flatten().tolist()
-            raise ValueError(f"box_qp: systems {bad}: " + _lib.lib().gato_last_error().decode())
-        _lib.check(rc)
+        self._check_marked("box_qp", rc, status, BAD_BOUNDS=_lib.QP_BAD_BOUNDS)
         res = res.view(B, 2)
         return BoxQPResult(x, z, y, lam, iters, status, res[:, 0], res[:, 1])
 
@@ -321,6 +318,30 @@ class Solver:
         for name, v in admm.items():
             setattr(p, name, type(getattr(p, name))(v))       # float or int, as the field is
         return p
+
+    @staticmethod
+    def _check_marked(what, rc, marks, **codes):
+        """After a box-QP entry returned rc: where its error names one of `codes` (name in the text = value in marks, the
+        entry's status or polish codes [B]), ValueError with the systems so marked; every other error as _lib.check raises it."""
+        msg = _lib.lib().gato_last_error().decode() if rc != 0 else ""
+        if any(name in msg for name in codes):
+            bad = [i for i, v in enumerate(marks.tolist()) if v in codes.values()]
+            raise ValueError(f"{what}: systems {bad}: " + msg)
+        _lib.check(rc)
+
+    def _new_point(self, what, act, x, z, y, lam):
+        """The output point of an active-set-type call: x, z, y [B N] and lam [B S K] (those given; new ones are zero), a copy
+        of the start act (None: nothing active), iters and status [B] int32, res [2 B] float64."""
+        B, N, sk = self.batch, self.N, self.sizes["sk"]
+        zeros = lambda n, dt=self.dtype: torch.zeros(n, dtype=dt, device=f"cuda:{self.device}")
+        x, z, y = (zeros(B * N) if t is None else t for t in (x, z, y))
+        lam = zeros(B * sk) if lam is None else lam
+        if act is None:
+            act = zeros(B * N, torch.int8)
+        else:
+            self._check_vecs(what, act=act)
+            act = act.detach().reshape(-1).clone()
+        return x, z, y, lam, act, zeros(B, torch.int32), self.new(B, torch.int32), zeros(2 * B, torch.float64)
 
     def box_qp_active_set(self, z, y, lo, hi, act=None):
         """The active set of an ADMM result (z, y [B N]) for the box (lo, hi): int8 [B N], +1 upper, -1 lower (and lo ==
@@ -348,12 +369,14 @@ class Solver:
         rc = _lib.lib().gato_box_qp_polish(self._h, _ptr(Gb), _ptr(Cb), _ptr(g), _ptr(c), _ptr(lo), _ptr(hi), _ptr(act), ct.byref(p),
                                            _ptr(result.x), _ptr(result.z), _ptr(result.y), _ptr(result.lam), _ptr(result.status),
                                            _ptr(res), _ptr(codes), self._stream())
-        if rc != 0 and "BAD_ACTIVE" in _lib.lib().gato_last_error().decode():
-            bad = (codes.cpu() == _lib.POLISH_BAD_ACTIVE).nonzero().flatten().tolist()
-            raise ValueError(f"box_qp_polish: systems {bad}: " + _lib.lib().gato_last_error().decode())
-        _lib.check(rc)
+        self._check_marked("box_qp_polish", rc, codes, BAD_ACTIVE=_lib.POLISH_BAD_ACTIVE)
         result.polished = codes
         return codes
+
+    # (weights, caps, line search) -> the C entry of box_qp_pdas and which of the weights (w) and caps (m) it has arguments for
+    _PDAS_ENTRIES = {(False, False, False): ("gato_box_qp_pdas", ""), (True, False, False): ("gato_box_qp_pdas_soft", "w"),
+                     (True, True, False): ("gato_box_qp_pdas_huber", "wm"), (True, False, True): ("gato_box_qp_pdas_ls", "wm"),
+                     (True, True, True): ("gato_box_qp_pdas_ls", "wm")}
 
     def box_qp_pdas(self, Gb, Cb, g, c, lo, hi, *, rho, exit_tol, max_iters, eps_abs=1e-6, eps_rel=1e-6, max_pdas_iters=30,
                     act=None, x=None, z=None, y=None, lam=None, soft_weight=None, soft_cap=None, line_search=False):
@@ -381,47 +404,21 @@ class Solver:
         if line_search and soft_weight is None:
             raise ValueError("box_qp_pdas: line_search=True needs soft_weight (the line search takes soft bounds only: every "
                              "variable with a finite bound needs a positive weight)")
-        B, N, sk = self.batch, self.N, self.sizes["sk"]
-        zeros = lambda n: torch.zeros(n, dtype=self.dtype, device=f"cuda:{self.device}")
-        x = zeros(B * N) if x is None else x
-        z = zeros(B * N) if z is None else z
-        y = zeros(B * N) if y is None else y
-        lam = zeros(B * sk) if lam is None else lam
-        if act is None:
-            act = torch.zeros(B * N, dtype=torch.int8, device=f"cuda:{self.device}")
-        else:
-            self._check_vecs("box_qp_pdas", act=act)
-            act = act.detach().reshape(-1).clone()
+        B = self.batch
+        x, z, y, lam, act, iters, status, res = self._new_point("box_qp_pdas", act, x, z, y, lam)
         self._check_vecs("box_qp_pdas", Gb=Gb, Cb=Cb, g=g, c=c, lo=lo, hi=hi, x=x, z=z, y=y, lam=lam)
         if soft_weight is not None:
             self._check_vecs("box_qp_pdas", soft_weight=soft_weight)
         if soft_cap is not None:
             self._check_vecs("box_qp_pdas", soft_cap=soft_cap)
-        iters = torch.zeros(B, dtype=torch.int32, device=act.device)
-        status = self.new(B, torch.int32)
-        res = torch.zeros(2 * B, dtype=torch.float64, device=act.device)
         p = self._qp_params(rho, exit_tol, max_iters, eps_abs, eps_rel)
-        tail = (ct.byref(p), int(max_pdas_iters), _ptr(x), _ptr(z), _ptr(y), _ptr(lam), _ptr(iters), _ptr(status), _ptr(res),
-                self._stream())
-        alpha = None
-        if line_search:
-            alpha = torch.zeros(B, int(max_pdas_iters), dtype=torch.float64, device=act.device)
-            rc = _lib.lib().gato_box_qp_pdas_ls(self._h, _ptr(Gb), _ptr(Cb), _ptr(g), _ptr(c), _ptr(lo), _ptr(hi), _ptr(soft_weight),
-                                                _ptr(soft_cap), _ptr(act), *tail[:-1], _ptr(alpha), tail[-1])
-        elif soft_weight is None:
-            rc = _lib.lib().gato_box_qp_pdas(self._h, _ptr(Gb), _ptr(Cb), _ptr(g), _ptr(c), _ptr(lo), _ptr(hi), _ptr(act), *tail)
-        elif soft_cap is None:
-            rc = _lib.lib().gato_box_qp_pdas_soft(self._h, _ptr(Gb), _ptr(Cb), _ptr(g), _ptr(c), _ptr(lo), _ptr(hi),
-                                                  _ptr(soft_weight), _ptr(act), *tail)
-        else:
-            rc = _lib.lib().gato_box_qp_pdas_huber(self._h, _ptr(Gb), _ptr(Cb), _ptr(g), _ptr(c), _ptr(lo), _ptr(hi),
-                                                   _ptr(soft_weight), _ptr(soft_cap), _ptr(act), *tail)
-        msg = _lib.lib().gato_last_error().decode() if rc != 0 else ""
-        if "BAD_BOUNDS" in msg or "BAD_ACTIVE" in msg:
-            st = status.cpu()
-            bad = ((st == _lib.QP_BAD_BOUNDS) | (st == _lib.QP_BAD_ACTIVE)).nonzero().flatten().tolist()
-            raise ValueError(f"box_qp_pdas: systems {bad}: " + msg)
-        _lib.check(rc)
+        alpha = torch.zeros(B, int(max_pdas_iters), dtype=torch.float64, device=act.device) if line_search else None
+        entry, takes = self._PDAS_ENTRIES[soft_weight is not None, soft_cap is not None, bool(line_search)]
+        soft = {"": (), "w": (soft_weight,), "wm": (soft_weight, soft_cap)}[takes]        # what the entry takes before act
+        steps = (alpha,) if line_search else ()                                            # and after res
+        rc = getattr(_lib.lib(), entry)(self._h, *map(_ptr, (Gb, Cb, g, c, lo, hi, *soft, act)), ct.byref(p), int(max_pdas_iters),
+                                        *map(_ptr, (x, z, y, lam, iters, status, res, *steps)), self._stream())
+        self._check_marked("box_qp_pdas", rc, status, BAD_BOUNDS=_lib.QP_BAD_BOUNDS, BAD_ACTIVE=_lib.QP_BAD_ACTIVE)
         res = res.view(B, 2)
         codes = torch.where(status == _lib.QP_CONVERGED, _lib.POLISH_ACCEPTED,
                             torch.where(status == _lib.QP_NONFINITE, _lib.POLISH_NONFINITE, _lib.POLISH_REJECTED)).to(torch.int32)
@@ -463,38 +460,20 @@ class Solver:
             raise ValueError("box_qp_alm: soft_cap needs soft_weight (a cap is read only where the weight is positive)")
         if alm_weight_max is None:
             alm_weight_max = max(ALM_WEIGHT_MAX[self.np_dtype], float(alm_weight))
-        B, N, sk = self.batch, self.N, self.sizes["sk"]
-        dev = f"cuda:{self.device}"
-        zeros = lambda n: torch.zeros(n, dtype=self.dtype, device=dev)
-        x = zeros(B * N) if x is None else x
-        z = zeros(B * N) if z is None else z
-        y = zeros(B * N) if y is None else y
-        lam = zeros(B * sk) if lam is None else lam
-        if act is None:
-            act = torch.zeros(B * N, dtype=torch.int8, device=dev)
-        else:
-            self._check_vecs("box_qp_alm", act=act)
-            act = act.detach().reshape(-1).clone()
+        B, dev = self.batch, f"cuda:{self.device}"
+        x, z, y, lam, act, iters, status, res = self._new_point("box_qp_alm", act, x, z, y, lam)
         own = dict(Gb=Gb, Cb=Cb, g=g, c=c, lo=lo, hi=hi, x=x, z=z, y=y, lam=lam)
         own.update({k: v for k, v in (("soft_weight", soft_weight), ("soft_cap", soft_cap), ("mu", mu)) if v is not None})
         self._check_vecs("box_qp_alm", **own)
-        iters = torch.zeros(B, dtype=torch.int32, device=dev)
         outer = torch.zeros(B, dtype=torch.int32, device=dev)
         weight = torch.zeros(B, dtype=torch.float64, device=dev)
-        status = self.new(B, torch.int32)
-        res = torch.zeros(2 * B, dtype=torch.float64, device=dev)
         p = self._qp_params(rho, exit_tol, max_iters, eps_abs, eps_rel)
         rc = _lib.lib().gato_box_qp_alm(self._h, _ptr(Gb), _ptr(Cb), _ptr(g), _ptr(c), _ptr(lo), _ptr(hi), _ptr(soft_weight),
                                         _ptr(soft_cap), _ptr(act), ct.byref(p), int(max_pdas_iters), float(alm_weight),
                                         float(alm_growth), float(alm_weight_max), int(max_alm_iters), _ptr(mu), _ptr(x), _ptr(z),
                                         _ptr(y), _ptr(lam), _ptr(iters), _ptr(status), _ptr(res), _ptr(outer), _ptr(weight),
                                         self._stream())
-        msg = _lib.lib().gato_last_error().decode() if rc != 0 else ""
-        if "BAD_BOUNDS" in msg or "BAD_ACTIVE" in msg:
-            st = status.cpu()
-            bad = ((st == _lib.QP_BAD_BOUNDS) | (st == _lib.QP_BAD_ACTIVE)).nonzero().flatten().tolist()
-            raise ValueError(f"box_qp_alm: systems {bad}: " + msg)
-        _lib.check(rc)
+        self._check_marked("box_qp_alm", rc, status, BAD_BOUNDS=_lib.QP_BAD_BOUNDS, BAD_ACTIVE=_lib.QP_BAD_ACTIVE)
         res = res.view(B, 2)
         return BoxQPResult(x, z, y, lam, iters, status, res[:, 0], res[:, 1], None, act, None, outer, weight)
 
@@ -527,22 +506,21 @@ class Solver:
         return dict(v=v, xinf=xinf, dec=dec, mu=mu, lo2=lo2, hi2=hi2, w2=w2, z=z)
 
     def _bound_grads(self, entry, what, Gb, Cb, act, soft, xbar, a, beta, **bars):
-        """The body of the two bound-gradient methods: allocates the outputs bars (by name) that are None, checks every
-        operand as `what`, calls the C entry and returns the outputs.  soft: the operands only the soft entry takes, in its
-        order (soft_weight, lo, hi, x, or soft_weight, soft_cap, lo, hi, x for the capped entry; a soft_weight or soft_cap of
-        None goes as a null pointer), or () for the entry without weights."""
+        """The body of the three bound-gradient methods: allocates the outputs bars (by name) that are None, checks every
+        operand as `what`, calls the C entry and returns the outputs.  soft: the operands only the soft and the capped entry
+        take, by name and in the entry's order (a soft_weight or soft_cap of None goes as a null pointer); {} for the entry
+        without weights."""
         bars = {name: self.new(self.batch * self.N) if t is None else t for name, t in bars.items()}
-        names = ("soft_weight", "soft_cap", "lo", "hi", "x") if len(soft) == 5 else ("soft_weight", "lo", "hi", "x")
-        own = {name: t for name, t in zip(names, soft) if name not in ("soft_weight", "soft_cap") or t is not None}
+        own = {name: t for name, t in soft.items() if name not in ("soft_weight", "soft_cap") or t is not None}
         self._check_vecs(what, Gb=Gb, Cb=Cb, act=act, **own, xbar=xbar, a=a, beta=beta, **bars)
-        _lib.check(entry(self._h, _ptr(Gb), _ptr(Cb), _ptr(act), *map(_ptr, soft), _ptr(xbar), _ptr(a), _ptr(beta),
+        _lib.check(entry(self._h, _ptr(Gb), _ptr(Cb), _ptr(act), *map(_ptr, soft.values()), _ptr(xbar), _ptr(a), _ptr(beta),
                          *map(_ptr, bars.values()), self._stream()))
         return tuple(bars.values())
 
     def box_qp_bound_grad(self, Gb, Cb, act, xbar, a, beta, lo_bar=None, hi_bar=None):
         """(lo_bar, hi_bar) [B N] of a polished solution from its active set, the upstream x_bar and the adjoint (a, beta) of
         the reduced system (solve_rhs after the polish)."""
-        return self._bound_grads(_lib.lib().gato_box_qp_bound_grad, "box_qp_bound_grad", Gb, Cb, act, (), xbar, a, beta,
+        return self._bound_grads(_lib.lib().gato_box_qp_bound_grad, "box_qp_bound_grad", Gb, Cb, act, {}, xbar, a, beta,
                                  lo_bar=lo_bar, hi_bar=hi_bar)
 
     def box_qp_soft_grad(self, Gb, Cb, act, soft_weight, lo, hi, x, xbar, a, beta, lo_bar=None, hi_bar=None, w_bar=None):
@@ -550,8 +528,8 @@ class Solver:
         the upstream x_bar and the adjoint (a, beta) of its last assembly (solve_rhs after the call): the hard formula of
         box_qp_bound_grad on the hard-active set, w_i a_i and a_i (b_i - x_i) on the soft-active one, 0 elsewhere.
         soft_weight None: all hard."""
-        return self._bound_grads(_lib.lib().gato_box_qp_soft_grad, "box_qp_soft_grad", Gb, Cb, act, (soft_weight, lo, hi, x),
-                                 xbar, a, beta, lo_bar=lo_bar, hi_bar=hi_bar, w_bar=w_bar)
+        return self._bound_grads(_lib.lib().gato_box_qp_soft_grad, "box_qp_soft_grad", Gb, Cb, act,
+                                 dict(soft_weight=soft_weight, lo=lo, hi=hi, x=x), xbar, a, beta, lo_bar=lo_bar, hi_bar=hi_bar, w_bar=w_bar)
 
     def box_qp_huber_grad(self, Gb, Cb, act, soft_weight, soft_cap, lo, hi, x, xbar, a, beta, lo_bar=None, hi_bar=None,
                           w_bar=None, cap_bar=None):
@@ -559,8 +537,8 @@ class Solver:
         (gato_box_qp_huber_grad): a saturated variable (act = +-2, s its sign) gets cap_bar_i = -s a_i and 0 in the other
         three, every other variable what box_qp_soft_grad gives it and cap_bar_i = 0.  soft_cap None: no caps."""
         return self._bound_grads(_lib.lib().gato_box_qp_huber_grad, "box_qp_huber_grad", Gb, Cb, act,
-                                 (soft_weight, soft_cap, lo, hi, x), xbar, a, beta, lo_bar=lo_bar, hi_bar=hi_bar, w_bar=w_bar,
-                                 cap_bar=cap_bar)
+                                 dict(soft_weight=soft_weight, soft_cap=soft_cap, lo=lo, hi=hi, x=x), xbar, a, beta, lo_bar=lo_bar,
+                                 hi_bar=hi_bar, w_bar=w_bar, cap_bar=cap_bar)
 
     def box_qp_pcg_iters(self):
         """PCG iterations of all x-steps of the latest box_qp call, per system (host int array)."""
