@@ -28,7 +28,7 @@ __device__ __forceinline__ void one_system_helper(const PcgLaunch &a, T *scratch
     asm volatile("" ::"v"(acc));
     // ... and then stay for the dz back-substitution (compute_dz, gato_schur.cuh:758-867): wave w of helper h takes knot
     // h * WT + w, brings Q_k^-1, R_k^-1, A_k, B_k and g_k into LDS while the solve runs, waits (sleeping) until the solving
-    // workgroup has stored launch_id in *dz_flag - lambda is complete and released - and finishes in about a microsecond.
+    // workgroup has stored launch_id in *dz_flag - lambda is complete and written through - and finishes in about a microsecond.
     // That replaces a launch of its own (5.3 us + the gap in front of it) at the end of every step.  Formulas and
     // accumulation order of dz_kernel (gato_assembly.hip), row by row: the same bits.  The solving workgroup never waits for
     // a helper, so helpers that are scheduled late (or after it has finished) just find the flag set.
@@ -67,7 +67,10 @@ __device__ __forceinline__ void one_system_helper(const PcgLaunch &a, T *scratch
             if (lane == 0) __hip_atomic_store((gi32 *)a.status, a.launch_id, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             return;
         }
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        // No agent-scope acquire (buffer_inv: 2.4 us of this wave's 4.2): lambda is all this wave reads of what the launch wrote,
+        // through agent-scope loads - past this CU's L1 - of bytes the solving workgroup stored write-through and drained in
+        // front of its flag store.  The wavefront-scope fence is no instruction; it keeps the loads below the poll.
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         for (int i = lane; i < (last ? S : 2 * S); i += 64) sl[i] = __hip_atomic_load(lg + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         wave_lds_fence();
         if (!last) {
@@ -323,12 +326,15 @@ __global__ __launch_bounds__(MAXT) void pcg_single_f32x2_kernel(PcgLaunch a)
         asm volatile("" : "+v"(gp) : : "memory");
         put_private(pw_p, p, gp);
     }
-    if (active) { dL[(size_t)j * S + r0] = lam[0]; dL[(size_t)j * S + r1] = lam[1]; }
-    if (a.dz_helpers && a.dz != nullptr && a.batch <= 1) {       // lambda is complete: release it and tell the helper blocks
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    if (a.dz_helpers && a.dz != nullptr && a.batch <= 1) {       // lambda is complete: to the helper blocks without fences, as in pcg_single_f64m_kernel
+        if (active) {
+            __hip_atomic_store(dL + (size_t)j * S + r0, lam[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(dL + (size_t)j * S + r1, lam[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if (tid == 0) __hip_atomic_store((gi32 *)a.dz_flag, a.launch_id, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    } else if (active) { dL[(size_t)j * S + r0] = lam[0]; dL[(size_t)j * S + r1] = lam[1]; }
     // ---- dz back-substitution in the same launch (batches: one workgroup per system), as in pcg_single_f64m_kernel: formulas and
     // accumulation order of dz_kernel (gato_assembly.hip; gato_schur.cuh:758-867, D2 fixed), row by row: bit-identical results.
     if (a.dz != nullptr && !a.dz_helpers) {
@@ -539,6 +545,24 @@ __global__ __launch_bounds__(64 * WT) void pcg_single_f64m_kernel(PcgLaunch a)
     const T *__restrict__ dG = static_cast<const T *>(a.gamma) + sys * S * K;
     T *__restrict__ dL = static_cast<T *>(a.lambda) + sys * S * K;
 
+    // gamma (and lambda0 of a warm start) FIRST: the assembly launch wrote them a moment ago on other XCDs, put(xs, r) and the
+    // first product need them at once, and loads return in order - issued behind the matrices they were one more fully exposed
+    // miss (entry -> loop entered 7.26 -> 6.80 us, tools/hs_single.py).  One straight line for cold and warm starts: a cold
+    // start loads gamma a second time where a warm start loads lambda0, and replaces it by zeros in front of the loop.  (With
+    // the lambda0 loads behind `if (a.lambda0)` the compiler zeroed their registers on the other side of the branch - behind
+    // an s_waitcnt vmcnt(0), a load of those registers being in flight on the side not taken: gamma's latency, exposed again.)
+    V2 lam = {0, 0}, r = {0, 0};
+    {
+        const T *__restrict__ dL0 = a.lambda0 ? static_cast<const T *>(a.lambda0) + sys * S * K : dG;
+        if (active) {
+            r[0] = dG[(size_t)j * S + r0];
+            lam[0] = dL0[(size_t)j * S + r0];
+            if (two) {
+                r[1] = dG[(size_t)j * S + r0 + 1];
+                lam[1] = dL0[(size_t)j * S + r0 + 1];
+            }
+        }
+    }
     // m: two-row lanes [S row a | S row b], one-row lanes [S row | Pinv row]; pr: the first NPR Pinv pairs of a two-row lane
     // The loads are issued in BATCHES with nothing that needs their data in between: written column by column (load S, load
     // Pinv, select, store the Pinv pair to LDS) the compiler reused one set of registers and waited for every column's loads
@@ -708,17 +732,7 @@ __global__ __launch_bounds__(64 * WT) void pcg_single_f64m_kernel(PcgLaunch a)
     };
     const T *wp_ = &xs[j * SP], *wr_ = wp_;                                      // the lane's window: slot j = left neighbour
 
-    V2 lam = {0, 0}, r = {0, 0};
-    if (active) {
-        r[0] = dG[(size_t)j * S + r0];
-        if (two) r[1] = dG[(size_t)j * S + r0 + 1];
-    }
-    if (a.lambda0) {                                                             // true warm start (opt-in)
-        const T *__restrict__ dL0 = static_cast<const T *>(a.lambda0) + sys * S * K;
-        if (active) {
-            lam[0] = dL0[(size_t)j * S + r0];
-            if (two) lam[1] = dL0[(size_t)j * S + r0 + 1];
-        }
+    if (a.lambda0) {                                                             // true warm start (opt-in): lam holds lambda0
         put(xs, lam);
         __syncthreads();
         r -= times_window(0, wp_, lam);
@@ -735,6 +749,7 @@ __global__ __launch_bounds__(64 * WT) void pcg_single_f64m_kernel(PcgLaunch a)
     if (rec) a.eta_hist[0] = (double)eta;
     V2 p = rt, ups;
     put(xs, p);
+    if (!a.lambda0) lam = V2{0, 0};                                              // cold start (see the loads of gamma)
     __syncthreads();
     for (int it = 0; it < a.max_iters; ++it) {                                   // gato_pcg.cuh:348
 #ifdef GATO_F64M_STAMP
@@ -770,14 +785,22 @@ __global__ __launch_bounds__(64 * WT) void pcg_single_f64m_kernel(PcgLaunch a)
     if (a.eta_hist && lane == 0 && sys == 0)
         for (int i = 0; i < 13; ++i) a.eta_hist[1024 + wave * 16 + i] = (double)(st_[i] & 0xffffffffffull);
 #endif
-    if (active) {                                                                // :433-435
-        dL[(size_t)j * S + r0] = lam[0];
-        if (two) dL[(size_t)j * S + r0 + 1] = lam[1];
-    }
-    if (a.dz_helpers && a.dz != nullptr && a.batch <= 1) {       // lambda is complete: release it and tell the helper blocks
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    if (a.dz_helpers && a.dz != nullptr && a.batch <= 1) {
+        // lambda is complete: hand it to the helper blocks WITHOUT fences.  Every byte is stored write-through (agent scope:
+        // sc1), every storing wave drains its stores, a workgroup barrier, then ONE lane stores the flag; the helpers poll the
+        // flag and read lambda with agent-scope loads, and nothing else that this launch wrote (one_system_helper).  An
+        // agent-scope release here (buffer_wbl2 in all 512 threads) and the acquire there cost 3.3 us: loop left -> dz
+        // stored 6.08 -> 2.82 us (tools/hs_single.py).  The kernel's end makes lambda visible to later launches as before.
+        if (active) {                                                            // :433-435
+            __hip_atomic_store(dL + (size_t)j * S + r0, lam[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (two) __hip_atomic_store(dL + (size_t)j * S + r0 + 1, lam[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if (tid == 0) __hip_atomic_store((gi32 *)a.dz_flag, a.launch_id, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    } else if (active) {                                                         // :433-435
+        dL[(size_t)j * S + r0] = lam[0];
+        if (two) dL[(size_t)j * S + r0 + 1] = lam[1];
     }
     // ---- dz back-substitution in the same launch (batches: one workgroup per system).  Formulas and accumulation order of
     // dz_kernel (gato_assembly.hip; gato_schur.cuh:758-867, D2 fixed), row by row: bit-identical results.

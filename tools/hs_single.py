@@ -1,18 +1,49 @@
-"""(scratch build with s_memrealtime stamps in pcg_single_f64m_kernel; option ablate bits 8..15 = a sleep of that many x 512 cycles
-before the matrix loads) where the one-workgroup fp64 launch spends its time outside the loop."""
-import sys, os, numpy as np
+"""Where the one-workgroup fp64 launch (pcg_single_f64m_kernel, 14/7/50) spends its time OUTSIDE the loop: s_memrealtime stamps
+(100 MHz) of the solving workgroup's thread 0 and of the helper wave that does knot 0's dz.
+
+Needs a SCRATCH build (a copy of csrc/ outside the tree, built as another .so and selected with GATO_HIP_LIB; not committed):
+__builtin_amdgcn_s_memrealtime() of thread 0 of the solving workgroup, kept in registers until the kernel's end (a store in
+between would count in the loads' vmcnt waits) and then written as doubles to eta_hist[2000 + i]:
+    0 kernel entry                           1 in front of the set-up barrier (own loads landed)   2 behind it
+    3 behind the first block sum             4 behind the barrier in front of the loop             5 loop left
+    6 behind the flag store
+and of lane 0 of the helper wave with kq == 0 in one_system_helper: [2007] behind the poll of the flag, [2008] behind its dz
+stores and an s_waitcnt vmcnt(0).
+    GATO_HIP_LIB=/path/to/libgato_hs.so python tools/hs_single.py [launches=30]
+Prints, per phase, the median and the range over the launches, in microseconds."""
+import os
+import sys
+
+import numpy as np
+
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import torch
-from gato_python_amd import synth
-from gato_python_amd.solver import Solver
-S, C, K = 14, 7, 50
+import torch                                           # noqa: E402
+from gato_python_amd import synth                      # noqa: E402
+from gato_python_amd.solver import Solver              # noqa: E402
+
+S, C, K, ITERS = 14, 7, 50, 100
+n = int(sys.argv[1]) if len(sys.argv) > 1 else 30
 s = synth.make_system(S, C, K, seed=0)
-sol = Solver(S, C, K, np.float64); sol.set_option("record_eta", 1); sol.set_option("time_pcg", 1)
-dev = sol.upload_system(s); lam, dz = sol.new(S * K), sol.new(sol.N)
-for sl in (0, 2, 4, 6, 8, 12, 16, 0):
-    sol.set_option("ablate", sl << 8)
-    for _ in range(3): sol.linsys(*dev, 0.0, 100, s.rho, lam, dz)
+sol = Solver(S, C, K, np.float64)
+sol.set_option("record_eta", 1)
+dev = sol.upload_system(s)
+lam, dz = sol.new(S * K), sol.new(sol.N)
+rows = []
+for i in range(n + 5):
+    sol.linsys(*dev, 0.0, ITERS, s.rho, lam, dz)
     torch.cuda.synchronize()
-    h = sol.eta_history(210)[200:206] / 100.0     # 100 MHz ticks -> us
-    print(f"sleep {sl} x 512 cycles: events around the launch {1e3*sol.pcg_last_ms():.1f} us; in the kernel (us since its first instruction): matrices loaded {h[1]:.2f}, windows zeroed {h[2]:.2f}, loop entered {h[3]:.2f}, loop left {h[4]:.2f}, lambda stored {h[5]:.2f}")
+    if i >= 5:
+        rows.append(sol.eta_history(2010)[2000:2009].copy())
+sol.check_status()
 sol.close()
+t = np.array(rows) / 100.0                              # us
+names = [("entry -> own loads of gamma and Pinv landed", 0, 1), ("-> set-up barrier passed", 1, 2),
+         ("-> first product and block sum done", 2, 3), ("-> loop entered (all of S landed)", 3, 4),
+         ("loop, %d iterations" % ITERS, 4, 5), ("loop left -> lambda stored and flag stored", 5, 6),
+         ("flag stored -> seen by knot 0's helper wave", 6, 7), ("-> that wave's dz stored", 7, 8),
+         ("OUTSIDE the loop: entry -> loop entered", 0, 4), ("OUTSIDE the loop: loop left -> dz stored", 5, 8),
+         ("entry -> dz stored", 0, 8)]
+print("library", os.environ.get("GATO_HIP_LIB", "(the package's own)"), "-", n, "launches")
+for name, a, b in names:
+    d = t[:, b] - t[:, a]
+    print(f"  {name:52s} median {np.median(d):7.2f}   min {d.min():7.2f}   max {d.max():7.2f}")
