@@ -5,6 +5,7 @@ Public surface:
   gato_python_amd.linsys_resolve(...)    the last linsys_solve's system again, for a new g / c (no re-assembly)
   gato_python_amd.Solver                 device-resident stage-level API over include/gato_hip.h
   gato_python_amd.kkt_solve(...)         differentiable solve from math-shaped blocks (torch autograd, autograd.py)
+  gato_python_amd.kkt_solve(..., M=M)    the same with a state-control cross term x_k^T M_k u_k in the stage cost
   gato_python_amd.kkt_solve_csr(...)     differentiable solve on device CSR input
   gato_python_amd.box_qp(...)            box-constrained QP (bounds on states and controls) by ADMM over the re-solve, or
                                          by the active-set iteration (method="pdas": hard, soft and capped soft bounds;

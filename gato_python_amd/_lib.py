@@ -36,6 +36,8 @@ SYMBOLS = [
     "gato_box_qp_active_set", "gato_box_qp_polish", "gato_box_qp_bound_grad", "gato_box_qp_pdas",
     "gato_box_qp_pdas_soft", "gato_box_qp_soft_grad", "gato_box_qp_pdas_huber", "gato_box_qp_huber_grad",
     "gato_box_qp_pdas_ls", "gato_box_qp_line_search", "gato_kkt_tangent_rhs", "gato_box_qp_alm", "gato_box_qp_alm_update",
+    "gato_linsys_device_blocks_cross", "gato_solve_rhs_cross", "gato_kkt_grad_cross", "gato_cross_prepare", "gato_cross_rhs",
+    "gato_cross_finish",
 ]
 
 
@@ -138,6 +140,12 @@ def lib() -> ct.CDLL:
         L.gato_kkt_tangent_rhs.argtypes = [vp, i] + [vp] * 20
         L.gato_box_qp_alm.argtypes = [vp] * 10 + [ct.POINTER(BoxQpParams), i, d, d, d, i] + [vp] * 11
         L.gato_box_qp_alm_update.argtypes = [vp] * 10 + [d, d, d, d, i] + [vp] * 8
+        L.gato_linsys_device_blocks_cross.argtypes = [vp, vp, vp, vp, vp, vp, d, i, d, vp, vp, vp]
+        L.gato_solve_rhs_cross.argtypes = [vp, i, vp, vp, d, i, vp, vp, vp, vp]
+        L.gato_kkt_grad_cross.argtypes = [vp] * 5
+        L.gato_cross_prepare.argtypes = [vp, vp, vp, vp, vp, d, vp]
+        L.gato_cross_rhs.argtypes = [vp, i, vp, vp, vp]
+        L.gato_cross_finish.argtypes = [vp, i, vp, vp]
         f = ct.c_float
         L.gato_linsys_solve_f32.argtypes = [ip, i, ip, vp, i, ip, i, ip, vp, i, vp, i, vp, i, vp,
                                             i, i, i, i, f, i, i, f, vp, vp, vp, vp]

@@ -1,6 +1,6 @@
 """torch autograd through the KKT solve.
 
-    kkt_solve(Q, R, A, B, q, r, c, *, rho, exit_tol, max_iters) -> (lam, dz)
+    kkt_solve(Q, R, A, B, q, r, c, *, M=None, rho, exit_tol, max_iters) -> (lam, dz)
     kkt_solve_csr(G_row, G_col, G_val, C_row, C_col, C_val, g, c, *, rho, exit_tol, max_iters) -> (lam, dz)
     kkt_solve_tangents(Q, R, A, B, q, r, c, tangents, *, rho, exit_tol, max_iters) -> (lam, dz, lam_dot, dz_dot)
 
@@ -10,6 +10,8 @@ matrix: Solver.solve_rhs), then one launch that forms the matrix gradients from 
 Forward mode: the tangent system has the same matrix, so a tangent is one launch for its right-hand side
 (gato_tangent.hip) and the same re-solve - through torch.autograd.forward_ad dual tensors (the jvp of the Function, one direction)
 or kkt_solve_tangents (R directions in one call).
+A cross term M (reverse mode only) takes a Function of its own over Solver.linsys_blocks_cross /
+solve_rhs_cross / kkt_grad_cross; without M the code path is the one above, untouched.
 Only device tensors are taken; there is no CPU fallback.  rho is not differentiated, and double backward is not supported.
 """
 from __future__ import annotations
@@ -134,6 +136,49 @@ class _BlocksSolve(torch.autograd.Function):
         return (Gbar, Cbar, a if need[2] else None, beta if need[3] else None) + (None,) * 4
 
 
+class _CrossSolve(torch.autograd.Function):
+    """_BlocksSolve with a cross term: (G_blocks, M_blocks [B, (K-1) S C], C_blocks, g, c) -> (lam, dz) of the original problem."""
+
+    @staticmethod
+    def forward(ctx, Gb, Mb, Cb, g, c, sol, rho, exit_tol, max_iters):
+        B = sol.batch
+        lam = torch.empty(B, sol.sizes["sk"], dtype=g.dtype, device=g.device)
+        dz = torch.empty(B, sol.N, dtype=g.dtype, device=g.device)
+        sol.linsys_blocks_cross(Gb, Mb, Cb, g, c, exit_tol, max_iters, rho, lam, dz)
+        sol.check_status()
+        ctx.sol, ctx.opts, ctx.gen = sol, (rho, exit_tol, max_iters), sol.get_option("assembly_gen")
+        ctx.save_for_backward(Gb, Mb, Cb, g, c, lam, dz)
+        ctx.set_materialize_grads(False)
+        return lam, dz
+
+    @staticmethod
+    def jvp(ctx, *_):
+        raise NotImplementedError("kkt_solve: forward mode with a cross term M is not built (DESIGN.md section 3.15); use reverse "
+                                  "mode, or kkt_solve without M")
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, lam_bar, dz_bar):
+        Gb, Mb, Cb, g, c, lam, dz = ctx.saved_tensors
+        sol = ctx.sol
+        rho, exit_tol, max_iters = ctx.opts
+        if lam_bar is None and dz_bar is None:
+            return (None,) * 9
+        if sol.get_option("assembly_gen") != ctx.gen or sol.get_option("assembly_valid") == 0:
+            sol.linsys_blocks_cross(Gb, Mb, Cb, g, c, exit_tol, max_iters, rho)    # another forward replaced the assembly
+            sol.check_status()
+        a, beta = _adjoint(sol, lam, dz, lam_bar, dz_bar, exit_tol, max_iters, cross=True)
+        need = ctx.needs_input_grad
+        Gbar = torch.empty_like(Gb) if need[0] else None
+        Mbar = torch.empty_like(Mb) if need[1] else None
+        Cbar = torch.empty_like(Cb) if need[2] else None
+        if Gbar is not None or Cbar is not None:
+            sol.kkt_grad_blocks(dz, lam, a, beta, Gbar, Cbar)
+        if Mbar is not None and Mbar.numel():
+            sol.kkt_grad_cross(dz, a, Mbar)
+        return (Gbar, Mbar, Cbar, a if need[3] else None, beta if need[4] else None) + (None,) * 4
+
+
 def _fresh(sol, gen, what):
     """RuntimeError unless the solver's assembly is still that of generation gen: a tangent re-solves it and never rebuilds it."""
     if sol.get_option("assembly_gen") != gen or sol.get_option("assembly_valid") == 0:
@@ -146,12 +191,13 @@ def _dots(dots, dtype):
     return {k: t.to(dtype).contiguous() for k, t in dots.items() if t is not None}
 
 
-def _adjoint(sol, lam, dz, lam_bar, dz_bar, exit_tol, max_iters):
-    """[a; beta] = M^-1 [dz_bar; lam_bar]: one re-solve of the current assembly (a missing gradient is zero)."""
+def _adjoint(sol, lam, dz, lam_bar, dz_bar, exit_tol, max_iters, cross=False):
+    """[a; beta] = M^-1 [dz_bar; lam_bar]: one re-solve of the current assembly (a missing gradient is zero).  cross: the
+    assembly is a cross solve's and the re-solve is solve_rhs_cross (the adjoint in the original variables)."""
     gin = torch.zeros_like(dz) if dz_bar is None else dz_bar.to(dz.dtype).contiguous()
     cin = torch.zeros_like(lam) if lam_bar is None else lam_bar.to(lam.dtype).contiguous()
     sol.reserve_rhs(1)
-    beta, a, _ = sol.solve_rhs(gin, cin, exit_tol, max_iters)
+    beta, a, _ = (sol.solve_rhs_cross if cross else sol.solve_rhs)(gin, cin, exit_tol, max_iters)
     sol.check_status()              # a hand-off time-out (iters = -1) raises, as in the forward; running to max_iters does not
     # a system whose right-hand side is all zero has a zero adjoint; its PCG would divide 0 by 0 (eta / p.Sp) instead
     zero = ~(gin.ne(0).any(1) | cin.ne(0).any(1))[:, None]
@@ -177,16 +223,35 @@ def _dz_layout(xv, uv):
     return torch.cat([torch.cat([xv[:, :K - 1], uv], 2).reshape(Bt, -1), xv[:, K - 1]], 1).contiguous()
 
 
-def kkt_solve(Q, R, A, B, q, r, c, *, rho, exit_tol, max_iters):
+def _check_cross(M, lead, K, S, C, ref, what):
+    """M [*, K-1, S, C] of ref's dtype and device; ValueError before any solver is created otherwise."""
+    if not isinstance(M, torch.Tensor):
+        raise ValueError(f"{what}: M must be a torch.Tensor, got {type(M).__name__}")
+    if tuple(M.shape) != lead + (K - 1, S, C):
+        raise ValueError(f"{what}: M has shape {tuple(M.shape)}, want {lead + (K - 1, S, C)} (S = {S}, C = {C}, K = {K})")
+    if M.dtype != ref.dtype:
+        raise ValueError(f"{what}: M is {M.dtype}, the other values are {ref.dtype}")
+    if M.device != ref.device:
+        raise ValueError(f"{what}: M is on {M.device}, the other values are on {ref.device}")
+
+
+def kkt_solve(Q, R, A, B, q, r, c, *, M=None, rho, exit_tol, max_iters):
     """Differentiable KKT solve from math-shaped blocks, at most one leading batch dimension:
     Q [*,K,S,S], R [*,K-1,C,C], A [*,K-1,S,S], B [*,K-1,S,C], q [*,K,S], r [*,K-1,C], c [*,K,S] (A, B as stored in C: the
     raw values, -A and -B of the dynamics).  Returns flat lam [*, S K] and dz [*, N], as linsys_solve does.
-    Q, R are taken as symmetric: their gradients are those of symmetric perturbations."""
+    Q, R are taken as symmetric: their gradients are those of symmetric perturbations.
+    M [*,K-1,S,C]: the stage cost gains x_k^T M_k u_k, G_k = [[Q_k, M_k], [M_k^T, R_k]]; every G_k + rho I
+    must be positive definite (not checked).  Its gradient is that of M_k and M_k^T perturbed together.  Reverse mode only:
+    under torch.autograd.forward_ad a given M raises NotImplementedError.  M=None is the solve without a cross term."""
     args = dict(Q=Q, R=R, A=A, B=B, q=q, r=r, c=c)
-    batched, _, K, S, C = _check_blocks(args, "kkt_solve")
+    batched, lead, K, S, C = _check_blocks(args, "kkt_solve")
     if K < 1 or S < 1 or C < 1:
         raise ValueError(f"kkt_solve: S = {S}, C = {C}, K = {K} must all be >= 1")
+    if M is not None:
+        _check_cross(M, lead, K, S, C, Q, "kkt_solve")
     device, dtype = _common(args, "kkt_solve")
+    if M is not None:
+        return _kkt_solve_cross(Q, R, A, B, q, r, c, M, batched, K, S, C, device, dtype, _opts(rho, exit_tol, max_iters))
     if not batched:
         Q, R, A, B, q, r, c = (t.unsqueeze(0) for t in (Q, R, A, B, q, r, c))
     Bt = Q.shape[0]
@@ -194,6 +259,18 @@ def kkt_solve(Q, R, A, B, q, r, c, *, rho, exit_tol, max_iters):
     Gb, Cb, g, cc = _pack(Q, R, A, B, q, r, c)
     sol = _solver(S, C, K, Bt, dtype, device)
     lam, dz = _BlocksSolve.apply(Gb, Cb, g, cc, sol, rho, exit_tol, max_iters)
+    return (lam, dz) if batched else (lam[0], dz[0])
+
+
+def _kkt_solve_cross(Q, R, A, B, q, r, c, M, batched, K, S, C, device, dtype, opts):
+    """kkt_solve with a checked M: the pack of kkt_solve, M in the layout of B, then _CrossSolve."""
+    if not batched:
+        Q, R, A, B, q, r, c, M = (t.unsqueeze(0) for t in (Q, R, A, B, q, r, c, M))
+    Bt = Q.shape[0]
+    Gb, Cb, g, cc = _pack(Q, R, A, B, q, r, c)
+    Mb = M.transpose(-1, -2).reshape(Bt, (K - 1) * S * C).contiguous()                 # column-major per knot
+    sol = _solver(S, C, K, Bt, dtype, device)
+    lam, dz = _CrossSolve.apply(Gb, Mb, Cb, g, cc, sol, *opts)
     return (lam, dz) if batched else (lam[0], dz[0])
 
 

@@ -231,6 +231,8 @@ extern "C" int gato_solver_destroy(gato_solver *s)
     if (s->rhs_ws) (void)hipFree(s->rhs_ws);
     if (s->qp_ws) (void)hipFree(s->qp_ws);
     if (s->pol_ws) (void)hipFree(s->pol_ws);
+    if (s->cross_ws) (void)hipFree(s->cross_ws);
+    if (s->cross_rhs_ws) (void)hipFree(s->cross_rhs_ws);
     if (s->in_arena) (void)hipFree(s->in_arena);
     for (int i = 0; i < 2; ++i)
         if (s->host_ev[i]) (void)hipEventDestroy(s->host_ev[i]);
@@ -255,6 +257,15 @@ extern "C" void *gato_solver_buffer(gato_solver *s, int which)
         case 10: return s->eta_hist;                              // double[max_iters + 1] (option record_eta)
         case 11: return s->rhs_ws;                                // gamma of the re-solves [B][rhs_R][S K] (nullptr: none reserved)
         case 12: return s->qp_pcg_total;                          // PCG iterations per system of the latest box QP solve [B] (int)
+        case 13: case 14: case 15: case 16: {                      // the cross-term work area: G', C', W, g' (nullptr: no cross solve yet)
+            if (!s->cross_ws) return nullptr;
+            const size_t e = s->esz, nb = (size_t)s->d.B;
+            size_t off = 0;
+            if (which > 13) off += align_up(s->d.g_dense() * e * nb);
+            if (which > 14) off += align_up(s->d.c_dense() * e * nb);
+            if (which > 15) off += align_up((size_t)(s->d.K - 1) * s->d.S * s->d.C * e * nb);
+            return s->cross_ws + off;
+        }
         default: return nullptr;
     }
 }

@@ -1,0 +1,158 @@
+// Host side of the stage-cost cross term (gato_cross.hip): the transformed problem in a work area of the
+// solver's own, the unchanged whole solve and re-solve on it, and the map back.
+#include "gato_solver.h"
+
+// The parts of cross_ws, as byte offsets: G' | C' | W | g'.  (gato_solver_buffer 13 .. 16 names them by the same sums.)
+struct CrossWs { size_t G, C, W, g, bytes; };
+static CrossWs cross_layout(const gato_solver *s)
+{
+    const size_t e = s->esz, nb = (size_t)s->d.B;
+    CrossWs o;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t at = off; off += align_up(bytes); return at; };
+    o.G = take(s->d.g_dense() * e * nb);
+    o.C = take(s->d.c_dense() * e * nb);
+    o.W = take((size_t)(s->d.K - 1) * s->d.S * s->d.C * e * nb);
+    o.g = take(s->d.N() * e * nb);
+    o.bytes = off ? off : 256;
+    return o;
+}
+
+// Grow-only: the first call of a solver (and the first re-solve of a larger R) allocates, no later one does.  Never while the
+// stream is being captured.
+static int grow(const char *who, char **ws, size_t *have, size_t bytes, hipStream_t st)
+{
+    if (bytes <= *have) return GATO_OK;
+    if (stream_is_capturing(st)) {
+        set_error("%s: the cross-term work area must grow and the stream is being captured; run the call once before the capture", who);
+        return GATO_EINVAL;
+    }
+    char *w = nullptr;
+    GATO_HIP_CHECK(hipStreamSynchronize(st));           // a call still queued may use the old area
+    GATO_HIP_CHECK(hipDeviceSynchronize());
+    GATO_HIP_CHECK(hipMalloc((void **)&w, bytes));
+    if (*ws) (void)hipFree(*ws);
+    *ws = w; *have = bytes;
+    return GATO_OK;
+}
+
+static Dims kernel_dims(const gato_solver *s)
+{
+    Dims d = s->d;
+    d.k_lo = d.k_hi = 0; d.rhs = 0;
+    return d;
+}
+
+// prepare into the work area; the assembly that read the area's C' (if any) is no longer the solver's
+static int prepare(gato_solver *s, const char *who, const void *d_G, const void *d_M, const void *d_C, const void *d_g, double rho,
+                   CrossWs *o, hipStream_t st)
+{
+    *o = cross_layout(s);
+    int rc;
+    if ((rc = grow(who, &s->cross_ws, &s->cross_ws_bytes, o->bytes, st))) return rc;
+    char *w = s->cross_ws;
+    s->cross.valid = 0;
+    if (s->as.Cd == w + o->C) s->as.valid = 0;
+    CrossArgs a{d_G, d_M, d_C, d_g, w + o->G, w + o->C, w + o->W, w + o->g, rho};
+    return cross_prepare(kernel_dims(s), s->dtype, a, st);
+}
+
+extern "C" int gato_cross_prepare(gato_solver *s, const void *d_G_blocks, const void *d_M_blocks, const void *d_C_blocks,
+                                  const void *d_g, double rho, void *stream)
+{
+    if (!solver_usable(s, "cross_prepare", "cross-term solves")) return GATO_EINVAL;
+    if (!d_G_blocks || !d_g || (s->d.K > 1 && (!d_M_blocks || !d_C_blocks))) {
+        set_error("cross_prepare: d_G_blocks and d_g are required, d_M_blocks and d_C_blocks too unless K = 1");
+        return GATO_EINVAL;
+    }
+    CrossWs o;
+    return prepare(s, "cross_prepare", d_G_blocks, d_M_blocks, d_C_blocks, d_g, rho, &o, (hipStream_t)stream);
+}
+
+static int check_stage(gato_solver *s, const char *who, int R, const void *p0, const void *p1)
+{
+    if (!solver_usable(s, who, "cross-term solves")) return GATO_EINVAL;
+    if (R < 1 || (long long)R * s->d.B > 65535) { set_error("%s: R = %d must be >= 1 and batch x R <= 65535 (batch %d)", who, R, s->d.B); return GATO_EINVAL; }
+    if (!p0 || !p1) { set_error("%s: every pointer is required", who); return GATO_EINVAL; }
+    if (!s->cross_ws) { set_error("%s: no W yet: run gato_linsys_device_blocks_cross or gato_cross_prepare first", who); return GATO_EINVAL; }
+    return GATO_OK;
+}
+
+extern "C" int gato_cross_rhs(gato_solver *s, int R, const void *d_g, void *d_gp, void *stream)
+{
+    int rc;
+    if ((rc = check_stage(s, "cross_rhs", R, d_g, d_gp))) return rc;
+    return cross_rhs(kernel_dims(s), s->dtype, R, s->cross_ws + cross_layout(s).W, d_g, d_gp, (hipStream_t)stream);
+}
+
+extern "C" int gato_cross_finish(gato_solver *s, int R, void *d_dz, void *stream)
+{
+    int rc;
+    if ((rc = check_stage(s, "cross_finish", R, d_dz, d_dz))) return rc;
+    return cross_finish(kernel_dims(s), s->dtype, R, s->cross_ws + cross_layout(s).W, d_dz, (hipStream_t)stream);
+}
+
+extern "C" int gato_linsys_device_blocks_cross(gato_solver *s, const void *d_G_blocks, const void *d_M_blocks, const void *d_C_blocks,
+                                               const void *d_g, const void *d_c, double exit_tol, int max_iters, double rho,
+                                               void *d_lambda, void *d_dz, void *stream)
+{
+    const char *who = "linsys_device_blocks_cross";
+    if (!solver_usable(s, who, "cross-term solves")) return GATO_EINVAL;
+    const int K = s->d.K;
+    if (!d_G_blocks || !d_g || !d_c || (K > 1 && (!d_M_blocks || !d_C_blocks))) {
+        set_error("%s: d_G_blocks, d_g and d_c are required, d_M_blocks and d_C_blocks too unless K = 1", who);
+        return GATO_EINVAL;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    int rc;
+    if (K == 1) {                                                            // no M at all: the plain solve
+        if ((rc = gato_linsys_device_blocks(s, d_G_blocks, d_C_blocks, d_g, d_c, exit_tol, max_iters, rho, d_lambda, d_dz, stream))) return rc;
+        s->cross = {1, s->as.gen};
+        return GATO_OK;
+    }
+    CrossWs o;
+    if ((rc = prepare(s, who, d_G_blocks, d_M_blocks, d_C_blocks, d_g, rho, &o, st))) return rc;
+    char *w = s->cross_ws;
+    void *dz = d_dz ? d_dz : s->dz;
+    const AsmInput in{2, nullptr, nullptr, w + o.G, nullptr, nullptr, nullptr, w + o.C, false};
+    if ((rc = whole_solve(s, pcg_opts(*s), in, w + o.g, d_c, exit_tol, max_iters, rho, d_lambda ? d_lambda : s->lambda, dz, st))) return rc;
+    s->lc.valid = 0;                                                         // a recover would leave dz in the transformed variables
+    if ((rc = cross_finish(kernel_dims(s), s->dtype, 1, w + o.W, dz, st))) return rc;
+    s->cross = {1, s->as.gen};
+    return GATO_OK;
+}
+
+extern "C" int gato_solve_rhs_cross(gato_solver *s, int R, const void *d_g, const void *d_c, double exit_tol, int max_iters,
+                                    void *d_lambda, void *d_dz, int *d_iters, void *stream)
+{
+    const char *who = "solve_rhs_cross";
+    if (!solver_usable(s, who, "cross-term solves")) return GATO_EINVAL;
+    if (!s->cross.valid || !s->as.valid || s->cross.gen != s->as.gen) {
+        set_error("%s: the solver's current assembly is not that of a cross solve: run gato_linsys_device_blocks_cross first; any "
+                  "other whole solve, box-QP call or stage entry since then replaces it", who);
+        return GATO_EINVAL;
+    }
+    if (R < 1 || (long long)R * s->d.B > 65535) {
+        set_error("%s: R = %d must be >= 1 and batch x R <= 65535 (batch %d)", who, R, s->d.B);
+        return GATO_EINVAL;
+    }
+    if (!d_g || !d_c || !d_lambda || !d_dz) { set_error("%s: d_g, d_c, d_lambda and d_dz are required", who); return GATO_EINVAL; }
+    hipStream_t st = (hipStream_t)stream;
+    if (s->d.K == 1) return solve_rhs(s, pcg_opts(*s), R, d_g, d_c, exit_tol, max_iters, d_lambda, d_dz, d_iters, st);
+    int rc;
+    if ((rc = grow(who, &s->cross_rhs_ws, &s->cross_rhs_ws_bytes, (size_t)s->d.B * R * s->d.N() * s->esz, st))) return rc;
+    const void *W = s->cross_ws + cross_layout(s).W;
+    const Dims d = kernel_dims(s);
+    if ((rc = cross_rhs(d, s->dtype, R, W, d_g, s->cross_rhs_ws, st))) return rc;
+    if ((rc = solve_rhs(s, pcg_opts(*s), R, s->cross_rhs_ws, d_c, exit_tol, max_iters, d_lambda, d_dz, d_iters, st))) return rc;
+    s->lc.valid = 0;                                                         // as in the whole solve
+    return cross_finish(d, s->dtype, R, W, d_dz, st);
+}
+
+extern "C" int gato_kkt_grad_cross(gato_solver *s, const void *d_dz, const void *d_adz, void *d_Mbar, void *stream)
+{
+    if (!solver_usable(s, "kkt_grad_cross", "gradients")) return GATO_EINVAL;
+    if (s->d.K == 1) return GATO_OK;                                         // no M at all
+    if (!d_dz || !d_adz || !d_Mbar) { set_error("kkt_grad_cross: d_dz, d_adz and d_Mbar are required"); return GATO_EINVAL; }
+    return cross_grad(kernel_dims(s), s->dtype, d_dz, d_adz, d_Mbar, (hipStream_t)stream);
+}

@@ -113,6 +113,14 @@ struct gato_solver {
     int *qp_pcg_total;                // in qp_ws: PCG iterations of every x-step of the latest QP solve, per system [B]
     char *pol_ws;                     // polish work area (gato_box_qp_polish; pdas_loop for every active-set entry; layouts: PolishWs, AlmWs in gato_qp_host.hip): g' | c' | dz' | lambda' | x, z, y polished | [act'] | [line search: xc | knot partials] | slots | counts | [gato_box_qp_alm: the inner runs' inputs and point, mu, its state and counts]
     size_t pol_ws_bytes;              // only grows
+    char *cross_ws;                   // cross-term work area (gato_cross_host.hip): G' [B][G_dense] | C' [B][C_dense] | W [B][(K-1) S C] | g' [B][N]
+    size_t cross_ws_bytes;            // only grows
+    char *cross_rhs_ws;               // g' of the cross re-solves [B][R][N], apart from cross_ws: a growing R must not move the C' a live assembly reads
+    size_t cross_rhs_ws_bytes;        // only grows
+    struct {                          // the most recent cross whole solve, for gato_solve_rhs_cross
+        int valid;
+        unsigned long long gen;       // its as.gen: another assembly since then is not a cross one
+    } cross;
 };
 
 inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
@@ -172,3 +180,14 @@ int solve_rhs(gato_solver *s, const PcgOpts &o, int R, const void *d_g, const vo
 int pcg_rhs(gato_solver *s, const PcgOpts &o, int R, const void *gam, void *lam, double exit_tol, int max_iters, int *its, hipStream_t st);
 int dz_rhs(gato_solver *s, int R, const void *g, const void *lam, void *dz, hipStream_t st);
 int *rhs_iters(gato_solver *s);
+
+// ---- cross term in the stage cost (gato_cross.hip; host side gato_cross_host.hip) ---------------------------------------------
+struct CrossArgs {
+    const void *G, *M, *Cd, *g;       // the caller's blocks (G without rho, C raw), M [B][(K-1) S C] and g [B][N]; never written
+    void *Gp, *Cp, *W, *gp;           // the work area: G' (Q'' | R), C' (A^' | B^), W and g'
+    double rho;
+};
+int cross_prepare(const Dims &d, int dtype, const CrossArgs &a, hipStream_t st);
+int cross_rhs(const Dims &d, int dtype, int R, const void *W, const void *g, void *gp, hipStream_t st);      // g, gp [B][R][N]
+int cross_finish(const Dims &d, int dtype, int R, const void *W, void *dz, hipStream_t st);                  // dz [B][R][N], in place
+int cross_grad(const Dims &d, int dtype, const void *dz, const void *a, void *Mbar, hipStream_t st);

@@ -200,8 +200,100 @@ class Solver:
                                                 _ptr(Cbar_val), self._stream()))
         return Gbar_val, Cbar_val
 
+    # ---- a state-control cross term in the stage cost (gato_*_cross) --------------------------------
+    def _check_cross(self, what, **tensors):
+        """ValueError unless every given operand is a contiguous CUDA tensor of the solver's dtype and of its size: name ->
+        (tensor, entries)."""
+        for name, (t, n) in tensors.items():
+            if not isinstance(t, torch.Tensor) or t.numel() != n or t.dtype != self.dtype or not t.is_cuda or not t.is_contiguous():
+                got = f"{t.dtype} {tuple(t.shape)} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
+                raise ValueError(f"{what}: {name} must be a contiguous {self.dtype} CUDA tensor of {n} entries, got {got}")
+
+    @property
+    def M_size(self):
+        """Entries of M_blocks per system: (K - 1) S C."""
+        return (self.K - 1) * self.S * self.C
+
+    def _cross_inputs(self, what, G_blocks, M_blocks, C_blocks, g):
+        B = self.batch
+        ops = dict(G_blocks=(G_blocks, B * self.sizes["G_dense"]), g=(g, B * self.N))
+        if self.K > 1:
+            ops.update(M_blocks=(M_blocks, B * self.M_size), C_blocks=(C_blocks, B * self.sizes["C_dense"]))
+        self._check_cross(what, **ops)
+
+    def linsys_blocks_cross(self, G_blocks, M_blocks, C_blocks, g, c, exit_tol, max_iters, rho, lam=None, dz=None):
+        """linsys_blocks with the cross term x_k^T M_k u_k in the stage cost (gato_linsys_device_blocks_cross): M_blocks [B (K-1) S C],
+        per knot M_k S x C column-major as B_k lies in C_blocks (K = 1: None).  Every G_k + rho I must be positive definite.  lam
+        and dz are those of the original problem; the solver's assembly afterwards is the transformed one (solve_rhs_cross
+        re-solves the original problem, plain solve_rhs the transformed one).  Asynchronous but for a solver's first call."""
+        self._cross_inputs("linsys_blocks_cross", G_blocks, M_blocks, C_blocks, g)
+        outs = {k: (t, self.batch * n) for k, t, n in (("lam", lam, self.sizes["sk"]), ("dz", dz, self.N)) if t is not None}
+        self._check_cross("linsys_blocks_cross", c=(c, self.batch * self.sizes["sk"]), **outs)
+        _lib.check(_lib.lib().gato_linsys_device_blocks_cross(self._h, _ptr(G_blocks), _ptr(M_blocks if self.K > 1 else None),
+                                                              _ptr(C_blocks), _ptr(g), _ptr(c), float(exit_tol), int(max_iters),
+                                                              float(rho), _ptr(lam), _ptr(dz), self._stream()))
+
+    def solve_rhs_cross(self, g, c, exit_tol, max_iters, lam=None, dz=None, iters=None):
+        """solve_rhs for the original problem of the latest linsys_blocks_cross (gato_solve_rhs_cross): g [B][R][N], c [B][R][S K]
+        -> (lam [B R S K], dz [B R N], iters [B R]).  Raises when the solver's current assembly is not that cross solve's."""
+        B, N, sk = self.batch, self.N, self.sizes["sk"]
+        R = g.numel() // (B * N) if isinstance(g, torch.Tensor) and g.numel() % (B * N) == 0 else 0
+        if R < 1 or c.numel() != B * R * sk:
+            raise ValueError(f"solve_rhs_cross: g and c must hold B*R*N and B*R*S*K entries with B = {B}, N = {N}, S*K = {sk}, R >= 1")
+        lam = self.new(B * R * sk) if lam is None else lam
+        dz = self.new(B * R * N) if dz is None else dz
+        iters = self.new(B * R, torch.int32) if iters is None else iters
+        self._check_cross("solve_rhs_cross", g=(g, B * R * N), c=(c, B * R * sk), lam=(lam, B * R * sk), dz=(dz, B * R * N))
+        if iters.numel() != B * R or iters.dtype != torch.int32:
+            raise ValueError("solve_rhs_cross: iters must hold B*R int32 entries")
+        _lib.check(_lib.lib().gato_solve_rhs_cross(self._h, R, _ptr(g), _ptr(c), float(exit_tol), int(max_iters), _ptr(lam),
+                                                   _ptr(dz), _ptr(iters), self._stream()))
+        return lam, dz, iters
+
+    def kkt_grad_cross(self, dz, adz, Mbar=None):
+        """M_bar [B (K-1) S C] (M's layout) of a cross solve from dz and the adjoint's a [B N], both in the original variables
+        (gato_kkt_grad_cross): -(a_x dz_u^T + dz_x a_u^T) per knot, M_k and M_k^T perturbed together."""
+        B = self.batch
+        Mbar = self.new(B * self.M_size) if Mbar is None else Mbar
+        self._check_cross("kkt_grad_cross", dz=(dz, B * self.N), adz=(adz, B * self.N), Mbar=(Mbar, B * self.M_size))
+        _lib.check(_lib.lib().gato_kkt_grad_cross(self._h, _ptr(dz), _ptr(adz), _ptr(Mbar), self._stream()))
+        return Mbar
+
+    def cross_prepare(self, G_blocks, M_blocks, C_blocks, g, rho):
+        """The first stage of linsys_blocks_cross alone (gato_cross_prepare): the transformed blocks, W and g' into the work area
+        (read_cross).  Forgets a recorded cross assembly."""
+        self._cross_inputs("cross_prepare", G_blocks, M_blocks, C_blocks, g)
+        _lib.check(_lib.lib().gato_cross_prepare(self._h, _ptr(G_blocks), _ptr(M_blocks if self.K > 1 else None), _ptr(C_blocks),
+                                                 _ptr(g), float(rho), self._stream()))
+
+    def cross_rhs(self, g, gp=None):
+        """g' [B R N] of R right-hand sides g [B R N] from the stored W (gato_cross_rhs)."""
+        R = g.numel() // (self.batch * self.N)
+        gp = self.new(g.numel()) if gp is None else gp
+        self._check_cross("cross_rhs", g=(g, self.batch * max(R, 1) * self.N), gp=(gp, g.numel()))
+        _lib.check(_lib.lib().gato_cross_rhs(self._h, R, _ptr(g), _ptr(gp), self._stream()))
+        return gp
+
+    def cross_finish(self, dz):
+        """u <- v - W x in place on R solutions dz [B R N] from the stored W (gato_cross_finish)."""
+        R = dz.numel() // (self.batch * self.N)
+        self._check_cross("cross_finish", dz=(dz, self.batch * max(R, 1) * self.N))
+        _lib.check(_lib.lib().gato_cross_finish(self._h, R, _ptr(dz), self._stream()))
+        return dz
+
+    _CROSS_BUFFERS = dict(G=13, C=14, W=15, g=16)
+
+    def cross_buffer_ptr(self, name: str) -> int:
+        return self.buffer_ptr(self._CROSS_BUFFERS[name])
+
+    def read_cross(self, name: str):
+        """Host copy of a part of the cross-term work area (all systems): G (Q'' | R), C (A^' | B^), W or g (g')."""
+        n = dict(G=self.sizes["G_dense"], C=self.sizes["C_dense"], W=self.M_size, g=self.N)[name] * self.batch
+        out = np.empty(n, self.np_dtype)
+        return out if n == 0 else self._read_device(self.cross_buffer_ptr(name), out)
+
     # ---- forward-mode sensitivities (gato_kkt_tangent_rhs, DESIGN.md section 3.13) ------------------------------------------
-    _TANGENTS = dict(G_dot="G_dense", C_dot="C_dense", g_dot=None, c_dot="sk", lo_dot=None, hi_dot=None, w_dot=None, m_dot=None)
+    _TANGENTS =dict(G_dot="G_dense", C_dot="C_dense", g_dot=None, c_dot="sk", lo_dot=None, hi_dot=None, w_dot=None, m_dot=None)
 
     def kkt_tangent_rhs(self, R, x, lam, *, G_dot=None, C_dot=None, g_dot=None, c_dot=None, lo_dot=None, hi_dot=None, w_dot=None,
                         m_dot=None, Gb=None, Cb=None, act=None, soft_weight=None, soft_cap=None, lo=None, hi=None, tg=None, tc=None):

@@ -112,6 +112,22 @@ def make_blocks(S: int, C: int, K: int, seed: int = 0, dense_q: bool = False):
     return Q, R, A, B, q, r, c
 
 
+def make_cross(Q, R, seed: int = 0, scale: float = 0.5):
+    """Seeded cross blocks M[K-1,S,C] for the stage cost x_k^T M_k u_k: M_k = scale L_Q Z L_R^T with
+    Q_k = L_Q L_Q^T, R_k = L_R L_R^T (Cholesky) and Z Gaussian, divided by its spectral norm.  For |scale| < 1 every
+    G_k = [[Q_k, M_k], [M_k^T, R_k]] is positive definite and Q_k - M_k R_k^-1 M_k^T >= (1 - scale^2) Q_k."""
+    Q, R = np.asarray(Q, np.float64), np.asarray(R, np.float64)
+    K1, C = R.shape[0], R.shape[-1]
+    S = Q.shape[-1]
+    rng = np.random.default_rng(seed)
+    M = np.zeros((K1, S, C))
+    for k in range(K1):
+        Z = rng.standard_normal((S, C))
+        Z /= np.linalg.norm(Z, 2)
+        M[k] = scale * np.linalg.cholesky(Q[k]) @ Z @ np.linalg.cholesky(R[k]).T
+    return M
+
+
 def blocks_to_csr(Q, R, A, B, q, r, c, rho: float = 1e-3, dense_q: bool | None = None) -> KKTSystem:
     """Emit the CSR arrays exactly as scipy.sparse.csr_matrix(...).indptr/.indices/.data
     would (sorted columns, explicit structural entries only), cf. test_pendulum_5.py:28-29."""

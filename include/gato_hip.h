@@ -81,7 +81,9 @@ int gato_solver_destroy(gato_solver *s);
  * 10 eta history (double[max_iters+1]: eta = r.Pinv r after the initial step and after every iteration; filled when
  * option record_eta = 1 and max_iters <= 4096 - the reference only prints it under DEBUG_MODE, gato_pcg.cuh:397-400),
  * 11 gamma of the re-solves (gato_solve_rhs: its first B*R*S*K entries are [B][R][S*K] of the latest re-solve of R
- * right-hand sides; NULL before gato_solver_reserve_rhs or the first re-solve) */
+ * right-hand sides; NULL before gato_solver_reserve_rhs or the first re-solve),
+ * 13 .. 16 the cross-term work area (gato_linsys_device_blocks_cross): G' [B][G_dense], C' [B][C_dense], W [B][(K-1)*S*C],
+ * g' [B][N]; NULL before the first cross call */
 void *gato_solver_buffer(gato_solver *s, int which);
 /* Options: pcg_mode (GATO_PCG_*), pcg_threads (0 = auto; threads per workgroup of the resident
  * kernel), pcg_groups (0 = auto; workgroups of the resident kernel), true_warm_start (0 = the
@@ -573,6 +575,42 @@ int gato_kkt_tangent_rhs(gato_solver *s, int R, const void *d_G_dot, const void 
 int gato_linsys_device_blocks(gato_solver *s, const void *d_G_blocks, const void *d_C_blocks, const void *d_g,
                               const void *d_c, double exit_tol, int max_iters, double rho, void *d_lambda, void *d_dz,
                               void *stream);
+
+/* ---- a state-control cross term in the stage cost (new) ------------------------------------------------
+ * G_k = [[Q_k, M_k], [M_k^T, R_k]] for k < K-1 (the last knot has no M; K = 1 has none at all): the term x_k^T M_k u_k that the
+ * block-diagonal inputs cannot express (the CSR scatter drops such entries).  d_M_blocks is [B][(K-1)*S*C], per knot M_k S x C
+ * column-major, as B_k lies in C_dense.  Every G_k + rho I must be positive definite (documented, not checked - as an
+ * indefinite Q_k is not checked today).
+ * The cross term is removed by the per-knot change of variables u_k = v_k - W_k x_k, W_k = (R_k + rho I)^-1 M_k^T (C x S):
+ *     Q''_k = Q_k - M_k W_k,   A^'_k = A^_k - B^_k W_k,   g'_x,k = g_x,k - W_k^T g_u,k;   R_k, B^_k, g_u, c, lambda unchanged
+ * (A^, B^: the raw values of C_dense).  One launch writes the transformed blocks and W into a work area of the solver's own
+ * (the caller's arrays are never written), the unchanged path of gato_linsys_device_blocks solves the transformed problem, one
+ * launch maps dz back in place.  lambda is that of the original problem.  Asynchronous as gato_linsys_device_blocks is, but
+ * for the first call of a solver, which allocates the work area (so: once before a graph capture).  The call records that
+ * the solver's current assembly is a cross one.  K = 1: d_M_blocks may be NULL and the call is the plain solve.
+ * After a cross solve the solver's assembly is the TRANSFORMED system: plain gato_solve_rhs solves that one, in the variables
+ * (x, v) for a right-hand side in g' form; gato_solver_recover does not apply (it reports the time-out). */
+int gato_linsys_device_blocks_cross(gato_solver *s, const void *d_G_blocks, const void *d_M_blocks, const void *d_C_blocks,
+                                    const void *d_g, const void *d_c, double exit_tol, int max_iters, double rho,
+                                    void *d_lambda, void *d_dz, void *stream);
+/* gato_solve_rhs for the original problem of the latest cross solve: R right-hand sides per system, d_g [B][R][N] -> g' (one
+ * launch, from the stored W), the re-solve, dz mapped back in place (one launch).  Arguments as gato_solve_rhs.  GATO_EINVAL
+ * when the solver's current assembly is not the cross one recorded (another whole solve, a box-QP call or a stage entry
+ * replaced it).  A larger R than any before allocates (not while capturing). */
+int gato_solve_rhs_cross(gato_solver *s, int R, const void *d_g, const void *d_c, double exit_tol, int max_iters,
+                         void *d_lambda, void *d_dz, int *d_iters, void *stream);
+/* The gradient of a cross solve with respect to M from dz and the adjoint's a (gato_solve_rhs_cross with g = dz_bar, c =
+ * lambda_bar), both in the original variables: M_bar_k = -(a_x,k dz_u,k^T + dz_x,k a_u,k^T), [B][(K-1)*S*C] in M's layout - the
+ * gradient for M_k and M_k^T perturbed together.  Q_bar, R_bar, A_bar, B_bar are gato_kkt_grad_blocks on the same vectors;
+ * g_bar = a, c_bar = beta.  Reads no assembly.  K = 1: nothing to write. */
+int gato_kkt_grad_cross(gato_solver *s, const void *d_dz, const void *d_adz, void *d_Mbar, void *stream);
+/* The three stages alone (tests, and callers that run the solve between them themselves): the transformed blocks, W and g'
+ * into the work area (buffers 13 .. 16; a cross assembly recorded before is forgotten); g' [B][R][N] of R right-hand sides from
+ * the stored W; u <- v - W x in place on d_dz [B][R][N]. */
+int gato_cross_prepare(gato_solver *s, const void *d_G_blocks, const void *d_M_blocks, const void *d_C_blocks, const void *d_g,
+                       double rho, void *stream);
+int gato_cross_rhs(gato_solver *s, int R, const void *d_g, void *d_gp, void *stream);
+int gato_cross_finish(gato_solver *s, int R, void *d_dz, void *stream);
 
 #ifdef __cplusplus
 }
