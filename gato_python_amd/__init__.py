@@ -12,6 +12,7 @@ Public surface:
                                          line_search=True: the exact line search that makes the all-soft iteration converge),
                                          or by the method of multipliers over that iteration (method="alm": hard bounds on
                                          states too, where ADMM is slow and the hard active-set iteration cycles)
+  gato_python_amd.box_qp(..., M=M)       the ADMM solve with the cross term x_k^T M_k u_k in the stage cost
   gato_python_amd.box_qp_layer(...)      differentiable box-constrained QP: ADMM, then the polish on its active set, or the
                                          active-set iteration alone, with hard or soft bounds (one autograd Function,
                                          qp._BoxQPLayer, whose backward branches on "weights present"); line_search=True

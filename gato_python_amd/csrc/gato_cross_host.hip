@@ -2,8 +2,7 @@
 // solver's own, the unchanged whole solve and re-solve on it, and the map back.
 #include "gato_solver.h"
 
-// The parts of cross_ws, as byte offsets: G' | C' | W | g'.  (gato_solver_buffer 13 .. 16 names them by the same sums.)
-struct CrossWs { size_t G, C, W, g, bytes; };
+// The parts of cross_ws (CrossWs, gato_solver.h)
 static CrossWs cross_layout(const gato_solver *s)
 {
     const size_t e = s->esz, nb = (size_t)s->d.B;
@@ -44,8 +43,8 @@ static Dims kernel_dims(const gato_solver *s)
 }
 
 // prepare into the work area; the assembly that read the area's C' (if any) is no longer the solver's
-static int prepare(gato_solver *s, const char *who, const void *d_G, const void *d_M, const void *d_C, const void *d_g, double rho,
-                   CrossWs *o, hipStream_t st)
+int cross_prepare_ws(gato_solver *s, const char *who, const void *d_G, const void *d_M, const void *d_C, const void *d_g, double rho,
+                     CrossWs *o, hipStream_t st)
 {
     *o = cross_layout(s);
     int rc;
@@ -66,7 +65,7 @@ extern "C" int gato_cross_prepare(gato_solver *s, const void *d_G_blocks, const 
         return GATO_EINVAL;
     }
     CrossWs o;
-    return prepare(s, "cross_prepare", d_G_blocks, d_M_blocks, d_C_blocks, d_g, rho, &o, (hipStream_t)stream);
+    return cross_prepare_ws(s, "cross_prepare", d_G_blocks, d_M_blocks, d_C_blocks, d_g, rho, &o, (hipStream_t)stream);
 }
 
 static int check_stage(gato_solver *s, const char *who, int R, const void *p0, const void *p1)
@@ -111,7 +110,7 @@ extern "C" int gato_linsys_device_blocks_cross(gato_solver *s, const void *d_G_b
         return GATO_OK;
     }
     CrossWs o;
-    if ((rc = prepare(s, who, d_G_blocks, d_M_blocks, d_C_blocks, d_g, rho, &o, st))) return rc;
+    if ((rc = cross_prepare_ws(s, who, d_G_blocks, d_M_blocks, d_C_blocks, d_g, rho, &o, st))) return rc;
     char *w = s->cross_ws;
     void *dz = d_dz ? d_dz : s->dz;
     const AsmInput in{2, nullptr, nullptr, w + o.G, nullptr, nullptr, nullptr, w + o.C, false};

@@ -91,24 +91,26 @@ extern "C" void gato_box_qp_default_params(gato_box_qp_params *p)
 
 // One call: prepare, the whole solve on G' (the only assembly), then re-solve + update per iteration and a last launch
 // that only tests.  Frozen systems are never written again, so the outputs do not depend on check_every.
-extern "C" int gato_box_qp_solve(gato_solver *s, const void *d_G_blocks, const void *d_C_blocks, const void *d_g,
-                                 const void *d_c, const void *d_lo, const void *d_hi, const gato_box_qp_params *p, void *d_x,
-                                 void *d_z, void *d_y, void *d_lambda, int *d_iters, int *d_status, double *d_res,
-                                 void *stream)
+// d_M_blocks (NULL: none): the cross blocks of gato_box_qp_solve_cross.  The cross prepare stage then
+// transforms (G', M, C, g~0) into cross_ws, the whole solve and the re-solves run on that assembly in the variables (x, v), and
+// qp_update_cross_kernel takes the place of qp_update_kernel: the iterates, the box and the residuals stay in (x, u).
+static int admm_solve(gato_solver *s, const char *who, const void *d_G_blocks, const void *d_M_blocks, const void *d_C_blocks,
+                      const void *d_g, const void *d_c, const void *d_lo, const void *d_hi, const gato_box_qp_params *p, void *d_x,
+                      void *d_z, void *d_y, void *d_lambda, int *d_iters, int *d_status, double *d_res, void *stream)
 {
-    if (check_pointers(s, "box_qp_solve", p, d_C_blocks,
-                       {d_G_blocks, d_g, d_c, d_lo, d_hi, d_x, d_z, d_y, d_lambda, d_iters, d_status, d_res}))
+    if (check_pointers(s, who, p, d_C_blocks, {d_G_blocks, d_g, d_c, d_lo, d_hi, d_x, d_z, d_y, d_lambda, d_iters, d_status, d_res}))
         return GATO_EINVAL;
     const bool fin = std::isfinite(p->rho) && std::isfinite(p->admm_rho) && std::isfinite(p->sigma) && std::isfinite(p->alpha) &&
                      std::isfinite(p->eps_abs) && std::isfinite(p->eps_rel) && std::isfinite(p->exit_tol);
     if (!fin || p->rho < 0 || !(p->admm_rho > 0) || p->sigma < 0 || !(p->alpha > 0 && p->alpha < 2) || p->eps_abs < 0 ||
         p->eps_rel < 0 || p->exit_tol < 0 || p->max_iters < 1 || p->max_admm_iters < 1 || p->check_every < 1) {
-        set_error("box_qp_solve: parameters out of range (want finite values, rho >= 0, admm_rho > 0, sigma >= 0, 0 < alpha < 2, "
-                  "eps_abs, eps_rel, exit_tol >= 0, max_iters, max_admm_iters, check_every >= 1)");
+        set_error("%s: parameters out of range (want finite values, rho >= 0, admm_rho > 0, sigma >= 0, 0 < alpha < 2, "
+                  "eps_abs, eps_rel, exit_tol >= 0, max_iters, max_admm_iters, check_every >= 1)", who);
         return GATO_EINVAL;
     }
     hipStream_t st = (hipStream_t)stream;
-    if (check_not_capturing("box_qp_solve", "the loop reads the live count", st)) return GATO_EINVAL;
+    if (check_not_capturing(who, "the loop reads the live count", st)) return GATO_EINVAL;
+    const bool cross = d_M_blocks != nullptr;
     GATO_HIP_CHECK(hipSetDevice(s->device));
     int rc = gato_solver_reserve_rhs(s, 1);
     if (rc) return rc;
@@ -117,12 +119,15 @@ extern "C" int gato_box_qp_solve(gato_solver *s, const void *d_G_blocks, const v
     const size_t o_Gp = 0, o_rho = o_Gp + align_up(B * d.g_dense() * e), o_x0 = o_rho + vN, o_x1 = o_x0 + vN, o_gt = o_x1 + vN;
     const size_t o_dz = o_gt + vN, o_lt = o_dz + vN, o_sl = o_lt + vK;
     const size_t o_tot = o_sl + align_up(B * 3 * GATO_QP_NSLOT * 8), o_ctr = o_tot + align_up(B * sizeof(int));
-    const size_t bytes = o_ctr + 256;
+    // option qp_cross_unfused: a W of zeros (zeroed with the counters) and the right-hand side cross_rhs transforms into
+    const bool unfused = cross && s->qp_cross_unfused;
+    const size_t o_W0 = o_ctr + 256, o_gp = o_W0 + (unfused ? align_up(B * (size_t)(d.K - 1) * d.S * d.C * e) : 0);
+    const size_t zero_end = unfused ? o_gp : o_ctr + 256, bytes = o_gp + (unfused ? vN : 0);
     if ((rc = grow_ws(&s->qp_ws, &s->qp_ws_bytes, bytes, st))) return rc;
     char *w = s->qp_ws;
     int *ctr = (int *)(w + o_ctr);
     s->qp_pcg_total = (int *)(w + o_tot);
-    if ((rc = start_call(w, o_sl, bytes, d_status, B, st))) return rc;                 // slots, PCG totals, counters
+    if ((rc = start_call(w, o_sl, zero_end, d_status, B, st))) return rc;              // slots, PCG totals, counters
     if (p->warm) GATO_HIP_CHECK(hipMemcpyAsync(w + o_lt, d_lambda, B * d.sk() * e, hipMemcpyDeviceToDevice, st));
     QpArgs a;
     memset(&a, 0, sizeof(a));
@@ -138,32 +143,84 @@ extern "C" int gato_box_qp_solve(gato_solver *s, const void *d_G_blocks, const v
     GATO_HIP_CHECK(hipMemcpyAsync(h, ctr, sizeof(h), hipMemcpyDeviceToHost, st));
     GATO_HIP_CHECK(hipStreamSynchronize(st));
     if (h[1] > 0) {
-        set_error("box_qp_solve: %d bound(s) with lo > hi or NaN; d_status marks the systems (3 = BAD_BOUNDS)", h[1]);
+        set_error("%s: %d bound(s) with lo > hi or NaN; d_status marks the systems (3 = BAD_BOUNDS)", who, h[1]);
         return GATO_EINVAL;
     }
     PcgOpts o = pcg_opts(*s);
     o.warm = p->warm ? 1 : 0;                          // the first x-step: cold, or from the caller's lambda
-    const AsmInput in{2, nullptr, nullptr, w + o_Gp, nullptr, nullptr, nullptr, d_C_blocks, false};
-    if ((rc = whole_solve(s, o, in, w + o_gt, d_c, p->exit_tol, p->max_iters, p->rho, w + o_lt, w + o_dz, st))) return rc;
+    AsmInput in{2, nullptr, nullptr, w + o_Gp, nullptr, nullptr, nullptr, d_C_blocks, false};
+    const void *g0 = w + o_gt;
+    QpCrossArgs ca{a, d_M_blocks, nullptr};
+    if (cross) {                                       // (G', M, C, g~0) -> the transformed blocks, W and g~0' in cross_ws
+        CrossWs cw;
+        if ((rc = cross_prepare_ws(s, who, w + o_Gp, d_M_blocks, d_C_blocks, w + o_gt, p->rho, &cw, st))) return rc;
+        char *xw = s->cross_ws;
+        in.G_val = xw + cw.G; in.C_dense = xw + cw.C; g0 = xw + cw.g; ca.W = xw + cw.W;
+    }
+    // either update launch: the cross kernel reads and writes what qp_update_kernel does, and M and W
+    const Dims kd = kernel_dims(s);
+    auto update = [&](int it, int last) {
+        if (!cross) return s->ops->qp_update(d, a, it, last, st);
+        ca.q = a;
+        return qp_update_cross(kd, s->dtype, ca, it, last, st);
+    };
+    rc = whole_solve(s, o, in, g0, d_c, p->exit_tol, p->max_iters, p->rho, w + o_lt, w + o_dz, st);
+    if (cross) s->lc.valid = 0;                        // a recover would leave the x-step's solution in other variables than the loop reads
+    if (rc) return rc;
+    // unfused: the two maps of an iteration as cross_finish and cross_rhs launches, the update kernel's own with W = 0 the identity
+    const void *W = ca.W;
+    if (unfused) {
+        ca.W = w + o_W0;
+        if ((rc = cross_finish(kd, s->dtype, 1, W, w + o_dz, st))) return rc;
+    }
     o.warm = 1;                                        // every later x-step: lambda warm from the previous one
     for (int it = 0;; ++it) {
         a.xr = w + (it % 2 ? o_x1 : o_x0);
         a.xw = w + (it % 2 ? o_x0 : o_x1);
         a.pcg_its = it == 0 ? s->iters : rhs_iters(s);
-        if ((rc = s->ops->qp_update(d, a, it, 0, st))) return rc;
+        if ((rc = update(it, 0))) return rc;
         if (it + 1 == p->max_admm_iters) {
             a.xr = a.xw;
-            if ((rc = s->ops->qp_update(d, a, it + 1, 1, st))) return rc;        // the test of the last iterate only
+            if ((rc = update(it + 1, 1))) return rc;        // the test of the last iterate only
             break;
         }
         if ((it + 1) % p->check_every == 0) {               // systems still live, after the test of iterate it
-            if ((rc = read_live("box_qp_solve", ctr, h, st))) return rc;
+            if ((rc = read_live(who, ctr, h, st))) return rc;
             if (h[0] == 0) break;
         }
-        if ((rc = solve_rhs(s, o, 1, w + o_gt, d_c, p->exit_tol, p->max_iters, w + o_lt, w + o_dz, rhs_iters(s), st))) return rc;
+        if (unfused && (rc = cross_rhs(kd, s->dtype, 1, W, w + o_gt, w + o_gp, st))) return rc;
+        rc = solve_rhs(s, o, 1, w + (unfused ? o_gp : o_gt), d_c, p->exit_tol, p->max_iters, w + o_lt, w + o_dz, rhs_iters(s), st);
+        if (cross) s->lc.valid = 0;
+        if (rc) return rc;
+        if (unfused && (rc = cross_finish(kd, s->dtype, 1, W, w + o_dz, st))) return rc;
     }
     GATO_HIP_CHECK(hipStreamSynchronize(st));
     return gato_pcg_status(s, nullptr);
+}
+
+extern "C" int gato_box_qp_solve(gato_solver *s, const void *d_G_blocks, const void *d_C_blocks, const void *d_g,
+                                 const void *d_c, const void *d_lo, const void *d_hi, const gato_box_qp_params *p, void *d_x,
+                                 void *d_z, void *d_y, void *d_lambda, int *d_iters, int *d_status, double *d_res,
+                                 void *stream)
+{
+    return admm_solve(s, "box_qp_solve", d_G_blocks, nullptr, d_C_blocks, d_g, d_c, d_lo, d_hi, p, d_x, d_z, d_y, d_lambda, d_iters,
+                      d_status, d_res, stream);
+}
+
+// ---- the same with a state-control cross term in the stage cost (gato_qp_cross.hip) -------------------
+extern "C" int gato_box_qp_solve_cross(gato_solver *s, const void *d_G_blocks, const void *d_M_blocks, const void *d_C_blocks,
+                                       const void *d_g, const void *d_c, const void *d_lo, const void *d_hi,
+                                       const gato_box_qp_params *p, void *d_x, void *d_z, void *d_y, void *d_lambda, int *d_iters,
+                                       int *d_status, double *d_res, void *stream)
+{
+    const char *who = "box_qp_solve_cross";
+    if (!solver_usable(s, who, "QP solves")) return GATO_EINVAL;
+    if (s->d.K > 1 && !d_M_blocks) {
+        set_error("%s: d_M_blocks is required (it may be NULL only for K = 1, which has no cross term)", who);
+        return GATO_EINVAL;
+    }
+    return admm_solve(s, who, d_G_blocks, s->d.K > 1 ? d_M_blocks : nullptr, d_C_blocks, d_g, d_c, d_lo, d_hi, p, d_x, d_z, d_y,
+                      d_lambda, d_iters, d_status, d_res, stream);
 }
 
 // ---- polish of a box QP and its bound gradients (gato_polish.hip) --------------------------------

@@ -121,6 +121,7 @@ struct gato_solver {
         int valid;
         unsigned long long gen;       // its as.gen: another assembly since then is not a cross one
     } cross;
+    int qp_cross_unfused;             // option (measurement, tests): gato_box_qp_solve_cross runs cross_rhs and cross_finish as launches of their own around every re-solve and gives the update kernel W = 0
 };
 
 inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
@@ -191,3 +192,16 @@ int cross_prepare(const Dims &d, int dtype, const CrossArgs &a, hipStream_t st);
 int cross_rhs(const Dims &d, int dtype, int R, const void *W, const void *g, void *gp, hipStream_t st);      // g, gp [B][R][N]
 int cross_finish(const Dims &d, int dtype, int R, const void *W, void *dz, hipStream_t st);                  // dz [B][R][N], in place
 int cross_grad(const Dims &d, int dtype, const void *dz, const void *a, void *Mbar, hipStream_t st);
+// The parts of cross_ws, as byte offsets: G' | C' | W | g'.  (gato_solver_buffer 13 .. 16 names them by the same sums.)
+struct CrossWs { size_t G, C, W, g, bytes; };
+// cross_prepare into the solver's work area (grown if need be; *o: its parts).  A recorded cross assembly is forgotten, and the
+// assembly that read the area's C' (if any) is no longer the solver's.  who names the entry in errors.
+int cross_prepare_ws(gato_solver *s, const char *who, const void *d_G, const void *d_M, const void *d_C, const void *d_g, double rho,
+                     CrossWs *o, hipStream_t st);
+
+// ---- ADMM update of a box QP with a cross term (gato_qp_cross.hip) -------------------------------------
+struct QpCrossArgs {
+    QpArgs q;                         // as qp_update_kernel takes it: G, Cd the caller's; xt the x-step's solution in (x, v); gt is written transformed
+    const void *M, *W;                // the caller's M and the stored W of cross_ws, [B][(K-1) S C] each
+};
+int qp_update_cross(const Dims &d, int dtype, const QpCrossArgs &a, int it, int last, hipStream_t st);

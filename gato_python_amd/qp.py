@@ -22,7 +22,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from .autograd import _adjoint, _check_blocks, _common, _dots, _dz_layout, _fresh, _pack, _pack_tangents, _solver, _tangent_dims
+from .autograd import _adjoint, _check_blocks, _check_cross, _common, _dots, _dz_layout, _fresh, _pack, _pack_tangents, _solver, _tangent_dims
 from .solver import BoxQPResult
 
 
@@ -114,6 +114,18 @@ def _layer_opts(method, max_pdas_iters, line_search, rho, exit_tol, max_iters, a
     return opts
 
 
+def _check_cross_qp(blocks, M, method, polish):
+    """The refusals of box_qp(M=): the method and the polish, then M's shape, dtype and device by kkt_solve's rules - all before
+    any solver is created."""
+    if method != "admm" or polish:
+        raise ValueError("box_qp: M needs method='admm' without polish: the polish and the active-set iteration (method='pdas', "
+                         "method='alm') invert G block by block and read it in every step, with no cross term (DESIGN.md section "
+                         "3.16)")
+    args = dict(zip("Q R A B q r c".split(), blocks))
+    _, lead, K, S, C = _check_blocks(args, "box_qp", qp=True)
+    _check_cross(M, lead, K, S, C, args["Q"], "box_qp")
+
+
 def _warm_act(warm, Bt, sol, device, starts):
     """warm.act of box_qp, flat, for an active-set start; `starts` ends the refusal of one that does not match the problem."""
     act = getattr(warm, "act", None)
@@ -125,7 +137,7 @@ def _warm_act(warm, Bt, sol, device, starts):
 def box_qp(Q, R, A, B, q, r, c, x_lo, x_hi, u_lo, u_hi, *, rho, exit_tol, max_iters, admm_rho=0.1, sigma=1e-6, alpha=1.6,
            eps_abs=1e-6, eps_rel=1e-6, max_admm_iters=4000, check_every=25, warm=None, polish=False, method="admm",
            polish_iters=1, max_pdas_iters=30, x_soft=None, u_soft=None, x_soft_max=None, u_soft_max=None, line_search=None,
-           alm_weight=100.0, alm_growth=10.0, alm_weight_max=None, max_alm_iters=50):
+           alm_weight=100.0, alm_growth=10.0, alm_weight_max=None, max_alm_iters=50, M=None):
     """Box-constrained QP from math-shaped blocks, at most one leading batch dimension:
     Q [*,K,S,S], R [*,K-1,C,C], A [*,K-1,S,S], B [*,K-1,S,C], q [*,K,S], r [*,K-1,C], c [*,K,S] as kkt_solve takes them (A, B
     the raw values stored in C: -A and -B of the dynamics), and the bounds x_lo, x_hi [*,K,S], u_lo, u_hi [*,K-1,C] - numbers
@@ -166,9 +178,16 @@ def box_qp(Q, R, A, B, q, r, c, x_lo, x_hi, u_lo, u_hi, *, rho, exit_tol, max_it
     the multipliers and its act the active set.  polish=True: the point is then polished on its active set
     (Solver.box_qp_polish) and replaced by the exact vertex where the polish is ACCEPTED (LICQ holds); no weights then.
     ValueError for an ADMM parameter or polish_iters that is not its default, for line_search (it is implied) and for
-    alm_weight <= 0, alm_growth <= 1, alm_weight_max < alm_weight or max_alm_iters < 1."""
+    alm_weight <= 0, alm_growth <= 1, alm_weight_max < alm_weight or max_alm_iters < 1.
+    M [*,K-1,S,C] (None: no cross term, the call as it always was): the stage cost gains x_k^T M_k u_k,
+    G_k = [[Q_k, M_k], [M_k^T, R_k]], as kkt_solve(M=) takes it; every G_k + rho I must be positive definite (not checked).  ADMM
+    only (Solver.box_qp_cross): method="admm" without polish, warm as without M; the bounds and the result are in the original
+    variables.  ValueError for polish=True, method="pdas" or method="alm" (the active-set kernels read G block by block), and
+    for an M of another shape, dtype or device, before any solver is created."""
     if method not in ("admm", "pdas", "alm"):
         raise ValueError(f"box_qp: method must be 'admm', 'pdas' or 'alm', got {method!r}")
+    if M is not None:
+        _check_cross_qp((Q, R, A, B, q, r, c), M, method, polish)
     if method == "alm":
         return _box_qp_alm((Q, R, A, B, q, r, c), (x_lo, x_hi, u_lo, u_hi), (x_soft, u_soft, x_soft_max, u_soft_max),
                            dict(admm_rho=(admm_rho, 0.1), sigma=(sigma, 1e-6), alpha=(alpha, 1.6), max_admm_iters=(max_admm_iters, 4000),
@@ -203,9 +222,13 @@ def box_qp(Q, R, A, B, q, r, c, x_lo, x_hi, u_lo, u_hi, *, rho, exit_tol, max_it
                 if not isinstance(t, torch.Tensor) or t.numel() != Bt * n or t.dtype != g.dtype or t.device != g.device:
                     raise ValueError(f"box_qp: warm.{name} does not match this problem ({Bt} x {n} {g.dtype} on {g.device})")
                 out[name] = t.detach().reshape(Bt, n).clone()
-        res = sol.box_qp(Gb, Cb, g, cc, lo, hi, rho=rho, exit_tol=exit_tol, max_iters=max_iters, admm_rho=admm_rho,
-                         sigma=sigma, alpha=alpha, eps_abs=eps_abs, eps_rel=eps_rel, max_admm_iters=max_admm_iters,
-                         check_every=check_every, warm=warm is not None, **out)
+        admm = dict(rho=rho, exit_tol=exit_tol, max_iters=max_iters, admm_rho=admm_rho, sigma=sigma, alpha=alpha, eps_abs=eps_abs,
+                    eps_rel=eps_rel, max_admm_iters=max_admm_iters, check_every=check_every, warm=warm is not None, **out)
+        if M is None:
+            res = sol.box_qp(Gb, Cb, g, cc, lo, hi, **admm)
+        else:                                                       # M_k S x C column-major per knot, as B_k lies in Cb
+            Mb = M.detach().transpose(-1, -2).reshape(Bt, -1).contiguous()
+            res = sol.box_qp_cross(Gb, Mb, Cb, g, cc, lo, hi, **admm)
         if polish:
             act = sol.box_qp_active_set(res.z, res.y, lo, hi)
             if int(polish_iters) == 1:

@@ -368,23 +368,42 @@ class Solver:
         (without rho), Cb [B C_dense], g / lo / hi [B N] (dz layout, +-inf allowed), c [B S K], flat or 2-D device tensors.
         x, z, y, lam: optional output tensors; warm=True reads z, y and lam (all three required) as the start.  Blocking.
         Raises ValueError for a NaN bound or lo > hi.  The solver's assembly is the QP's x-step matrix afterwards."""
+        return self._box_qp_admm("box_qp", None, Gb, Cb, g, c, lo, hi, x, z, y, lam, warm, rho, exit_tol, max_iters, eps_abs, eps_rel,
+                                 admm_rho=admm_rho, sigma=sigma, alpha=alpha, max_admm_iters=max_admm_iters, check_every=check_every)
+
+    def box_qp_cross(self, Gb, Mb, Cb, g, c, lo, hi, *, rho, exit_tol, max_iters, admm_rho=0.1, sigma=1e-6, alpha=1.6, eps_abs=1e-6,
+                     eps_rel=1e-6, max_admm_iters=4000, check_every=25, x=None, z=None, y=None, lam=None, warm=False):
+        """box_qp with the cross term x_k^T M_k u_k in the stage cost (gato_box_qp_solve_cross): Mb [B (K-1)
+        S C] in the layout of linsys_blocks_cross (K = 1: None, and the call is box_qp).  Every G_k + rho I must be positive
+        definite.  The result is in the original variables (x, u), as are lo and hi.  The solver's assembly afterwards is the
+        x-step matrix in the transformed variables of section 3.15; no cross assembly is recorded (solve_rhs_cross refuses)."""
+        if self.K > 1:
+            self._check_cross("box_qp_cross", Mb=(Mb, self.batch * self.M_size))
+        return self._box_qp_admm("box_qp_cross", Mb if self.K > 1 else None, Gb, Cb, g, c, lo, hi, x, z, y, lam, warm, rho, exit_tol,
+                                 max_iters, eps_abs, eps_rel, admm_rho=admm_rho, sigma=sigma, alpha=alpha,
+                                 max_admm_iters=max_admm_iters, check_every=check_every)
+
+    def _box_qp_admm(self, what, Mb, Gb, Cb, g, c, lo, hi, x, z, y, lam, warm, rho, exit_tol, max_iters, eps_abs, eps_rel, **admm):
+        """box_qp (Mb None, what = "box_qp") or box_qp_cross: the outputs, the checks, the entry and the result record."""
         B, N, sk = self.batch, self.N, self.sizes["sk"]
         if warm and (z is None or y is None or lam is None):
-            raise ValueError("box_qp: warm=True reads z, y and lam: give all three")
+            raise ValueError(f"{what}: warm=True reads z, y and lam: give all three")
         x = self.new(B * N) if x is None else x
         z = self.new(B * N) if z is None else z
         y = self.new(B * N) if y is None else y
         lam = self.new(B * sk) if lam is None else lam
-        self._check_vecs("box_qp", Gb=Gb, Cb=Cb, g=g, c=c, lo=lo, hi=hi, x=x, z=z, y=y, lam=lam)
+        self._check_vecs(what, Gb=Gb, Cb=Cb, g=g, c=c, lo=lo, hi=hi, x=x, z=z, y=y, lam=lam)
         iters = self.new(B, torch.int32)
         status = self.new(B, torch.int32)
         res = self.new(2 * B, torch.float64)
-        p = self._qp_params(rho, exit_tol, max_iters, eps_abs, eps_rel, admm_rho=admm_rho, sigma=sigma, alpha=alpha,
-                            max_admm_iters=max_admm_iters, check_every=check_every, warm=bool(warm))
-        rc = _lib.lib().gato_box_qp_solve(self._h, _ptr(Gb), _ptr(Cb), _ptr(g), _ptr(c), _ptr(lo), _ptr(hi), ct.byref(p),
-                                          _ptr(x), _ptr(z), _ptr(y), _ptr(lam), _ptr(iters), _ptr(status), _ptr(res),
-                                          self._stream())
-        self._check_marked("box_qp", rc, status, BAD_BOUNDS=_lib.QP_BAD_BOUNDS)
+        p = self._qp_params(rho, exit_tol, max_iters, eps_abs, eps_rel, warm=bool(warm), **admm)
+        tail = (_ptr(Cb), _ptr(g), _ptr(c), _ptr(lo), _ptr(hi), ct.byref(p), _ptr(x), _ptr(z), _ptr(y), _ptr(lam), _ptr(iters),
+                _ptr(status), _ptr(res), self._stream())
+        if what == "box_qp":
+            rc = _lib.lib().gato_box_qp_solve(self._h, _ptr(Gb), *tail)
+        else:
+            rc = _lib.lib().gato_box_qp_solve_cross(self._h, _ptr(Gb), _ptr(Mb), *tail)
+        self._check_marked(what, rc, status, BAD_BOUNDS=_lib.QP_BAD_BOUNDS)
         res = res.view(B, 2)
         return BoxQPResult(x, z, y, lam, iters, status, res[:, 0], res[:, 1])
 

@@ -612,6 +612,20 @@ int gato_cross_prepare(gato_solver *s, const void *d_G_blocks, const void *d_M_b
 int gato_cross_rhs(gato_solver *s, int R, const void *d_g, void *d_gp, void *stream);
 int gato_cross_finish(gato_solver *s, int R, void *d_dz, void *stream);
 
+/* ---- box-constrained QP by ADMM with the cross term in the stage cost (new) ------------------------------
+ * gato_box_qp_solve for H = G + rho I with G_k = [[Q_k, M_k], [M_k^T, R_k]]: arguments, checks, outputs, status codes and blocking
+ * behaviour are gato_box_qp_solve's, plus d_M_blocks [B][(K-1)*S*C] in the layout of gato_linsys_device_blocks_cross.  The x-step
+ * matrix [[H + sigma I + diag(rho_i), C^T], [C, 0]] is assembled once in the variables (x, v), u_k = v_k - W_k x_k with W_k =
+ * (R_k + diag(sigma + rho_i) + rho I)^-1 M_k^T; the projection onto the box, x, z, y, lambda and the residuals (H with M) are in
+ * the original variables, so the bounds on u are the caller's.  Every iteration is one gato_solve_rhs on the transformed assembly
+ * plus one update launch, as without M.  Every G_k + rho I must be positive definite (not checked).  The caller's arrays are never
+ * written.  K = 1: d_M_blocks may be NULL and the call is gato_box_qp_solve; K > 1 with a NULL d_M_blocks: GATO_EINVAL.
+ * Side effect: afterwards the solver's assembly is the TRANSFORMED x-step matrix (assembly_gen advances by one), no cross assembly
+ * is recorded - gato_solve_rhs_cross refuses - and gato_solver_recover does not apply. */
+int gato_box_qp_solve_cross(gato_solver *s, const void *d_G_blocks, const void *d_M_blocks, const void *d_C_blocks, const void *d_g,
+                            const void *d_c, const void *d_lo, const void *d_hi, const gato_box_qp_params *p, void *d_x, void *d_z,
+                            void *d_y, void *d_lambda, int *d_iters, int *d_status, double *d_res /* [B][2] */, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
