@@ -17,7 +17,8 @@ Public surface:
                                          active-set iteration alone, with hard or soft bounds (one autograd Function,
                                          qp._BoxQPLayer, whose backward branches on "weights present"); line_search=True
                                          changes the forward pass only
-  gato_python_amd.kkt_solve_tangents(...)      kkt_solve and its forward-mode sensitivities along R directions (one re-solve)
+  gato_python_amd.kkt_solve_tangents(...)      kkt_solve and its forward-mode sensitivities along R directions (one re-solve);
+                                         M=M: with the cross term, a tangent named "M" included
   gato_python_amd.box_qp_layer_tangents(...)   box_qp_layer and its forward-mode sensitivities; both also take
                                          torch.autograd.forward_ad dual tensors (one direction per pass)
   gato_python_amd.synth                  synthetic OCP inputs (the reference ships pendulum data only)

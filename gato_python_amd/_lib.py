@@ -37,7 +37,7 @@ SYMBOLS = [
     "gato_box_qp_pdas_soft", "gato_box_qp_soft_grad", "gato_box_qp_pdas_huber", "gato_box_qp_huber_grad",
     "gato_box_qp_pdas_ls", "gato_box_qp_line_search", "gato_kkt_tangent_rhs", "gato_box_qp_alm", "gato_box_qp_alm_update",
     "gato_linsys_device_blocks_cross", "gato_solve_rhs_cross", "gato_kkt_grad_cross", "gato_cross_prepare", "gato_cross_rhs",
-    "gato_cross_finish", "gato_box_qp_solve_cross",
+    "gato_cross_finish", "gato_box_qp_solve_cross", "gato_kkt_tangent_rhs_cross",
 ]
 
 
@@ -147,6 +147,7 @@ def lib() -> ct.CDLL:
         L.gato_cross_rhs.argtypes = [vp, i, vp, vp, vp]
         L.gato_cross_finish.argtypes = [vp, i, vp, vp]
         L.gato_box_qp_solve_cross.argtypes = [vp] * 8 + [ct.POINTER(BoxQpParams)] + [vp] * 8
+        L.gato_kkt_tangent_rhs_cross.argtypes = [vp, i] + [vp] * 11
         f = ct.c_float
         L.gato_linsys_solve_f32.argtypes = [ip, i, ip, vp, i, ip, i, ip, vp, i, vp, i, vp, i, vp,
                                             i, i, i, i, f, i, i, f, vp, vp, vp, vp]

@@ -2,7 +2,7 @@
 
     kkt_solve(Q, R, A, B, q, r, c, *, M=None, rho, exit_tol, max_iters) -> (lam, dz)
     kkt_solve_csr(G_row, G_col, G_val, C_row, C_col, C_val, g, c, *, rho, exit_tol, max_iters) -> (lam, dz)
-    kkt_solve_tangents(Q, R, A, B, q, r, c, tangents, *, rho, exit_tol, max_iters) -> (lam, dz, lam_dot, dz_dot)
+    kkt_solve_tangents(Q, R, A, B, q, r, c, tangents, *, M=None, rho, exit_tol, max_iters) -> (lam, dz, lam_dot, dz_dot)
 
 The forward is the device solve (Solver.linsys_blocks / linsys / linsys_batched).  The backward is one re-solve of the same
 assembly with the incoming gradients as right-hand side (the KKT matrix is symmetric, so the adjoint system has the forward's
@@ -10,8 +10,9 @@ matrix: Solver.solve_rhs), then one launch that forms the matrix gradients from 
 Forward mode: the tangent system has the same matrix, so a tangent is one launch for its right-hand side
 (gato_tangent.hip) and the same re-solve - through torch.autograd.forward_ad dual tensors (the jvp of the Function, one direction)
 or kkt_solve_tangents (R directions in one call).
-A cross term M (reverse mode only) takes a Function of its own over Solver.linsys_blocks_cross /
-solve_rhs_cross / kkt_grad_cross; without M the code path is the one above, untouched.
+A cross term M takes a Function of its own over Solver.linsys_blocks_cross / solve_rhs_cross /
+kkt_grad_cross (reverse mode); its forward mode is kkt_solve_tangents(..., M=M) over Solver.tangents_cross (section 3.17), not
+forward_ad dual tensors.  Without M the code path is the one above, untouched.
 Only device tensors are taken; there is no CPU fallback.  rho is not differentiated, and double backward is not supported.
 """
 from __future__ import annotations
@@ -153,8 +154,9 @@ class _CrossSolve(torch.autograd.Function):
 
     @staticmethod
     def jvp(ctx, *_):
-        raise NotImplementedError("kkt_solve: forward mode with a cross term M is not built (DESIGN.md section 3.15); use reverse "
-                                  "mode, or kkt_solve without M")
+        raise NotImplementedError("kkt_solve: forward mode with a cross term M is not built through torch.autograd.forward_ad "
+                                  "(DESIGN.md section 3.17); use kkt_solve_tangents(..., M=M) for R directions in one call, or "
+                                  "reverse mode")
 
     @staticmethod
     @once_differentiable
@@ -310,19 +312,28 @@ def _pack_tangents(tangents, shapes, Bt, R, ref):
                 c_dot=cd if have("c") else None)
 
 
-def kkt_solve_tangents(Q, R, A, B, q, r, c, tangents, *, rho, exit_tol, max_iters):
+def kkt_solve_tangents(Q, R, A, B, q, r, c, tangents, *, M=None, rho, exit_tol, max_iters):
     """kkt_solve and its forward-mode sensitivities along R directions in one call:
     -> (lam [*, S K], dz [*, N], lam_dot [*, R, S K], dz_dot [*, R, N]).  tangents: a dict from input name (Q, R, A, B, q, r,
     c) to a tensor of that input's shape with one extra dimension R after the batch dimension; the given ones share R, a
     missing name is a zero tangent.  Q and R tangents are used as given (symmetric perturbations).  One solve, one launch for the
-    R right-hand sides, one re-solve for all of them.  Nothing returned carries a grad_fn."""
+    R right-hand sides, one re-solve for all of them.  Nothing returned carries a grad_fn.
+    M [*, K-1, S, C]: the cross term of kkt_solve; tangents may then name "M" as well, [*, R, K-1, S, C],
+    used as given (M_k and M_k^T perturbed together, the convention of kkt_solve's gradient of M).  One launch more: the map
+    back to the original variables.  M=None is the call without a cross term."""
     what = "kkt_solve_tangents"
     args = dict(Q=Q, R=R, A=A, B=B, q=q, r=r, c=c)
     batched, lead, K, S, C = _check_blocks(args, what)
     if K < 1 or S < 1 or C < 1:
         raise ValueError(f"{what}: S = {S}, C = {C}, K = {K} must all be >= 1")
-    device, dtype = _common(args, what)
     shapes = dict(Q=(K, S, S), R=(K - 1, C, C), A=(K - 1, S, S), B=(K - 1, S, C), q=(K, S), r=(K - 1, C), c=(K, S))
+    if M is not None:                                                      # M and its tangent: checked before any device is asked for
+        _check_cross(M, lead, K, S, C, Q, what)
+        shapes["M"] = (K - 1, S, C)
+        _tangent_dims(tangents, shapes, lead, what)
+    elif isinstance(tangents, dict) and "M" in tangents:
+        raise ValueError(f"{what}: a tangent of M needs the input itself (M=...)")
+    device, dtype = _common(args, what)
     Rn = _tangent_dims(tangents, shapes, lead, what)
     _common(dict(tangents, q=q), what)
     rho, exit_tol, max_iters = _opts(rho, exit_tol, max_iters)
@@ -333,10 +344,19 @@ def kkt_solve_tangents(Q, R, A, B, q, r, c, tangents, *, rho, exit_tol, max_iter
         sol = _solver(S, C, K, Bt, dtype, device)
         lam = torch.empty(Bt, sol.sizes["sk"], dtype=dtype, device=g.device)
         dz = torch.empty(Bt, sol.N, dtype=dtype, device=g.device)
-        sol.linsys_blocks(Gb, Cb, g, cc, exit_tol, max_iters, rho, lam, dz)
-        sol.check_status()
-        dots = _pack_tangents(tangents, shapes, Bt, Rn, q)
-        lam_dot, dz_dot = sol.tangents(Rn, dz, lam, exit_tol, max_iters, **_dots(dots, dtype))
+        dots = _pack_tangents({n: t for n, t in tangents.items() if n != "M"}, shapes, Bt, Rn, q)
+        if M is None or K == 1:                                            # K = 1 has no M at all: the plain path
+            sol.linsys_blocks(Gb, Cb, g, cc, exit_tol, max_iters, rho, lam, dz)
+            sol.check_status()
+            lam_dot, dz_dot = sol.tangents(Rn, dz, lam, exit_tol, max_iters, **_dots(dots, dtype))
+        else:
+            Mb = M.detach().reshape(Bt, K - 1, S, C).transpose(-1, -2).reshape(Bt, -1).contiguous()      # column-major per knot
+            sol.linsys_blocks_cross(Gb, Mb, Cb, g, cc, exit_tol, max_iters, rho, lam, dz)
+            sol.check_status()
+            Md = tangents.get("M")
+            if Md is not None:
+                dots["M_dot"] = Md.detach().reshape(Bt * Rn, K - 1, S, C).transpose(-1, -2).reshape(Bt, -1)
+            lam_dot, dz_dot = sol.tangents_cross(Rn, dz, lam, exit_tol, max_iters, **_dots(dots, dtype))
     return (lam, dz, lam_dot, dz_dot) if batched else (lam[0], dz[0], lam_dot[0], dz_dot[0])
 
 

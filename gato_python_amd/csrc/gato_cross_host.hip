@@ -148,6 +148,34 @@ extern "C" int gato_solve_rhs_cross(gato_solver *s, int R, const void *d_g, cons
     return cross_finish(d, s->dtype, R, W, d_dz, st);
 }
 
+// ---- right-hand side of the tangent system of a cross solve (gato_tangent_cross.hip) -------------------
+extern "C" int gato_kkt_tangent_rhs_cross(gato_solver *s, int R, const void *d_G_dot, const void *d_M_dot, const void *d_C_dot,
+                                          const void *d_g_dot, const void *d_c_dot, const void *d_x, const void *d_lambda,
+                                          void *d_tg, void *d_gp, void *d_tc, void *stream)
+{
+    const char *who = "kkt_tangent_rhs_cross";
+    if (!solver_usable(s, who, "tangents")) return GATO_EINVAL;
+    if (R < 1) { set_error("%s: R = %d: at least one direction", who, R); return GATO_EINVAL; }
+    if (!d_x || !d_lambda || !d_tc || (!d_tg && !d_gp)) {
+        set_error("%s: d_x, d_lambda, d_tc and one of d_tg and d_gp are required", who);
+        return GATO_EINVAL;
+    }
+    if (!s->cross.valid || !s->as.valid || s->cross.gen != s->as.gen) {
+        set_error("%s: the solver's current assembly is not that of a cross solve: run gato_linsys_device_blocks_cross first; any "
+                  "other whole solve, box-QP call or stage entry since then replaces it", who);
+        return GATO_EINVAL;
+    }
+    const bool one = s->d.K == 1;                                             // no M and no W at all: the plain right-hand side
+    const CrossTangentArgs a{d_G_dot, one ? nullptr : d_M_dot, d_C_dot, d_g_dot, d_c_dot, d_x, d_lambda,
+                             one ? nullptr : s->cross_ws + cross_layout(s).W, d_tg, d_gp, d_tc};
+    // Staging the tangent blocks in LDS pays once the launch is bound by memory traffic and costs a round trip through LDS on
+    // every knot while it is bound by latency (DESIGN.md section 3.17 has both measurements): in place below CROSS_TANGENT_STAGE_WAVES
+    // waves per compute unit.  Both forms give the same bits.
+    const long long waves = (long long)s->d.B * (s->d.K < 8192 ? s->d.K : 8192);
+    const bool in_place = s->cross_tangent_form ? s->cross_tangent_form == 2 : waves < (long long)CROSS_TANGENT_STAGE_WAVES * s->num_cus;
+    return cross_tangent_rhs(kernel_dims(s), s->dtype, R, a, in_place, (hipStream_t)stream);
+}
+
 extern "C" int gato_kkt_grad_cross(gato_solver *s, const void *d_dz, const void *d_adz, void *d_Mbar, void *stream)
 {
     if (!solver_usable(s, "kkt_grad_cross", "gradients")) return GATO_EINVAL;

@@ -122,6 +122,7 @@ struct gato_solver {
         unsigned long long gen;       // its as.gen: another assembly since then is not a cross one
     } cross;
     int qp_cross_unfused;             // option (measurement, tests): gato_box_qp_solve_cross runs cross_rhs and cross_finish as launches of their own around every re-solve and gives the update kernel W = 0
+    int cross_tangent_form;           // option (measurement, tests): gato_kkt_tangent_rhs_cross stages the tangent blocks in LDS (1) or reads them in place (2); 0: by the size of the launch
 };
 
 inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
@@ -198,6 +199,19 @@ struct CrossWs { size_t G, C, W, g, bytes; };
 // assembly that read the area's C' (if any) is no longer the solver's.  who names the entry in errors.
 int cross_prepare_ws(gato_solver *s, const char *who, const void *d_G, const void *d_M, const void *d_C, const void *d_g, double rho,
                      CrossWs *o, hipStream_t st);
+
+// ---- tangent right-hand side of a cross solve (gato_tangent_cross.hip) ----------------------------------
+struct CrossTangentArgs {
+    const void *G_dot, *M_dot, *C_dot;      // [B][R][G_dense], [B][R][(K-1) S C], [B][R][C_dense]; nullptr: zero
+    const void *g_dot, *c_dot;              // [B][R][N], [B][R][S K]; nullptr: zero
+    const void *x, *lam;                    // the point [B][N], [B][S K], original variables
+    const void *W;                          // the stored W of cross_ws [B][(K-1) S C]; read for gp only (K = 1: nullptr)
+    void *tg, *gp, *tc;                     // t_g and the transformed g' [B][R][N] (either may be nullptr), t_c [B][R][S K]
+};
+// in_place: the tangent blocks are read where they lie instead of through LDS; same bits.  gato_kkt_tangent_rhs_cross stages them
+// from CROSS_TANGENT_STAGE_WAVES waves per compute unit on (option cross_tangent_form: 1 always staged, 2 always in place).
+constexpr int CROSS_TANGENT_STAGE_WAVES = 3;
+int cross_tangent_rhs(const Dims &d, int dtype, int R, const CrossTangentArgs &a, bool in_place, hipStream_t st);
 
 // ---- ADMM update of a box QP with a cross term (gato_qp_cross.hip) -------------------------------------
 struct QpCrossArgs {

@@ -361,6 +361,49 @@ class Solver:
             x_d = torch.where(hard, b_dot, x_d)
         return lam_d, x_d
 
+    # ---- forward-mode sensitivities of a cross solve (gato_kkt_tangent_rhs_cross) ------------------
+    def kkt_tangent_rhs_cross(self, R, x, lam, *, G_dot=None, M_dot=None, C_dot=None, g_dot=None, c_dot=None, tg=None, gp=None,
+                              tc=None):
+        """The right-hand side of the tangent system of the point x [B N], lam [B S K] of the latest linsys_blocks_cross for R
+        directions per system (gato_kkt_tangent_rhs_cross): tangents G_dot [B R G_dense], M_dot [B R (K-1) S C] (M's layout, M_k
+        and M_k^T perturbed together), C_dot [B R C_dense], g_dot [B R N], c_dot [B R S K], None = zero.  -> (tg, gp, tc): t_g
+        and the transformed g' [B R N] from the stored W, t_c [B R S K]; tg and gp both None: both are written, one given: only
+        that one (the other is returned as None).  Raises when the solver's current assembly is not that cross solve's.
+        Asynchronous; touches no solver state."""
+        B, R = self.batch, int(R)
+        if R < 1:
+            raise ValueError(f"kkt_tangent_rhs_cross: R = {R}: at least one direction")
+        per = dict(G_dot=self.sizes["G_dense"], M_dot=self.M_size, C_dot=self.sizes["C_dense"], g_dot=self.N, c_dot=self.sizes["sk"])
+        dots = dict(G_dot=G_dot, M_dot=M_dot, C_dot=C_dot, g_dot=g_dot, c_dot=c_dot)
+        if tg is None and gp is None:
+            tg, gp = self.new(B * R * self.N), self.new(B * R * self.N)
+        tc = self.new(B * R * self.sizes["sk"]) if tc is None else tc
+        outs = dict(tg=(tg, B * R * self.N), gp=(gp, B * R * self.N), tc=(tc, B * R * self.sizes["sk"]))
+        self._check_cross("kkt_tangent_rhs_cross", x=(x, B * self.N), lam=(lam, B * self.sizes["sk"]),
+                          **{k: (t, B * R * per[k]) for k, t in dots.items() if t is not None},
+                          **{k: v for k, v in outs.items() if v[0] is not None})
+        _lib.check(_lib.lib().gato_kkt_tangent_rhs_cross(self._h, R, *(_ptr(t) if t is not None and t.numel() else None for t in dots.values()),
+                                                         _ptr(x), _ptr(lam), _ptr(tg), _ptr(gp), _ptr(tc), self._stream()))
+        return tg, gp, tc
+
+    def tangents_cross(self, R, x, lam, exit_tol, max_iters, **dots):
+        """(lam_dot [B, R, S K], x_dot [B, R, N]): the tangents of the point (x, lam) of the latest linsys_blocks_cross along R
+        directions per system, in the original variables: kkt_tangent_rhs_cross(R, x, lam, **dots) for
+        g' and t_c, one plain re-solve of the transformed assembly for the B R right-hand sides, cross_finish on the solutions -
+        three launches.  A (system, direction) pair whose right-hand side is all zero gets zeros without its PCG, which would
+        form 0/0.  The assembly stays the cross one.  Blocking (reserve_rhs)."""
+        B, R, N, sk = self.batch, int(R), self.N, self.sizes["sk"]
+        gp = self.new(B * max(R, 1) * N)
+        _, gp, tc = self.kkt_tangent_rhs_cross(R, x, lam, gp=gp, **dots)
+        self.reserve_rhs(R)
+        lam_d, x_d, _ = self.solve_rhs(gp, tc, exit_tol, max_iters)
+        if self.K > 1:
+            self.cross_finish(x_d)
+        self.check_status()
+        # g' = 0 exactly where t_g = 0 (g'_u = t_g,u, and then g'_x = t_g,x), so the rule of Solver.tangents holds on g'
+        zero = ~(gp.view(B, R, N).ne(0).any(2) | tc.view(B, R, sk).ne(0).any(2))[:, :, None]
+        return torch.where(zero, 0, lam_d.view(B, R, sk)), torch.where(zero, 0, x_d.view(B, R, N))
+
     # ---- box-constrained QP by ADMM over the re-solve (gato_box_qp_solve, DESIGN.md section 3.7) ------------------------
     def box_qp(self, Gb, Cb, g, c, lo, hi, *, rho, exit_tol, max_iters, admm_rho=0.1, sigma=1e-6, alpha=1.6, eps_abs=1e-6,
                eps_rel=1e-6, max_admm_iters=4000, check_every=25, x=None, z=None, y=None, lam=None, warm=False):

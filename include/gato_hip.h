@@ -612,6 +612,22 @@ int gato_cross_prepare(gato_solver *s, const void *d_G_blocks, const void *d_M_b
 int gato_cross_rhs(gato_solver *s, int R, const void *d_g, void *d_gp, void *stream);
 int gato_cross_finish(gato_solver *s, int R, void *d_dz, void *stream);
 
+/* ---- forward-mode sensitivities of a cross solve (new): the right-hand side of its tangent system ------
+ * gato_kkt_tangent_rhs for a plain solve with the cross term, one launch.  For R directions per system, from the point of the
+ * latest cross solve (d_x [B][N], d_lambda [B][S*K], original variables) and the input tangents (a dot; NULL: zero, not read):
+ *     t_g = g. - G. x - C.^T lambda,   (G. x)_x,k = Q._k x_k + M._k u_k,  (G. x)_u,k = M._k^T x_k + R._k u_k   (the last knot has no M)
+ *     t_c = c. - C. x
+ * d_M_dot [B][R][(K-1)*S*C] in M's layout is used as given: M_k and M_k^T perturbed together, the convention of
+ * gato_kkt_grad_cross.  d_tg [B][R][N] receives t_g, d_gp [B][R][N] the transformed g'_x,k = t_g,x,k - W_k^T t_g,u,k, g'_u = t_g,u
+ * from the W the cross solve stored (value for value gato_cross_rhs of d_tg); either may be NULL, not both.  d_tc [B][R][S*K].
+ * [x.'; lambda.] = gato_solve_rhs(d_gp, d_tc) on the transformed assembly and gato_cross_finish on x.' give the tangent: W is part
+ * of how the inverse is applied and carries no tangent of its own.  The other argument checks are gato_kkt_tangent_rhs's.
+ * GATO_EINVAL when the solver's current assembly is not the cross one recorded, as gato_solve_rhs_cross refuses.  Writes no solver
+ * state.  K = 1: d_M_dot may be NULL (it is not read) and the result is the plain right-hand side. */
+int gato_kkt_tangent_rhs_cross(gato_solver *s, int R, const void *d_G_dot, const void *d_M_dot, const void *d_C_dot,
+                               const void *d_g_dot, const void *d_c_dot, const void *d_x, const void *d_lambda, void *d_tg,
+                               void *d_gp, void *d_tc, void *stream);
+
 /* ---- box-constrained QP by ADMM with the cross term in the stage cost (new) ------------------------------
  * gato_box_qp_solve for H = G + rho I with G_k = [[Q_k, M_k], [M_k^T, R_k]]: arguments, checks, outputs, status codes and blocking
  * behaviour are gato_box_qp_solve's, plus d_M_blocks [B][(K-1)*S*C] in the layout of gato_linsys_device_blocks_cross.  The x-step
