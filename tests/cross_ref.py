@@ -30,7 +30,9 @@ def cell(S, C, K, seed=0, dense_q=False, scale=0.5):
 
 
 def batch_cells(S, C, K, B, seed=0):
-    """B different systems of one shape: system 1 has dense Q blocks, the others diagonal ones."""
+    """B different systems of one shape: system 1 has dense Q blocks, the others diagonal ones.  R_k is diagonal in every system
+    (synth.make_blocks), A_k = -(I + 1 % noise), c_0 = 0 and every knot has the same O(1) scale; tests/cross_hard_cells.py has
+    the cells without these."""
     return [cell(S, C, K, seed=seed + 17 * b, dense_q=(b == 1)) for b in range(B)]
 
 
@@ -178,17 +180,18 @@ def transformed_solve(blocks, M, rho=RHO, dtype=np.float64, g=None, c=None):
     return finish(t["W"], x[:N], S, C, K), x[N:]
 
 
-def oracle32_solve(blocks, M, tol, max_iters, rho=RHO):
+def oracle32_solve(blocks, M, tol, max_iters, rho=RHO, iters=False):
     """The float32 restatement of a whole cross solve: the transform per block in float32, the oracle's float32 solve (the
     reference's algorithm in its own order of the sums, same exit_tol and max_iters as the device) of the transformed system,
-    the finish in float32.  -> (dz, lam)."""
+    the finish in float32.  -> (dz, lam), with iters also the oracle's iteration count."""
     from oracle import gato_oracle as o
     Q, R, A, B, q, r, cc = blocks
     K, S, C = Q.shape[0], Q.shape[1], R.shape[-1]
     t = transform(Q, R, A, B, q, r, M, rho, np.float32)
     s = synth.blocks_to_csr(*(np.asarray(x, np.float64) for x in (t["Q2"], R, t["A2"], B, t["q2"], r, cc)), rho=rho)
-    lam, dzp, _ = o.linsys_solve(*s.csr_args(), S, C, K, tol, max_iters, rho, dtype=np.float32)
-    return finish(t["W"], np.asarray(dzp, np.float32), S, C, K), np.asarray(lam)
+    lam, dzp, it = o.linsys_solve(*s.csr_args(), S, C, K, tol, max_iters, rho, dtype=np.float32)
+    out = finish(t["W"], np.asarray(dzp, np.float32), S, C, K), np.asarray(lam)
+    return out + (int(it),) if iters else out
 
 
 # ---- gradients ------------------------------------------------------------------------------------------------------------

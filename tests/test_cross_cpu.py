@@ -38,7 +38,13 @@ def test_analytic_gradients_match_central_differences(case):
     """<grad, D> of every input against the central difference of the dense solve, the bar of tests/test_gpu_kkt_grad.py:
     1e-6 max(|an|, 1).  Q and R directions symmetric; M_k and M_k^T move together (M enters the matrix twice)."""
     S, C, K, dq = case
-    blocks, M = X.cell(S, C, K, seed=5, dense_q=dq)
+    central_differences_hold(*X.cell(S, C, K, seed=5, dense_q=dq))
+
+
+def central_differences_hold(blocks, M):
+    """The assertion of test_analytic_gradients_match_central_differences on one system (tests/test_cross_hard_cpu.py runs it on
+    dense, graded cells)."""
+    K, S, C = M.shape[0] + 1, M.shape[1], M.shape[2]
     rng = np.random.default_rng(6)
     N, SK = (S + C) * K - C, S * K
     w1, w2 = rng.standard_normal(N), rng.standard_normal(SK)

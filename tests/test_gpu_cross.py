@@ -134,8 +134,13 @@ KERNEL_CELLS = [(S, C, K) for S, C in X.SHAPES for K in X.KERNEL_K]
 def test_prepare_fp64_per_block(S, C, K):
     """W, Q'', A^', g' of three different systems per block against the longdouble restatement; R, B^, the last knot's Q and
     g_x and every g_u are copies, bit for bit; no entry of the poisoned work area is left unwritten."""
-    cells = X.batch_cells(S, C, K, 3, seed=K)
-    sol = solver(S, C, K, batch=3)
+    prepare_fp64_case(S, C, K, X.batch_cells(S, C, K, 3, seed=K))
+
+
+def prepare_fp64_case(S, C, K, cells):
+    """The body of test_prepare_fp64_per_block on the given cells -> the worst per-block error of W, Q'', A^' and g'."""
+    sol = solver(S, C, K, batch=len(cells))
+    worst = 0.0
     for (blocks, M), got in zip(cells, prepared(sol, cells)):
         Q, R, A, B, q, r, c = blocks
         t = X.transform(Q, R, A, B, q, r, M, X.RHO, LD)
@@ -143,25 +148,32 @@ def test_prepare_fp64_per_block(S, C, K):
             e = blockwise(got[name], want, name)
             print("prepare %d/%d/%d %s: %.3g" % (S, C, K, name, e))
             assert e < BLOCK_BAR, (name, e)
+            worst = max(worst, e)
         n = S + C
         gw = g_of(t, t["q2"], r.astype(LD), S, C, K)
         knots = [slice(k * n, min((k + 1) * n, gw.size)) for k in range(K)]
         e = max(rel(got["g"][s], gw[s]) for s in knots)
         assert e < BLOCK_BAR, ("g'", e)
+        worst = max(worst, e)
         assert np.array_equal(got["R"], R) and np.array_equal(got["B"], B) and np.array_equal(got["Q2"][K - 1], Q[K - 1])
         g0 = X.pack(*blocks)[2]
         assert np.array_equal(got["g"][(K - 1) * n:], g0[(K - 1) * n:])
         for k in range(K - 1):
             assert np.array_equal(got["g"][k * n + S:(k + 1) * n], r[k])
     sol.close()
+    return worst
 
 
 @pytest.mark.parametrize("S,C,K", KERNEL_CELLS, ids=["%d-%d-%d" % c for c in KERNEL_CELLS])
 def test_prepare_fp32_beside_the_float32_restatement(S, C, K):
     """err_gpu <= 2 err_restatement32 + 5e-6 (tests/f32_parity.py) for W, Q'', A^' and g'; truth = the longdouble restatement
     on the float32-rounded inputs.  The copied blocks are copies."""
-    cells = rounded(X.batch_cells(S, C, K, 3, seed=K), np.float32)
-    sol = solver(S, C, K, np.float32, batch=3)
+    prepare_fp32_case(S, C, K, rounded(X.batch_cells(S, C, K, 3, seed=K), np.float32))
+
+
+def prepare_fp32_case(S, C, K, cells):
+    """The body of test_prepare_fp32_beside_the_float32_restatement on the given (float32-rounded) cells."""
+    sol = solver(S, C, K, np.float32, batch=len(cells))
     for b, ((blocks, M), got) in enumerate(zip(cells, prepared(sol, cells))):
         Q, R, A, B, q, r, c = blocks
         assert np.array_equal(got["R"], R.astype(np.float32)) and np.array_equal(got["B"], B.astype(np.float32))
@@ -183,8 +195,12 @@ def test_rhs_and_finish_alone(S, C, K, dt):
     """cross_rhs and cross_finish on R = 2 vectors per system from the W that cross_prepare stored, outputs one element off the
     16-byte grid, against the restatement on the device's own W (longdouble for fp64; the float32 restatement beside it for
     fp32).  x-parts and g_u pass through bit for bit."""
-    B, R = 3, 2
-    cells = rounded(X.batch_cells(S, C, K, B, seed=K), dt)
+    rhs_and_finish_case(S, C, K, dt, rounded(X.batch_cells(S, C, K, 3, seed=K), dt))
+
+
+def rhs_and_finish_case(S, C, K, dt, cells):
+    """The body of test_rhs_and_finish_alone on the given cells (rounded to dt)."""
+    B, R = len(cells), 2
     sol = solver(S, C, K, dt, batch=B)
     Gb, Mb, Cb, g, _ = dev_inputs(sol, cells)
     sol.cross_prepare(Gb, Mb, Cb, g, X.RHO)
@@ -259,26 +275,35 @@ SOLVES = [(S, C, K, B) for S, C, K in X.SOLVE_CELLS for B in (1, 3)]
 def test_whole_solve_fp64_against_the_dense_cross_kkt(S, C, K, B):
     """lambda and dz of every system within 1e-6 of the dense solve with M and M^T in place; a second identical call repeats
     bit for bit; every system of a batch has the bits of its solo run; the caller's arrays are not written."""
-    cells = X.batch_cells(S, C, K, B, seed=20 + K)
+    whole_solve_fp64_case(S, C, K, X.batch_cells(S, C, K, B, seed=20 + K), TIGHT)
+
+
+def whole_solve_fp64_case(S, C, K, cells, pcg):
+    """The body of test_whole_solve_fp64_against_the_dense_cross_kkt on the given cells at the PCG settings pcg (exit_tol,
+    max_iters) -> the worst error of lambda and dz."""
+    B = len(cells)
     sol = solver(S, C, K, batch=B)
     inp = dev_inputs(sol, cells)
     before = [host(t).copy() for t in inp]
-    lam, dz = cross_solve(sol, inp, TIGHT)
+    lam, dz = cross_solve(sol, inp, pcg)
+    worst = 0.0
     for b, (blocks, M) in enumerate(cells):
         dz_w, lam_w = X.dense_solve(blocks, M)
         e = rel(lam[b], lam_w), rel(dz[b], dz_w)
         print("solve %d/%d/%d B%d sys %d: lam %.3g dz %.3g" % (S, C, K, B, b, *e))
         assert max(e) < SOLVE_BAR, (b, e)
-    lam2, dz2 = cross_solve(sol, inp, TIGHT)
+        worst = max(worst, *e)
+    lam2, dz2 = cross_solve(sol, inp, pcg)
     assert lam2.tobytes() == lam.tobytes() and dz2.tobytes() == dz.tobytes()
     assert all(np.array_equal(host(t), w) for t, w in zip(inp, before))
     if B > 1:
         for b in range(B):
             one = solver(S, C, K)
-            l1, d1 = cross_solve(one, dev_inputs(one, cells[b:b + 1]), TIGHT)
+            l1, d1 = cross_solve(one, dev_inputs(one, cells[b:b + 1]), pcg)
             assert l1[0].tobytes() == lam[b].tobytes() and d1[0].tobytes() == dz[b].tobytes(), b
             one.close()
     sol.close()
+    return worst
 
 
 @pytest.mark.parametrize("S,C,K,B", SOLVES, ids=["%d-%d-%d-B%d" % c for c in SOLVES])
@@ -287,7 +312,13 @@ def test_whole_solve_fp32_beside_the_float32_restatement(S, C, K, B):
     restatement (cross_ref.oracle32_solve: transform and finish in float32 around the oracle's float32 solve, same exit_tol
     and max_iters: F32_TIGHT, both run to rounding) - the margin of DESIGN.md section 3.14 for this comparison; it covers the order of the sums.  Both numbers
     go to profiles/cross_accuracy.json."""
-    cells = rounded(X.batch_cells(S, C, K, B, seed=20 + K), np.float32)
+    whole_solve_fp32_case(S, C, K, rounded(X.batch_cells(S, C, K, B, seed=20 + K), np.float32), ACCURACY)
+
+
+def whole_solve_fp32_case(S, C, K, cells, log):
+    """The body of test_whole_solve_fp32_beside_the_float32_restatement on the given (float32-rounded) cells; both errors of
+    every system are appended to log."""
+    B = len(cells)
     sol = solver(S, C, K, np.float32, batch=B)
     lam, dz = cross_solve(sol, dev_inputs(sol, cells), F32_TIGHT)
     rho32 = np.float64(np.float32(X.RHO))
@@ -295,7 +326,7 @@ def test_whole_solve_fp32_beside_the_float32_restatement(S, C, K, B):
         dz_w, lam_w = X.dense_solve(blocks, M, rho=rho32)
         dz_r, lam_r = X.oracle32_solve(blocks, M, F32_TIGHT["exit_tol"], F32_TIGHT["max_iters"])
         eg, er = max(rel(lam[b], lam_w), rel(dz[b], dz_w)), max(rel(lam_r, lam_w), rel(dz_r, dz_w))
-        ACCURACY.append(dict(S=S, C=C, K=K, B=B, system=b, err_device=float(eg), err_restatement32=float(er)))
+        log.append(dict(S=S, C=C, K=K, B=B, system=b, err_device=float(eg), err_restatement32=float(er)))
         print("fp32 %d/%d/%d B%d sys %d: device %.3g restatement %.3g" % (S, C, K, B, b, eg, er))
         assert eg <= 10.0 * er, (b, eg, er)
     sol.close()
@@ -330,20 +361,24 @@ RESOLVES = [(S, C, K, R) for S, C, K in X.RESOLVE_CELLS for R in (1, 3)]
 def test_solve_rhs_cross_against_the_dense_solve(S, C, K, R):
     """R right-hand sides for each of two systems: every one within 1e-6 of the dense cross solve; dz is the restatement's
     finish of what the plain re-solve (which solves the transformed system) gives for the device's g', lambda its lambda."""
-    B = 2
-    cells = X.batch_cells(S, C, K, B, seed=30 + K)
+    solve_rhs_cross_case(S, C, K, R, X.batch_cells(S, C, K, 2, seed=30 + K), TIGHT)
+
+
+def solve_rhs_cross_case(S, C, K, R, cells, pcg):
+    """The body of test_solve_rhs_cross_against_the_dense_solve on the given cells at the PCG settings pcg (exit_tol, max_iters)."""
+    B = len(cells)
     sol = solver(S, C, K, batch=B)
     inp = dev_inputs(sol, cells)
-    cross_solve(sol, inp, TIGHT)
+    cross_solve(sol, inp, pcg)
     gen = sol.get_option("assembly_gen")
     rng = np.random.default_rng(R)
     g, c = rng.standard_normal((B, R, sol.N)), rng.standard_normal((B, R, S * K))
     gd, cd = sol.to_device(g.reshape(-1)), sol.to_device(c.reshape(-1))
     sol.reserve_rhs(R)
-    lam, dz, its = sol.solve_rhs_cross(gd, cd, TIGHT["exit_tol"], TIGHT["max_iters"])
+    lam, dz, its = sol.solve_rhs_cross(gd, cd, pcg["exit_tol"], pcg["max_iters"])
     sol.check_status()
     assert sol.get_option("assembly_gen") == gen
-    lam_p, dz_p, _ = sol.solve_rhs(sol.cross_rhs(gd), cd, TIGHT["exit_tol"], TIGHT["max_iters"])
+    lam_p, dz_p, _ = sol.solve_rhs(sol.cross_rhs(gd), cd, pcg["exit_tol"], pcg["max_iters"])
     W = sol.read_cross("W").reshape(B, sol.M_size)
     lam, dz, lam_p, dz_p = (host(t).reshape(B, R, -1) for t in (lam, dz, lam_p, dz_p))
     assert (host(its) > 0).all()
@@ -450,13 +485,13 @@ def test_grad_cross_kernel_against_the_outer_products(S, C, K):
         sol.close()
 
 
-def loss_grads(cells, w1, w2, only=None, M_zero=False):
+def loss_grads(cells, w1, w2, only=None, M_zero=False, **pcg):
     """kkt_solve(M=...) forward and the backward of L = w1 . dz + w2 . lam -> (tensors, M tensor); only: the one name that
     requires a gradient."""
     t, Mt = math_tensors(cells, grad=only is None)
     if only == "M":
         Mt.requires_grad_(True)
-    lam, dz = ag().kkt_solve(*t, M=Mt, rho=X.RHO, **TIGHT)
+    lam, dz = ag().kkt_solve(*t, M=Mt, rho=X.RHO, **(pcg or TIGHT))
     dv = lambda a: torch.tensor(a, dtype=torch.float64, device="cuda:0")
     ((dz * dv(w1)).sum() + (lam * dv(w2)).sum()).backward()
     return t, Mt
@@ -466,14 +501,19 @@ def loss_grads(cells, w1, w2, only=None, M_zero=False):
 def test_gradients_of_a_batch_against_the_dense_reference(S, C, K):
     """Every gradient of three systems within 1e-6 of the formulas on the dense forward and adjoint solves; the third system's
     upstream gradient is all zero: its gradients are exactly zero (no 0 / 0 of a PCG leaks out)."""
+    gradients_of_a_batch_case(S, C, K, X.batch_cells(S, C, K, 3, seed=20 + K))
+
+
+def gradients_of_a_batch_case(S, C, K, cells, **pcg):
+    """The body of test_gradients_of_a_batch_against_the_dense_reference on three given cells (pcg: other PCG settings than
+    TIGHT)."""
     B = 3
-    cells = X.batch_cells(S, C, K, B, seed=20 + K)
     rng = np.random.default_rng(5)
     N = (S + C) * K - C
     w1, w2 = rng.standard_normal((B, N)), rng.standard_normal((B, S * K))
     w1[2] = 0
     w2[2] = 0
-    t, Mt = loss_grads(cells, w1, w2)
+    t, Mt = loss_grads(cells, w1, w2, **pcg)
     for b in range(2):
         want = X.dense_reference(*cells[b], w1[b], w2[b])
         for n, x in zip(NAMES + ("M",), t + [Mt]):
