@@ -7,6 +7,8 @@ Public surface:
   gato_python_amd.kkt_solve(...)         differentiable solve from math-shaped blocks (torch autograd, autograd.py)
   gato_python_amd.kkt_solve(..., M=M)    the same with a state-control cross term x_k^T M_k u_k in the stage cost
   gato_python_amd.kkt_solve_csr(...)     differentiable solve on device CSR input
+  gato_python_amd.kkt_solve_csr(..., cross=True)   the same for a G whose state rows hold control columns: the cross term read
+                                         from the CSR itself; without it such entries are dropped
   gato_python_amd.box_qp(...)            box-constrained QP (bounds on states and controls) by ADMM over the re-solve, or
                                          by the active-set iteration (method="pdas": hard, soft and capped soft bounds;
                                          line_search=True: the exact line search that makes the all-soft iteration converge),

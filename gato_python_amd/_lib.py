@@ -38,6 +38,7 @@ SYMBOLS = [
     "gato_box_qp_pdas_ls", "gato_box_qp_line_search", "gato_kkt_tangent_rhs", "gato_box_qp_alm", "gato_box_qp_alm_update",
     "gato_linsys_device_blocks_cross", "gato_solve_rhs_cross", "gato_kkt_grad_cross", "gato_cross_prepare", "gato_cross_rhs",
     "gato_cross_finish", "gato_box_qp_solve_cross", "gato_kkt_tangent_rhs_cross",
+    "gato_cross_prepare_csr", "gato_linsys_device_cross", "gato_kkt_grad_csr_cross",
 ]
 
 
@@ -148,6 +149,9 @@ def lib() -> ct.CDLL:
         L.gato_cross_finish.argtypes = [vp, i, vp, vp]
         L.gato_box_qp_solve_cross.argtypes = [vp] * 8 + [ct.POINTER(BoxQpParams)] + [vp] * 8
         L.gato_kkt_tangent_rhs_cross.argtypes = [vp, i] + [vp] * 11
+        L.gato_cross_prepare_csr.argtypes = [vp, ip, ip, vp, i, ip, ip, vp, i, vp, d, vp, vp, vp, vp]
+        L.gato_linsys_device_cross.argtypes = [vp, ip, ip, vp, i, ip, ip, vp, i, vp, vp, d, i, d, vp, vp, vp]
+        L.gato_kkt_grad_csr_cross.argtypes = [vp, ip, ip, i, ip, ip, i, vp, vp, vp, vp, vp, vp, vp]
         f = ct.c_float
         L.gato_linsys_solve_f32.argtypes = [ip, i, ip, vp, i, ip, i, ip, vp, i, vp, i, vp, i, vp,
                                             i, i, i, i, f, i, i, f, vp, vp, vp, vp]

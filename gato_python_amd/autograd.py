@@ -1,7 +1,7 @@
 """torch autograd through the KKT solve.
 
     kkt_solve(Q, R, A, B, q, r, c, *, M=None, rho, exit_tol, max_iters) -> (lam, dz)
-    kkt_solve_csr(G_row, G_col, G_val, C_row, C_col, C_val, g, c, *, rho, exit_tol, max_iters) -> (lam, dz)
+    kkt_solve_csr(G_row, G_col, G_val, C_row, C_col, C_val, g, c, *, cross=False, rho, exit_tol, max_iters) -> (lam, dz)
     kkt_solve_tangents(Q, R, A, B, q, r, c, tangents, *, M=None, rho, exit_tol, max_iters) -> (lam, dz, lam_dot, dz_dot)
 
 The forward is the device solve (Solver.linsys_blocks / linsys / linsys_batched).  The backward is one re-solve of the same
@@ -13,6 +13,8 @@ or kkt_solve_tangents (R directions in one call).
 A cross term M takes a Function of its own over Solver.linsys_blocks_cross / solve_rhs_cross /
 kkt_grad_cross (reverse mode); its forward mode is kkt_solve_tangents(..., M=M) over Solver.tangents_cross (section 3.17), not
 forward_ad dual tensors.  Without M the code path is the one above, untouched.
+kkt_solve_csr(..., cross=True) reads the cross term from the CSR itself - G entries of state rows in
+control columns - through Solver.linsys_cross and kkt_grad_csr_cross; cross=False is the path it was, which drops such entries.
 Only device tensors are taken; there is no CPU fallback.  rho is not differentiated, and double backward is not supported.
 """
 from __future__ import annotations
@@ -394,6 +396,51 @@ class _CsrSolve(torch.autograd.Function):
         return (Gbar, Cbar, a if need[2] else None, beta if need[3] else None) + (None,) * 5
 
 
+class _CsrCrossSolve(torch.autograd.Function):
+    """_CsrSolve on a G with cross entries: the forward is Solver.linsys_cross, the adjoint re-solve is
+    solve_rhs_cross, and a kept cross entry's gradient is M_bar at its slot (kkt_grad_csr_cross)."""
+
+    @staticmethod
+    def forward(ctx, G_val, C_val, g, c, idx, sol, rho, exit_tol, max_iters):
+        B = sol.batch
+        lam = torch.empty(B, sol.sizes["sk"], dtype=g.dtype, device=g.device)
+        dz = torch.empty(B, sol.N, dtype=g.dtype, device=g.device)
+        _csr_cross_forward(sol, idx, G_val, C_val, g, c, exit_tol, max_iters, rho, lam, dz)
+        ctx.sol, ctx.idx, ctx.opts, ctx.gen = sol, idx, (rho, exit_tol, max_iters), sol.get_option("assembly_gen")
+        ctx.save_for_backward(G_val, C_val, g, c, lam, dz)
+        ctx.set_materialize_grads(False)
+        return lam, dz
+
+    @staticmethod
+    def jvp(ctx, *_):
+        raise NotImplementedError("kkt_solve_csr: forward mode with cross=True is not built through torch.autograd.forward_ad "
+                                  "(DESIGN.md sections 3.17, 3.18); use kkt_solve_tangents(..., M=M) on blocks, or reverse mode")
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, lam_bar, dz_bar):
+        G_val, C_val, g, c, lam, dz = ctx.saved_tensors
+        sol, idx = ctx.sol, ctx.idx
+        rho, exit_tol, max_iters = ctx.opts
+        if lam_bar is None and dz_bar is None:
+            return (None,) * 9
+        if sol.get_option("assembly_gen") != ctx.gen or sol.get_option("assembly_valid") == 0:
+            _csr_cross_forward(sol, idx, G_val, C_val, g, c, exit_tol, max_iters, rho, None, None)    # another forward replaced the assembly
+        a, beta = _adjoint(sol, lam, dz, lam_bar, dz_bar, exit_tol, max_iters, cross=True)
+        need = ctx.needs_input_grad
+        Gbar = torch.empty_like(G_val) if need[0] else None
+        Cbar = torch.empty_like(C_val) if need[1] else None
+        if Gbar is not None or Cbar is not None:
+            sol.kkt_grad_csr_cross(*idx, dz, lam, a, beta, Gbar, Cbar)
+        return (Gbar, Cbar, a if need[2] else None, beta if need[3] else None) + (None,) * 5
+
+
+def _csr_cross_forward(sol, idx, G_val, C_val, g, c, exit_tol, max_iters, rho, lam, dz):
+    G_row, G_col, C_row, C_col = idx
+    sol.linsys_cross(G_row, G_col, G_val, C_row, C_col, C_val, g, c, exit_tol, max_iters, rho, lam, dz)
+    sol.check_status()
+
+
 def _csr_forward(sol, idx, G_val, C_val, g, c, exit_tol, max_iters, rho, lam, dz):
     G_row, G_col, C_row, C_col = idx
     if sol.batch == 1:
@@ -411,15 +458,42 @@ def _index(t, name, what, device):
     return t.to(torch.int32).contiguous()
 
 
-def _check_pattern(G_row, G_col, C_row, C_col, N):
-    """The scatter kernels trust the indices (as the reference does): refuse, on the host, what would send them out of range."""
+def _check_pattern(G_row, G_col, C_row, C_col, N, host=None):
+    """The scatter kernels trust the indices (as the reference does): refuse, on the host, what would send them out of range.
+    host: a dict that receives the host copies made here (G_row, G_col, C_row, C_col)."""
     for name, ptr, col in (("G", G_row, G_col), ("C", C_row, C_col)):
         p, cidx = ptr.cpu().numpy(), col.cpu().numpy()
+        if host is not None:
+            host[name + "_row"], host[name + "_col"] = p, cidx
         if p[0] < 0 or p[-1] > cidx.size or np.any(np.diff(p) < 0):
             raise ValueError(f"kkt_solve_csr: {name}_row must rise from >= 0 to <= len({name}_col) = {cidx.size}")
         if cidx.size and (cidx.min() < 0 or cidx.max() >= N):
             raise ValueError(f"kkt_solve_csr: {name}_col holds an index outside [0, {N})")
     return C_row.cpu().numpy()
+
+
+def _check_mirrors(G_row_host, G_col_host, S, C, K):
+    """cross=True reads the cross term from the state rows only: a mirror entry (control row, state column) whose state-row
+    partner is not stored would be dropped silently - ValueError instead.  Upper-only storage passes.  The partner is looked
+    for the way the scatter addresses: the mirror entry stands for M_k[col % n, row % n - S] with k = row // n, and the partner is
+    a kept entry of that slot - a state row of the same knot (control rows exist below the last knot only, so it has an M) in a
+    column that folds to row % n, whichever knot that column lies in."""
+    n, N = S + C, (S + C) * K - C
+    row = np.repeat(np.arange(N, dtype=np.int64), np.diff(np.asarray(G_row_host, np.int64)))
+    col = np.asarray(G_col_host, np.int64)[int(G_row_host[0]):int(G_row_host[0]) + row.size]
+    knot, isr, isc = row // n, row % n, col % n
+    mirror = (isr >= S) & (isc < S)
+    if not mirror.any():
+        return
+    kept = (isr < S) & (isc >= S) & (knot < K - 1)
+    slot = lambda a, b: (knot * n + a) * n + b              # (knot, state row, control column) of an M slot
+    lone = mirror & ~np.isin(slot(isc, isr), slot(isr, isc)[kept])
+    if lone.any():
+        e = int(np.flatnonzero(lone)[0])
+        raise ValueError(f"kkt_solve_csr: cross=True reads G's cross term from the state rows, and {int(lone.sum())} entries of "
+                         f"control rows in state columns have no partner there (the first: row {int(row[e])}, column "
+                         f"{int(col[e])}, no entry at row {int(knot[e] * n + isc[e])}, column {int(row[e])}); store the upper "
+                         f"triangle or both")
 
 
 def _infer_shape(C_row_host, len_g, len_c):
@@ -432,11 +506,35 @@ def _infer_shape(C_row_host, len_g, len_c):
     return S.value, C.value, K.value
 
 
-def kkt_solve_csr(G_row, G_col, G_val, C_row, C_col, C_val, g, c, *, rho, exit_tol, max_iters):
+def _cross_pattern(G_row, G_col, C_row, C_col, N, SK):
+    """The host-side checks of kkt_solve_csr(cross=True), before any device is asked for: index tensors on any device, the
+    pattern in range, (S, C, K), no mirror entry without its partner.  -> (S, C, K)."""
+    what = "kkt_solve_csr"
+    for name, t in (("G_row", G_row), ("G_col", G_col), ("C_row", C_row), ("C_col", C_col)):
+        if not isinstance(t, torch.Tensor) or t.dtype not in (torch.int32, torch.int64) or t.dim() != 1:
+            got = f"{t.dtype} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
+            raise ValueError(f"{what}: {name} must be a 1-D int32 / int64 tensor, got {got}")
+    if G_row.numel() != N + 1 or C_row.numel() != SK + 1:
+        raise ValueError(f"{what}: len(G_row) = {G_row.numel()} and len(C_row) = {C_row.numel()}, want N + 1 = {N + 1} and "
+                         f"S K + 1 = {SK + 1}")
+    host = {}
+    S, C, K = _infer_shape(_check_pattern(G_row, G_col, C_row, C_col, N, host), N, SK)
+    _check_mirrors(host["G_row"], host["G_col"], S, C, K)
+    return S, C, K
+
+
+def kkt_solve_csr(G_row, G_col, G_val, C_row, C_col, C_val, g, c, *, cross=False, rho, exit_tol, max_iters):
     """Differentiable KKT solve on CSR input (gpu_library.linsys_solve's arrays, on the device).  Differentiable in G_val,
     C_val, g and c; the indices are shared by a batch: values [B, nnz] / g [B, N] / c [B, S K], or unbatched [nnz] / [N] /
     [S K].  The gradient of a value is that of the dense slot the scatter writes it into - 0 where the scatter drops it or a
-    later entry of its row overwrites it.  (S, C, K) come from the lengths and C's leading identity rows."""
+    later entry of its row overwrites it.  (S, C, K) come from the lengths and C's leading identity rows.
+    cross=False: G entries between the Q and R parts (a state row with a control column and its mirror) are dropped, as the
+    reference's scatter drops them.  cross=True: a G entry of a state row of knot k < K-1 in a control
+    column is M_k[row % n, col % n - S] of the stage cost's cross term x_k^T M_k u_k; its gradient is that of M_k and M_k^T
+    perturbed together.  The mirror entries in the control rows are not read and get a zero gradient (G is taken as symmetric;
+    upper-only storage is accepted, a mirror entry without its state-row partner raises ValueError), rho is added to every
+    diagonal entry of G whether the CSR stores it or not, and every G_k + rho I must be positive definite (not checked).
+    Reverse mode only: under torch.autograd.forward_ad it raises NotImplementedError."""
     what = "kkt_solve_csr"
     vals = dict(G_val=G_val, C_val=C_val, g=g, c=c)
     for name, t in vals.items():
@@ -449,6 +547,7 @@ def kkt_solve_csr(G_row, G_col, G_val, C_row, C_col, C_val, g, c, *, rho, exit_t
     Bt = g.shape[0] if batched else 1
     if batched and any(t.shape[0] != Bt for t in vals.values()):
         raise ValueError(f"{what}: the batch sizes differ: {[tuple(t.shape) for t in vals.values()]}")
+    shape = _cross_pattern(G_row, G_col, C_row, C_col, g.shape[-1], c.shape[-1]) if cross else None
     device, dtype = _common(vals, what)
     G_row, G_col, C_row, C_col = (_index(t, n, what, device) for t, n in
                                   ((G_row, "G_row"), (G_col, "G_col"), (C_row, "C_row"), (C_col, "C_col")))
@@ -456,12 +555,12 @@ def kkt_solve_csr(G_row, G_col, G_val, C_row, C_col, C_val, g, c, *, rho, exit_t
         raise ValueError(f"{what}: G_val / C_val hold {G_val.shape[-1]} / {C_val.shape[-1]} values per system, G_col / C_col "
                          f"{G_col.numel()} / {C_col.numel()} indices")
     N, SK = g.shape[-1], c.shape[-1]
-    if G_row.numel() != N + 1 or C_row.numel() != SK + 1:
+    if shape is None and (G_row.numel() != N + 1 or C_row.numel() != SK + 1):       # _cross_pattern has checked the lengths
         raise ValueError(f"{what}: len(G_row) = {G_row.numel()} and len(C_row) = {C_row.numel()}, want N + 1 = {N + 1} and "
                          f"S K + 1 = {SK + 1}")
-    S, C, K = _infer_shape(_check_pattern(G_row, G_col, C_row, C_col, N), N, SK)
+    S, C, K = shape if cross else _infer_shape(_check_pattern(G_row, G_col, C_row, C_col, N), N, SK)
     rho, exit_tol, max_iters = _opts(rho, exit_tol, max_iters)
     G_val2, C_val2, g2, c2 = (t.reshape(Bt, -1).contiguous() for t in (G_val, C_val, g, c))
     sol = _solver(S, C, K, Bt, dtype, device)
-    lam, dz = _CsrSolve.apply(G_val2, C_val2, g2, c2, (G_row, G_col, C_row, C_col), sol, rho, exit_tol, max_iters)
+    lam, dz = (_CsrCrossSolve if cross else _CsrSolve).apply(G_val2, C_val2, g2, c2, (G_row, G_col, C_row, C_col), sol, rho, exit_tol, max_iters)
     return (lam, dz) if batched else (lam[0], dz[0])

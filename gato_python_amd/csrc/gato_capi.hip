@@ -297,6 +297,7 @@ extern "C" int gato_solver_set_option(gato_solver *s, const char *name, int valu
     else if (!strcmp(name, "no_image")) s->no_image = value;
     else if (!strcmp(name, "qp_cross_unfused")) s->qp_cross_unfused = value;
     else if (!strcmp(name, "cross_tangent_form")) s->cross_tangent_form = value;
+    else if (!strcmp(name, "cross_csr_threads")) s->cross_csr_threads = value;
     else if (!strcmp(name, "coop_launch")) s->coop_launch = value;
     else if (!strcmp(name, "cluster_flat")) s->cluster_flat = value;
     else if (!strcmp(name, "knot_lo") || !strcmp(name, "knot_hi")) {          // stage-level entries: knots [knot_lo, knot_hi)

@@ -12,6 +12,7 @@
 // depend on the launch geometry.
 #include "gato_solver.h"
 #include "gato_gj.h"
+#include "gato_grad_elem.h"
 #include "gato_qp_common.h"
 
 namespace gato {
@@ -152,23 +153,19 @@ __global__ __launch_bounds__(WAVE) void cross_finish_kernel(const T *__restrict_
     }
 }
 
-// M_bar_k = -(a_x,k dz_u,k^T + dz_x,k a_u,k^T) in M's layout, M_k and M_k^T perturbed together.  Contraction off, as in
-// gato_grad.hip: p + q is one rounding of two rounded products.  Thread = output entry over [B][(K-1) S C].
+// M_bar_k = -(a_x,k dz_u,k^T + dz_x,k a_u,k^T) in M's layout, M_k and M_k^T perturbed together: grad_M_elem (gato_grad_elem.h,
+// contraction off), which the CSR gradient of a cross entry evaluates too.  Thread = output entry over [B][(K-1) S C].
 template <typename T, int S, int C>
 __global__ __launch_bounds__(NT) void grad_cross_kernel(const T *__restrict__ dz, const T *__restrict__ a, T *__restrict__ Mbar,
                                                         size_t per, size_t total, BatchStride bs)
 {
 #pragma clang fp contract(off)
-    constexpr int n = S + C, SC = S * C;
+    constexpr int SC = S * C;
     const size_t e = (size_t)blockIdx.x * NT + threadIdx.x;
     if (e >= total) return;
     const size_t sys = e / per, r = e - sys * per;
     const size_t k = r / SC;
-    const int w = (int)(r - k * SC), i = w % S, j = w / S;
-    const T *dzs = dz + sys * bs.n + k * n, *as = a + sys * bs.n + k * n;
-    const T p = as[i] * dzs[S + j];
-    const T q = dzs[i] * as[S + j];
-    Mbar[e] = -(p + q);
+    Mbar[e] = grad_M_elem<T, S, C>(dz + sys * bs.n, a + sys * bs.n, k, (int)(r - k * SC));
 }
 
 template <typename T, int S, int C>

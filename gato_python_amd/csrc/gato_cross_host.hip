@@ -183,3 +183,100 @@ extern "C" int gato_kkt_grad_cross(gato_solver *s, const void *d_dz, const void 
     if (!d_dz || !d_adz || !d_Mbar) { set_error("kkt_grad_cross: d_dz, d_adz and d_Mbar are required"); return GATO_EINVAL; }
     return cross_grad(kernel_dims(s), s->dtype, d_dz, d_adz, d_Mbar, (hipStream_t)stream);
 }
+
+// ---- CSR entry (gato_cross_csr.hip) -----------------------------------------------------------------------
+static int check_csr(gato_solver *s, const char *who, const int *G_row, const int *G_col, const void *G_val, int nnz_G, const int *C_row,
+                     const int *C_col, const void *C_val, int nnz_C, const void *d_g)
+{
+    if (!solver_usable(s, who, "cross-term solves")) return GATO_EINVAL;
+    if (!G_row || !G_col || !G_val || !C_row || !C_col || !C_val || !d_g) {
+        set_error("%s: the six CSR arrays and d_g are required", who);
+        return GATO_EINVAL;
+    }
+    if (nnz_G <= 0 || nnz_C <= 0) { set_error("%s: nnz_G = %d and nnz_C = %d must be positive (values per system)", who, nnz_G, nnz_C); return GATO_EINVAL; }
+    return GATO_OK;
+}
+
+// the fused gather and prepare into the work area; as cross_prepare_ws
+static int cross_prepare_csr_ws(gato_solver *s, const char *who, const int *G_row, const int *G_col, const void *G_val, int nnz_G,
+                                const int *C_row, const int *C_col, const void *C_val, int nnz_C, const void *d_g, double rho,
+                                void *G_out, void *M_out, void *C_out, CrossWs *o, hipStream_t st)
+{
+    *o = cross_layout(s);
+    int rc;
+    if ((rc = grow(who, &s->cross_ws, &s->cross_ws_bytes, o->bytes, st))) return rc;
+    char *w = s->cross_ws;
+    s->cross.valid = 0;
+    if (s->as.Cd == w + o->C) s->as.valid = 0;
+    Dims d = kernel_dims(s);
+    d.nnzG = nnz_G; d.nnzC = nnz_C;
+    const CrossCsrArgs a{G_row, G_col, C_row, C_col, G_val, C_val, d_g, w + o->G, w + o->C, w + o->W, w + o->g, G_out, M_out, C_out, rho};
+    // Four waves gather a knot's entries faster than one while the launch is bound by latency; once the workgroups queue for the
+    // compute units one wave per knot wastes fewer lanes in the transform - at the shapes up to 14/7, whose knot one wave gathers in
+    // a dozen rounds; at 32/16 (61 rounds) four waves win at every size (DESIGN.md section 3.18 has the measurements).  Same bits.
+    const long long knots = (long long)s->d.B * (s->d.K < 8192 ? s->d.K : 8192);
+    const bool one_wave = s->d.S + s->d.C <= CROSS_CSR_WAVE_N && knots >= (long long)CROSS_CSR_WAVE_KNOTS * s->num_cus;
+    const int threads = s->cross_csr_threads ? (s->cross_csr_threads == 64 ? 64 : 256) : one_wave ? 64 : 256;
+    return cross_prepare_csr(d, s->dtype, a, threads, st);
+}
+
+extern "C" int gato_cross_prepare_csr(gato_solver *s, const int *d_G_row, const int *d_G_col, const void *d_G_val, int nnz_G,
+                                      const int *d_C_row, const int *d_C_col, const void *d_C_val, int nnz_C, const void *d_g,
+                                      double rho, void *d_G_out, void *d_M_out, void *d_C_out, void *stream)
+{
+    const char *who = "cross_prepare_csr";
+    int rc;
+    if ((rc = check_csr(s, who, d_G_row, d_G_col, d_G_val, nnz_G, d_C_row, d_C_col, d_C_val, nnz_C, d_g))) return rc;
+    CrossWs o;
+    return cross_prepare_csr_ws(s, who, d_G_row, d_G_col, d_G_val, nnz_G, d_C_row, d_C_col, d_C_val, nnz_C, d_g, rho, d_G_out, d_M_out,
+                                d_C_out, &o, (hipStream_t)stream);
+}
+
+extern "C" int gato_linsys_device_cross(gato_solver *s, const int *d_G_row, const int *d_G_col, const void *d_G_val, int nnz_G,
+                                        const int *d_C_row, const int *d_C_col, const void *d_C_val, int nnz_C, const void *d_g,
+                                        const void *d_c, double exit_tol, int max_iters, double rho, void *d_lambda, void *d_dz,
+                                        void *stream)
+{
+    const char *who = "linsys_device_cross";
+    int rc;
+    if ((rc = check_csr(s, who, d_G_row, d_G_col, d_G_val, nnz_G, d_C_row, d_C_col, d_C_val, nnz_C, d_g))) return rc;
+    if (!d_c) { set_error("%s: d_c is required", who); return GATO_EINVAL; }
+    hipStream_t st = (hipStream_t)stream;
+    if (s->d.K == 1) {                                                       // no M at all: the plain CSR solve
+        rc = s->d.B > 1 ? gato_linsys_device_batched(s, d_G_row, d_G_col, d_G_val, nnz_G, d_C_row, d_C_col, d_C_val, nnz_C, d_g, d_c,
+                                                     exit_tol, max_iters, rho, d_lambda, d_dz, nullptr, stream)
+                        : gato_linsys_device(s, d_G_row, d_G_col, d_G_val, d_C_row, d_C_col, d_C_val, d_g, d_c, exit_tol, max_iters, rho,
+                                             d_lambda, d_dz, stream);
+        if (rc) return rc;
+        s->cross = {1, s->as.gen};
+        return GATO_OK;
+    }
+    CrossWs o;
+    if ((rc = cross_prepare_csr_ws(s, who, d_G_row, d_G_col, d_G_val, nnz_G, d_C_row, d_C_col, d_C_val, nnz_C, d_g, rho, nullptr, nullptr,
+                                   nullptr, &o, st)))
+        return rc;
+    char *w = s->cross_ws;
+    void *dz = d_dz ? d_dz : s->dz;
+    const AsmInput in{2, nullptr, nullptr, w + o.G, nullptr, nullptr, nullptr, w + o.C, false};
+    if ((rc = whole_solve(s, pcg_opts(*s), in, w + o.g, d_c, exit_tol, max_iters, rho, d_lambda ? d_lambda : s->lambda, dz, st))) return rc;
+    s->lc.valid = 0;                                                         // a recover would leave dz in the transformed variables
+    if ((rc = cross_finish(kernel_dims(s), s->dtype, 1, w + o.W, dz, st))) return rc;
+    s->cross = {1, s->as.gen};
+    return GATO_OK;
+}
+
+extern "C" int gato_kkt_grad_csr_cross(gato_solver *s, const int *d_G_row, const int *d_G_col, int nnz_G, const int *d_C_row,
+                                       const int *d_C_col, int nnz_C, const void *d_dz, const void *d_lam, const void *d_adz,
+                                       const void *d_alam, void *d_Gbar_val, void *d_Cbar_val, void *stream)
+{
+    const char *who = "kkt_grad_csr_cross";
+    if (!solver_usable(s, who, "gradients")) return GATO_EINVAL;
+    if (!d_dz || !d_lam || !d_adz || !d_alam) { set_error("%s: d_dz, d_lam, d_adz and d_alam are required", who); return GATO_EINVAL; }
+    if (!d_Gbar_val && !d_Cbar_val) { set_error("%s: both outputs are NULL", who); return GATO_EINVAL; }
+    if ((d_Gbar_val && (!d_G_row || !d_G_col || nnz_G < 0)) || (d_Cbar_val && (!d_C_row || !d_C_col || nnz_C < 0))) {
+        set_error("%s: an output needs its row pointers, column indices and nnz >= 0", who);
+        return GATO_EINVAL;
+    }
+    return grad_csr_cross(kernel_dims(s), s->dtype, d_G_row, d_G_col, nnz_G, d_C_row, d_C_col, nnz_C, d_dz, d_lam, d_adz, d_alam,
+                          d_Gbar_val, d_Cbar_val, (hipStream_t)stream);
+}

@@ -122,6 +122,7 @@ struct gato_solver {
         unsigned long long gen;       // its as.gen: another assembly since then is not a cross one
     } cross;
     int qp_cross_unfused;             // option (measurement, tests): gato_box_qp_solve_cross runs cross_rhs and cross_finish as launches of their own around every re-solve and gives the update kernel W = 0
+    int cross_csr_threads;            // option (measurement, tests): threads per workgroup of cross_prepare_csr_kernel, 64 or 256; 0: by the size of the launch; same bits
     int cross_tangent_form;           // option (measurement, tests): gato_kkt_tangent_rhs_cross stages the tangent blocks in LDS (1) or reads them in place (2); 0: by the size of the launch
 };
 
@@ -199,6 +200,24 @@ struct CrossWs { size_t G, C, W, g, bytes; };
 // assembly that read the area's C' (if any) is no longer the solver's.  who names the entry in errors.
 int cross_prepare_ws(gato_solver *s, const char *who, const void *d_G, const void *d_M, const void *d_C, const void *d_g, double rho,
                      CrossWs *o, hipStream_t st);
+
+// ---- CSR entry to the cross solve (gato_cross_csr.hip) ---------------------------------------------------
+struct CrossCsrArgs {
+    const int *G_row, *G_col, *C_row, *C_col;   // the pattern the B systems share; d.nnzG / d.nnzC values per system
+    const void *G_val, *C_val, *g;          // never written
+    void *Gp, *Cp, *W, *gp;                 // the work area, as CrossArgs
+    void *G_out, *M_out, *C_out;            // optional: the scattered blocks [B][G_dense] (without rho), [B][(K-1) S C], [B][C_dense]
+    double rho;
+};
+// threads: 64 or 256 per workgroup (same bits).  gato_cross_prepare_csr / gato_linsys_device_cross take 64 from
+// CROSS_CSR_WAVE_KNOTS knots per compute unit on where S + C <= CROSS_CSR_WAVE_N (14/7, the largest shape at which one wave was
+// measured the faster; 32/16 is not, nothing between them was measured) (option cross_csr_threads: 64 or 256 always).
+constexpr int CROSS_CSR_WAVE_KNOTS = 8;
+constexpr int CROSS_CSR_WAVE_N = 21;
+int cross_prepare_csr(const Dims &d, int dtype, const CrossCsrArgs &a, int threads, hipStream_t st);
+// gato_kkt_grad_csr with the cross entries of G (gato_grad.hip): a kept state-row entry carries M_bar at its slot
+int grad_csr_cross(const Dims &d, int dtype, const int *G_row, const int *G_col, int nnzG, const int *C_row, const int *C_col, int nnzC,
+                   const void *dz, const void *lam, const void *a, const void *beta, void *Gbar, void *Cbar, hipStream_t st);
 
 // ---- tangent right-hand side of a cross solve (gato_tangent_cross.hip) ----------------------------------
 struct CrossTangentArgs {

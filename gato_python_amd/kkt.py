@@ -101,8 +101,11 @@ def _dense_block_to_csr_rows(blocks):
     return (np.asarray(indptr, np.int32), np.asarray(indices, np.int32), np.asarray(data, np.float64))
 
 
-def get_kkt(plant: Plant, x, u, xs, xg, dt: float, Q, R, QF, rho: float = 1e-3) -> KKTSystem:
-    """One linearisation of the OCP around (x [K,S], u [K-1,C]) as a KKTSystem in `linsys_solve` argument order."""
+def get_kkt(plant: Plant, x, u, xs, xg, dt: float, Q, R, QF, rho: float = 1e-3, M=None) -> KKTSystem:
+    """One linearisation of the OCP around (x [K,S], u [K-1,C]) as a KKTSystem in `linsys_solve` argument order.
+    M [S,C]: the stage cost gains (x_k - xg)' M u_k for k < K-1 - G holds M and M' between the Q and R blocks of those knots
+    (both triangles, as csr_matrix(dense) would emit them) and g gains M u_k and M' (x_k - xg).  Such a G is solved by
+    kkt_solve_csr(cross=True) / Solver.linsys_cross; every other CSR entry drops the cross entries."""
     x = np.atleast_2d(np.asarray(x, np.float64))
     K, S = x.shape
     C = plant.C
@@ -110,19 +113,26 @@ def get_kkt(plant: Plant, x, u, xs, xg, dt: float, Q, R, QF, rho: float = 1e-3) 
     xs, xg = np.asarray(xs, np.float64), np.asarray(xg, np.float64)
     Q, R, QF = (np.asarray(m, np.float64) for m in (Q, R, QF))
     assert S == plant.S and Q.shape == (S, S) and QF.shape == (S, S) and R.shape == (C, C)
+    if M is not None:
+        M = np.asarray(M, np.float64)
+        assert M.shape == (S, C)
     n = S + C
     G_rows, C_rows = [], []
     g = np.zeros(n * K - C)
     c = np.zeros(S * K)
     for k in range(K):
         Qk = QF if k == K - 1 else Q
+        cross = M is not None and k < K - 1
         for i in range(S):
-            G_rows.append([(k * n, Qk[i])])
+            G_rows.append([(k * n, Qk[i])] + ([(k * n + S, M[i])] if cross else []))
         g[k * n:k * n + S] = Qk @ (x[k] - xg)
         if k < K - 1:
             for i in range(C):
-                G_rows.append([(k * n + S, R[i])])
+                G_rows.append(([(k * n, M[:, i])] if cross else []) + [(k * n + S, R[i])])
             g[k * n + S:(k + 1) * n] = R @ u[k]
+        if cross:
+            g[k * n:k * n + S] += M @ u[k]
+            g[k * n + S:(k + 1) * n] += M.T @ (x[k] - xg)
     eye = np.eye(S)
     for i in range(S):
         C_rows.append([(0, eye[i])])

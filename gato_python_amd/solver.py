@@ -281,6 +281,60 @@ class Solver:
         _lib.check(_lib.lib().gato_cross_finish(self._h, R, _ptr(dz), self._stream()))
         return dz
 
+    # ---- CSR entry to the cross solve (gato_*_csr*cross) ----------------------------------------------
+    def _csr_cross_inputs(self, what, G_row, G_col, G_val, C_row, C_col, C_val, g):
+        """ValueError unless the index arrays are contiguous int32 CUDA tensors of N + 1 / S K + 1 pointers and one column per
+        value, and the values [B nnz] and g [B N] contiguous CUDA tensors of the solver's dtype.  -> (nnz_G, nnz_C) per system."""
+        B = self.batch
+        for name, t, n in (("G_row", G_row, self.N + 1), ("G_col", G_col, None), ("C_row", C_row, self.sizes["sk"] + 1),
+                           ("C_col", C_col, None)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous() or \
+                    (n is not None and t.numel() != n) or t.numel() < 1:
+                got = f"{t.dtype} {tuple(t.shape)} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
+                raise ValueError(f"{what}: {name} must be a contiguous int32 CUDA tensor"
+                                 f"{'' if n is None else ' of %d entries' % n}, got {got}")
+        nnzG, nnzC = G_col.numel(), C_col.numel()
+        self._check_cross(what, G_val=(G_val, B * nnzG), C_val=(C_val, B * nnzC), g=(g, B * self.N))
+        return nnzG, nnzC
+
+    def linsys_cross(self, G_row, G_col, G_val, C_row, C_col, C_val, g, c, exit_tol, max_iters, rho, lam=None, dz=None):
+        """linsys / linsys_batched for a G whose state rows hold control columns (gato_linsys_device_cross): such an entry of knot
+        k < K-1 is M_k[isr, isc - S] of the stage cost's x_k^T M_k u_k, its mirror in the control rows is not read, and rho goes
+        onto every diagonal entry of G, stored or not (the scatter rule: include/gato_hip.h).  Values [B nnz] on one shared
+        pattern, one call for B = 1 and batches.  Afterwards the solver's assembly is a cross one, as after linsys_blocks_cross:
+        solve_rhs_cross, tangents_cross and kkt_grad_cross follow it.  Asynchronous but for a solver's first cross call."""
+        what = "linsys_cross"
+        nnzG, nnzC = self._csr_cross_inputs(what, G_row, G_col, G_val, C_row, C_col, C_val, g)
+        outs = {k: (t, self.batch * n) for k, t, n in (("lam", lam, self.sizes["sk"]), ("dz", dz, self.N)) if t is not None}
+        self._check_cross(what, c=(c, self.batch * self.sizes["sk"]), **outs)
+        _lib.check(_lib.lib().gato_linsys_device_cross(self._h, _ptr(G_row), _ptr(G_col), _ptr(G_val), nnzG, _ptr(C_row), _ptr(C_col),
+                                                       _ptr(C_val), nnzC, _ptr(g), _ptr(c), float(exit_tol), int(max_iters),
+                                                       float(rho), _ptr(lam), _ptr(dz), self._stream()))
+
+    def cross_prepare_csr(self, G_row, G_col, G_val, C_row, C_col, C_val, g, rho, G_out=None, M_out=None, C_out=None):
+        """The first stage of linsys_cross alone (gato_cross_prepare_csr): one launch gathers the CSR values and writes what
+        cross_prepare writes into the work area (read_cross), bit for bit cross_prepare on the scattered blocks.  G_out
+        [B G_dense] (without rho), M_out [B (K-1) S C], C_out [B C_dense]: each None or written whole with the scattered blocks.
+        Forgets a recorded cross assembly."""
+        what = "cross_prepare_csr"
+        nnzG, nnzC = self._csr_cross_inputs(what, G_row, G_col, G_val, C_row, C_col, C_val, g)
+        B = self.batch
+        outs = {k: (t, B * n) for k, t, n in (("G_out", G_out, self.sizes["G_dense"]), ("M_out", M_out, self.M_size),
+                                              ("C_out", C_out, self.sizes["C_dense"])) if t is not None}
+        self._check_cross(what, **outs)
+        _lib.check(_lib.lib().gato_cross_prepare_csr(self._h, _ptr(G_row), _ptr(G_col), _ptr(G_val), nnzG, _ptr(C_row), _ptr(C_col),
+                                                     _ptr(C_val), nnzC, _ptr(g), float(rho), _ptr(G_out), _ptr(M_out), _ptr(C_out),
+                                                     self._stream()))
+        return G_out, M_out, C_out
+
+    def kkt_grad_csr_cross(self, G_row, G_col, C_row, C_col, dz, lam, adz, alam, Gbar_val=None, Cbar_val=None):
+        """kkt_grad_csr through linsys_cross's scatter (gato_kkt_grad_csr_cross): a kept cross entry of G carries M_bar at its
+        slot (kkt_grad_cross, bit for bit); a mirror entry, a cross entry of the last knot and an overwritten entry get 0."""
+        _lib.check(_lib.lib().gato_kkt_grad_csr_cross(self._h, _ptr(G_row), _ptr(G_col), G_col.numel(), _ptr(C_row), _ptr(C_col),
+                                                      C_col.numel(), _ptr(dz), _ptr(lam), _ptr(adz), _ptr(alam), _ptr(Gbar_val),
+                                                      _ptr(Cbar_val), self._stream()))
+        return Gbar_val, Cbar_val
+
     _CROSS_BUFFERS = dict(G=13, C=14, W=15, g=16)
 
     def cross_buffer_ptr(self, name: str) -> int:

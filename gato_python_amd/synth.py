@@ -128,9 +128,28 @@ def make_cross(Q, R, seed: int = 0, scale: float = 0.5):
     return M
 
 
-def blocks_to_csr(Q, R, A, B, q, r, c, rho: float = 1e-3, dense_q: bool | None = None) -> KKTSystem:
+def _cross_G_csr(Q, R, M):
+    """G = blockdiag([[Q_k, M_k], [M_k^T, R_k]], ..., Q_{K-1}) as csr_matrix(dense) would emit it: both triangles, columns
+    ascending, zeros dropped."""
+    K, S, _ = Q.shape
+    C = R.shape[1]
+    n = S + C
+    ptr, idx, dat = [0], [], []
+    for k in range(K):
+        Gk = Q[k] if k == K - 1 else np.block([[Q[k], M[k]], [M[k].T, R[k]]])
+        for i in range(Gk.shape[0]):
+            nz = np.nonzero(Gk[i])[0]
+            idx.extend((k * n + nz).tolist())
+            dat.extend(Gk[i, nz].tolist())
+            ptr.append(len(idx))
+    return np.asarray(ptr, np.int64), np.asarray(idx, np.int64), np.asarray(dat, np.float64)
+
+
+def blocks_to_csr(Q, R, A, B, q, r, c, rho: float = 1e-3, dense_q: bool | None = None, M=None) -> KKTSystem:
     """Emit the CSR arrays exactly as scipy.sparse.csr_matrix(...).indptr/.indices/.data
-    would (sorted columns, explicit structural entries only), cf. test_pendulum_5.py:28-29."""
+    would (sorted columns, explicit structural entries only), cf. test_pendulum_5.py:28-29.
+    M [K-1,S,C]: the cross blocks of the stage cost go into G in both triangles, and G is then
+    emitted the way csr_matrix(dense) would (zeros dropped); M=None gives the arrays it always gave."""
     K, S, _ = Q.shape
     C = R.shape[1] if K > 1 else 0
     n = S + C
@@ -180,6 +199,9 @@ def blocks_to_csr(Q, R, A, B, q, r, c, rho: float = 1e-3, dense_q: bool | None =
             G_col[G_row[crows]] = crows
             G_val[G_row[crows]] = R[ck, ci, ci]
 
+    if M is not None and K > 1:
+        G_row, G_col, G_val = _cross_G_csr(np.asarray(Q, np.float64), np.asarray(R, np.float64), np.asarray(M, np.float64))
+
     # ---- C: row-block 0 identity; row-block k>=1: [A_{k-1} B_{k-1}] on (x_{k-1},u_{k-1}), I on x_k
     SK = S * K
     c_nnz = np.full(SK, n + 1, np.int64)
@@ -214,8 +236,11 @@ def blocks_to_csr(Q, R, A, B, q, r, c, rho: float = 1e-3, dense_q: bool | None =
 
 
 def make_system(S: int, C: int, K: int, seed: int = 0, dense_q: bool = False,
-                rho: float = 1e-3) -> KKTSystem:
-    return blocks_to_csr(*make_blocks(S, C, K, seed, dense_q), rho=rho, dense_q=dense_q)
+                rho: float = 1e-3, cross_scale: float | None = None) -> KKTSystem:
+    """cross_scale: G also holds the cross blocks make_cross(Q, R, seed + 1000, cross_scale), in both triangles."""
+    blocks = make_blocks(S, C, K, seed, dense_q)
+    M = None if cross_scale is None else make_cross(blocks[0], blocks[1], seed=seed + 1000, scale=cross_scale)
+    return blocks_to_csr(*blocks, rho=rho, dense_q=dense_q, M=M)
 
 
 def dense_kkt(sys: KKTSystem, with_rho: bool = True):

@@ -612,6 +612,40 @@ int gato_cross_prepare(gato_solver *s, const void *d_G_blocks, const void *d_M_b
 int gato_cross_rhs(gato_solver *s, int R, const void *d_g, void *d_gp, void *stream);
 int gato_cross_finish(gato_solver *s, int R, void *d_dz, void *stream);
 
+/* ---- CSR entry to the cross solve (new) ---------------------------------------------------------------
+ * gato_linsys_device / _batched for a G whose state rows hold control columns: the term x_k^T M_k u_k of a non-separable stage
+ * cost, which every other CSR entry drops (as the reference does).  Opt-in: no other entry changes.
+ * SCATTER RULE.  Addressing is that of gato_convert: knot = row / n, in-knot column = col % n (n = S + C), the last entry in
+ * storage order wins a slot written twice, explicit zeros are values.  New: a G entry with in-knot row isr < S and in-knot
+ * column isc >= S in a knot k < K-1 lands in M_k[isr + (isc - S)*S] (S x C column-major, the layout of d_M_blocks above).  The
+ * mirror entries (isr >= S, isc < S) are NOT read: G is taken as symmetric, and where the two triangles disagree the state-row
+ * one counts (upper-only storage is fine; lower-only storage loses M).  State rows of the last knot have no M: a control column
+ * there is dropped.  rho is not added while gathering: the solve adds it to EVERY diagonal entry of G, where gato_linsys_device
+ * adds it to the diagonal entries the CSR stores - the two differ exactly on a diagonal entry that is not stored.
+ * gato_cross_prepare_csr is the stage alone: ONE launch gathers the CSR values into per-knot blocks and writes what
+ * gato_cross_prepare writes (buffers 13 .. 16), bit for bit gato_cross_prepare on the blocks the rule gives.  d_G_out
+ * [B][G_dense] (without rho), d_M_out [B][(K-1)*S*C], d_C_out [B][C_dense]: each NULL or written whole - the scattered blocks,
+ * for callers that go on to gato_box_qp_solve_cross and the like.  The batch shares the index arrays; d_G_val [B][nnz_G],
+ * d_C_val [B][nnz_C].  The indices are trusted, as gato_convert trusts them.
+ * gato_linsys_device_cross: that launch, the whole solve of the transformed problem and the map back - three launches where the
+ * one-workgroup solve applies, as gato_linsys_device_blocks_cross.  It records a cross assembly, so gato_solve_rhs_cross,
+ * gato_kkt_tangent_rhs_cross and gato_kkt_grad_cross follow it unchanged; gato_solver_recover does not apply.  One entry for
+ * B = 1 and batched solvers.  K = 1: the plain gato_linsys_device / _batched call.  GATO_EINVAL: a NULL array, nnz <= 0, a
+ * cluster rank, a capturing stream on a solver's first call (the work area must grow).  The caller's arrays are never written. */
+int gato_cross_prepare_csr(gato_solver *s, const int *d_G_row, const int *d_G_col, const void *d_G_val, int nnz_G,
+                           const int *d_C_row, const int *d_C_col, const void *d_C_val, int nnz_C, const void *d_g, double rho,
+                           void *d_G_out, void *d_M_out, void *d_C_out, void *stream);
+int gato_linsys_device_cross(gato_solver *s, const int *d_G_row, const int *d_G_col, const void *d_G_val, int nnz_G,
+                             const int *d_C_row, const int *d_C_col, const void *d_C_val, int nnz_C, const void *d_g,
+                             const void *d_c, double exit_tol, int max_iters, double rho, void *d_lambda, void *d_dz,
+                             void *stream);
+/* gato_kkt_grad_csr through the scatter rule above: a kept cross entry carries M_bar_k (gato_kkt_grad_cross) at its slot, bit for
+ * bit; a mirror entry, a cross entry of the last knot and an overwritten entry get 0.  Arguments and NULL rules of
+ * gato_kkt_grad_csr. */
+int gato_kkt_grad_csr_cross(gato_solver *s, const int *d_G_row, const int *d_G_col, int nnz_G, const int *d_C_row,
+                            const int *d_C_col, int nnz_C, const void *d_dz, const void *d_lam, const void *d_adz,
+                            const void *d_alam, void *d_Gbar_val, void *d_Cbar_val, void *stream);
+
 /* ---- forward-mode sensitivities of a cross solve (new): the right-hand side of its tangent system ------
  * gato_kkt_tangent_rhs for a plain solve with the cross term, one launch.  For R directions per system, from the point of the
  * latest cross solve (d_x [B][N], d_lambda [B][S*K], original variables) and the input tangents (a dot; NULL: zero, not read):

@@ -9,8 +9,8 @@ OBJ=${OBJ:-/tmp/gato_dev}; OUT=${OUT:-libgato_hip_dev.so}
 mkdir -p $OBJ ../../build/ab
 pids=()
 newer() { for h in "$@"; do [ $h -nt $OBJ/$f.o ] && return 0; done; return 1; }
-for f in gato_capi gato_ops gato_plan gato_pcg_host gato_solve gato_qp_host gato_cross_host gato_dropin gato_cluster gato_assembly gato_pcg_resident gato_pcg_resident_dpp gato_pcg_resident_single gato_pcg_cg1 gato_pcg_stream gato_pcg_dma gato_rhs gato_grad gato_qp gato_polish gato_pdas gato_pdas_ls gato_alm gato_tangent gato_cross gato_qp_cross gato_tangent_cross; do
-  hdrs="gato_common.h gato_solver.h gato_gj.h gato_qp_common.h gato_pcg_device.h"
+for f in gato_capi gato_ops gato_plan gato_pcg_host gato_solve gato_qp_host gato_cross_host gato_dropin gato_cluster gato_assembly gato_pcg_resident gato_pcg_resident_dpp gato_pcg_resident_single gato_pcg_cg1 gato_pcg_stream gato_pcg_dma gato_rhs gato_grad gato_qp gato_polish gato_pdas gato_pdas_ls gato_alm gato_tangent gato_cross gato_cross_csr gato_qp_cross gato_tangent_cross; do
+  hdrs="gato_common.h gato_solver.h gato_gj.h gato_grad_elem.h gato_qp_common.h gato_pcg_device.h"
   case $f in
     gato_pcg_resident|gato_pcg_resident_dpp) hdrs+=" gato_pcg_resident_launch.h gato_pcg_resident_kernel.h gato_pcg_geometry.h gato_pcg_launch.h";;
     gato_pcg_resident_single) hdrs+=" gato_pcg_geometry.h gato_pcg_launch.h";;
