@@ -11,7 +11,8 @@ and is off the S states of x_0; a variable with a user weight keeps its soft bou
 
 refined_inner runs the same loop over a dense solve with iterative refinement: what an infeasible box, whose multiplier grows
 without bound, needs for its stalled violation to be free of the solve's rounding.  PINNED lists, per cell, the seed the walk found, the form of its state box (boxes(states=True) as it is, widened around a feasible
-trajectory, or that trajectory's tube) and the one margin the cell drops, if any."""
+trajectory, or that trajectory's tube) and the one margin the cell drops, if any; HARD_PINNED the same for the cells of
+tests/box_qp_hard_cells.py."""
 import os
 import sys
 
@@ -275,10 +276,10 @@ def widen_states(s, lo, hi, tube=False):
     return lo, hi
 
 
-def state_problem(S, C, K, seed, widen=False):
-    """synth.make_system(S, C, K, seed) with box_qp_polish_ref.boxes(s, seed + 1, eq=K >= 3, states=True): bounds on the controls
+def state_problem(S, C, K, seed, widen=False, system=synth.make_system):
+    """system(S, C, K, seed) (synth.make_system, or a family of tests/box_qp_hard_cells.py) with box_qp_polish_ref.boxes(s, seed + 1, eq=K >= 3, states=True): bounds on the controls
     and on every other state; widen: widen_states on it ("tube": its tube form)."""
-    s = synth.make_system(S, C, K, seed=seed)
+    s = system(S, C, K, seed)
     lo, hi = P.boxes(s, seed + 1, eq=K >= 3, states=True)
     if widen:
         lo, hi = widen_states(s, lo, hi, tube=widen == "tube")
@@ -382,10 +383,10 @@ def seed_checks(p, run, eps):
     return out
 
 
-def cell_problem(S, C, K, f32, seed, form, weight_max=None):
+def cell_problem(S, C, K, f32, seed, form, weight_max=None, system=synth.make_system):
     """state_problem(S, C, K, seed) in the form `form` with its reference run ("run"), eps ("eps") and seed_checks ("checks");
     f32: the problem rounded to fp32, eps = F32_EPS, alm_weight_max = weight_max (None: F32_WEIGHT_MAX)."""
-    p = state_problem(S, C, K, seed, {"box": False, "wide": True, "tube": "tube"}[form])
+    p = state_problem(S, C, K, seed, {"box": False, "wide": True, "tube": "tube"}[form], system)
     eps, kw = 1e-6, {}
     if f32:
         p, eps = rounded(p), P.F32_EPS
@@ -403,14 +404,14 @@ def meets(p, drop=None, f32=False):
     return not f32 or f32_follows(p, slack=drop != "slack")
 
 
-def walk_cell(S, C, K, f32=False, weight_max=None):
+def walk_cell(S, C, K, f32=False, weight_max=None, system=synth.make_system):
     """The walk of a cell: the first seed < WALK_SEEDS that meets the rule on the plain box, else on the widened one, else on the
     tube; if none does, the same again with one margin dropped.  -> (seed, form, drop) or None.  Slow at the large shapes (minutes
     at 32/16/9): PINNED holds its results, and the tests check the pinned seed against the rule."""
     for drop in DROPS:
         for form in FORMS:
             for seed in range(AS.WALK_SEEDS):
-                if meets(cell_problem(S, C, K, f32, seed, form, weight_max), drop, f32):
+                if meets(cell_problem(S, C, K, f32, seed, form, weight_max, system), drop, f32):
                     return seed, form, drop
     return None
 
@@ -418,14 +419,14 @@ def walk_cell(S, C, K, f32=False, weight_max=None):
 _CELLS = {}
 
 
-def alm_box(S, C, K, f32=False):
+def alm_box(S, C, K, f32=False, system=synth.make_system, pinned=None):
     """The pinned problem of a cell (cell_problem of PINNED's seed and form, memoised) with "drop", the margin PINNED drops for it,
-    or None where the walk found none."""
+    or None where the walk found none.  system, pinned: another family of systems and its table (HARD_PINNED)."""
     cell = (S, C, K, bool(f32))
-    if cell not in _CELLS:
-        pin = PINNED.get(cell)
-        _CELLS[cell] = None if pin is None else dict(cell_problem(S, C, K, f32, pin[0], pin[1]), drop=pin[2])
-    return _CELLS[cell]
+    if (cell, system) not in _CELLS:
+        pin = (PINNED if pinned is None else pinned).get(cell)
+        _CELLS[cell, system] = None if pin is None else dict(cell_problem(S, C, K, f32, pin[0], pin[1], system=system), drop=pin[2])
+    return _CELLS[cell, system]
 
 
 def rounded(p):
@@ -488,6 +489,14 @@ PINNED = {
     (12, 6, 3, True): (10, "box", "growth"),
     (14, 7, 3, True): (1, "wide", "growth"),
     (32, 16, 3, True): (16, "box", None),
+}
+
+# walk_cell's results on the hard family of tests/box_qp_hard_cells.py (asm_ref.hard_blocks at grade 4, fp64): dense graded Q_k and
+# R_k under weights up to alm_weight_max.  tests/test_box_qp_hard_cpu.py checks each pinned seed against the rule.
+HARD_PINNED = {
+    (4, 2, 3, False): (6, "box", None),
+    (6, 3, 9, False): (19, "wide", "growth"),
+    (14, 7, 3, False): (4, "wide", None),
 }
 
 

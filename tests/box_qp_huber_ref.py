@@ -14,14 +14,15 @@ import box_qp_active_ref as AS                    # noqa: E402
 import box_qp_pdas_ref as D                       # noqa: E402
 import box_qp_polish_ref as P                     # noqa: E402
 import box_qp_soft_ref as SR                      # noqa: E402
+from gato_python_amd import synth                 # noqa: E402
 
 WEIGHT, CAP = SR.WEIGHT, 1.0                      # the weight and the cap of the walked problems' soft state bounds
 
 
 # ---- walked problems -------------------------------------------------------------------------------------------------------
-def huber_problem(S, C, K, seed, sparse=False, weight=WEIGHT, cap=CAP):
+def huber_problem(S, C, K, seed, sparse=False, weight=WEIGHT, cap=CAP, system=synth.make_system):
     """box_qp_soft_ref.soft_problem with the cap `cap` on every state.  -> (s, H, Cm, g, c, lo, hi, w, m)."""
-    s, H, Cm, g, c, lo, hi, w = SR.soft_problem(S, C, K, seed, sparse=sparse, weight=weight)
+    s, H, Cm, g, c, lo, hi, w = SR.soft_problem(S, C, K, seed, sparse=sparse, weight=weight, system=system)
     return s, H, Cm, g, c, lo, hi, w, np.where(w > 0, float(cap), np.inf)
 
 
@@ -36,14 +37,14 @@ def final_kinds(run, w, lo, hi):
 MAY_BE_EMPTY = {(2, 1, 2), (2, 1, 3), (4, 2, 2), (4, 2, 3)}
 
 
-def huber_box(S, C, K, f32=False, count=1):
+def huber_box(S, C, K, f32=False, count=1, system=synth.make_system):
     """The first `count` problems huber_problem(S, C, K, seed) of seeds 0, 1, ... < WALK_SEEDS whose cold reference run meets
     walk_ok and whose final act holds a saturated lo != hi variable and - off MAY_BE_EMPTY - a soft quadratic-active one (f32:
     with eps = F32_EPS, and f32_ok), as problem dicts with "w", "m" and the run under "run"."""
     def kinds(p):
         sat, quad = final_kinds(p["run"], p["w"], p["lo"], p["hi"])
         return sat and (quad or (S, C, K) in MAY_BE_EMPTY)
-    return AS.walk(("huber", S, C, K, f32), lambda seed: SR.walked(huber_problem, S, C, K, seed, P.F32_EPS if f32 else 1e-6),
+    return AS.walk(("huber", S, C, K, f32, system), lambda seed: SR.walked(huber_problem, S, C, K, seed, P.F32_EPS if f32 else 1e-6, system=system),
                   lambda p: AS.walk_ok(p["run"], p["H"], p["Cm"], p["w"], lambda run: kinds(p)) and (not f32 or AS.f32_ok(p)), count)
 
 
@@ -72,9 +73,9 @@ def mixed_caps(N, seed):
     return np.where(rng.random(N) < 0.5, 10.0 ** rng.uniform(-1.0, 1.0, N), np.inf)
 
 
-def mixed_problem(S, C, K, seed):
+def mixed_problem(S, C, K, seed, system=synth.make_system):
     """box_qp_soft_ref.mixed_problem with mixed_caps.  -> (s, H, Cm, g, c, lo, hi, w, m)."""
-    s, H, Cm, g, c, lo, hi, w = SR.mixed_problem(S, C, K, seed)
+    s, H, Cm, g, c, lo, hi, w = SR.mixed_problem(S, C, K, seed, system=system)
     return s, H, Cm, g, c, lo, hi, w, mixed_caps(s.N, seed)
 
 

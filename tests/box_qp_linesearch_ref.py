@@ -27,6 +27,7 @@ import box_qp_pdas_ref as D                       # noqa: E402
 import box_qp_polish_ref as P                     # noqa: E402
 import box_qp_ref as ref                          # noqa: E402
 import box_qp_soft_ref as SR                      # noqa: E402
+from gato_python_amd import synth                 # noqa: E402
 
 CONVERGED, MAX_ITERS, NONFINITE = AS.CONVERGED, AS.MAX_ITERS, AS.NONFINITE
 LS_SOLVES = 30                                    # a seed's damped run converges, and its undamped run does not, within these
@@ -171,11 +172,11 @@ LONG = D.LONG
 LONG_SOLVES = 2                                   # of the sparse reference at LONG (seconds each): the first search of a run
 
 
-def ls_problem(S, C, K, seed, weight, cap, sparse=False, eps=1e-6, undamped=True, max_pdas_iters=LS_SOLVES):
+def ls_problem(S, C, K, seed, weight, cap, sparse=False, eps=1e-6, undamped=True, max_pdas_iters=LS_SOLVES, system=synth.make_system):
     """soft_problem(S, C, K, seed) with `weight` on every variable (and `cap`, None: no caps), as a problem dict with "w" (and
     "m"), its damped reference run under "run" and - undamped - box_qp_active_ref.iterate's run of LS_SOLVES solves under
     "undamped"."""
-    s, H, Cm, g, c, lo, hi, _ = SR.soft_problem(S, C, K, seed, sparse=sparse, weight=weight)
+    s, H, Cm, g, c, lo, hi, _ = SR.soft_problem(S, C, K, seed, sparse=sparse, weight=weight, system=system)
     w = np.full(s.N, float(weight))
     wm = dict(w=w) if cap is None else dict(w=w, m=np.full(s.N, float(cap)))
     run = iterate_ls(H, Cm, g, c, lo, hi, S, w, wm.get("m"), eps_abs=eps, eps_rel=eps, max_pdas_iters=max_pdas_iters)
@@ -224,10 +225,10 @@ def f32_ok(p):
     return True
 
 
-def ls_box(S, C, K, form=CAPPED, f32=False, count=1):
+def ls_box(S, C, K, form=CAPPED, f32=False, count=1, system=synth.make_system):
     """The first `count` problems ls_problem(S, C, K, seed, *form) of seeds < WALK_SEEDS that meet ls_ok (f32: at eps = F32_EPS,
     and f32_ok)."""
-    return AS.walk(("ls", S, C, K, form, f32), lambda seed: ls_problem(S, C, K, seed, *form, eps=P.F32_EPS if f32 else 1e-6),
+    return AS.walk(("ls", S, C, K, form, f32, system), lambda seed: ls_problem(S, C, K, seed, *form, eps=P.F32_EPS if f32 else 1e-6, system=system),
                   lambda p: ls_ok(p) and (not f32 or f32_ok(p)), count)
 
 
@@ -267,18 +268,18 @@ def search_inputs(p, dtype, damped, margin=False):
     return None
 
 
-def kernel_inputs(S, C, K, form, dtype, damped, count=1, sparse=False, margin=False):
+def kernel_inputs(S, C, K, form, dtype, damped, count=1, sparse=False, margin=False, system=synth.make_system):
     """The first `count` seeds < WALK_SEEDS whose damped run (it need not converge) holds a solve that search_inputs takes, as a
     list of (p, xc, xp, exact_alpha's dict)."""
     def make(seed):
-        p = ls_problem(S, C, K, seed, *form, sparse=sparse, undamped=False, max_pdas_iters=LONG_SOLVES if sparse else LS_SOLVES)
+        p = ls_problem(S, C, K, seed, *form, sparse=sparse, undamped=False, max_pdas_iters=LONG_SOLVES if sparse else LS_SOLVES, system=system)
         return dict(p, inputs=search_inputs(p, dtype, damped, margin))
-    ps = AS.walk(("ls kernel", S, C, K, form, np.dtype(dtype).name, damped, sparse, margin), make, lambda p: p["inputs"] is not None, count)
+    ps = AS.walk(("ls kernel", S, C, K, form, np.dtype(dtype).name, damped, sparse, margin, system), make, lambda p: p["inputs"] is not None, count)
     return [(p,) + p["inputs"] for p in ps]
 
 
-def kernel_batch(S, C, K, form, dtype):
+def kernel_batch(S, C, K, form, dtype, system=synth.make_system):
     """The systems of a kernel test: two damped searches and one full step between them, of different seeds where the walks
     allow (the first one alone is the B = 1 case)."""
-    d, f = kernel_inputs(S, C, K, form, dtype, True, 2), kernel_inputs(S, C, K, form, dtype, False, 1)
+    d, f = kernel_inputs(S, C, K, form, dtype, True, 2, system=system), kernel_inputs(S, C, K, form, dtype, False, 1, system=system)
     return [d[0], f[0], d[1]] if len(d) == 2 and f else None

@@ -17,10 +17,10 @@ import kkt_grad_ref as kgr                        # noqa: E402
 from gato_python_amd import synth                 # noqa: E402
 
 
-def control_problem(S, C, K, seed, sparse=False, eps=1e-6):
-    """synth.make_system(S, C, K, seed) with box_qp_polish_ref.boxes(s, seed + 1, eq = K >= 3, states=False) and its cold
-    reference run, as a problem dict."""
-    s = synth.make_system(S, C, K, seed=seed)
+def control_problem(S, C, K, seed, sparse=False, eps=1e-6, system=synth.make_system):
+    """system(S, C, K, seed) (a callable -> KKTSystem; synth.make_system, or a family of tests/box_qp_hard_cells.py) with
+    box_qp_polish_ref.boxes(s, seed + 1, eq = K >= 3, states=False) and its cold reference run, as a problem dict."""
+    s = system(S, C, K, seed)
     if sparse:
         H, Cm, g, c = ref.sparse_parts(s)
         dz = ref.kkt_solver(H, Cm)(np.concatenate([g, c]))[:s.N]
@@ -32,10 +32,12 @@ def control_problem(S, C, K, seed, sparse=False, eps=1e-6):
     return AS.as_problem(s, H, Cm, g, c, lo, hi, run, seed)
 
 
-def control_box(S, C, K, f32=False, count=1, sparse=False):
+def control_box(S, C, K, f32=False, count=1, sparse=False, system=synth.make_system):
     """The first `count` control-only problems control_problem(S, C, K, seed) of seeds 0, 1, ... < WALK_SEEDS whose cold
-    reference run meets walk_ok (f32: with eps = F32_EPS, and f32_ok), as a list of problem dicts with the run under "run"."""
-    return AS.walk(("control", S, C, K, f32, sparse), lambda seed: control_problem(S, C, K, seed, sparse, P.F32_EPS if f32 else 1e-6),
+    reference run meets walk_ok (f32: with eps = F32_EPS, and f32_ok), as a list of problem dicts with the run under "run".
+    system: the family of systems the walk draws from, part of the walk's cache key."""
+    return AS.walk(("control", S, C, K, f32, sparse, system),
+                   lambda seed: control_problem(S, C, K, seed, sparse, P.F32_EPS if f32 else 1e-6, system),
                   lambda p: AS.walk_ok(p["run"], p["H"], p["Cm"]) and (not f32 or AS.f32_ok(p)), count)
 
 

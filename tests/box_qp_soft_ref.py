@@ -26,11 +26,11 @@ def state_weights(s, weight=WEIGHT):
     return np.where(np.arange(s.N) % n < s.S, float(weight), 0.0)
 
 
-def soft_problem(S, C, K, seed, sparse=False, weight=WEIGHT):
-    """synth.make_system(S, C, K, seed) with box_qp_polish_ref.boxes(s, seed + 1, eq = K >= 3, states=True), every state bound
+def soft_problem(S, C, K, seed, sparse=False, weight=WEIGHT, system=synth.make_system):
+    """system(S, C, K, seed) (synth.make_system, or a family of tests/box_qp_hard_cells.py) with box_qp_polish_ref.boxes(s, seed + 1, eq = K >= 3, states=True), every state bound
     soft with `weight`, every control bound hard, and for K >= 3 one soft lo == hi (a tracking term, at a quarter of the
     unconstrained value) on the first state of the last knot.  -> (s, H, Cm, g, c, lo, hi, w)."""
-    s = synth.make_system(S, C, K, seed=seed)
+    s = system(S, C, K, seed)
     if sparse:
         H, Cm, g, c = ref.sparse_parts(s)
         dz = ref.kkt_solver(H, Cm)(np.concatenate([g, c]))[:s.N]
@@ -57,11 +57,11 @@ def walked(make_problem, S, C, K, seed, eps=1e-6, **kw):
     return AS.as_problem(s, H, Cm, g, c, lo, hi, run, seed, **dict(zip(("w", "m"), wm)))
 
 
-def soft_box(S, C, K, f32=False, count=1):
+def soft_box(S, C, K, f32=False, count=1, system=synth.make_system):
     """The first `count` problems soft_problem(S, C, K, seed) of seeds 0, 1, ... < WALK_SEEDS whose cold reference run meets
     walk_ok with a soft non-equality variable active on the way (f32: with eps = F32_EPS, and f32_ok), as problem dicts with "w"
     and the run under "run"."""
-    return AS.walk(("soft", S, C, K, f32), lambda seed: walked(soft_problem, S, C, K, seed, P.F32_EPS if f32 else 1e-6),
+    return AS.walk(("soft", S, C, K, f32, system), lambda seed: walked(soft_problem, S, C, K, seed, P.F32_EPS if f32 else 1e-6, system=system),
                   lambda p: AS.walk_ok(p["run"], p["H"], p["Cm"], p["w"], soft_active_on_the_way(p)) and (not f32 or AS.f32_ok(p)), count)
 
 
@@ -83,11 +83,11 @@ def mixed_weights(N, seed):
     return np.where(rng.random(N) < 0.5, 10.0 ** rng.uniform(0.0, 3.0, N), 0.0)
 
 
-def mixed_problem(S, C, K, seed, sparse=False, hard_states=True):
+def mixed_problem(S, C, K, seed, sparse=False, hard_states=True, system=synth.make_system):
     """soft_problem's system, boxes and (K >= 3) lo == hi tracking state with mixed_weights: states and controls both draw, so
     both may be soft, and the tracking state may be hard.  hard_states=False: a state that drew 0 draws a weight of the same
     law instead - every state soft, each with its own weight; the controls as before.  -> (s, H, Cm, g, c, lo, hi, w)."""
-    s, H, Cm, g, c, lo, hi, _ = soft_problem(S, C, K, seed, sparse=sparse)
+    s, H, Cm, g, c, lo, hi, _ = soft_problem(S, C, K, seed, sparse=sparse, system=system)
     w = mixed_weights(s.N, seed)
     if not hard_states:
         rng = np.random.default_rng([seed, 311])
@@ -132,15 +132,15 @@ def covers(got, need):
     return all(g or not n for g, n in zip(got, need))
 
 
-def mixed_box(S, C, K, f32=False, count=1):
+def mixed_box(S, C, K, f32=False, count=1, system=synth.make_system):
     """soft_box's seed walk over mixed_problem: the first `count` seeds < WALK_SEEDS whose trace meets cover_need and whose cold
     reference run meets walk_ok (f32: with eps = F32_EPS, and f32_ok); each dict also holds its cover() under "cover"."""
     need = cover_need(S, C, K)
 
     def make(seed):
-        p = walked(mixed_problem, S, C, K, seed, P.F32_EPS if f32 else 1e-6)
+        p = walked(mixed_problem, S, C, K, seed, P.F32_EPS if f32 else 1e-6, system=system)
         return dict(p, cover=cover(p["run"], p["w"], p["lo"], p["hi"], S, C, K))
-    return AS.walk(("mixed", S, C, K, f32), make, lambda p: covers(p["cover"], need) and
+    return AS.walk(("mixed", S, C, K, f32, system), make, lambda p: covers(p["cover"], need) and
                   AS.walk_ok(p["run"], p["H"], p["Cm"], p["w"], soft_active_on_the_way(p)) and (not f32 or AS.f32_ok(p)), count)
 
 

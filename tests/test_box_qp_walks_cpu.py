@@ -77,9 +77,9 @@ def grads_of(p, x, lam, xbar, lambar):
     return SR.reference_grads(p, x, lam, xbar, lambar)
 
 
-def entry(name):
-    """The manifest entry of one walk: a list with one record per chosen problem."""
-    got = WALKS[name]()
+def record(got, grads=False):
+    """The manifest entry of one walk's result (a list of problems, or of (seed, run) pairs): one record per chosen problem;
+    grads: the first problem's reference gradients for a fixed upstream too."""
     pairs = got if got and isinstance(got[0], tuple) else runs_of(got)
     out = []
     for seed, run in pairs:
@@ -89,12 +89,17 @@ def entry(name):
                         trace=sha([np.asarray(t["act"], np.int8) for t in trace] + [changed]),
                         point=sha([np.asarray(run[k], np.float64) for k in ("x", "z", "y", "lam")]),
                         margin=float(min(t["margin"] for t in trace)).hex()))
-    if name in GRADS:
+    if grads:
         p = got[0]
         rng = np.random.default_rng(0)
         g = grads_of(p, p["run"]["x"], p["run"]["lam"], rng.standard_normal(len(p["run"]["x"])), rng.standard_normal(len(p["run"]["lam"])))
         out[0]["grads"] = sha([np.asarray(g[k], np.float64) for k in sorted(g)])
     return out
+
+
+def entry(name):
+    """The manifest entry of one walk: a list with one record per chosen problem."""
+    return record(WALKS[name](), name in GRADS)
 
 
 with open(MANIFEST) as f:

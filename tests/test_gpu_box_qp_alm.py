@@ -15,39 +15,14 @@ import box_qp_alm_ref as A                        # noqa: E402
 import box_qp_polish_ref as P                     # noqa: E402
 import box_qp_ref as ref                          # noqa: E402
 from gato_python_amd import _lib                  # noqa: E402
-from box_qp_device import CAP, F64, dev_inputs, dev_w, host, math_inputs, sentinels, solver, untouched  # noqa: E402
+from box_qp_device import (CAP, F64, alm_bits, alm_cold_case, alm_point as point, alm_run, check_alm_run as check_run,  # noqa: E402
+                           check_alm_steps as check_steps, dev_inputs, math_inputs, sentinels, solver, untouched)
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _need_gpu():
     assert torch.cuda.is_available(), "GPU suite needs a GPU"
     _lib.lib()
-
-
-def alm_run(sol, ps, eps=1e-6, act=None, mu=None, outs=None, **kw):
-    """Solver.box_qp_alm on the problems ps (their weights "w" and caps "m" where the first one has them)."""
-    inp = dev_inputs(sol, [p["s"] for p in ps], [(p["lo"], p["hi"]) for p in ps])
-    kw.setdefault("exit_tol", F64["exit_tol"] if sol.np_dtype == np.float64 else AS.F32_EXIT_TOL)
-    kw.setdefault("max_iters", 1000)
-    wm = {k: dev_w(sol, [p[v] for p in ps]) for k, v in (("soft_weight", "w"), ("soft_cap", "m")) if v in ps[0]}
-    if act is not None:
-        act = torch.from_numpy(np.ascontiguousarray(act, np.int8).reshape(-1)).cuda()
-    if mu is not None:
-        mu = sol.to_device(np.asarray(mu, np.float64).reshape(-1))
-    r = sol.box_qp_alm(*inp, rho=ps[0]["s"].rho, eps_abs=eps, eps_rel=eps, act=act, mu=mu, **wm, **(outs or {}), **kw)
-    torch.cuda.synchronize()
-    return r
-
-
-def alm_bits(r, b, sol):
-    B = sol.batch
-    return [t.cpu().numpy().reshape(B, -1)[b].tobytes() for t in (r.x, r.z, r.y, r.lam, r.iters, r.status, r.res_prim, r.res_dual, r.act,
-                                                                   r.outer, r.weight)]
-
-
-def point(r, b, sol):
-    B = sol.batch
-    return host(r.x, B, sol.N)[b], host(r.z, B, sol.N)[b], host(r.y, B, sol.N)[b], host(r.lam, B, sol.sizes["sk"])[b]
 
 
 # ---- 1. the two kernels alone --------------------------------------------------------------------------------------------------
@@ -148,51 +123,11 @@ def test_update_kernels_past_the_grid_cap():
 
 
 # ---- 2. end to end on the pinned seeds -----------------------------------------------------------------------------------------
-def check_run(sol, p, r, b=0):
-    """System b against problem p's reference run and x*: CONVERGED with the reference's outer steps, solves and last weight; the
-    hard QP's stationarity and equality <= 1e-7 (fp64) and its bound violation within the acceptance bar; |x - x*|_inf within ten
-    times the reference's own distance at the same eps."""
-    run, xs, eps = p["run"], p["exact"], p["eps"]
-    x, z, y, lam = point(r, b, sol)
-    print("seed", p["seed"], p["form"], "outer", int(r.outer[b]), run["outer"], "iters", int(r.iters[b]), run["iters"], "weight", float(r.weight[b]), run["weight"])
-    assert int(r.status[b]) == _lib.QP_CONVERGED
-    assert (int(r.outer[b]), int(r.iters[b]), float(r.weight[b])) == (run["outer"], run["iters"], run["weight"])
-    assert np.array_equal(r.act.cpu().numpy().reshape(sol.batch, -1)[b], run["act"])
-    lo, hi = A.hard_box(p)
-    kk = ref.qp_kkt_residuals(p["H"], p["Cm"], p["g"], p["c"], lo, hi, x, y, lam)
-    bar = eps + eps * float(np.abs(x).max())
-    dist, own = float(np.abs(x - xs["x"]).max()), float(np.abs(run["x"] - xs["x"]).max())
-    print("kkt", kk, "bar", bar, "|x - x*|", dist, "reference's own", own)
-    if sol.np_dtype == np.float64:
-        assert kk["stat"] <= 1e-7 and kk["eq"] <= 1e-7, kk
-    assert kk["bound"] <= bar and float(r.res_prim[b]) <= bar
-    assert dist <= 10 * own, (dist, own)
-    av = A.alm_set(p["lo"], p["hi"], p["s"].S, p.get("w"))
-    assert np.array_equal(z[av], np.clip(x, p["lo"], p["hi"])[av])
-    return dist, own
-
-
-def check_steps(sol, p, **kw):
-    """The reference's weight sequence and per-step solves: a run stopped after j outer steps is MAX_ITERS with the solves of the
-    first j steps, step j's weight and step j's violation."""
-    run = p["run"]
-    for j in range(1, run["outer"]):
-        part = alm_run(sol, [p], eps=p["eps"], max_alm_iters=j, outs=sentinels(sol), **kw)
-        st = run["steps"][j - 1]
-        assert int(part.status[0]) == _lib.QP_MAX_ITERS and untouched(part, 0, sol), j
-        assert (int(part.iters[0]), float(part.weight[0])) == (sum(t["solves"] for t in run["steps"][:j]), st["w"]), j
-        assert abs(float(part.res_prim[0]) - st["v"]) <= 1e-3 * st["v"] + (0 if sol.np_dtype == np.float64 else p["eps"]), (j, float(part.res_prim[0]), st["v"])
-
-
 @pytest.mark.parametrize("S,C,K", A.F64_CASES, ids=["%d-%d-%d" % c for c in A.F64_CASES])
 def test_converges_on_hard_state_bounds(S, C, K):
     p = A.alm_box(S, C, K)
     assert p is not None, "no pinned seed"
-    sol = solver(S, C, K, np.float64)
-    r = alm_run(sol, [p])
-    check_run(sol, p, r)
-    check_steps(sol, p)
-    assert alm_bits(alm_run(sol, [p]), 0, sol) == alm_bits(r, 0, sol)
+    alm_cold_case(p)
 
 
 @pytest.mark.parametrize("S,C,K", A.F32_CASES, ids=["%d-%d-%d" % c for c in A.F32_CASES])

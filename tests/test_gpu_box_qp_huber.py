@@ -16,7 +16,7 @@ import box_qp_pdas_ref as D                       # noqa: E402
 import box_qp_polish_ref as P                     # noqa: E402
 import box_qp_soft_ref as SR                      # noqa: E402
 from gato_python_amd import _lib                  # noqa: E402
-from box_qp_device import (CAP, F64, SENTINEL, check_point, cold_case, dev_inputs, dev_w, host, math_inputs, pdas, point_bits,  # noqa: E402
+from box_qp_device import (CAP, F64, SENTINEL, check_point, cold_case, dev_inputs, dev_w, fp32_case, host, math_inputs, pdas, point_bits,  # noqa: E402
                            raw_pdas, sentinels, solver, untouched)
 
 
@@ -63,18 +63,8 @@ def test_fp32_ends_on_the_reference_act(S, C, K):
     """fp32 under the fp32 seed rule at eps = F32_EPS, PCG exit tolerance F32_EXIT_TOL (box_qp_soft_ref): the reference's solves
     and act, the hard bounds and y = +-m on the saturated set bit for bit."""
     p = R.huber_box(S, C, K, f32=True)[0]
-    q = P.rounded(p)
-    sol = solver(S, C, K, np.float32)
-    r = huber(sol, dev_inputs(sol, [q["s"]], [(q["lo"], q["hi"])]), dev_w(sol, [q["w"]]), dev_w(sol, [q["m"]]), q["s"].rho,
-              eps=P.F32_EPS, exit_tol=AS.F32_EXIT_TOL, max_iters=1000)
-    print("seed", p["seed"], "solves", int(r.iters[0]), "reference", p["run"]["iters"])
-    assert int(r.status[0]) == _lib.QP_CONVERGED and int(r.iters[0]) == p["run"]["iters"]
-    act = p["run"]["act"]
-    assert np.array_equal(r.act.cpu().numpy(), act) and P.sat_set(act).any()
-    hard = (act != 0) & ~P.soft_set(act, p["w"])
-    assert np.array_equal(r.x.cpu().numpy()[hard], P.bound_values(act, q["lo"], q["hi"])[hard].astype(np.float32))
-    sat = P.sat_set(act)
-    assert np.array_equal(r.y.cpu().numpy()[sat], (np.sign(act)[sat] * q["m"][sat]).astype(np.float32))
+    assert P.sat_set(p["run"]["act"]).any()
+    fp32_case(p)
 
 
 # ---- 3. no caps: gato_box_qp_pdas_soft, bit for bit -----------------------------------------------------------------------------

@@ -10,13 +10,11 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-import box_qp_active_ref as AS                    # noqa: E402
 import box_qp_linesearch_ref as L                 # noqa: E402
 import box_qp_pdas_ref as D                       # noqa: E402
-import box_qp_polish_ref as P                     # noqa: E402
 from gato_python_amd import _lib                  # noqa: E402
-from box_qp_device import (CAP, F64, SENTINEL, check_point, dev_inputs, dev_w, math_inputs, pdas, point_bits, sentinels,  # noqa: E402
-                           solver, untouched)
+from box_qp_device import (CAP, F64, SENTINEL, check_point, check_search, dev_inputs, ls_bits, ls_converges_case, ls_fp32_case,  # noqa: E402
+                           ls_layer_gradients_case, ls_run, math_inputs, sentinels, solver)
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -25,63 +23,7 @@ def _need_gpu():
     _lib.lib()
 
 
-def caps_of(p):
-    return p["m"] if "m" in p else np.full(p["s"].N, np.inf)
-
-
-def weights_and_caps(sol, ps):
-    """soft_weight and soft_cap of Solver.box_qp_pdas for the problems ps (a cap of +inf where a problem has none)."""
-    return dict(soft_weight=dev_w(sol, [p["w"] for p in ps]), soft_cap=dev_w(sol, [caps_of(p) for p in ps]))
-
-
-def ls_run(sol, ps, **kw):
-    inp = dev_inputs(sol, [p["s"] for p in ps], [(p["lo"], p["hi"]) for p in ps])
-    return pdas(sol, inp, ps[0]["s"].rho, line_search=True, **weights_and_caps(sol, ps), **kw)
-
-
-def ls_bits(r, b, sol):
-    return point_bits(r, b, sol) + [r.alpha[b].cpu().numpy().tobytes()]
-
-
 # ---- 1. the two kernels alone --------------------------------------------------------------------------------------------------
-def check_search(sol, cases, dt, with_caps=True):
-    """Solver.box_qp_line_search on the systems `cases` (box_qp_linesearch_ref.kernel_inputs' tuples), the stepped point behind
-    a sentinel at an unaligned address.  -> the largest |phi'(alpha)| / (N eps scale) over the damped systems."""
-    B, N = len(cases), cases[0][0]["s"].N
-    eps = float(np.finfo(dt).eps)
-    ps = [c[0] for c in cases]
-    inp = dev_inputs(sol, [p["s"] for p in ps], [(p["lo"], p["hi"]) for p in ps])
-    dev = lambda vs: sol.to_device(np.concatenate(vs).astype(dt))
-    wd = dev_w(sol, [p["w"] for p in ps])
-    md = dev_w(sol, [caps_of(p) for p in ps]) if with_caps else None
-    buf = sol.new(B * N + 1).fill_(SENTINEL)
-    rho = float(np.float32(ps[0]["s"].rho)) if dt == np.float32 else ps[0]["s"].rho
-    alpha, slope, x = sol.box_qp_line_search(inp[0], inp[2], inp[4], inp[5], wd, md, dev([c[1] for c in cases]),
-                                             dev([c[2] for c in cases]), rho=rho, x=buf[1:])
-    torch.cuda.synchronize()
-    alpha, slope, x = alpha.cpu().numpy(), slope.cpu().numpy(), x.cpu().numpy().reshape(B, N)
-    assert float(buf[0]) == SENTINEL
-    worst = 0.0
-    for b, (p, xc, xp, e) in enumerate(cases):
-        q = P.rounded(p) if dt == np.float32 else p
-        H, g, lo, hi, m, w = q["H"], q["g"], q["lo"], q["hi"], q.get("m"), L.off_x0(q["w"], p["s"].S)
-        d = xp - xc
-        for j, a in enumerate((0.0, 1.0)):
-            bar = L.SLACK * N * eps * L.slope_scale(H, g, lo, hi, w, m, xc, d, a)
-            assert abs(slope[b, j] - (e["s0"], e["s1"])[j]) <= bar, (b, j, slope[b, j], e)
-        if e["alpha"] == 1.0:
-            assert alpha[b] == 1.0 and x[b].tobytes() == xp.astype(dt).tobytes(), (b, alpha[b])
-            continue
-        got = L.slope(H, g, lo, hi, w, m, xc, d, alpha[b])
-        unit = N * eps * L.slope_scale(H, g, lo, hi, w, m, xc, d, alpha[b])
-        print("system", b, "seed", p["seed"], "alpha", alpha[b], "reference", e["alpha"], "piece", e["piece"], "slope / (N eps scale)", abs(got) / unit)
-        assert e["piece"][0] <= alpha[b] <= e["piece"][1], (alpha[b], e["piece"])
-        assert abs(got) <= L.SLACK * unit, (got, unit)
-        assert np.abs(x[b] - (xc + alpha[b] * d)).max() <= 4 * eps * max(1.0, np.abs(xc).max(), np.abs(xp).max())
-        worst = max(worst, abs(got) / unit)
-    return worst
-
-
 KERNEL = [(S, C, K, dt, form) for S, C, K in L.CAPPED_CASES for dt in (np.float64, np.float32) for form in (L.CAPPED, L.UNCAPPED)]
 
 
@@ -108,15 +50,6 @@ def test_line_search_kernels_past_the_grid_cap():
 
 
 # ---- 2. end to end, fp64 -------------------------------------------------------------------------------------------------------
-def check_alphas(alpha, run):
-    want = np.array(run["alpha"])
-    got = alpha[:len(want)]
-    print("alpha", got.tolist(), "reference", want.tolist())
-    for a, t in zip(got, want):
-        assert (a == t) if t in (0.0, 1.0) else (0.0 < a < 1.0), (got, want)
-    assert not alpha[len(want):].any()
-
-
 E2E = [(c, L.CAPPED) for c in L.CAPPED_CASES] + [(c, L.UNCAPPED) for c in L.UNCAPPED_CASES]
 
 
@@ -128,20 +61,7 @@ def test_line_search_converges_where_the_undamped_iteration_does_not(case, form)
     S, C, K = case
     ps = L.ls_box(S, C, K, form)
     assert ps, "the walk finds no seed"
-    p = ps[0]
-    run = p["run"]
-    print("seed", p["seed"], "solves", run["iters"], "margin", AS.min_margin(run))
-    sol = solver(S, C, K, np.float64)
-    r = ls_run(sol, [p])
-    check_point(sol, r, 0, p, run)
-    check_alphas(r.alpha[0].cpu().numpy(), run)
-    assert ls_bits(ls_run(sol, [p]), 0, sol) == ls_bits(r, 0, sol)
-    for j in range(1, run["iters"]):
-        part = ls_run(sol, [p], max_pdas_iters=j)
-        assert int(part.status[0]) == _lib.QP_MAX_ITERS and np.array_equal(part.act.cpu().numpy(), run["trace"][j - 1]["act"]), j
-    inp = dev_inputs(sol, [p["s"]], [(p["lo"], p["hi"])])
-    und = pdas(sol, inp, p["s"].rho, outs=sentinels(sol), **weights_and_caps(sol, [p]))
-    assert int(und.status[0]) == _lib.QP_MAX_ITERS and untouched(und, 0, sol) and und.alpha is None
+    ls_converges_case(ps[0])
 
 
 @pytest.mark.parametrize("S,C,K", L.F32_CASES, ids=["%d-%d-%d" % c for c in L.F32_CASES])
@@ -150,14 +70,7 @@ def test_fp32_follows_the_reference(S, C, K):
     the reference's solves, final act and full steps."""
     ps = L.ls_box(S, C, K, L.CAPPED, f32=True)
     assert ps, "the walk finds no seed"
-    p = ps[0]
-    q = P.rounded(p)
-    sol = solver(S, C, K, np.float32)
-    r = ls_run(sol, [q], eps=P.F32_EPS, exit_tol=AS.F32_EXIT_TOL, max_iters=1000)
-    print("seed", p["seed"], "solves", int(r.iters[0]), "reference", p["run"]["iters"])
-    assert int(r.status[0]) == _lib.QP_CONVERGED and int(r.iters[0]) == p["run"]["iters"]
-    assert np.array_equal(r.act.cpu().numpy(), p["run"]["act"])
-    check_alphas(r.alpha[0].cpu().numpy(), p["run"])
+    ls_fp32_case(ps[0])
 
 
 # ---- 3. batches, warm starts, refusals -----------------------------------------------------------------------------------------
@@ -233,29 +146,4 @@ def test_layer_gradients(S, C, K, stale):
     """box_qp_layer(line_search=True): all fifteen gradients against the reference through the final act, err < 1e-6 max(1,
     |want|).  stale: another solve on the cached solver between the passes; the backward pass rebuilds its assembly with one
     solve on the saved act, without the option."""
-    import gato_python_amd
-    from box_qp_huber_ref import HUBER_KEYS
-    p = L.ls_box(S, C, K, L.CAPPED)[0]
-    s, run = p["s"], p["run"]
-    ts = math_inputs(p, requires_grad=True)
-    x, lam, info = gato_python_amd.box_qp_layer(*ts[:11], rho=s.rho, method="pdas", x_soft=ts[11], u_soft=ts[12], x_soft_max=ts[13],
-                                                u_soft_max=ts[14], line_search=True, **F64)
-    assert int(info.polished) == _lib.POLISH_ACCEPTED and int(info.iters) == run["iters"]
-    assert np.array_equal(info.act.cpu().numpy(), run["act"])
-    if stale:
-        from gato_python_amd import autograd
-        sol = autograd._SOLVERS[(S, C, K, 1, torch.float64, torch.cuda.current_device())]     # the layer's cached solver
-        q = D.control_box(S, C, K)[0]
-        gato_python_amd.kkt_solve(*math_inputs(q)[:7], rho=q["s"].rho, **F64)            # replaces the layer's assembly
-        gen = sol.get_option("assembly_gen")
-    rng = np.random.default_rng(7)
-    xbar, lbar = rng.standard_normal(s.N), rng.standard_normal(S * K)
-    ((x * torch.from_numpy(xbar).cuda()).sum() + (lam * torch.from_numpy(lbar).cuda()).sum()).backward()
-    if stale:
-        assert sol.get_option("assembly_gen") == gen + 1 and sol.get_option("assembly_valid") == 1
-    want = P.grads(p["H"], p["Cm"], run["act"], x.detach().cpu().numpy(), lam.detach().cpu().numpy(), xbar, lbar, S, C, K,
-                   w=p["w"], m=p["m"], lo=p["lo"], hi=p["hi"])
-    for k, t in zip(HUBER_KEYS, ts):
-        err = np.abs(t.grad.cpu().numpy() - want[k]).max()
-        print(k, err, np.abs(want[k]).max())
-        assert err < 1e-6 * max(1.0, np.abs(want[k]).max()), (k, err)
+    ls_layer_gradients_case(L.ls_box(S, C, K, L.CAPPED)[0], stale, D.control_box(S, C, K)[0])

@@ -15,7 +15,7 @@ import box_qp_active_ref as AS                    # noqa: E402
 import box_qp_pdas_ref as D                       # noqa: E402
 import box_qp_polish_ref as P                     # noqa: E402
 import box_qp_ref as ref                          # noqa: E402
-from box_qp_device import (CAP, F64, SENTINEL, admm, check_point, cold_case, dev_inputs, host, math_inputs, pdas, point_bits,  # noqa: E402
+from box_qp_device import (CAP, F64, SENTINEL, admm, check_point, cold_case, dev_inputs, fp32_case, host, math_inputs, pdas, point_bits,  # noqa: E402
                            polish, sentinels, solver, untouched)
 from gato_python_amd import _lib                  # noqa: E402
 
@@ -151,14 +151,7 @@ def test_fp32_ends_on_the_reference_act(shape):
     S, C = shape
     K = 9
     p = D.control_box(S, C, K, f32=True)[0]
-    q = P.rounded(p)
-    sol = solver(S, C, K, np.float32)
-    r = pdas(sol, dev_inputs(sol, [q["s"]], [(q["lo"], q["hi"])]), q["s"].rho, eps=P.F32_EPS, exit_tol=1e-8, max_iters=1000)
-    print("seed", p["seed"], "solves", int(r.iters[0]), "reference", p["run"]["iters"])
-    assert int(r.status[0]) == _lib.QP_CONVERGED
-    assert np.array_equal(r.act.cpu().numpy(), p["run"]["act"])
-    on = p["run"]["act"] != 0
-    assert np.array_equal(r.x.cpu().numpy()[on], P.bound_values(p["run"]["act"], q["lo"], q["hi"])[on].astype(np.float32))
+    fp32_case(p, iters=False)
 
 
 # ---- 7. the Python surface ----------------------------------------------------------------------------------------------------

@@ -16,7 +16,7 @@ import box_qp_pdas_ref as D                       # noqa: E402
 import box_qp_polish_ref as P                     # noqa: E402
 import box_qp_soft_ref as R                       # noqa: E402
 from gato_python_amd import _lib                  # noqa: E402
-from box_qp_device import (CAP, F64, SENTINEL, check_point, cold_case, dev_inputs, dev_w, host, math_inputs, pdas, point_bits,  # noqa: E402
+from box_qp_device import (CAP, F64, SENTINEL, check_point, cold_case, dev_inputs, dev_w, fp32_case, host, math_inputs, pdas, point_bits,  # noqa: E402
                            raw_pdas, sentinels, solver, untouched)
 
 
@@ -64,16 +64,7 @@ def test_fp32_ends_on_the_reference_act(S, C, K):
     """fp32 under the fp32 seed rule at eps = F32_EPS, PCG exit tolerance box_qp_soft_ref.F32_EXIT_TOL (see there: at 1e-8
     the device takes the reference's nine acts at 14/7/9 and then misses the primal bar on the last one, 3.8e-4 against 3.0e-4)."""
     p = R.soft_box(S, C, K, f32=True)[0]
-    q = P.rounded(p)
-    sol = solver(S, C, K, np.float32)
-    r = soft(sol, dev_inputs(sol, [q["s"]], [(q["lo"], q["hi"])]), dev_w(sol, [q["w"]]), q["s"].rho, eps=P.F32_EPS,
-             exit_tol=AS.F32_EXIT_TOL, max_iters=1000)
-    print("seed", p["seed"], "solves", int(r.iters[0]), "reference", p["run"]["iters"])
-    assert int(r.status[0]) == _lib.QP_CONVERGED and int(r.iters[0]) == p["run"]["iters"]
-    act = p["run"]["act"]
-    assert np.array_equal(r.act.cpu().numpy(), act)
-    hard = (act != 0) & ~P.soft_set(act, p["w"])
-    assert np.array_equal(r.x.cpu().numpy()[hard], P.bound_values(act, q["lo"], q["hi"])[hard].astype(np.float32))
+    fp32_case(p)
 
 
 # ---- 3. no weights: gato_box_qp_pdas, bit for bit ---------------------------------------------------------------------------

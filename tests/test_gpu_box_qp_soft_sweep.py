@@ -18,8 +18,8 @@ import box_qp_polish_ref as P                     # noqa: E402
 import box_qp_soft_ref as R                       # noqa: E402
 from f32_parity import check_f32                  # noqa: E402
 from gato_python_amd import _lib                  # noqa: E402
-from box_qp_device import (CAP, F64, SENTINEL, check_point, cold_case, dev_inputs, dev_w, g_and_c, host, math_inputs, pdas,  # noqa: E402
-                           point_bits, solver)
+from box_qp_device import (CAP, F64, SENTINEL, check_point, cold_case, dev_inputs, dev_w, fp32_case, g_and_c, host, math_inputs,  # noqa: E402
+                           pdas, point_bits, solver)
 
 SHAPES = R.SHAPES
 NAMES = ("lo_bar", "hi_bar", "w_bar")
@@ -56,16 +56,7 @@ def test_fp32_mixed_ends_on_the_reference_act(shape):
     K = R.MIXED_F32_K
     p = R.mixed_box(S, C, K, f32=True)[0]
     describe(p)
-    q = P.rounded(p)
-    sol = solver(S, C, K, np.float32)
-    r = pdas(sol, dev_inputs(sol, [q["s"]], [(q["lo"], q["hi"])]), q["s"].rho, soft_weight=dev_w(sol, [q["w"]]), eps=P.F32_EPS,
-             exit_tol=AS.F32_EXIT_TOL, max_iters=1000)
-    print("solves", int(r.iters[0]), "reference", p["run"]["iters"])
-    assert int(r.status[0]) == _lib.QP_CONVERGED and int(r.iters[0]) == p["run"]["iters"]
-    act = p["run"]["act"]
-    assert np.array_equal(r.act.cpu().numpy(), act)
-    hard = (act != 0) & ~P.soft_set(act, p["w"])
-    assert np.array_equal(r.x.cpu().numpy()[hard], P.bound_values(act, q["lo"], q["hi"])[hard].astype(np.float32))
+    fp32_case(p)
 
 
 # ---- the gradient kernel as a function of its arrays ------------------------------------------------------------------------
