@@ -10,9 +10,10 @@ matrix: Solver.solve_rhs), then one launch that forms the matrix gradients from 
 Forward mode: the tangent system has the same matrix, so a tangent is one launch for its right-hand side
 (gato_tangent.hip) and the same re-solve - through torch.autograd.forward_ad dual tensors (the jvp of the Function, one direction)
 or kkt_solve_tangents (R directions in one call).
-A cross term M takes a Function of its own over Solver.linsys_blocks_cross / solve_rhs_cross /
-kkt_grad_cross (reverse mode); its forward mode is kkt_solve_tangents(..., M=M) over Solver.tangents_cross (section 3.17), not
-forward_ad dual tensors.  Without M the code path is the one above, untouched.
+One Function, _KktSolve, serves the four input forms (blocks, blocks with a cross term, CSR, CSR with cross entries); a _Form
+record names what differs between them: the forward call, the gradient call and whether the re-solve is the cross one.
+A cross term M goes through Solver.linsys_blocks_cross / solve_rhs_cross / kkt_grad_cross (reverse
+mode); its forward mode is kkt_solve_tangents(..., M=M) over Solver.tangents_cross (section 3.17), not forward_ad dual tensors.
 kkt_solve_csr(..., cross=True) reads the cross term from the CSR itself - G entries of state rows in
 control columns - through Solver.linsys_cross and kkt_grad_csr_cross; cross=False is the path it was, which drops such entries.
 Only device tensors are taken; there is no CPU fallback.  rho is not differentiated, and double backward is not supported.
@@ -20,6 +21,7 @@ Only device tensors are taken; there is no CPU fallback.  rho is not differentia
 from __future__ import annotations
 
 import ctypes as ct
+from typing import Callable, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -90,97 +92,136 @@ def _opts(rho, exit_tol, max_iters):
     return float(rho), float(exit_tol), int(max_iters)
 
 
-# ---- block form ------------------------------------------------------------------------------------------------------
-class _BlocksSolve(torch.autograd.Function):
-    """(G_blocks [B, G_dense], C_blocks [B, C_dense], g [B, N], c [B, S K]) -> (lam [B, S K], dz [B, N])."""
+# ---- the one Function and its four input forms ----------------------------------------------------------------------------
+class _Form(NamedTuple):
+    """What one input form of the KKT solve gives _KktSolve.  vals: the form's matrix tensors, in the order of apply; idx: the
+    CSR forms' (G_row, G_col, C_row, C_col), None for blocks; opts: (rho, exit_tol, max_iters)."""
+    forward: Callable       # (sol, idx, vals, g, c, opts, lam, dz): the whole solve and check_status; lam = dz = None: into the solver's own
+    grad: Callable          # (sol, idx, vals, dz, lam, a, beta, need) -> the bars of vals, None where need (one flag per val) is False
+    cross: bool             # the assembly is a cross solve's: the adjoint re-solve is solve_rhs_cross
+    no_jvp: Optional[str]   # why forward_ad raises NotImplementedError; None: the tangent of the blocks form
+
+
+def _blocks_forward(sol, idx, vals, g, c, opts, lam, dz):
+    rho, exit_tol, max_iters = opts
+    sol.linsys_blocks(*vals, g, c, exit_tol, max_iters, rho, lam, dz)      # Cb itself: a re-solve reads the caller's C blocks again
+    sol.check_status()
+
+
+def _blocks_cross_forward(sol, idx, vals, g, c, opts, lam, dz):
+    rho, exit_tol, max_iters = opts
+    sol.linsys_blocks_cross(*vals, g, c, exit_tol, max_iters, rho, lam, dz)
+    sol.check_status()
+
+
+def _csr_forward(sol, idx, vals, g, c, opts, lam, dz):
+    rho, exit_tol, max_iters = opts
+    G_row, G_col, C_row, C_col = idx
+    G_val, C_val = vals
+    if sol.batch == 1:
+        sol.linsys(G_row, G_col, G_val, C_row, C_col, C_val, g, c, exit_tol, max_iters, rho, lam, dz)
+    else:
+        sol.linsys_batched(G_row, G_col, G_val, C_row, C_col, C_val, g, c, exit_tol, max_iters, rho, lam, dz)
+    sol.check_status()
+
+
+def _csr_cross_forward(sol, idx, vals, g, c, opts, lam, dz):
+    rho, exit_tol, max_iters = opts
+    G_row, G_col, C_row, C_col = idx
+    G_val, C_val = vals
+    sol.linsys_cross(G_row, G_col, G_val, C_row, C_col, C_val, g, c, exit_tol, max_iters, rho, lam, dz)
+    sol.check_status()
+
+
+def _pair_grad(call, vals, need):
+    """(G_bar, C_bar) like vals where need says so, filled by one call(G_bar, C_bar) unless neither is wanted."""
+    Gbar, Cbar = (torch.empty_like(v) if n else None for v, n in zip(vals, need))
+    if Gbar is not None or Cbar is not None:
+        call(Gbar, Cbar)
+    return Gbar, Cbar
+
+
+def _blocks_grad(sol, idx, vals, dz, lam, a, beta, need):
+    return _pair_grad(lambda Gbar, Cbar: sol.kkt_grad_blocks(dz, lam, a, beta, Gbar, Cbar), vals, need)
+
+
+def _blocks_cross_grad(sol, idx, vals, dz, lam, a, beta, need):
+    Gb, Mb, Cb = vals
+    Gbar, Cbar = _blocks_grad(sol, idx, (Gb, Cb), dz, lam, a, beta, (need[0], need[2]))
+    Mbar = torch.empty_like(Mb) if need[1] else None
+    if Mbar is not None and Mbar.numel():
+        sol.kkt_grad_cross(dz, a, Mbar)
+    return Gbar, Mbar, Cbar
+
+
+def _csr_grad(sol, idx, vals, dz, lam, a, beta, need):
+    return _pair_grad(lambda Gbar, Cbar: sol.kkt_grad_csr(*idx, dz, lam, a, beta, Gbar, Cbar), vals, need)
+
+
+def _csr_cross_grad(sol, idx, vals, dz, lam, a, beta, need):
+    return _pair_grad(lambda Gbar, Cbar: sol.kkt_grad_csr_cross(*idx, dz, lam, a, beta, Gbar, Cbar), vals, need)
+
+
+# vals: (G_blocks [B, G_dense], C_blocks [B, C_dense]); with a cross term (G_blocks, M_blocks [B, (K-1) S C], C_blocks); the CSR
+# pair (G_val [B, nnz_G], C_val [B, nnz_C]) on a shared pattern
+_BLOCKS = _Form(_blocks_forward, _blocks_grad, False, None)
+_BLOCKS_CROSS = _Form(_blocks_cross_forward, _blocks_cross_grad, True,
+                      "kkt_solve: forward mode with a cross term M is not built through torch.autograd.forward_ad "
+                      "(DESIGN.md section 3.17); use kkt_solve_tangents(..., M=M) for R directions in one call, or reverse mode")
+_CSR = _Form(_csr_forward, _csr_grad, False,
+             "kkt_solve_csr: forward mode is not built through torch.autograd.forward_ad; use kkt_solve_tangents on blocks, or "
+             "reverse mode")
+_CSR_CROSS = _Form(_csr_cross_forward, _csr_cross_grad, True,
+                   "kkt_solve_csr: forward mode with cross=True is not built through torch.autograd.forward_ad "
+                   "(DESIGN.md sections 3.17, 3.18); use kkt_solve_tangents(..., M=M) on blocks, or reverse mode")
+
+
+class _KktSolve(torch.autograd.Function):
+    """(g [B, N], c [B, S K], *vals of the form) -> (lam [B, S K], dz [B, N]) of the original problem."""
 
     @staticmethod
-    def forward(ctx, Gb, Cb, g, c, sol, rho, exit_tol, max_iters):
+    def forward(ctx, form, idx, sol, rho, exit_tol, max_iters, g, c, *vals):
         B = sol.batch
         lam = torch.empty(B, sol.sizes["sk"], dtype=g.dtype, device=g.device)
         dz = torch.empty(B, sol.N, dtype=g.dtype, device=g.device)
-        sol.linsys_blocks(Gb, Cb, g, c, exit_tol, max_iters, rho, lam, dz)
-        sol.check_status()
-        ctx.sol, ctx.opts, ctx.gen = sol, (rho, exit_tol, max_iters), sol.get_option("assembly_gen")
-        ctx.save_for_backward(Gb, Cb, g, c, lam, dz)      # Cb itself: the re-solve reads the caller's C blocks again
-        ctx.save_for_forward(lam, dz)
+        opts = (rho, exit_tol, max_iters)
+        form.forward(sol, idx, vals, g, c, opts, lam, dz)
+        ctx.form, ctx.idx, ctx.sol, ctx.opts, ctx.gen = form, idx, sol, opts, sol.get_option("assembly_gen")
+        ctx.save_for_backward(g, c, lam, dz, *vals)
+        if form.no_jvp is None:
+            ctx.save_for_forward(lam, dz)
         ctx.set_materialize_grads(False)
         return lam, dz
 
     @staticmethod
-    def jvp(ctx, Gb_dot, Cb_dot, g_dot, c_dot, *_):
-        """Forward mode, one direction: the tangent right-hand side and one re-solve.  It runs straight
-        after its forward, so the assembly is the forward's; a stale one raises."""
+    def jvp(ctx, *dots):
+        """Forward mode, one direction, the blocks form only: the tangent right-hand side and one
+        re-solve.  It runs straight after its forward, so the assembly is the forward's; a stale one raises."""
+        if ctx.form.no_jvp is not None:
+            raise NotImplementedError(ctx.form.no_jvp)
         lam, dz = ctx.saved_tensors
         sol = ctx.sol
         _, exit_tol, max_iters = ctx.opts
         _fresh(sol, ctx.gen, "kkt_solve")
-        dots = dict(G_dot=Gb_dot, C_dot=Cb_dot, g_dot=g_dot, c_dot=c_dot)
-        lam_dot, dz_dot = sol.tangents(1, dz, lam, exit_tol, max_iters, **_dots(dots, dz.dtype))
+        g_dot, c_dot, Gb_dot, Cb_dot = dots[6:]
+        given = dict(G_dot=Gb_dot, C_dot=Cb_dot, g_dot=g_dot, c_dot=c_dot)
+        lam_dot, dz_dot = sol.tangents(1, dz, lam, exit_tol, max_iters, **_dots(given, dz.dtype))
         return lam_dot[:, 0], dz_dot[:, 0]
 
     @staticmethod
     @once_differentiable
     def backward(ctx, lam_bar, dz_bar):
-        Gb, Cb, g, c, lam, dz = ctx.saved_tensors
-        sol = ctx.sol
-        rho, exit_tol, max_iters = ctx.opts
+        g, c, lam, dz, *vals = ctx.saved_tensors
+        form, idx, sol = ctx.form, ctx.idx, ctx.sol
+        _, exit_tol, max_iters = ctx.opts
         if lam_bar is None and dz_bar is None:
-            return (None,) * 8
+            return (None,) * (8 + len(vals))
         if sol.get_option("assembly_gen") != ctx.gen or sol.get_option("assembly_valid") == 0:
-            sol.linsys_blocks(Gb, Cb, g, c, exit_tol, max_iters, rho)    # another forward replaced the assembly
-            sol.check_status()
-        a, beta = _adjoint(sol, lam, dz, lam_bar, dz_bar, exit_tol, max_iters)
+            form.forward(sol, idx, vals, g, c, ctx.opts, None, None)      # another forward replaced the assembly
+        a, beta = _adjoint(sol, lam, dz, lam_bar, dz_bar, exit_tol, max_iters, cross=form.cross)
         need = ctx.needs_input_grad
-        Gbar = torch.empty_like(Gb) if need[0] else None
-        Cbar = torch.empty_like(Cb) if need[1] else None
-        if Gbar is not None or Cbar is not None:
-            sol.kkt_grad_blocks(dz, lam, a, beta, Gbar, Cbar)
-        return (Gbar, Cbar, a if need[2] else None, beta if need[3] else None) + (None,) * 4
-
-
-class _CrossSolve(torch.autograd.Function):
-    """_BlocksSolve with a cross term: (G_blocks, M_blocks [B, (K-1) S C], C_blocks, g, c) -> (lam, dz) of the original problem."""
-
-    @staticmethod
-    def forward(ctx, Gb, Mb, Cb, g, c, sol, rho, exit_tol, max_iters):
-        B = sol.batch
-        lam = torch.empty(B, sol.sizes["sk"], dtype=g.dtype, device=g.device)
-        dz = torch.empty(B, sol.N, dtype=g.dtype, device=g.device)
-        sol.linsys_blocks_cross(Gb, Mb, Cb, g, c, exit_tol, max_iters, rho, lam, dz)
-        sol.check_status()
-        ctx.sol, ctx.opts, ctx.gen = sol, (rho, exit_tol, max_iters), sol.get_option("assembly_gen")
-        ctx.save_for_backward(Gb, Mb, Cb, g, c, lam, dz)
-        ctx.set_materialize_grads(False)
-        return lam, dz
-
-    @staticmethod
-    def jvp(ctx, *_):
-        raise NotImplementedError("kkt_solve: forward mode with a cross term M is not built through torch.autograd.forward_ad "
-                                  "(DESIGN.md section 3.17); use kkt_solve_tangents(..., M=M) for R directions in one call, or "
-                                  "reverse mode")
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, lam_bar, dz_bar):
-        Gb, Mb, Cb, g, c, lam, dz = ctx.saved_tensors
-        sol = ctx.sol
-        rho, exit_tol, max_iters = ctx.opts
-        if lam_bar is None and dz_bar is None:
-            return (None,) * 9
-        if sol.get_option("assembly_gen") != ctx.gen or sol.get_option("assembly_valid") == 0:
-            sol.linsys_blocks_cross(Gb, Mb, Cb, g, c, exit_tol, max_iters, rho)    # another forward replaced the assembly
-            sol.check_status()
-        a, beta = _adjoint(sol, lam, dz, lam_bar, dz_bar, exit_tol, max_iters, cross=True)
-        need = ctx.needs_input_grad
-        Gbar = torch.empty_like(Gb) if need[0] else None
-        Mbar = torch.empty_like(Mb) if need[1] else None
-        Cbar = torch.empty_like(Cb) if need[2] else None
-        if Gbar is not None or Cbar is not None:
-            sol.kkt_grad_blocks(dz, lam, a, beta, Gbar, Cbar)
-        if Mbar is not None and Mbar.numel():
-            sol.kkt_grad_cross(dz, a, Mbar)
-        return (Gbar, Mbar, Cbar, a if need[3] else None, beta if need[4] else None) + (None,) * 4
+        bars = form.grad(sol, idx, vals, dz, lam, a, beta, need[8:])
+        return (None,) * 6 + (a if need[6] else None, beta if need[7] else None) + tuple(bars)
 
 
 def _fresh(sol, gen, what):
@@ -254,27 +295,15 @@ def kkt_solve(Q, R, A, B, q, r, c, *, M=None, rho, exit_tol, max_iters):
     if M is not None:
         _check_cross(M, lead, K, S, C, Q, "kkt_solve")
     device, dtype = _common(args, "kkt_solve")
-    if M is not None:
-        return _kkt_solve_cross(Q, R, A, B, q, r, c, M, batched, K, S, C, device, dtype, _opts(rho, exit_tol, max_iters))
-    if not batched:
-        Q, R, A, B, q, r, c = (t.unsqueeze(0) for t in (Q, R, A, B, q, r, c))
-    Bt = Q.shape[0]
+    blocks = (Q, R, A, B, q, r, c) if batched else tuple(t.unsqueeze(0) for t in (Q, R, A, B, q, r, c))
+    Bt = blocks[0].shape[0]
     rho, exit_tol, max_iters = _opts(rho, exit_tol, max_iters)
-    Gb, Cb, g, cc = _pack(Q, R, A, B, q, r, c)
+    Gb, Cb, g, cc = _pack(*blocks)
+    form, vals = _BLOCKS, (Gb, Cb)
+    if M is not None:                                                      # M in the layout of B: column-major per knot
+        form, vals = _BLOCKS_CROSS, (Gb, M.transpose(-1, -2).reshape(Bt, (K - 1) * S * C).contiguous(), Cb)
     sol = _solver(S, C, K, Bt, dtype, device)
-    lam, dz = _BlocksSolve.apply(Gb, Cb, g, cc, sol, rho, exit_tol, max_iters)
-    return (lam, dz) if batched else (lam[0], dz[0])
-
-
-def _kkt_solve_cross(Q, R, A, B, q, r, c, M, batched, K, S, C, device, dtype, opts):
-    """kkt_solve with a checked M: the pack of kkt_solve, M in the layout of B, then _CrossSolve."""
-    if not batched:
-        Q, R, A, B, q, r, c, M = (t.unsqueeze(0) for t in (Q, R, A, B, q, r, c, M))
-    Bt = Q.shape[0]
-    Gb, Cb, g, cc = _pack(Q, R, A, B, q, r, c)
-    Mb = M.transpose(-1, -2).reshape(Bt, (K - 1) * S * C).contiguous()                 # column-major per knot
-    sol = _solver(S, C, K, Bt, dtype, device)
-    lam, dz = _CrossSolve.apply(Gb, Mb, Cb, g, cc, sol, *opts)
+    lam, dz = _KktSolve.apply(form, None, sol, rho, exit_tol, max_iters, g, cc, *vals)
     return (lam, dz) if batched else (lam[0], dz[0])
 
 
@@ -363,93 +392,6 @@ def kkt_solve_tangents(Q, R, A, B, q, r, c, tangents, *, M=None, rho, exit_tol, 
 
 
 # ---- CSR form ----------------------------------------------------------------------------------------------------------
-class _CsrSolve(torch.autograd.Function):
-    """(G_val [B, nnz_G], C_val [B, nnz_C], g [B, N], c [B, S K]) on a shared pattern -> (lam [B, S K], dz [B, N])."""
-
-    @staticmethod
-    def forward(ctx, G_val, C_val, g, c, idx, sol, rho, exit_tol, max_iters):
-        B = sol.batch
-        lam = torch.empty(B, sol.sizes["sk"], dtype=g.dtype, device=g.device)
-        dz = torch.empty(B, sol.N, dtype=g.dtype, device=g.device)
-        _csr_forward(sol, idx, G_val, C_val, g, c, exit_tol, max_iters, rho, lam, dz)
-        ctx.sol, ctx.idx, ctx.opts, ctx.gen = sol, idx, (rho, exit_tol, max_iters), sol.get_option("assembly_gen")
-        ctx.save_for_backward(G_val, C_val, g, c, lam, dz)
-        ctx.set_materialize_grads(False)
-        return lam, dz
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, lam_bar, dz_bar):
-        G_val, C_val, g, c, lam, dz = ctx.saved_tensors
-        sol, idx = ctx.sol, ctx.idx
-        rho, exit_tol, max_iters = ctx.opts
-        if lam_bar is None and dz_bar is None:
-            return (None,) * 9
-        if sol.get_option("assembly_gen") != ctx.gen or sol.get_option("assembly_valid") == 0:
-            _csr_forward(sol, idx, G_val, C_val, g, c, exit_tol, max_iters, rho, None, None)
-        a, beta = _adjoint(sol, lam, dz, lam_bar, dz_bar, exit_tol, max_iters)
-        need = ctx.needs_input_grad
-        Gbar = torch.empty_like(G_val) if need[0] else None
-        Cbar = torch.empty_like(C_val) if need[1] else None
-        if Gbar is not None or Cbar is not None:
-            sol.kkt_grad_csr(*idx, dz, lam, a, beta, Gbar, Cbar)
-        return (Gbar, Cbar, a if need[2] else None, beta if need[3] else None) + (None,) * 5
-
-
-class _CsrCrossSolve(torch.autograd.Function):
-    """_CsrSolve on a G with cross entries: the forward is Solver.linsys_cross, the adjoint re-solve is
-    solve_rhs_cross, and a kept cross entry's gradient is M_bar at its slot (kkt_grad_csr_cross)."""
-
-    @staticmethod
-    def forward(ctx, G_val, C_val, g, c, idx, sol, rho, exit_tol, max_iters):
-        B = sol.batch
-        lam = torch.empty(B, sol.sizes["sk"], dtype=g.dtype, device=g.device)
-        dz = torch.empty(B, sol.N, dtype=g.dtype, device=g.device)
-        _csr_cross_forward(sol, idx, G_val, C_val, g, c, exit_tol, max_iters, rho, lam, dz)
-        ctx.sol, ctx.idx, ctx.opts, ctx.gen = sol, idx, (rho, exit_tol, max_iters), sol.get_option("assembly_gen")
-        ctx.save_for_backward(G_val, C_val, g, c, lam, dz)
-        ctx.set_materialize_grads(False)
-        return lam, dz
-
-    @staticmethod
-    def jvp(ctx, *_):
-        raise NotImplementedError("kkt_solve_csr: forward mode with cross=True is not built through torch.autograd.forward_ad "
-                                  "(DESIGN.md sections 3.17, 3.18); use kkt_solve_tangents(..., M=M) on blocks, or reverse mode")
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, lam_bar, dz_bar):
-        G_val, C_val, g, c, lam, dz = ctx.saved_tensors
-        sol, idx = ctx.sol, ctx.idx
-        rho, exit_tol, max_iters = ctx.opts
-        if lam_bar is None and dz_bar is None:
-            return (None,) * 9
-        if sol.get_option("assembly_gen") != ctx.gen or sol.get_option("assembly_valid") == 0:
-            _csr_cross_forward(sol, idx, G_val, C_val, g, c, exit_tol, max_iters, rho, None, None)    # another forward replaced the assembly
-        a, beta = _adjoint(sol, lam, dz, lam_bar, dz_bar, exit_tol, max_iters, cross=True)
-        need = ctx.needs_input_grad
-        Gbar = torch.empty_like(G_val) if need[0] else None
-        Cbar = torch.empty_like(C_val) if need[1] else None
-        if Gbar is not None or Cbar is not None:
-            sol.kkt_grad_csr_cross(*idx, dz, lam, a, beta, Gbar, Cbar)
-        return (Gbar, Cbar, a if need[2] else None, beta if need[3] else None) + (None,) * 5
-
-
-def _csr_cross_forward(sol, idx, G_val, C_val, g, c, exit_tol, max_iters, rho, lam, dz):
-    G_row, G_col, C_row, C_col = idx
-    sol.linsys_cross(G_row, G_col, G_val, C_row, C_col, C_val, g, c, exit_tol, max_iters, rho, lam, dz)
-    sol.check_status()
-
-
-def _csr_forward(sol, idx, G_val, C_val, g, c, exit_tol, max_iters, rho, lam, dz):
-    G_row, G_col, C_row, C_col = idx
-    if sol.batch == 1:
-        sol.linsys(G_row, G_col, G_val, C_row, C_col, C_val, g, c, exit_tol, max_iters, rho, lam, dz)
-    else:
-        sol.linsys_batched(G_row, G_col, G_val, C_row, C_col, C_val, g, c, exit_tol, max_iters, rho, lam, dz)
-    sol.check_status()
-
-
 def _index(t, name, what, device):
     if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device.index != device:
         raise ValueError(f"{what}: {name} must be a CUDA tensor on cuda:{device} (there is no CPU fallback)")
@@ -562,5 +504,5 @@ def kkt_solve_csr(G_row, G_col, G_val, C_row, C_col, C_val, g, c, *, cross=False
     rho, exit_tol, max_iters = _opts(rho, exit_tol, max_iters)
     G_val2, C_val2, g2, c2 = (t.reshape(Bt, -1).contiguous() for t in (G_val, C_val, g, c))
     sol = _solver(S, C, K, Bt, dtype, device)
-    lam, dz = (_CsrCrossSolve if cross else _CsrSolve).apply(G_val2, C_val2, g2, c2, (G_row, G_col, C_row, C_col), sol, rho, exit_tol, max_iters)
+    lam, dz = _KktSolve.apply(_CSR_CROSS if cross else _CSR, (G_row, G_col, C_row, C_col), sol, rho, exit_tol, max_iters, g2, c2, G_val2, C_val2)
     return (lam, dz) if batched else (lam[0], dz[0])

@@ -305,7 +305,7 @@ int launch_rhs_gamma(const Dims &d, int R, const T *Ginv, const T *Cd, const T *
 // C_bar [B][c_dense] (either may be null), or per CSR entry of a pattern the systems share, [B][nnz] (either may be null)
 template <typename T, int S, int C>
 int launch_grad_blocks(const Dims &d, const T *dz, const T *lam, const T *a, const T *beta, T *Gbar, T *Cbar, hipStream_t st);
-template <typename T, int S, int C>
+template <typename T, int S, int C, bool CROSS = false>     // CROSS: gato_kkt_grad_csr_cross, a unit-local instantiation of gato_grad.hip
 int launch_grad_csr(const Dims &d, const int *G_row, const int *G_col, int nnzG, const int *C_row, const int *C_col, int nnzC,
                     const T *dz, const T *lam, const T *a, const T *beta, T *Gbar, T *Cbar, hipStream_t st);
 // Box-constrained QP by ADMM over the KKT re-solve (gato_qp.hip).  Per-system arrays [B][...]:

@@ -10,10 +10,8 @@
 // The per-knot kernels: one wave per knot, grid.x strides over the knots, grid.y = system, operands staged in LDS.  Every output
 // element has one writer and one chain of fused multiply-adds over the ascending inner index: no atomics, and the bits do not
 // depend on the launch geometry.
-#include "gato_solver.h"
-#include "gato_gj.h"
+#include "gato_cross_device.h"
 #include "gato_grad_elem.h"
-#include "gato_qp_common.h"
 
 namespace gato {
 namespace {
@@ -47,51 +45,7 @@ __global__ __launch_bounds__(WAVE) void cross_prepare_kernel(CrossArgs a, int K,
         for (int e = lane; e < CC; e += WAVE) sR[e] = G[gb + SS + e];
         if (lane < n) sg[lane] = g[v0 + lane];
         __syncthreads();
-        {                                                                    // (R_k + rho I)^-1 by the assembly's Gauss-Jordan
-            T col[C];
-#pragma unroll
-            for (int r = 0; r < C; ++r) {
-                T e = (T)(lane - C == r);
-                if (lane < C) {
-                    e = sR[lane * C + r];
-                    if (lane == r) e += rho;
-                }
-                col[r] = e;
-            }
-            gj_inverse_reg<T, C>(col);
-            if (lane >= C && lane < 2 * C) {
-#pragma unroll
-                for (int r = 0; r < C; ++r) sRi[(lane - C) * C + r] = col[r];
-            }
-        }
-        __syncthreads();
-        for (int e = lane; e < SC; e += WAVE) {                              // W = Rinv M^T: W[c][s] = sum_j Rinv[c][j] M[s][j]
-            const int c = e % C, s = e / C;
-            T t = (T)0;
-            for (int j = 0; j < C; ++j) t = fmaT(sRi[c + j * C], sM[s + j * S], t);
-            sW[e] = t;
-            W[mb + e] = t;
-        }
-        __syncthreads();
-        for (int e = lane; e < SS; e += WAVE) {                              // Q'' = Q - M W and A^' = A^ - B^ W
-            const int i = e % S, j = e / S;
-            T q = sQ[e], t = sA[e];
-            for (int c = 0; c < C; ++c) {
-                const T w = sW[c + j * C];
-                q = fmaT(-sM[i + c * S], w, q);
-                t = fmaT(-sB[i + c * S], w, t);
-            }
-            Gp[gb + e] = q;
-            Cp[cb + e] = t;
-        }
-        for (int e = lane; e < CC; e += WAVE) Gp[gb + SS + e] = sR[e];       // R and B^ unchanged
-        for (int e = lane; e < SC; e += WAVE) Cp[cb + SS + e] = sB[e];
-        if (lane < n) {                                                      // g'_x = g_x - W^T g_u, g'_u = g_u
-            T t = sg[lane];
-            if (lane < S)
-                for (int c = 0; c < C; ++c) t = fmaT(-sW[c + lane * C], sg[S + c], t);
-            gp[v0 + lane] = t;
-        }
+        cross_transform_knot<T, S, C, WAVE>(sQ, sR, sA, sB, sM, sg, sW, sRi, rho, lane, Gp, gb, Cp, cb, W, mb, gp, v0);
     }
 }
 
@@ -117,8 +71,7 @@ __global__ __launch_bounds__(WAVE) void cross_rhs_kernel(const T *__restrict__ W
             __syncthreads();
             if (lane < (full ? n : S)) {
                 T t = sg[lane];
-                if (full && lane < S)
-                    for (int c = 0; c < C; ++c) t = fmaT(-sW[c + lane * C], sg[S + c], t);
+                if (full && lane < S) t = cross_fold_g<T, S, C>(sW, sg + S, t, lane);
                 gp[o + lane] = t;
             }
             __syncthreads();                                                 // sg is free for the next right-hand side
@@ -143,11 +96,7 @@ __global__ __launch_bounds__(WAVE) void cross_finish_kernel(const T *__restrict_
             const size_t o = (sys * R + r) * bs.n + v0;
             if (lane < S) sx[lane] = dz[o + lane];
             __syncthreads();
-            if (lane < C) {
-                T t = dz[o + S + lane];
-                for (int s = 0; s < S; ++s) t = fmaT(-sW[lane + s * C], sx[s], t);
-                dz[o + S + lane] = t;
-            }
+            if (lane < C) dz[o + S + lane] = cross_unfold_u<T, S, C>(sW, sx, dz[o + S + lane], lane);
             __syncthreads();                                                 // sx is free for the next solution
         }
     }
@@ -206,38 +155,30 @@ int launch_grad(const Dims &d, const void *dz, const void *a, void *Mbar, hipStr
 }  // namespace
 }  // namespace gato
 
-// The launcher's instantiation (X, defined around each use) for the solver's (dtype, S, C): every compiled shape, both precisions.
-#define GATO_CROSS_DISPATCH()                                                                                          \
-    do {                                                                                                               \
-        GATO_SHAPES(X)                                                                                                 \
-        set_error("cross term: (STATE_SIZE=%d, CONTROL_SIZE=%d) is not a compiled shape", d.S, d.C);                   \
-        return GATO_ESHAPE;                                                                                            \
-    } while (0)
-
 int cross_prepare(const Dims &d, int dtype, const CrossArgs &a, hipStream_t st)
 {
-#define X(S_, C_) if (d.S == S_ && d.C == C_) return dtype == GATO_F32 ? launch_prepare<float, S_, C_>(d, a, st) : launch_prepare<double, S_, C_>(d, a, st);
-    GATO_CROSS_DISPATCH();
-#undef X
+#define GATO_CROSS_LAUNCH(T, S_, C_) launch_prepare<T, S_, C_>(d, a, st)
+    GATO_CROSS_DISPATCH("cross term");
+#undef GATO_CROSS_LAUNCH
 }
 
 int cross_rhs(const Dims &d, int dtype, int R, const void *W, const void *g, void *gp, hipStream_t st)
 {
-#define X(S_, C_) if (d.S == S_ && d.C == C_) return dtype == GATO_F32 ? launch_rhs<float, S_, C_>(d, R, W, g, gp, st) : launch_rhs<double, S_, C_>(d, R, W, g, gp, st);
-    GATO_CROSS_DISPATCH();
-#undef X
+#define GATO_CROSS_LAUNCH(T, S_, C_) launch_rhs<T, S_, C_>(d, R, W, g, gp, st)
+    GATO_CROSS_DISPATCH("cross term");
+#undef GATO_CROSS_LAUNCH
 }
 
 int cross_finish(const Dims &d, int dtype, int R, const void *W, void *dz, hipStream_t st)
 {
-#define X(S_, C_) if (d.S == S_ && d.C == C_) return dtype == GATO_F32 ? launch_finish<float, S_, C_>(d, R, W, dz, st) : launch_finish<double, S_, C_>(d, R, W, dz, st);
-    GATO_CROSS_DISPATCH();
-#undef X
+#define GATO_CROSS_LAUNCH(T, S_, C_) launch_finish<T, S_, C_>(d, R, W, dz, st)
+    GATO_CROSS_DISPATCH("cross term");
+#undef GATO_CROSS_LAUNCH
 }
 
 int cross_grad(const Dims &d, int dtype, const void *dz, const void *a, void *Mbar, hipStream_t st)
 {
-#define X(S_, C_) if (d.S == S_ && d.C == C_) return dtype == GATO_F32 ? launch_grad<float, S_, C_>(d, dz, a, Mbar, st) : launch_grad<double, S_, C_>(d, dz, a, Mbar, st);
-    GATO_CROSS_DISPATCH();
-#undef X
+#define GATO_CROSS_LAUNCH(T, S_, C_) launch_grad<T, S_, C_>(d, dz, a, Mbar, st)
+    GATO_CROSS_DISPATCH("cross term");
+#undef GATO_CROSS_LAUNCH
 }

@@ -9,13 +9,11 @@
 // rho is NOT added while gathering: the work area's G' is "without rho", as gato_cross_prepare takes its blocks, and the whole
 // solve adds rho to every diagonal entry - the plain CSR path adds it to the diagonal entries the CSR stores, so the two differ
 // exactly on a diagonal entry that is not stored.
-// One workgroup per knot, grid.x strides over the knots, grid.y = system (shared index arrays, own values).  The transform is
-// cross_prepare_kernel's statement for statement on the LDS blocks: one writer and one chain of fused multiply-adds over the
-// ascending inner index per output element, so the work area equals, bit for bit, gato_cross_prepare on the scattered blocks,
-// whatever the workgroup size.
-#include "gato_solver.h"
-#include "gato_gj.h"
-#include "gato_qp_common.h"
+// One workgroup per knot, grid.x strides over the knots, grid.y = system (shared index arrays, own values).  The transform calls
+// cross_transform_knot (gato_cross_device.h) on the LDS blocks, as cross_prepare_kernel does: one writer and one chain of fused
+// multiply-adds over the ascending inner index per output element, so the work area equals, bit for bit, gato_cross_prepare on
+// the scattered blocks, whatever the workgroup size.
+#include "gato_cross_device.h"
 
 namespace gato {
 namespace {
@@ -47,7 +45,7 @@ __global__ __launch_bounds__(NT) void cross_prepare_csr_kernel(CrossCsrArgs a, i
     __shared__ int sown[NSLOT];
     __shared__ int s_coll;
     T *sQ = blk, *sR = blk + OR, *sA = blk + OA, *sB = blk + OB, *sM = blk + OM;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const size_t sys = blockIdx.y, ms = (size_t)(K - 1) * SC;
     const int *__restrict__ G_row = a.G_row, *__restrict__ G_col = a.G_col, *__restrict__ C_row = a.C_row, *__restrict__ C_col = a.C_col;
     const T *__restrict__ G_val = (const T *)a.G_val + sys * bs.nnzG, *__restrict__ C_val = (const T *)a.C_val + sys * bs.nnzC;
@@ -132,51 +130,7 @@ __global__ __launch_bounds__(NT) void cross_prepare_csr_kernel(CrossCsrArgs a, i
         const size_t cb = (size_t)k * ABS, mb = (size_t)k * SC;
         if (Co) for (int i = tid; i < ABS; i += NT) Co[cb + i] = sA[i];
         if (Mo) for (int i = tid; i < SC; i += NT) Mo[mb + i] = sM[i];
-        if (wave == 0) {                                                     // (R_k + rho I)^-1 by the assembly's Gauss-Jordan, one wave
-            T col[C];
-#pragma unroll
-            for (int r = 0; r < C; ++r) {
-                T e = (T)(lane - C == r);
-                if (lane < C) {
-                    e = sR[lane * C + r];
-                    if (lane == r) e += rho;
-                }
-                col[r] = e;
-            }
-            gj_inverse_reg<T, C>(col);
-            if (lane >= C && lane < 2 * C) {
-#pragma unroll
-                for (int r = 0; r < C; ++r) sRi[(lane - C) * C + r] = col[r];
-            }
-        }
-        __syncthreads();
-        for (int e = tid; e < SC; e += NT) {                                 // W = Rinv M^T: W[c][s] = sum_j Rinv[c][j] M[s][j]
-            const int c = e % C, s = e / C;
-            T t = (T)0;
-            for (int j = 0; j < C; ++j) t = fmaT(sRi[c + j * C], sM[s + j * S], t);
-            sW[e] = t;
-            W[mb + e] = t;
-        }
-        __syncthreads();
-        for (int e = tid; e < SS; e += NT) {                                 // Q'' = Q - M W and A^' = A^ - B^ W
-            const int i = e % S, j = e / S;
-            T q = sQ[e], t = sA[e];
-            for (int c = 0; c < C; ++c) {
-                const T w = sW[c + j * C];
-                q = fmaT(-sM[i + c * S], w, q);
-                t = fmaT(-sB[i + c * S], w, t);
-            }
-            Gp[gb + e] = q;
-            Cp[cb + e] = t;
-        }
-        for (int e = tid; e < CC; e += NT) Gp[gb + SS + e] = sR[e];          // R and B^ unchanged
-        for (int e = tid; e < SC; e += NT) Cp[cb + SS + e] = sB[e];
-        if (tid < n) {                                                       // g'_x = g_x - W^T g_u, g'_u = g_u
-            T t = sg[tid];
-            if (tid < S)
-                for (int c = 0; c < C; ++c) t = fmaT(-sW[c + tid * C], sg[S + c], t);
-            gp[v0 + tid] = t;
-        }
+        cross_transform_knot<T, S, C, NT>(sQ, sR, sA, sB, sM, sg, sW, sRi, rho, tid, Gp, gb, Cp, cb, W, mb, gp, v0);
     }
 }
 
@@ -196,9 +150,7 @@ int launch_prepare_csr(const Dims &d, const CrossCsrArgs &a, int threads, hipStr
 
 int cross_prepare_csr(const Dims &d, int dtype, const CrossCsrArgs &a, int threads, hipStream_t st)
 {
-#define X(S_, C_) if (d.S == S_ && d.C == C_) return dtype == GATO_F32 ? launch_prepare_csr<float, S_, C_>(d, a, threads, st) : launch_prepare_csr<double, S_, C_>(d, a, threads, st);
-    GATO_SHAPES(X)
-#undef X
-    set_error("cross term: (STATE_SIZE=%d, CONTROL_SIZE=%d) is not a compiled shape", d.S, d.C);
-    return GATO_ESHAPE;
+#define GATO_CROSS_LAUNCH(T, S_, C_) launch_prepare_csr<T, S_, C_>(d, a, threads, st)
+    GATO_CROSS_DISPATCH("cross term");
+#undef GATO_CROSS_LAUNCH
 }

@@ -42,16 +42,56 @@ static Dims kernel_dims(const gato_solver *s)
     return d;
 }
 
-// prepare into the work area; the assembly that read the area's C' (if any) is no longer the solver's
-int cross_prepare_ws(gato_solver *s, const char *who, const void *d_G, const void *d_M, const void *d_C, const void *d_g, double rho,
-                     CrossWs *o, hipStream_t st)
+// "R >= 1 and batch x R <= 65535": the right-hand sides of a batch are the y of one grid
+static int check_R(const gato_solver *s, const char *who, int R)
+{
+    if (R >= 1 && (long long)R * s->d.B <= 65535) return GATO_OK;
+    set_error("%s: R = %d must be >= 1 and batch x R <= 65535 (batch %d)", who, R, s->d.B);
+    return GATO_EINVAL;
+}
+
+static int check_cross_assembly(const gato_solver *s, const char *who)
+{
+    if (s->cross.valid && s->as.valid && s->cross.gen == s->as.gen) return GATO_OK;
+    set_error("%s: the solver's current assembly is not that of a cross solve: run gato_linsys_device_blocks_cross first; any "
+              "other whole solve, box-QP call or stage entry since then replaces it", who);
+    return GATO_EINVAL;
+}
+
+// The work area, laid out (*o) and grown if need be, about to be written: a recorded cross assembly is forgotten, and the
+// assembly that read the area's C' (if any) is no longer the solver's.
+static int cross_ws_begin(gato_solver *s, const char *who, CrossWs *o, hipStream_t st)
 {
     *o = cross_layout(s);
     int rc;
     if ((rc = grow(who, &s->cross_ws, &s->cross_ws_bytes, o->bytes, st))) return rc;
-    char *w = s->cross_ws;
     s->cross.valid = 0;
-    if (s->as.Cd == w + o->C) s->as.valid = 0;
+    if (s->as.Cd == s->cross_ws + o->C) s->as.valid = 0;
+    return GATO_OK;
+}
+
+// The whole solve of the problem prepared in the work area and the map back: the tail of both whole-solve entries (K > 1)
+static int cross_solve_ws(gato_solver *s, const CrossWs &o, const void *d_c, double exit_tol, int max_iters, double rho, void *d_lambda,
+                          void *d_dz, hipStream_t st)
+{
+    char *w = s->cross_ws;
+    void *dz = d_dz ? d_dz : s->dz;
+    const AsmInput in{2, nullptr, nullptr, w + o.G, nullptr, nullptr, nullptr, w + o.C, false};
+    int rc;
+    if ((rc = whole_solve(s, pcg_opts(*s), in, w + o.g, d_c, exit_tol, max_iters, rho, d_lambda ? d_lambda : s->lambda, dz, st))) return rc;
+    s->lc.valid = 0;                                                         // a recover would leave dz in the transformed variables
+    if ((rc = cross_finish(kernel_dims(s), s->dtype, 1, w + o.W, dz, st))) return rc;
+    s->cross = {1, s->as.gen};
+    return GATO_OK;
+}
+
+// prepare into the work area
+int cross_prepare_ws(gato_solver *s, const char *who, const void *d_G, const void *d_M, const void *d_C, const void *d_g, double rho,
+                     CrossWs *o, hipStream_t st)
+{
+    int rc;
+    if ((rc = cross_ws_begin(s, who, o, st))) return rc;
+    char *w = s->cross_ws;
     CrossArgs a{d_G, d_M, d_C, d_g, w + o->G, w + o->C, w + o->W, w + o->g, rho};
     return cross_prepare(kernel_dims(s), s->dtype, a, st);
 }
@@ -71,7 +111,7 @@ extern "C" int gato_cross_prepare(gato_solver *s, const void *d_G_blocks, const 
 static int check_stage(gato_solver *s, const char *who, int R, const void *p0, const void *p1)
 {
     if (!solver_usable(s, who, "cross-term solves")) return GATO_EINVAL;
-    if (R < 1 || (long long)R * s->d.B > 65535) { set_error("%s: R = %d must be >= 1 and batch x R <= 65535 (batch %d)", who, R, s->d.B); return GATO_EINVAL; }
+    if (check_R(s, who, R)) return GATO_EINVAL;
     if (!p0 || !p1) { set_error("%s: every pointer is required", who); return GATO_EINVAL; }
     if (!s->cross_ws) { set_error("%s: no W yet: run gato_linsys_device_blocks_cross or gato_cross_prepare first", who); return GATO_EINVAL; }
     return GATO_OK;
@@ -111,14 +151,7 @@ extern "C" int gato_linsys_device_blocks_cross(gato_solver *s, const void *d_G_b
     }
     CrossWs o;
     if ((rc = cross_prepare_ws(s, who, d_G_blocks, d_M_blocks, d_C_blocks, d_g, rho, &o, st))) return rc;
-    char *w = s->cross_ws;
-    void *dz = d_dz ? d_dz : s->dz;
-    const AsmInput in{2, nullptr, nullptr, w + o.G, nullptr, nullptr, nullptr, w + o.C, false};
-    if ((rc = whole_solve(s, pcg_opts(*s), in, w + o.g, d_c, exit_tol, max_iters, rho, d_lambda ? d_lambda : s->lambda, dz, st))) return rc;
-    s->lc.valid = 0;                                                         // a recover would leave dz in the transformed variables
-    if ((rc = cross_finish(kernel_dims(s), s->dtype, 1, w + o.W, dz, st))) return rc;
-    s->cross = {1, s->as.gen};
-    return GATO_OK;
+    return cross_solve_ws(s, o, d_c, exit_tol, max_iters, rho, d_lambda, d_dz, st);
 }
 
 extern "C" int gato_solve_rhs_cross(gato_solver *s, int R, const void *d_g, const void *d_c, double exit_tol, int max_iters,
@@ -126,15 +159,7 @@ extern "C" int gato_solve_rhs_cross(gato_solver *s, int R, const void *d_g, cons
 {
     const char *who = "solve_rhs_cross";
     if (!solver_usable(s, who, "cross-term solves")) return GATO_EINVAL;
-    if (!s->cross.valid || !s->as.valid || s->cross.gen != s->as.gen) {
-        set_error("%s: the solver's current assembly is not that of a cross solve: run gato_linsys_device_blocks_cross first; any "
-                  "other whole solve, box-QP call or stage entry since then replaces it", who);
-        return GATO_EINVAL;
-    }
-    if (R < 1 || (long long)R * s->d.B > 65535) {
-        set_error("%s: R = %d must be >= 1 and batch x R <= 65535 (batch %d)", who, R, s->d.B);
-        return GATO_EINVAL;
-    }
+    if (check_cross_assembly(s, who) || check_R(s, who, R)) return GATO_EINVAL;
     if (!d_g || !d_c || !d_lambda || !d_dz) { set_error("%s: d_g, d_c, d_lambda and d_dz are required", who); return GATO_EINVAL; }
     hipStream_t st = (hipStream_t)stream;
     if (s->d.K == 1) return solve_rhs(s, pcg_opts(*s), R, d_g, d_c, exit_tol, max_iters, d_lambda, d_dz, d_iters, st);
@@ -160,11 +185,7 @@ extern "C" int gato_kkt_tangent_rhs_cross(gato_solver *s, int R, const void *d_G
         set_error("%s: d_x, d_lambda, d_tc and one of d_tg and d_gp are required", who);
         return GATO_EINVAL;
     }
-    if (!s->cross.valid || !s->as.valid || s->cross.gen != s->as.gen) {
-        set_error("%s: the solver's current assembly is not that of a cross solve: run gato_linsys_device_blocks_cross first; any "
-                  "other whole solve, box-QP call or stage entry since then replaces it", who);
-        return GATO_EINVAL;
-    }
+    if (check_cross_assembly(s, who)) return GATO_EINVAL;
     const bool one = s->d.K == 1;                                             // no M and no W at all: the plain right-hand side
     const CrossTangentArgs a{d_G_dot, one ? nullptr : d_M_dot, d_C_dot, d_g_dot, d_c_dot, d_x, d_lambda,
                              one ? nullptr : s->cross_ws + cross_layout(s).W, d_tg, d_gp, d_tc};
@@ -202,12 +223,9 @@ static int cross_prepare_csr_ws(gato_solver *s, const char *who, const int *G_ro
                                 const int *C_row, const int *C_col, const void *C_val, int nnz_C, const void *d_g, double rho,
                                 void *G_out, void *M_out, void *C_out, CrossWs *o, hipStream_t st)
 {
-    *o = cross_layout(s);
     int rc;
-    if ((rc = grow(who, &s->cross_ws, &s->cross_ws_bytes, o->bytes, st))) return rc;
+    if ((rc = cross_ws_begin(s, who, o, st))) return rc;
     char *w = s->cross_ws;
-    s->cross.valid = 0;
-    if (s->as.Cd == w + o->C) s->as.valid = 0;
     Dims d = kernel_dims(s);
     d.nnzG = nnz_G; d.nnzC = nnz_C;
     const CrossCsrArgs a{G_row, G_col, C_row, C_col, G_val, C_val, d_g, w + o->G, w + o->C, w + o->W, w + o->g, G_out, M_out, C_out, rho};
@@ -255,14 +273,7 @@ extern "C" int gato_linsys_device_cross(gato_solver *s, const int *d_G_row, cons
     if ((rc = cross_prepare_csr_ws(s, who, d_G_row, d_G_col, d_G_val, nnz_G, d_C_row, d_C_col, d_C_val, nnz_C, d_g, rho, nullptr, nullptr,
                                    nullptr, &o, st)))
         return rc;
-    char *w = s->cross_ws;
-    void *dz = d_dz ? d_dz : s->dz;
-    const AsmInput in{2, nullptr, nullptr, w + o.G, nullptr, nullptr, nullptr, w + o.C, false};
-    if ((rc = whole_solve(s, pcg_opts(*s), in, w + o.g, d_c, exit_tol, max_iters, rho, d_lambda ? d_lambda : s->lambda, dz, st))) return rc;
-    s->lc.valid = 0;                                                         // a recover would leave dz in the transformed variables
-    if ((rc = cross_finish(kernel_dims(s), s->dtype, 1, w + o.W, dz, st))) return rc;
-    s->cross = {1, s->as.gen};
-    return GATO_OK;
+    return cross_solve_ws(s, o, d_c, exit_tol, max_iters, rho, d_lambda, d_dz, st);
 }
 
 extern "C" int gato_kkt_grad_csr_cross(gato_solver *s, const int *d_G_row, const int *d_G_col, int nnz_G, const int *d_C_row,

@@ -5,7 +5,7 @@
 //   A_bar_k = -(beta_k+1 dz_x,k^T + lambda_k+1 a_x,k^T),  B_bar_k = -(beta_k+1 dz_u,k^T + lambda_k+1 a_u,k^T)
 // Both kernels evaluate an output entry through the same two device functions, so a CSR entry's gradient is bit for bit
 // the block gradient at the slot the forward scatter wrote it into.  Nothing here reads the assembly: four vectors in.
-#include "gato_solver.h"
+#include "gato_cross_device.h"
 #include "gato_grad_elem.h"
 
 namespace gato {
@@ -98,15 +98,15 @@ constexpr int SYS_PER = 8;   // systems per thread of the CSR kernel: the slot o
 // carries the gradient of the dense slot it was written into, or 0 when the scatter dropped it (rows of C's block row 0,
 // C columns beyond the block row, G entries between the Q and R parts) or a later entry of the same row wrote that slot
 // again (the last entry in storage order wins).  Thread = entry (G entries first, then C), grid.y = groups of systems.
-// CROSS (grad_csr_cross_kernel): the scatter is cross_prepare_csr_kernel's, where a G entry of a state
+// CROSS (gato_kkt_grad_csr_cross): the scatter is cross_prepare_csr_kernel's, where a G entry of a state
 // row with a control column in a knot k < K - 1 is M_k's and carries M_bar at its slot (grad_M_elem, the expression of
 // grad_cross_kernel); its mirror, such an entry in the last knot and an overwritten one get 0.  Everything else as without.
 template <typename T, int S, int C, bool CROSS>
-__device__ __forceinline__ void grad_csr_body(const int *__restrict__ G_row, const int *__restrict__ G_col, int nnzG,
-                                              const int *__restrict__ C_row, const int *__restrict__ C_col, int nnzC,
-                                              const T *__restrict__ dz, const T *__restrict__ lam,
-                                              const T *__restrict__ a, const T *__restrict__ beta,
-                                              T *__restrict__ Gbar, T *__restrict__ Cbar, int K, int B, BatchStride bs)
+__global__ __launch_bounds__(NT) void grad_csr_kernel(const int *__restrict__ G_row, const int *__restrict__ G_col, int nnzG,
+                                                      const int *__restrict__ C_row, const int *__restrict__ C_col, int nnzC,
+                                                      const T *__restrict__ dz, const T *__restrict__ lam,
+                                                      const T *__restrict__ a, const T *__restrict__ beta,
+                                                      T *__restrict__ Gbar, T *__restrict__ Cbar, int K, int B, BatchStride bs)
 {
     constexpr int n = S + C, SS = S * S;
     bool isM = false;
@@ -156,26 +156,6 @@ __device__ __forceinline__ void grad_csr_body(const int *__restrict__ G_row, con
     }
 }
 
-template <typename T, int S, int C>
-__global__ __launch_bounds__(NT) void grad_csr_kernel(const int *__restrict__ G_row, const int *__restrict__ G_col, int nnzG,
-                                                      const int *__restrict__ C_row, const int *__restrict__ C_col, int nnzC,
-                                                      const T *__restrict__ dz, const T *__restrict__ lam,
-                                                      const T *__restrict__ a, const T *__restrict__ beta,
-                                                      T *__restrict__ Gbar, T *__restrict__ Cbar, int K, int B, BatchStride bs)
-{
-    grad_csr_body<T, S, C, false>(G_row, G_col, nnzG, C_row, C_col, nnzC, dz, lam, a, beta, Gbar, Cbar, K, B, bs);
-}
-
-template <typename T, int S, int C>
-__global__ __launch_bounds__(NT) void grad_csr_cross_kernel(const int *__restrict__ G_row, const int *__restrict__ G_col, int nnzG,
-                                                            const int *__restrict__ C_row, const int *__restrict__ C_col, int nnzC,
-                                                            const T *__restrict__ dz, const T *__restrict__ lam,
-                                                            const T *__restrict__ a, const T *__restrict__ beta,
-                                                            T *__restrict__ Gbar, T *__restrict__ Cbar, int K, int B, BatchStride bs)
-{
-    grad_csr_body<T, S, C, true>(G_row, G_col, nnzG, C_row, C_col, nnzC, dz, lam, a, beta, Gbar, Cbar, K, B, bs);
-}
-
 }  // namespace
 
 template <typename T, int S, int C>
@@ -193,29 +173,18 @@ int launch_grad_blocks(const Dims &d, const T *dz, const T *lam, const T *a, con
     return GATO_OK;
 }
 
-template <typename T, int S, int C>
+template <typename T, int S, int C, bool CROSS>
 int launch_grad_csr(const Dims &d, const int *G_row, const int *G_col, int nnzG, const int *C_row, const int *C_col, int nnzC,
                     const T *dz, const T *lam, const T *a, const T *beta, T *Gbar, T *Cbar, hipStream_t st)
 {
     const long long ent = (long long)(Gbar ? nnzG : 0) + (Cbar ? nnzC : 0);
     if (ent == 0) return GATO_OK;
     const long long bx = (ent + NT - 1) / NT, by = (d.B + SYS_PER - 1) / SYS_PER;
-    if (bx > 0x7fffffff || by > 65535) { set_error("kkt_grad_csr: %lld entries x %d systems are beyond one launch", ent, d.B); return GATO_EINVAL; }
-    hipLaunchKernelGGL((grad_csr_kernel<T, S, C>), dim3((unsigned)bx, (unsigned)by), dim3(NT), 0, st, G_row, G_col, nnzG,
-                       C_row, C_col, nnzC, dz, lam, a, beta, Gbar, Cbar, d.K, d.B, batch_stride(d));
-    GATO_HIP_CHECK(hipGetLastError());
-    return GATO_OK;
-}
-
-template <typename T, int S, int C>
-static int launch_grad_csr_cross(const Dims &d, const int *G_row, const int *G_col, int nnzG, const int *C_row, const int *C_col, int nnzC,
-                                 const T *dz, const T *lam, const T *a, const T *beta, T *Gbar, T *Cbar, hipStream_t st)
-{
-    const long long ent = (long long)(Gbar ? nnzG : 0) + (Cbar ? nnzC : 0);
-    if (ent == 0) return GATO_OK;
-    const long long bx = (ent + NT - 1) / NT, by = (d.B + SYS_PER - 1) / SYS_PER;
-    if (bx > 0x7fffffff || by > 65535) { set_error("kkt_grad_csr_cross: %lld entries x %d systems are beyond one launch", ent, d.B); return GATO_EINVAL; }
-    hipLaunchKernelGGL((grad_csr_cross_kernel<T, S, C>), dim3((unsigned)bx, (unsigned)by), dim3(NT), 0, st, G_row, G_col, nnzG,
+    if (bx > 0x7fffffff || by > 65535) {
+        set_error("%s: %lld entries x %d systems are beyond one launch", CROSS ? "kkt_grad_csr_cross" : "kkt_grad_csr", ent, d.B);
+        return GATO_EINVAL;
+    }
+    hipLaunchKernelGGL((grad_csr_kernel<T, S, C, CROSS>), dim3((unsigned)bx, (unsigned)by), dim3(NT), 0, st, G_row, G_col, nnzG,
                        C_row, C_col, nnzC, dz, lam, a, beta, Gbar, Cbar, d.K, d.B, batch_stride(d));
     GATO_HIP_CHECK(hipGetLastError());
     return GATO_OK;
@@ -240,16 +209,9 @@ GATO_SHAPES(X)
 int grad_csr_cross(const Dims &d, int dtype, const int *G_row, const int *G_col, int nnzG, const int *C_row, const int *C_col, int nnzC,
                    const void *dz, const void *lam, const void *a, const void *beta, void *Gbar, void *Cbar, hipStream_t st)
 {
-#define X(S_, C_)                                                                                                                      \
-    if (d.S == S_ && d.C == C_)                                                                                                        \
-        return dtype == GATO_F32 ? launch_grad_csr_cross<float, S_, C_>(d, G_row, G_col, nnzG, C_row, C_col, nnzC, (const float *)dz,  \
-                                                                       (const float *)lam, (const float *)a, (const float *)beta,     \
-                                                                       (float *)Gbar, (float *)Cbar, st)                              \
-                                 : launch_grad_csr_cross<double, S_, C_>(d, G_row, G_col, nnzG, C_row, C_col, nnzC, (const double *)dz, \
-                                                                        (const double *)lam, (const double *)a, (const double *)beta, \
-                                                                        (double *)Gbar, (double *)Cbar, st);
-    GATO_SHAPES(X)
-#undef X
-    set_error("kkt_grad_csr_cross: (STATE_SIZE=%d, CONTROL_SIZE=%d) is not a compiled shape", d.S, d.C);
-    return GATO_ESHAPE;
+#define GATO_CROSS_LAUNCH(T, S_, C_)                                                                                           \
+    launch_grad_csr<T, S_, C_, true>(d, G_row, G_col, nnzG, C_row, C_col, nnzC, (const T *)dz, (const T *)lam, (const T *)a,   \
+                                     (const T *)beta, (T *)Gbar, (T *)Cbar, st)
+    GATO_CROSS_DISPATCH("kkt_grad_csr_cross");
+#undef GATO_CROSS_LAUNCH
 }

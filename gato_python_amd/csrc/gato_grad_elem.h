@@ -1,4 +1,4 @@
-// One entry of M_bar, shared by grad_cross_kernel (gato_cross.hip) and grad_csr_cross_kernel
+// One entry of M_bar, shared by grad_cross_kernel (gato_cross.hip) and grad_csr_kernel<..., CROSS = true>
 // (gato_grad.hip) so that a CSR cross entry's gradient is bit for bit the block gradient of its slot.  Internal header.
 #pragma once
 #include "gato_common.h"

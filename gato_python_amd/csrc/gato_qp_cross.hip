@@ -8,8 +8,7 @@
 // One wave per knot, grid.x strides over the knots, grid.y = system, lane i = variable i, operands staged in LDS.  Every output
 // element has one writer and one chain of fused multiply-adds over the ascending inner index; the only atomics are the integer
 // atomicMax on the bit patterns of the maxima and the atomicSub of the live count, as in qp_update_kernel.
-#include "gato_solver.h"
-#include "gato_qp_common.h"
+#include "gato_cross_device.h"
 
 namespace gato {
 namespace {
@@ -104,9 +103,7 @@ __global__ __launch_bounds__(WAVE) void qp_update_cross_kernel(QpCrossArgs ca, i
         if (lane < nk) {
             const size_t v = v0 + lane;
             T xs = sTk[lane];
-            if (lane >= S) {                                                // u~ = v~ - W_k x~
-                for (int s = 0; s < S; ++s) xs = fmaT(-sWk[(lane - S) + s * C], sTk[s], xs);
-            }
+            if (lane >= S) xs = cross_unfold_u<T, S, C>(sWk, sTk, xs, lane - S);    // u~ = v~ - W_k x~
             const T xh = fmaT(alpha, xs, beta * z[v]);
             xn = fmaT(alpha, xs, beta * xr[v]);
             const T r = rho[v];
@@ -125,9 +122,7 @@ __global__ __launch_bounds__(WAVE) void qp_update_cross_kernel(QpCrossArgs ca, i
         if (k > 0 && lane < n) {                                            // knot k-1's x+
             const size_t v = v0 - n + lane;
             T xs = sTp[lane];
-            if (lane >= S) {
-                for (int s = 0; s < S; ++s) xs = fmaT(-sWp[(lane - S) + s * C], sTp[s], xs);
-            }
+            if (lane >= S) xs = cross_unfold_u<T, S, C>(sWp, sTp, xs, lane - S);
             sXp[lane] = fmaT(alpha, xs, beta * xr[v]);
         }
         __syncthreads();
@@ -155,9 +150,7 @@ __global__ __launch_bounds__(WAVE) void qp_update_cross_kernel(QpCrossArgs ca, i
                 for (int r = 0; r < S; ++r) ctl = fmaT(sCk[r + i * S], sLn[r], ctl);
             }
             const T rd = (hx - gv) + ctl + yn;
-            if (full && i < S) {                                            // g~'_x = g~+_x - W_k^T g~+_u
-                for (int cc = 0; cc < C; ++cc) t = fmaT(-sWk[cc + i * C], sGt[S + cc], t);
-            }
+            if (full && i < S) t = cross_fold_g<T, S, C>(sWk, sGt + S, t, i);      // g~'_x = g~+_x - W_k^T g~+_u
             xw[v] = xn; x[v] = xn; z[v] = zn; y[v] = yn; gt[v] = t;
             fold(F_PRIM, xn - zn);
             fold(F_DUAL, rd);
@@ -207,10 +200,7 @@ int launch_update(const Dims &d, const QpCrossArgs &a, int it, int last, hipStre
 
 int qp_update_cross(const Dims &d, int dtype, const QpCrossArgs &a, int it, int last, hipStream_t st)
 {
-#define X(S_, C_) \
-    if (d.S == S_ && d.C == C_) return dtype == GATO_F32 ? launch_update<float, S_, C_>(d, a, it, last, st) : launch_update<double, S_, C_>(d, a, it, last, st);
-    GATO_SHAPES(X)
-#undef X
-    set_error("qp_update_cross: (STATE_SIZE=%d, CONTROL_SIZE=%d) is not a compiled shape", d.S, d.C);
-    return GATO_ESHAPE;
+#define GATO_CROSS_LAUNCH(T, S_, C_) launch_update<T, S_, C_>(d, a, it, last, st)
+    GATO_CROSS_DISPATCH("qp_update_cross");
+#undef GATO_CROSS_LAUNCH
 }

@@ -13,8 +13,7 @@
 // blocks of one direction instead (STAGE), with whole-wave contiguous loads.  M._k and C._k are read along a row by the lanes
 // of a column, so their staged copies have a leading dimension of S + 1 (LDS banks).  STAGE = false reads the blocks where they
 // lie, as kkt_tangent_rhs_kernel does; the bits are the same.
-#include "gato_solver.h"
-#include "gato_qp_common.h"
+#include "gato_cross_device.h"
 
 namespace gato {
 namespace {
@@ -119,8 +118,7 @@ __global__ __launch_bounds__(WAVE) void cross_tangent_rhs_kernel(CrossTangentArg
                 if (full) {
                     if (lane >= S && lane < n) sTu[lane - S] = t;
                     __syncthreads();
-                    if (lane < S)
-                        for (int c = 0; c < C; ++c) t = fmaT(-sW[c + lane * C], sTu[c], t);
+                    if (lane < S) t = cross_fold_g<T, S, C>(sW, sTu, t, lane);
                 }
                 if (lane < nk) ((T *)a.gp)[dir * bs.n + v0 + lane] = t;
             }
@@ -140,9 +138,7 @@ int launch_tangent(const Dims &d, int R, const CrossTangentArgs &a, bool in_plac
 
 int cross_tangent_rhs(const Dims &d, int dtype, int R, const CrossTangentArgs &a, bool in_place, hipStream_t st)
 {
-#define X(S_, C_) if (d.S == S_ && d.C == C_) return dtype == GATO_F32 ? launch_tangent<float, S_, C_>(d, R, a, in_place, st) : launch_tangent<double, S_, C_>(d, R, a, in_place, st);
-    GATO_SHAPES(X)
-#undef X
-    set_error("kkt_tangent_rhs_cross: (STATE_SIZE=%d, CONTROL_SIZE=%d) is not a compiled shape", d.S, d.C);
-    return GATO_ESHAPE;
+#define GATO_CROSS_LAUNCH(T, S_, C_) launch_tangent<T, S_, C_>(d, R, a, in_place, st)
+    GATO_CROSS_DISPATCH("kkt_tangent_rhs_cross");
+#undef GATO_CROSS_LAUNCH
 }

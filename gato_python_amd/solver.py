@@ -169,17 +169,23 @@ class Solver:
         """Room for up to R right-hand sides per system in the re-solve work area (blocking; only grows)."""
         _lib.check(_lib.lib().gato_solver_reserve_rhs(self._h, int(R)))
 
+    def _rhs_outputs(self, g, lam, dz, iters):
+        """R of right-hand sides g [B][R][N] (0: g is no tensor of B R N entries), and lam / dz / iters as given or new."""
+        B, N, sk = self.batch, self.N, self.sizes["sk"]
+        R = g.numel() // (B * N) if isinstance(g, torch.Tensor) and g.numel() % (B * N) == 0 else 0
+        if R < 1:
+            return R, lam, dz, iters
+        return (R, self.new(B * R * sk) if lam is None else lam, self.new(B * R * N) if dz is None else dz,
+                self.new(B * R, torch.int32) if iters is None else iters)
+
     def solve_rhs(self, g, c, exit_tol, max_iters, lam=None, dz=None, iters=None):
         """Re-solve the matrices of the most recent linsys / linsys_blocks / linsys_batched call for new right-hand sides:
         g [B][R][N], c [B][R][S K] (flat device tensors; R = g.numel() / (B N)) -> (lam [B R S K], dz [B R N], iters [B R])."""
         B, N, sk = self.batch, self.N, self.sizes["sk"]
-        R = g.numel() // (B * N) if g.numel() % (B * N) == 0 else 0
+        R, lam, dz, iters = self._rhs_outputs(g, lam, dz, iters)
         if R < 1 or c.numel() != B * R * sk:
             raise ValueError(f"solve_rhs: g has {g.numel()} entries and c {c.numel()}: want B*R*N and B*R*S*K with B = {B}, "
                              f"N = {N}, S*K = {sk}, R >= 1")
-        lam = self.new(B * R * sk) if lam is None else lam
-        dz = self.new(B * R * N) if dz is None else dz
-        iters = self.new(B * R, torch.int32) if iters is None else iters
         if lam.numel() != B * R * sk or dz.numel() != B * R * N or iters.numel() != B * R:
             raise ValueError("solve_rhs: lam / dz / iters do not hold B*R*S*K / B*R*N / B*R entries")
         _lib.check(_lib.lib().gato_solve_rhs(self._h, R, _ptr(g), _ptr(c), float(exit_tol), int(max_iters), _ptr(lam),
@@ -221,14 +227,18 @@ class Solver:
             ops.update(M_blocks=(M_blocks, B * self.M_size), C_blocks=(C_blocks, B * self.sizes["C_dense"]))
         self._check_cross(what, **ops)
 
+    def _check_solve_io(self, what, c, lam, dz):
+        """_check_cross of a whole cross solve's c [B S K] and of the outputs lam [B S K] and dz [B N] that are given."""
+        outs = {k: (t, self.batch * n) for k, t, n in (("lam", lam, self.sizes["sk"]), ("dz", dz, self.N)) if t is not None}
+        self._check_cross(what, c=(c, self.batch * self.sizes["sk"]), **outs)
+
     def linsys_blocks_cross(self, G_blocks, M_blocks, C_blocks, g, c, exit_tol, max_iters, rho, lam=None, dz=None):
         """linsys_blocks with the cross term x_k^T M_k u_k in the stage cost (gato_linsys_device_blocks_cross): M_blocks [B (K-1) S C],
         per knot M_k S x C column-major as B_k lies in C_blocks (K = 1: None).  Every G_k + rho I must be positive definite.  lam
         and dz are those of the original problem; the solver's assembly afterwards is the transformed one (solve_rhs_cross
         re-solves the original problem, plain solve_rhs the transformed one).  Asynchronous but for a solver's first call."""
         self._cross_inputs("linsys_blocks_cross", G_blocks, M_blocks, C_blocks, g)
-        outs = {k: (t, self.batch * n) for k, t, n in (("lam", lam, self.sizes["sk"]), ("dz", dz, self.N)) if t is not None}
-        self._check_cross("linsys_blocks_cross", c=(c, self.batch * self.sizes["sk"]), **outs)
+        self._check_solve_io("linsys_blocks_cross", c, lam, dz)
         _lib.check(_lib.lib().gato_linsys_device_blocks_cross(self._h, _ptr(G_blocks), _ptr(M_blocks if self.K > 1 else None),
                                                               _ptr(C_blocks), _ptr(g), _ptr(c), float(exit_tol), int(max_iters),
                                                               float(rho), _ptr(lam), _ptr(dz), self._stream()))
@@ -237,12 +247,9 @@ class Solver:
         """solve_rhs for the original problem of the latest linsys_blocks_cross (gato_solve_rhs_cross): g [B][R][N], c [B][R][S K]
         -> (lam [B R S K], dz [B R N], iters [B R]).  Raises when the solver's current assembly is not that cross solve's."""
         B, N, sk = self.batch, self.N, self.sizes["sk"]
-        R = g.numel() // (B * N) if isinstance(g, torch.Tensor) and g.numel() % (B * N) == 0 else 0
+        R, lam, dz, iters = self._rhs_outputs(g, lam, dz, iters)
         if R < 1 or c.numel() != B * R * sk:
             raise ValueError(f"solve_rhs_cross: g and c must hold B*R*N and B*R*S*K entries with B = {B}, N = {N}, S*K = {sk}, R >= 1")
-        lam = self.new(B * R * sk) if lam is None else lam
-        dz = self.new(B * R * N) if dz is None else dz
-        iters = self.new(B * R, torch.int32) if iters is None else iters
         self._check_cross("solve_rhs_cross", g=(g, B * R * N), c=(c, B * R * sk), lam=(lam, B * R * sk), dz=(dz, B * R * N))
         if iters.numel() != B * R or iters.dtype != torch.int32:
             raise ValueError("solve_rhs_cross: iters must hold B*R int32 entries")
@@ -305,8 +312,7 @@ class Solver:
         solve_rhs_cross, tangents_cross and kkt_grad_cross follow it.  Asynchronous but for a solver's first cross call."""
         what = "linsys_cross"
         nnzG, nnzC = self._csr_cross_inputs(what, G_row, G_col, G_val, C_row, C_col, C_val, g)
-        outs = {k: (t, self.batch * n) for k, t, n in (("lam", lam, self.sizes["sk"]), ("dz", dz, self.N)) if t is not None}
-        self._check_cross(what, c=(c, self.batch * self.sizes["sk"]), **outs)
+        self._check_solve_io(what, c, lam, dz)
         _lib.check(_lib.lib().gato_linsys_device_cross(self._h, _ptr(G_row), _ptr(G_col), _ptr(G_val), nnzG, _ptr(C_row), _ptr(C_col),
                                                        _ptr(C_val), nnzC, _ptr(g), _ptr(c), float(exit_tol), int(max_iters),
                                                        float(rho), _ptr(lam), _ptr(dz), self._stream()))

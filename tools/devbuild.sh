@@ -15,6 +15,7 @@ for f in gato_capi gato_ops gato_plan gato_pcg_host gato_solve gato_qp_host gato
     gato_pcg_resident|gato_pcg_resident_dpp) hdrs+=" gato_pcg_resident_launch.h gato_pcg_resident_kernel.h gato_pcg_geometry.h gato_pcg_launch.h";;
     gato_pcg_resident_single) hdrs+=" gato_pcg_geometry.h gato_pcg_launch.h";;
     gato_pcg_cg1|gato_pcg_dma) hdrs+=" gato_pcg_launch.h";;
+    gato_cross|gato_cross_csr|gato_qp_cross|gato_tangent_cross|gato_grad) hdrs+=" gato_cross_device.h";;
   esac
   if [ ! -f $OBJ/$f.o ] || newer $f.hip $hdrs; then
     /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall "-DGATO_SHAPES(X)=X($S,$C)" "$@" -c $f.hip -o $OBJ/$f.o &
