@@ -28,7 +28,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from .solver import Solver
+from .solver import Solver, zero_rhs
 
 _NP = {torch.float32: np.float32, torch.float64: np.float64}
 _SOLVERS = {}
@@ -244,8 +244,7 @@ def _adjoint(sol, lam, dz, lam_bar, dz_bar, exit_tol, max_iters, cross=False):
     sol.reserve_rhs(1)
     beta, a, _ = (sol.solve_rhs_cross if cross else sol.solve_rhs)(gin, cin, exit_tol, max_iters)
     sol.check_status()              # a hand-off time-out (iters = -1) raises, as in the forward; running to max_iters does not
-    # a system whose right-hand side is all zero has a zero adjoint; its PCG would divide 0 by 0 (eta / p.Sp) instead
-    zero = ~(gin.ne(0).any(1) | cin.ne(0).any(1))[:, None]
+    zero = zero_rhs(gin, cin)[:, None]          # such a system has a zero adjoint; its PCG would divide 0 by 0 instead
     return torch.where(zero, 0, a.view_as(dz)), torch.where(zero, 0, beta.view_as(lam))
 
 

@@ -23,7 +23,7 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 from .autograd import _adjoint, _check_blocks, _check_cross, _common, _dots, _dz_layout, _fresh, _pack, _pack_tangents, _solver, _tangent_dims
-from .solver import BoxQPResult
+from .solver import BoxQPResult, hard_active, zero_rhs
 
 
 def _bound(v, shape, name, ref, what):
@@ -340,7 +340,7 @@ class _BoxQPLayer(torch.autograd.Function):
             return (None,) * 11
         xb = torch.zeros_like(x) if x_bar is None else x_bar.to(x.dtype).contiguous()
         lb = torch.zeros_like(lam) if lam_bar is None else lam_bar.to(lam.dtype).contiguous()
-        live = (xb.ne(0).any(1) | lb.ne(0).any(1)).cpu()
+        live = (~zero_rhs(xb, lb)).cpu()
         unpolished = live & (ctx.codes != _lib.POLISH_ACCEPTED)
         if unpolished.any():
             bad = unpolished.nonzero().flatten().tolist()
@@ -354,9 +354,7 @@ class _BoxQPLayer(torch.autograd.Function):
         # the reduced system reads x_bar off the hard-active set only (Ginv' has zero rows there; a soft-active variable is in
         # the system): with those masked, a system whose upstream gradient lives on its hard-active set alone has a zero
         # right-hand side, and _adjoint's zero test gives it a = beta = 0 instead of the PCG's 0/0
-        hard = act.view_as(xb) != 0
-        if w is not None:
-            hard = hard & ~(w.view_as(xb) > 0)
+        hard = hard_active(act.view_as(xb), None if w is None else w.view_as(xb))
         xf = torch.where(hard, torch.zeros((), dtype=xb.dtype, device=xb.device), xb)
         a, beta = _adjoint(sol, lam, x, lb, xf, pol["exit_tol"], pol["max_iters"])
         Gbar = torch.empty_like(Gb) if need[0] else None

@@ -8,6 +8,7 @@ names, on device buffers.  torch is used only to hold device memory and name the
 from __future__ import annotations
 
 import ctypes as ct
+import functools
 
 import numpy as np
 import torch
@@ -40,6 +41,70 @@ class BoxQPResult:
                 f"res_prim={self.res_prim.tolist()}, res_dual={self.res_dual.tolist()}{pol})")
 
 
+def operand_sizes(S, C, K):
+    """Entries per system of every layout an operand can have: the blocks G_dense, C_dense and M (the cross term's), the
+    block-tridiagonal bd, and the vectors N (dz's layout) and sk (lambda's)."""
+    return dict(G_dense=(S * S + C * C) * K - C * C, C_dense=(S * S + S * C) * (K - 1), M=(K - 1) * S * C, bd=3 * S * S * K,
+                sk=S * K, N=(S + C) * K - C)
+
+
+# dtype kind -> (torch dtype, its name in a message); "value": the solver's own dtype, "index": a CSR index array
+_KINDS = dict(int8=(torch.int8, "torch.int8"), int32=(torch.int32, "torch.int32"), index=(torch.int32, "int32"),
+              float64=(torch.float64, "float64"))
+# The one operand table: name -> (key of operand_sizes: the entries per system, None: one; dtype kind), for every operand a
+# Solver method takes by that name.  The CSR arrays have no size here: their callers state it (check_operands' entries).
+OPERANDS = {name: (key, kind) for key, kind, names in (
+    ("G_dense", "value", "Gb G_blocks G_dot G_out Gbar"), ("C_dense", "value", "Cb C_blocks C_dot C_out Cbar"),
+    ("M", "value", "Mb M_blocks M_dot M_out Mbar"), ("sk", "value", "c lam beta alam c_dot tc"),
+    ("N", "value", "g x z y lo hi dz adz a xbar gp tg g_dot lo_dot hi_dot w_dot m_dot soft_weight soft_cap mu xc xplus lo2 hi2 w2 "
+                   "lo_bar hi_bar w_bar cap_bar"),
+    ("N", "int8", "act"), (None, "int32", "status iters"), (None, "float64", "w v_prev"), (None, "value", "G_val C_val"),
+    (None, "index", "G_row G_col C_row C_col")) for name in names.split()}
+
+
+def operand_table(sizes, batch, dtype):
+    """OPERANDS resolved for `batch` systems of operand_sizes `sizes` and the value dtype `dtype`: name -> (entries per right-hand
+    side or direction, torch dtype, the dtype's name in a message)."""
+    return {name: (batch * (sizes[key] if key else 1), *((dtype, str(dtype)) if kind == "value" else _KINDS[kind]))
+            for name, (key, kind) in OPERANDS.items()}
+
+
+def check_operands(table, what, operands, R=1, entries=None, got=True, optional=False):
+    """ValueError in the name of the method `what` unless every operand of the dict `operands` (name -> tensor) is a contiguous CUDA
+    tensor of the dtype and of R times the entries that `table` (an operand_table) has for it.  entries: name -> the count of an
+    operand whose size the table cannot know (nnz; None: any, at least one).  optional: an operand that is None is skipped.
+    got=False: the message does not say what was given."""
+    for name, t in operands.items():
+        if t is None and optional:
+            continue
+        n, dt, text = table[name]
+        n = entries[name] if entries and name in entries else n * R
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or not t.is_cuda or not t.is_contiguous() or \
+                (t.numel() < 1 if n is None else t.numel() != n):
+            given = f"{t.dtype} {tuple(t.shape)} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
+            raise ValueError(f"{what}: {name} must be a contiguous {text} CUDA tensor{'' if n is None else ' of %d entries' % n}"
+                             + (f", got {given}" if got else ""))
+
+
+def zero_rhs(g, c):
+    """The re-solve's zero rule: the mask [...] of the right-hand sides (g [..., N], c [..., S K]) that are all zero.  Such a
+    system's solution is zero, and its PCG would form 0/0 (eta / p.Sp): every caller of a re-solve writes zeros there."""
+    return ~(g.ne(0).any(-1) | c.ne(0).any(-1))
+
+
+def hard_active(act, w=None):
+    """The hard-active rule: the mask of the variables that sit on a hard bound - act != 0 and no positive soft weight w.  The
+    reduced system does not read a right-hand side there (Ginv' has zero rows), so it is masked before zero_rhs."""
+    return act != 0 if w is None else (act != 0) & ~(w > 0)
+
+
+def bound_tangents(x_d, act, hard, lo_dot=None, hi_dot=None):
+    """x_d with the tangent of the bound a variable sits on (hi_dot where act > 0, lo_dot elsewhere; None: zero) on the
+    hard-active set: such a variable moves with its bound."""
+    z = torch.zeros((), dtype=x_d.dtype, device=x_d.device)
+    return torch.where(hard, torch.where(act > 0, z if hi_dot is None else hi_dot, z if lo_dot is None else lo_dot), x_d)
+
+
 def _ptr(t):
     if t is None:
         return None
@@ -47,6 +112,11 @@ def _ptr(t):
         assert t.is_cuda and t.is_contiguous()
         return ct.c_void_p(t.data_ptr())
     return ct.c_void_p(int(t))
+
+
+def _given(**operands):
+    """The operands that are not None, by name."""
+    return {name: t for name, t in operands.items() if t is not None}
 
 
 class Solver:
@@ -64,8 +134,9 @@ class Solver:
                                                          ct.byref(self._h)))
         self.n = self.S + self.C
         self.N = self.n * self.K - self.C
-        self.sizes = dict(G_dense=(S * S + C * C) * K - C * C, C_dense=(S * S + S * C) * (K - 1),
-                          bd=3 * S * S * K, sk=S * K)
+        self.sizes = operand_sizes(self.S, self.C, self.K)
+        self._operands = operand_table(self.sizes, self.batch, self.dtype)
+        self._check = functools.partial(check_operands, self._operands)      # _check(what, {name: tensor}, R=1, ...)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
@@ -104,6 +175,10 @@ class Solver:
     def to_device(self, a, dtype=None):
         a = np.ascontiguousarray(a, dtype or self.np_dtype)
         return torch.from_numpy(a).to(f"cuda:{self.device}")
+
+    def _out(self, name, t, R=1):
+        """The output operand `name`: t where given, else a new, uninitialised tensor of the table's size and dtype."""
+        return self.new(self._operands[name][0] * R, self._operands[name][1]) if t is None else t
 
     # ---- stages (device tensors in, device tensors out) -------------------------------------
     def convert(self, G_row, G_col, G_val, C_row, C_col, C_val, rho):
@@ -169,28 +244,32 @@ class Solver:
         """Room for up to R right-hand sides per system in the re-solve work area (blocking; only grows)."""
         _lib.check(_lib.lib().gato_solver_reserve_rhs(self._h, int(R)))
 
-    def _rhs_outputs(self, g, lam, dz, iters):
-        """R of right-hand sides g [B][R][N] (0: g is no tensor of B R N entries), and lam / dz / iters as given or new."""
+    def _resolve(self, cross, g, c, exit_tol, max_iters, lam, dz, iters):
+        """The body of solve_rhs (cross False) and solve_rhs_cross: R from g, lam / dz / iters as given or new, the method's own
+        checks - entry counts for the plain one, which sits on timed paths; every operand for the cross one - and the entry."""
         B, N, sk = self.batch, self.N, self.sizes["sk"]
         R = g.numel() // (B * N) if isinstance(g, torch.Tensor) and g.numel() % (B * N) == 0 else 0
-        if R < 1:
-            return R, lam, dz, iters
-        return (R, self.new(B * R * sk) if lam is None else lam, self.new(B * R * N) if dz is None else dz,
-                self.new(B * R, torch.int32) if iters is None else iters)
+        if R < 1 or c.numel() != B * R * sk:
+            raise ValueError(f"solve_rhs_cross: g and c must hold B*R*N and B*R*S*K entries with B = {B}, N = {N}, S*K = {sk}, R >= 1"
+                             if cross else f"solve_rhs: g has {g.numel()} entries and c {c.numel()}: want B*R*N and B*R*S*K with "
+                             f"B = {B}, N = {N}, S*K = {sk}, R >= 1")
+        lam = self.new(B * R * sk) if lam is None else lam
+        dz = self.new(B * R * N) if dz is None else dz
+        iters = self.new(B * R, torch.int32) if iters is None else iters
+        if cross:
+            self._check("solve_rhs_cross", dict(g=g, c=c, lam=lam, dz=dz), R)
+            if iters.numel() != B * R or iters.dtype != torch.int32:
+                raise ValueError("solve_rhs_cross: iters must hold B*R int32 entries")
+        elif lam.numel() != B * R * sk or dz.numel() != B * R * N or iters.numel() != B * R:
+            raise ValueError("solve_rhs: lam / dz / iters do not hold B*R*S*K / B*R*N / B*R entries")
+        entry = _lib.lib().gato_solve_rhs_cross if cross else _lib.lib().gato_solve_rhs
+        _lib.check(entry(self._h, R, _ptr(g), _ptr(c), float(exit_tol), int(max_iters), _ptr(lam), _ptr(dz), _ptr(iters), self._stream()))
+        return lam, dz, iters
 
     def solve_rhs(self, g, c, exit_tol, max_iters, lam=None, dz=None, iters=None):
         """Re-solve the matrices of the most recent linsys / linsys_blocks / linsys_batched call for new right-hand sides:
         g [B][R][N], c [B][R][S K] (flat device tensors; R = g.numel() / (B N)) -> (lam [B R S K], dz [B R N], iters [B R])."""
-        B, N, sk = self.batch, self.N, self.sizes["sk"]
-        R, lam, dz, iters = self._rhs_outputs(g, lam, dz, iters)
-        if R < 1 or c.numel() != B * R * sk:
-            raise ValueError(f"solve_rhs: g has {g.numel()} entries and c {c.numel()}: want B*R*N and B*R*S*K with B = {B}, "
-                             f"N = {N}, S*K = {sk}, R >= 1")
-        if lam.numel() != B * R * sk or dz.numel() != B * R * N or iters.numel() != B * R:
-            raise ValueError("solve_rhs: lam / dz / iters do not hold B*R*S*K / B*R*N / B*R entries")
-        _lib.check(_lib.lib().gato_solve_rhs(self._h, R, _ptr(g), _ptr(c), float(exit_tol), int(max_iters), _ptr(lam),
-                                             _ptr(dz), _ptr(iters), self._stream()))
-        return lam, dz, iters
+        return self._resolve(False, g, c, exit_tol, max_iters, lam, dz, iters)
 
     # ---- gradients of a solve from dz, lambda and the adjoint (a, beta) (gato_kkt_grad_*) --------------------------------
     def kkt_grad_blocks(self, dz, lam, adz, alam, Gbar=None, Cbar=None):
@@ -207,30 +286,17 @@ class Solver:
         return Gbar_val, Cbar_val
 
     # ---- a state-control cross term in the stage cost (gato_*_cross) --------------------------------
-    def _check_cross(self, what, **tensors):
-        """ValueError unless every given operand is a contiguous CUDA tensor of the solver's dtype and of its size: name ->
-        (tensor, entries)."""
-        for name, (t, n) in tensors.items():
-            if not isinstance(t, torch.Tensor) or t.numel() != n or t.dtype != self.dtype or not t.is_cuda or not t.is_contiguous():
-                got = f"{t.dtype} {tuple(t.shape)} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
-                raise ValueError(f"{what}: {name} must be a contiguous {self.dtype} CUDA tensor of {n} entries, got {got}")
-
     @property
     def M_size(self):
         """Entries of M_blocks per system: (K - 1) S C."""
-        return (self.K - 1) * self.S * self.C
+        return self.sizes["M"]
 
     def _cross_inputs(self, what, G_blocks, M_blocks, C_blocks, g):
-        B = self.batch
-        ops = dict(G_blocks=(G_blocks, B * self.sizes["G_dense"]), g=(g, B * self.N))
-        if self.K > 1:
-            ops.update(M_blocks=(M_blocks, B * self.M_size), C_blocks=(C_blocks, B * self.sizes["C_dense"]))
-        self._check_cross(what, **ops)
+        self._check(what, dict(G_blocks=G_blocks, g=g, **(dict(M_blocks=M_blocks, C_blocks=C_blocks) if self.K > 1 else {})))
 
     def _check_solve_io(self, what, c, lam, dz):
-        """_check_cross of a whole cross solve's c [B S K] and of the outputs lam [B S K] and dz [B N] that are given."""
-        outs = {k: (t, self.batch * n) for k, t, n in (("lam", lam, self.sizes["sk"]), ("dz", dz, self.N)) if t is not None}
-        self._check_cross(what, c=(c, self.batch * self.sizes["sk"]), **outs)
+        """The check of a whole cross solve's c [B S K] and of the outputs lam [B S K] and dz [B N] that are given."""
+        self._check(what, dict(c=c, **_given(lam=lam, dz=dz)))
 
     def linsys_blocks_cross(self, G_blocks, M_blocks, C_blocks, g, c, exit_tol, max_iters, rho, lam=None, dz=None):
         """linsys_blocks with the cross term x_k^T M_k u_k in the stage cost (gato_linsys_device_blocks_cross): M_blocks [B (K-1) S C],
@@ -246,23 +312,13 @@ class Solver:
     def solve_rhs_cross(self, g, c, exit_tol, max_iters, lam=None, dz=None, iters=None):
         """solve_rhs for the original problem of the latest linsys_blocks_cross (gato_solve_rhs_cross): g [B][R][N], c [B][R][S K]
         -> (lam [B R S K], dz [B R N], iters [B R]).  Raises when the solver's current assembly is not that cross solve's."""
-        B, N, sk = self.batch, self.N, self.sizes["sk"]
-        R, lam, dz, iters = self._rhs_outputs(g, lam, dz, iters)
-        if R < 1 or c.numel() != B * R * sk:
-            raise ValueError(f"solve_rhs_cross: g and c must hold B*R*N and B*R*S*K entries with B = {B}, N = {N}, S*K = {sk}, R >= 1")
-        self._check_cross("solve_rhs_cross", g=(g, B * R * N), c=(c, B * R * sk), lam=(lam, B * R * sk), dz=(dz, B * R * N))
-        if iters.numel() != B * R or iters.dtype != torch.int32:
-            raise ValueError("solve_rhs_cross: iters must hold B*R int32 entries")
-        _lib.check(_lib.lib().gato_solve_rhs_cross(self._h, R, _ptr(g), _ptr(c), float(exit_tol), int(max_iters), _ptr(lam),
-                                                   _ptr(dz), _ptr(iters), self._stream()))
-        return lam, dz, iters
+        return self._resolve(True, g, c, exit_tol, max_iters, lam, dz, iters)
 
     def kkt_grad_cross(self, dz, adz, Mbar=None):
         """M_bar [B (K-1) S C] (M's layout) of a cross solve from dz and the adjoint's a [B N], both in the original variables
         (gato_kkt_grad_cross): -(a_x dz_u^T + dz_x a_u^T) per knot, M_k and M_k^T perturbed together."""
-        B = self.batch
-        Mbar = self.new(B * self.M_size) if Mbar is None else Mbar
-        self._check_cross("kkt_grad_cross", dz=(dz, B * self.N), adz=(adz, B * self.N), Mbar=(Mbar, B * self.M_size))
+        Mbar = self._out("Mbar", Mbar)
+        self._check("kkt_grad_cross", dict(dz=dz, adz=adz, Mbar=Mbar))
         _lib.check(_lib.lib().gato_kkt_grad_cross(self._h, _ptr(dz), _ptr(adz), _ptr(Mbar), self._stream()))
         return Mbar
 
@@ -277,14 +333,14 @@ class Solver:
         """g' [B R N] of R right-hand sides g [B R N] from the stored W (gato_cross_rhs)."""
         R = g.numel() // (self.batch * self.N)
         gp = self.new(g.numel()) if gp is None else gp
-        self._check_cross("cross_rhs", g=(g, self.batch * max(R, 1) * self.N), gp=(gp, g.numel()))
+        self._check("cross_rhs", dict(g=g, gp=gp), max(R, 1), entries=dict(gp=g.numel()))
         _lib.check(_lib.lib().gato_cross_rhs(self._h, R, _ptr(g), _ptr(gp), self._stream()))
         return gp
 
     def cross_finish(self, dz):
         """u <- v - W x in place on R solutions dz [B R N] from the stored W (gato_cross_finish)."""
         R = dz.numel() // (self.batch * self.N)
-        self._check_cross("cross_finish", dz=(dz, self.batch * max(R, 1) * self.N))
+        self._check("cross_finish", dict(dz=dz), max(R, 1))
         _lib.check(_lib.lib().gato_cross_finish(self._h, R, _ptr(dz), self._stream()))
         return dz
 
@@ -292,16 +348,10 @@ class Solver:
     def _csr_cross_inputs(self, what, G_row, G_col, G_val, C_row, C_col, C_val, g):
         """ValueError unless the index arrays are contiguous int32 CUDA tensors of N + 1 / S K + 1 pointers and one column per
         value, and the values [B nnz] and g [B N] contiguous CUDA tensors of the solver's dtype.  -> (nnz_G, nnz_C) per system."""
-        B = self.batch
-        for name, t, n in (("G_row", G_row, self.N + 1), ("G_col", G_col, None), ("C_row", C_row, self.sizes["sk"] + 1),
-                           ("C_col", C_col, None)):
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous() or \
-                    (n is not None and t.numel() != n) or t.numel() < 1:
-                got = f"{t.dtype} {tuple(t.shape)} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
-                raise ValueError(f"{what}: {name} must be a contiguous int32 CUDA tensor"
-                                 f"{'' if n is None else ' of %d entries' % n}, got {got}")
+        self._check(what, dict(G_row=G_row, G_col=G_col, C_row=C_row, C_col=C_col),
+                    entries=dict(G_row=self.N + 1, G_col=None, C_row=self.sizes["sk"] + 1, C_col=None))
         nnzG, nnzC = G_col.numel(), C_col.numel()
-        self._check_cross(what, G_val=(G_val, B * nnzG), C_val=(C_val, B * nnzC), g=(g, B * self.N))
+        self._check(what, dict(G_val=G_val, C_val=C_val, g=g), entries=dict(G_val=self.batch * nnzG, C_val=self.batch * nnzC))
         return nnzG, nnzC
 
     def linsys_cross(self, G_row, G_col, G_val, C_row, C_col, C_val, g, c, exit_tol, max_iters, rho, lam=None, dz=None):
@@ -324,10 +374,7 @@ class Solver:
         Forgets a recorded cross assembly."""
         what = "cross_prepare_csr"
         nnzG, nnzC = self._csr_cross_inputs(what, G_row, G_col, G_val, C_row, C_col, C_val, g)
-        B = self.batch
-        outs = {k: (t, B * n) for k, t, n in (("G_out", G_out, self.sizes["G_dense"]), ("M_out", M_out, self.M_size),
-                                              ("C_out", C_out, self.sizes["C_dense"])) if t is not None}
-        self._check_cross(what, **outs)
+        self._check(what, dict(G_out=G_out, M_out=M_out, C_out=C_out), optional=True)
         _lib.check(_lib.lib().gato_cross_prepare_csr(self._h, _ptr(G_row), _ptr(G_col), _ptr(G_val), nnzG, _ptr(C_row), _ptr(C_col),
                                                      _ptr(C_val), nnzC, _ptr(g), float(rho), _ptr(G_out), _ptr(M_out), _ptr(C_out),
                                                      self._stream()))
@@ -341,50 +388,35 @@ class Solver:
                                                       _ptr(Cbar_val), self._stream()))
         return Gbar_val, Cbar_val
 
-    _CROSS_BUFFERS = dict(G=13, C=14, W=15, g=16)
+    _CROSS_BUFFERS = dict(G=(13, "G_dense"), C=(14, "C_dense"), W=(15, "M"), g=(16, "N"))       # name -> (buffer, key of sizes)
 
     def cross_buffer_ptr(self, name: str) -> int:
-        return self.buffer_ptr(self._CROSS_BUFFERS[name])
+        return self.buffer_ptr(self._CROSS_BUFFERS[name][0])
 
     def read_cross(self, name: str):
         """Host copy of a part of the cross-term work area (all systems): G (Q'' | R), C (A^' | B^), W or g (g')."""
-        n = dict(G=self.sizes["G_dense"], C=self.sizes["C_dense"], W=self.M_size, g=self.N)[name] * self.batch
-        out = np.empty(n, self.np_dtype)
-        return out if n == 0 else self._read_device(self.cross_buffer_ptr(name), out)
+        return self._read_buffer(*self._CROSS_BUFFERS[name])
 
     # ---- forward-mode sensitivities (gato_kkt_tangent_rhs, DESIGN.md section 3.13) ------------------------------------------
-    _TANGENTS =dict(G_dot="G_dense", C_dot="C_dense", g_dot=None, c_dot="sk", lo_dot=None, hi_dot=None, w_dot=None, m_dot=None)
-
     def kkt_tangent_rhs(self, R, x, lam, *, G_dot=None, C_dot=None, g_dot=None, c_dot=None, lo_dot=None, hi_dot=None, w_dot=None,
                         m_dot=None, Gb=None, Cb=None, act=None, soft_weight=None, soft_cap=None, lo=None, hi=None, tg=None, tc=None):
         """The right-hand side (tg [B R N], tc [B R S K]) of the tangent system of the point x [B N], lam [B S K] for R directions
         per system (gato_kkt_tangent_rhs): tangents G_dot [B R G_dense], C_dot [B R C_dense], g_dot, lo_dot, hi_dot, w_dot, m_dot
         [B R N], c_dot [B R S K], None = zero.  act [B N] int8 with Gb, Cb (and soft_weight with lo, hi; soft_cap) names the
         active set of a box-QP point; None: a plain KKT solve.  Asynchronous; touches no solver state."""
-        B, R = self.batch, int(R)
+        R = int(R)
         if R < 1:
             raise ValueError(f"kkt_tangent_rhs: R = {R}: at least one direction")
         dots = dict(G_dot=G_dot, C_dot=C_dot, g_dot=g_dot, c_dot=c_dot, lo_dot=lo_dot, hi_dot=hi_dot, w_dot=w_dot, m_dot=m_dot)
-        for name, t in dots.items():
-            if t is None:
-                continue
-            per = self.sizes[self._TANGENTS[name]] if self._TANGENTS[name] else self.N
-            if not isinstance(t, torch.Tensor) or t.numel() != B * R * per or t.dtype != self.dtype or not t.is_cuda or not t.is_contiguous():
-                got = f"{t.dtype} {tuple(t.shape)} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
-                raise ValueError(f"kkt_tangent_rhs: {name} must be a contiguous {self.dtype} CUDA tensor of {B * R * per} entries, got {got}")
+        self._check("kkt_tangent_rhs", dots, R, optional=True)
         shared = dict(x=x, lam=lam)
         if act is not None:
             shared.update(Gb=Gb, Cb=Cb, act=act)
             if soft_weight is not None:
-                shared.update(soft_weight=soft_weight, lo=lo, hi=hi)
-                if soft_cap is not None:
-                    shared.update(soft_cap=soft_cap)
-        self._check_vecs("kkt_tangent_rhs", **shared)
-        tg = self.new(B * R * self.N) if tg is None else tg
-        tc = self.new(B * R * self.sizes["sk"]) if tc is None else tc
-        for name, t, per in (("tg", tg, self.N), ("tc", tc, self.sizes["sk"])):
-            if not isinstance(t, torch.Tensor) or t.numel() != B * R * per or t.dtype != self.dtype or not t.is_cuda or not t.is_contiguous():
-                raise ValueError(f"kkt_tangent_rhs: {name} must be a contiguous {self.dtype} CUDA tensor of {B * R * per} entries")
+                shared.update(soft_weight=soft_weight, lo=lo, hi=hi, **_given(soft_cap=soft_cap))
+        self._check("kkt_tangent_rhs", shared)
+        tg, tc = self._out("tg", tg, R), self._out("tc", tc, R)
+        self._check("kkt_tangent_rhs", dict(tg=tg, tc=tc), R, got=False)
         on = act is not None
         soft = on and soft_weight is not None
         _lib.check(_lib.lib().gato_kkt_tangent_rhs(
@@ -399,27 +431,30 @@ class Solver:
         the B R right-hand sides, x_dot = b_dot on the hard-active set.  A (system, direction) pair whose right-hand side is all
         zero (off the hard-active set) gets x_dot = b_dot there, 0 elsewhere and lam_dot = 0 without its PCG, which would form
         0/0.  Blocking (reserve_rhs)."""
-        B, R, N, sk = self.batch, int(R), self.N, self.sizes["sk"]
+        B, R, N = self.batch, int(R), self.N
         tg, tc = self.kkt_tangent_rhs(R, x, lam, **inputs)
+        act = inputs.get("act")
+        if act is None:
+            return self._tangent_solve(R, tg, tc, exit_tol, max_iters)
+        act = act.view(B, 1, N)
+        hard = hard_active(act, None if inputs.get("soft_weight") is None else inputs["soft_weight"].view(B, 1, N))
+        lam_d, x_d = self._tangent_solve(R, tg, tc, exit_tol, max_iters, hard=hard)
+        lo_d, hi_d = (None if t is None else t.view(B, R, N) for t in (inputs.get("lo_dot"), inputs.get("hi_dot")))
+        return lam_d, bound_tangents(x_d, act, hard, lo_d, hi_d)
+
+    def _tangent_solve(self, R, g, c, exit_tol, max_iters, finish=False, hard=None):
+        """The middle of tangents and tangents_cross: room for R, one plain re-solve of the right-hand sides g [B R N], c [B R S K],
+        cross_finish on the solutions where finish, check_status, and zeros for the pairs zero_rhs names (g masked on hard [B, 1,
+        N] first, hard_active's set).  -> (lam_dot [B, R, S K], x_dot [B, R, N])."""
+        B, N, sk = self.batch, self.N, self.sizes["sk"]
         self.reserve_rhs(R)
-        lam_d, x_d, _ = self.solve_rhs(tg, tc, exit_tol, max_iters)
+        lam_d, x_d, _ = self.solve_rhs(g, c, exit_tol, max_iters)
+        if finish:
+            self.cross_finish(x_d)
         self.check_status()
-        tg, tc, lam_d, x_d = tg.view(B, R, N), tc.view(B, R, sk), lam_d.view(B, R, sk), x_d.view(B, R, N)
-        act, w = inputs.get("act"), inputs.get("soft_weight")
-        hard = None
-        if act is not None:
-            hard = act.view(B, 1, N) != 0
-            if w is not None:
-                hard = hard & ~(w.view(B, 1, N) > 0)
-            tg = torch.where(hard, 0, tg)
-        zero = ~(tg.ne(0).any(2) | tc.ne(0).any(2))[:, :, None]
-        lam_d, x_d = torch.where(zero, 0, lam_d), torch.where(zero, 0, x_d)
-        if hard is not None:
-            lo_d, hi_d = inputs.get("lo_dot"), inputs.get("hi_dot")
-            z = torch.zeros((), dtype=self.dtype, device=x_d.device)
-            b_dot = torch.where(act.view(B, 1, N) > 0, z if hi_d is None else hi_d.view(B, R, N), z if lo_d is None else lo_d.view(B, R, N))
-            x_d = torch.where(hard, b_dot, x_d)
-        return lam_d, x_d
+        g = g.view(B, R, N)
+        zero = zero_rhs(g if hard is None else torch.where(hard, 0, g), c.view(B, R, sk))[:, :, None]
+        return torch.where(zero, 0, lam_d.view(B, R, sk)), torch.where(zero, 0, x_d.view(B, R, N))
 
     # ---- forward-mode sensitivities of a cross solve (gato_kkt_tangent_rhs_cross, DESIGN.md section 3.17) ------------------
     def kkt_tangent_rhs_cross(self, R, x, lam, *, G_dot=None, M_dot=None, C_dot=None, g_dot=None, c_dot=None, tg=None, gp=None,
@@ -430,18 +465,15 @@ class Solver:
         and the transformed g' [B R N] from the stored W, t_c [B R S K]; tg and gp both None: both are written, one given: only
         that one (the other is returned as None).  Raises when the solver's current assembly is not that cross solve's.
         Asynchronous; touches no solver state."""
-        B, R = self.batch, int(R)
+        R = int(R)
         if R < 1:
             raise ValueError(f"kkt_tangent_rhs_cross: R = {R}: at least one direction")
-        per = dict(G_dot=self.sizes["G_dense"], M_dot=self.M_size, C_dot=self.sizes["C_dense"], g_dot=self.N, c_dot=self.sizes["sk"])
         dots = dict(G_dot=G_dot, M_dot=M_dot, C_dot=C_dot, g_dot=g_dot, c_dot=c_dot)
         if tg is None and gp is None:
-            tg, gp = self.new(B * R * self.N), self.new(B * R * self.N)
-        tc = self.new(B * R * self.sizes["sk"]) if tc is None else tc
-        outs = dict(tg=(tg, B * R * self.N), gp=(gp, B * R * self.N), tc=(tc, B * R * self.sizes["sk"]))
-        self._check_cross("kkt_tangent_rhs_cross", x=(x, B * self.N), lam=(lam, B * self.sizes["sk"]),
-                          **{k: (t, B * R * per[k]) for k, t in dots.items() if t is not None},
-                          **{k: v for k, v in outs.items() if v[0] is not None})
+            tg, gp = self._out("tg", None, R), self._out("gp", None, R)
+        tc = self._out("tc", tc, R)
+        self._check("kkt_tangent_rhs_cross", dict(x=x, lam=lam))
+        self._check("kkt_tangent_rhs_cross", dict(dots, tg=tg, gp=gp, tc=tc), R, optional=True)
         _lib.check(_lib.lib().gato_kkt_tangent_rhs_cross(self._h, R, *(_ptr(t) if t is not None and t.numel() else None for t in dots.values()),
                                                          _ptr(x), _ptr(lam), _ptr(tg), _ptr(gp), _ptr(tc), self._stream()))
         return tg, gp, tc
@@ -452,17 +484,10 @@ class Solver:
         g' and t_c, one plain re-solve of the transformed assembly for the B R right-hand sides, cross_finish on the solutions -
         three launches.  A (system, direction) pair whose right-hand side is all zero gets zeros without its PCG, which would
         form 0/0.  The assembly stays the cross one.  Blocking (reserve_rhs)."""
-        B, R, N, sk = self.batch, int(R), self.N, self.sizes["sk"]
-        gp = self.new(B * max(R, 1) * N)
-        _, gp, tc = self.kkt_tangent_rhs_cross(R, x, lam, gp=gp, **dots)
-        self.reserve_rhs(R)
-        lam_d, x_d, _ = self.solve_rhs(gp, tc, exit_tol, max_iters)
-        if self.K > 1:
-            self.cross_finish(x_d)
-        self.check_status()
+        R = int(R)
+        _, gp, tc = self.kkt_tangent_rhs_cross(R, x, lam, gp=self._out("gp", None, max(R, 1)), **dots)
         # g' = 0 exactly where t_g = 0 (g'_u = t_g,u, and then g'_x = t_g,x), so the rule of Solver.tangents holds on g'
-        zero = ~(gp.view(B, R, N).ne(0).any(2) | tc.view(B, R, sk).ne(0).any(2))[:, :, None]
-        return torch.where(zero, 0, lam_d.view(B, R, sk)), torch.where(zero, 0, x_d.view(B, R, N))
+        return self._tangent_solve(R, gp, tc, exit_tol, max_iters, finish=self.K > 1)
 
     # ---- box-constrained QP by ADMM over the re-solve (gato_box_qp_solve, DESIGN.md section 3.7) ------------------------
     def box_qp(self, Gb, Cb, g, c, lo, hi, *, rho, exit_tol, max_iters, admm_rho=0.1, sigma=1e-6, alpha=1.6, eps_abs=1e-6,
@@ -481,21 +506,18 @@ class Solver:
         definite.  The result is in the original variables (x, u), as are lo and hi.  The solver's assembly afterwards is the
         x-step matrix in the transformed variables of section 3.15; no cross assembly is recorded (solve_rhs_cross refuses)."""
         if self.K > 1:
-            self._check_cross("box_qp_cross", Mb=(Mb, self.batch * self.M_size))
+            self._check("box_qp_cross", dict(Mb=Mb))
         return self._box_qp_admm("box_qp_cross", Mb if self.K > 1 else None, Gb, Cb, g, c, lo, hi, x, z, y, lam, warm, rho, exit_tol,
                                  max_iters, eps_abs, eps_rel, admm_rho=admm_rho, sigma=sigma, alpha=alpha,
                                  max_admm_iters=max_admm_iters, check_every=check_every)
 
     def _box_qp_admm(self, what, Mb, Gb, Cb, g, c, lo, hi, x, z, y, lam, warm, rho, exit_tol, max_iters, eps_abs, eps_rel, **admm):
         """box_qp (Mb None, what = "box_qp") or box_qp_cross: the outputs, the checks, the entry and the result record."""
-        B, N, sk = self.batch, self.N, self.sizes["sk"]
+        B = self.batch
         if warm and (z is None or y is None or lam is None):
             raise ValueError(f"{what}: warm=True reads z, y and lam: give all three")
-        x = self.new(B * N) if x is None else x
-        z = self.new(B * N) if z is None else z
-        y = self.new(B * N) if y is None else y
-        lam = self.new(B * sk) if lam is None else lam
-        self._check_vecs(what, Gb=Gb, Cb=Cb, g=g, c=c, lo=lo, hi=hi, x=x, z=z, y=y, lam=lam)
+        x, z, y, lam = self._out("x", x), self._out("z", z), self._out("y", y), self._out("lam", lam)
+        self._check(what, dict(Gb=Gb, Cb=Cb, g=g, c=c, lo=lo, hi=hi, x=x, z=z, y=y, lam=lam))
         iters = self.new(B, torch.int32)
         status = self.new(B, torch.int32)
         res = self.new(2 * B, torch.float64)
@@ -511,18 +533,6 @@ class Solver:
         return BoxQPResult(x, z, y, lam, iters, status, res[:, 0], res[:, 1])
 
     # ---- polish of a box QP and its bound gradients (gato_box_qp_polish) --------------------------
-    def _check_vecs(self, what, **tensors):
-        """ValueError unless every box-QP operand, given by its name, is a contiguous CUDA tensor of its size and dtype: Gb
-        [B G_dense], Cb [B C_dense], c / lam / beta [B S K], act [B N] int8, status [B] int32, every other one [B N]."""
-        per = dict(Gb=self.sizes["G_dense"], Cb=self.sizes["C_dense"], c=self.sizes["sk"], lam=self.sizes["sk"],
-                   beta=self.sizes["sk"], status=1)
-        ints = dict(act=torch.int8, status=torch.int32)
-        for name, t in tensors.items():
-            n, dt = self.batch * per.get(name, self.N), ints.get(name, self.dtype)
-            if not isinstance(t, torch.Tensor) or t.numel() != n or t.dtype != dt or not t.is_cuda or not t.is_contiguous():
-                got = f"{t.dtype} {tuple(t.shape)} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
-                raise ValueError(f"{what}: {name} must be a contiguous {dt} CUDA tensor of {n} entries, got {got}")
-
     @staticmethod
     def _qp_params(rho, exit_tol, max_iters, eps_abs, eps_rel, **admm):
         """A gato_box_qp_params: the library's defaults, the five values every box-QP entry reads, and the ADMM fields given."""
@@ -553,15 +563,15 @@ class Solver:
         if act is None:
             act = zeros(B * N, torch.int8)
         else:
-            self._check_vecs(what, act=act)
+            self._check(what, dict(act=act))
             act = act.detach().reshape(-1).clone()
         return x, z, y, lam, act, zeros(B, torch.int32), self.new(B, torch.int32), zeros(2 * B, torch.float64)
 
     def box_qp_active_set(self, z, y, lo, hi, act=None):
         """The active set of an ADMM result (z, y [B N]) for the box (lo, hi): int8 [B N], +1 upper, -1 lower (and lo ==
         hi), 0 free and on the states of x_0."""
-        act = self.new(self.batch * self.N, torch.int8) if act is None else act
-        self._check_vecs("box_qp_active_set", z=z, y=y, lo=lo, hi=hi, act=act)
+        act = self._out("act", act)
+        self._check("box_qp_active_set", dict(z=z, y=y, lo=lo, hi=hi, act=act))
         _lib.check(_lib.lib().gato_box_qp_active_set(self._h, _ptr(z), _ptr(y), _ptr(lo), _ptr(hi), _ptr(act), self._stream()))
         return act
 
@@ -576,8 +586,8 @@ class Solver:
         if (res is None or res is not getattr(result.res_dual, "_base", None) or res.numel() != 2 * B
                 or result.res_prim.data_ptr() != res.data_ptr() or res.dtype != torch.float64 or not res.is_contiguous()):
             raise ValueError("box_qp_polish: result must be the BoxQPResult of Solver.box_qp on this solver")
-        self._check_vecs("box_qp_polish", Gb=Gb, Cb=Cb, g=g, c=c, lo=lo, hi=hi, act=act, x=result.x, z=result.z, y=result.y,
-                         lam=result.lam, status=result.status)
+        self._check("box_qp_polish", dict(Gb=Gb, Cb=Cb, g=g, c=c, lo=lo, hi=hi, act=act, x=result.x, z=result.z, y=result.y,
+                                          lam=result.lam, status=result.status))
         p = self._qp_params(rho, exit_tol, max_iters, eps_abs, eps_rel)
         codes = self.new(B, torch.int32)
         rc = _lib.lib().gato_box_qp_polish(self._h, _ptr(Gb), _ptr(Cb), _ptr(g), _ptr(c), _ptr(lo), _ptr(hi), _ptr(act), ct.byref(p),
@@ -620,11 +630,8 @@ class Solver:
                              "variable with a finite bound needs a positive weight)")
         B = self.batch
         x, z, y, lam, act, iters, status, res = self._new_point("box_qp_pdas", act, x, z, y, lam)
-        self._check_vecs("box_qp_pdas", Gb=Gb, Cb=Cb, g=g, c=c, lo=lo, hi=hi, x=x, z=z, y=y, lam=lam)
-        if soft_weight is not None:
-            self._check_vecs("box_qp_pdas", soft_weight=soft_weight)
-        if soft_cap is not None:
-            self._check_vecs("box_qp_pdas", soft_cap=soft_cap)
+        self._check("box_qp_pdas", dict(Gb=Gb, Cb=Cb, g=g, c=c, lo=lo, hi=hi, x=x, z=z, y=y, lam=lam,
+                                        **_given(soft_weight=soft_weight, soft_cap=soft_cap)))
         p = self._qp_params(rho, exit_tol, max_iters, eps_abs, eps_rel)
         alpha = torch.zeros(B, int(max_pdas_iters), dtype=torch.float64, device=act.device) if line_search else None
         entry, takes = self._PDAS_ENTRIES[soft_weight is not None, soft_cap is not None, bool(line_search)]
@@ -644,9 +651,8 @@ class Solver:
         and phi'(1) of the penalised objective with H = G + rho I (float64), the step length alpha (float64; 1 where phi'(1) <=
         0 or phi'(0) >= 0, else the root of phi' in (0, 1)) and, where x [B N] is given, x = xc + alpha d (xplus bit for bit where
         alpha = 1).  soft_cap None: no caps.  Asynchronous."""
-        own = dict(Gb=Gb, g=g, lo=lo, hi=hi, soft_weight=soft_weight, xc=xc, xplus=xplus)
-        own.update({k: v for k, v in (("soft_cap", soft_cap), ("x", x)) if v is not None})
-        self._check_vecs("box_qp_line_search", **own)
+        self._check("box_qp_line_search", dict(Gb=Gb, g=g, lo=lo, hi=hi, soft_weight=soft_weight, xc=xc, xplus=xplus,
+                                               **_given(soft_cap=soft_cap, x=x)))
         alpha = torch.zeros(self.batch, dtype=torch.float64, device=g.device)
         slope = torch.zeros(self.batch, 2, dtype=torch.float64, device=g.device)
         _lib.check(_lib.lib().gato_box_qp_line_search(self._h, _ptr(Gb), _ptr(g), _ptr(lo), _ptr(hi), _ptr(soft_weight), _ptr(soft_cap),
@@ -676,9 +682,8 @@ class Solver:
             alm_weight_max = max(ALM_WEIGHT_MAX[self.np_dtype], float(alm_weight))
         B, dev = self.batch, f"cuda:{self.device}"
         x, z, y, lam, act, iters, status, res = self._new_point("box_qp_alm", act, x, z, y, lam)
-        own = dict(Gb=Gb, Cb=Cb, g=g, c=c, lo=lo, hi=hi, x=x, z=z, y=y, lam=lam)
-        own.update({k: v for k, v in (("soft_weight", soft_weight), ("soft_cap", soft_cap), ("mu", mu)) if v is not None})
-        self._check_vecs("box_qp_alm", **own)
+        self._check("box_qp_alm", dict(Gb=Gb, Cb=Cb, g=g, c=c, lo=lo, hi=hi, x=x, z=z, y=y, lam=lam,
+                                       **_given(soft_weight=soft_weight, soft_cap=soft_cap, mu=mu)))
         outer = torch.zeros(B, dtype=torch.int32, device=dev)
         weight = torch.zeros(B, dtype=torch.float64, device=dev)
         p = self._qp_params(rho, exit_tol, max_iters, eps_abs, eps_rel)
@@ -703,13 +708,9 @@ class Solver:
         dev = f"cuda:{self.device}"
         nans = lambda: torch.full((B * N,), float("nan"), dtype=self.dtype, device=dev)
         lo2, hi2, w2, z = (nans() if t is None else t for t in (lo2, hi2, w2, z))
-        own = dict(x=x, y=y, lam=lam, mu=mu, lo=lo, hi=hi, lo2=lo2, hi2=hi2, w2=w2, z=z)
-        if soft_weight is not None:
-            own["soft_weight"] = soft_weight
-        self._check_vecs("box_qp_alm_update", **own)
-        for name, t in (("w", w), ("v_prev", v_prev)):
-            if not isinstance(t, torch.Tensor) or t.numel() != B or t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous():
-                raise ValueError(f"box_qp_alm_update: {name} must be a contiguous float64 CUDA tensor of {B} entries")
+        self._check("box_qp_alm_update", dict(x=x, y=y, lam=lam, mu=mu, lo=lo, hi=hi, lo2=lo2, hi2=hi2, w2=w2, z=z,
+                                              **_given(soft_weight=soft_weight)))
+        self._check("box_qp_alm_update", dict(w=w, v_prev=v_prev), got=False)
         v = torch.zeros(B, dtype=torch.float64, device=dev)
         xinf = torch.zeros(B, dtype=torch.float64, device=dev)
         dec = torch.zeros(B, dtype=torch.int32, device=dev)
@@ -724,9 +725,9 @@ class Solver:
         operand as `what`, calls the C entry and returns the outputs.  soft: the operands only the soft and the capped entry
         take, by name and in the entry's order (a soft_weight or soft_cap of None goes as a null pointer); {} for the entry
         without weights."""
-        bars = {name: self.new(self.batch * self.N) if t is None else t for name, t in bars.items()}
+        bars = {name: self._out(name, t) for name, t in bars.items()}
         own = {name: t for name, t in soft.items() if name not in ("soft_weight", "soft_cap") or t is not None}
-        self._check_vecs(what, Gb=Gb, Cb=Cb, act=act, **own, xbar=xbar, a=a, beta=beta, **bars)
+        self._check(what, dict(Gb=Gb, Cb=Cb, act=act, **own, xbar=xbar, a=a, beta=beta, **bars))
         _lib.check(entry(self._h, _ptr(Gb), _ptr(Cb), _ptr(act), *map(_ptr, soft.values()), _ptr(xbar), _ptr(a), _ptr(beta),
                          *map(_ptr, bars.values()), self._stream()))
         return tuple(bars.values())
@@ -766,6 +767,11 @@ class Solver:
             raise RuntimeError(f"hipMemcpy failed: {rc}")
         return out
 
+    def _read_buffer(self, which, key):
+        """Host copy of the work buffer `which`, of sizes[key] entries per system (all systems of a batch)."""
+        out = np.empty(self.sizes[key] * self.batch, self.np_dtype)
+        return out if out.size == 0 else self._read_device(self.buffer_ptr(which), out)
+
     def read_rhs_gamma(self, R: int):
         """Host copy of the re-solve's gamma [B][R][S K] (buffer 11) after a re-solve of R right-hand sides."""
         n = self.batch * int(R) * self.sizes["sk"]
@@ -787,15 +793,13 @@ class Solver:
     def buffer_ptr(self, which: int) -> int:
         return int(_lib.lib().gato_solver_buffer(self._h, which))
 
-    _BUFFERS = dict(G_dense=0, C_dense=1, Ginv=2, S=3, Pinv=4, gamma=5, lam=6, dz=7)
+    # name -> (buffer, key of sizes)
+    _BUFFERS = dict(G_dense=(0, "G_dense"), C_dense=(1, "C_dense"), Ginv=(2, "G_dense"), S=(3, "bd"), Pinv=(4, "bd"), gamma=(5, "sk"),
+                    lam=(6, "sk"), dz=(7, "N"))
 
     def read_buffer(self, name: str):
         """Host copy of one of the solver's own work buffers (all systems of a batch), for tests and debugging."""
-        which = self._BUFFERS[name]
-        n = {0: self.sizes["G_dense"], 1: self.sizes["C_dense"], 2: self.sizes["G_dense"], 3: self.sizes["bd"],
-             4: self.sizes["bd"], 5: self.sizes["sk"], 6: self.sizes["sk"], 7: self.N}[which] * self.batch
-        out = np.empty(n, self.np_dtype)
-        return out if n == 0 else self._read_device(self.buffer_ptr(which), out)
+        return self._read_buffer(*self._BUFFERS[name])
 
     def pcg_last_ms(self) -> float:
         """Device time of the last PCG launch (needs set_option("time_pcg", 1))."""
@@ -826,9 +830,4 @@ class Solver:
 
     def upload_system(self, sysm):
         """KKTSystem (host CSR) -> tuple of device tensors in linsys() argument order."""
-        i32 = torch.int32
-        dev = f"cuda:{self.device}"
-        t = lambda a, dt=None: torch.from_numpy(np.ascontiguousarray(a, dt)).to(dev)
-        return (t(sysm.G_row, np.int32), t(sysm.G_col, np.int32), t(sysm.G_val, self.np_dtype),
-                t(sysm.C_row, np.int32), t(sysm.C_col, np.int32), t(sysm.C_val, self.np_dtype),
-                t(sysm.g, self.np_dtype), t(sysm.c, self.np_dtype))
+        return self.upload_batch([sysm])
